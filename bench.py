@@ -11,12 +11,20 @@ rank classifies its own shard, the confidence head writes its packed (label, con
 records straight into the all-gather send slot and one all-gather moves them.
 
 `--config` selects another BASELINE.json config as the measured line (same JSON contract,
-same sharding + all-gather, its own `roofline`):
+same sharding + all-gather, with `--full` its own `roofline`):
   mc30    configs[2]  ResNet-50 MC-Dropout T=30, 256 frames per GPU      (weak scaling; the default / headline)
   single  configs[1]  ResNet-50 single pass, 256 frames per GPU           (weak scaling)
   ens5    configs[3]  5-member ResNet-50 ensemble, global batch 256 / N   (strong scaling)
   vit     configs[4]  ViT-B/16 + temperature entropy, global batch 512 / N (strong scaling)
-Without `--config` the line is the headline's, with the other configs' per-GPU shares under `extra`.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line: nothing else runs.  `--full` adds
+everything beyond the headline figure: the per-launch HIP-event profile (`roofline`, `kernel_ms_per_step`), and
+on one GPU without `--config` the other configs' per-GPU shares and the 320x240 seam latency under `extra` plus
+the two CPU baselines (`cpu_baseline`, `cpu_baseline_fp32_module`).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller: DIR/labels.npy (float64) and
+DIR/confidence.npy (float32), one entry per frame of the global batch.  Inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 `python bench.py --gpus N` with no torchrun environment starts the N ranks itself
 (a child `python -m torch.distributed.run ... bench.py`), BEFORE this process has
@@ -286,7 +294,8 @@ def measure(be, frames, n_total, rank, world, steps, warmup, torch, dist, classi
     """The timed region: `steps` sharded classify calls between two fences (synchronize + barrier), max over ranks.
     profile: HIP events around every launch - inside the timed region (the headline: < 2 % of a 78 ms step), or with
     separate=True in a second pass of the same calls right after it (the 4-5 ms steps of the other configs, where
-    ~200 event records per call would cost 10-20 % of the step).  -> (elapsed s, per-step ms, profile, labels, profiled wall s)"""
+    ~200 event records per call would cost 10-20 % of the step).
+    -> (elapsed s, per-step ms, profile, (labels, confidences) of the last timed step, profiled wall s)"""
     def step():
         return classify_sharded(be, frames, n_total, rank, world)
 
@@ -325,7 +334,7 @@ def measure(be, frames, n_total, rank, world, steps, warmup, torch, dist, classi
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    return elapsed, lat_ms, prof, labels, prof_wall
+    return elapsed, lat_ms, prof, (labels, conf), prof_wall
 
 
 SEPARATE_NOTE = ("HIP events recorded on the launch streams around every launch, in a second pass of the same calls right after the "
@@ -377,6 +386,25 @@ def seam_latency(blob, torch, synth, Backend):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, labels, conf):
+    """labels (float64) and confidences (float32) of the last timed step -> path/{labels,confidence}.npy.  A global batch
+    whose two arrays would exceed 64 MB is cut to a fixed, seeded sample of frames, whose indices go to path/index.npy."""
+    import numpy as np
+    lab = labels.cpu().numpy().astype(np.float64)
+    cf = conf.cpu().numpy().astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_LIMIT_BYTES // (lab.itemsize + cf.itemsize + 8)
+    if len(lab) > cap:
+        idx = np.sort(np.random.default_rng(0).choice(len(lab), cap, replace=False))
+        lab, cf = lab[idx], cf[idx]
+        np.save(os.path.join(path, "index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "labels.npy"), lab)
+    np.save(os.path.join(path, "confidence.npy"), cf)
+
+
 def launch_command(gpus: int, argv, port: int | None = None):
     """The child command `python bench.py --gpus N` runs when no torchrun environment is present."""
     if port is None:
@@ -409,9 +437,17 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0 = the CPUs this job may use)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearse the N > 1 path with all ranks on ONE GPU (records cross the host; not a measurement)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary configs and the seam latency")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-launch profile (roofline), and on one GPU "
+                         "without --config the secondary configs, the seam latency and the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary configs and the seam latency")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not bracket kernels with HIP events")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the labels and confidences of the last timed step to DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def main():
@@ -456,17 +492,20 @@ def main():
         n_total = c["global_batch"]
     start, stop = shard_range(n_total, rank, world)
     n_local = stop - start
-    blob, info = weights.make_synthetic("resnet50", seed=1)
+    blob = weights.make_synthetic("resnet50", seed=1)[0] if name != "vit" else None   # the ViT line builds its own checkpoint
     be = make_backend(name, c, args, max(1, -(-n_total // world)), local_rank, weights, Backend, blob)
     frames = make_frames(n_local, start, args, torch, synth, args.device_corrupt)
     T = c["T"]
 
     separate = name != "mc30"
-    elapsed, lat_ms, prof, labels, pwall = measure(be, frames, n_total, rank, world, args.steps, args.warmup, torch, dist,
-                                                   classify_sharded, profile=not args.no_profile, separate=separate)
+    elapsed, lat_ms, prof, (labels, conf), pwall = measure(be, frames, n_total, rank, world, args.steps, args.warmup, torch, dist,
+                                                           classify_sharded, profile=args.full and not args.no_profile,
+                                                           separate=separate)
 
     out = None
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, labels, conf)
         fps = n_total * args.steps / elapsed
         gf = c["gflop"]
         out = {
@@ -496,7 +535,7 @@ def main():
             out["kernel_ms_per_step"] = {k: v["ms"] / args.steps for k, v in prof.items()}
     be.close()
     if rank == 0:
-        if world == 1 and not args.no_extra and args.config is None:
+        if args.full and world == 1 and not args.no_extra and args.config is None:
             try:
                 out["extra"] = secondary_configs(blob, args, torch, dist, synth, weights, Backend, classify_sharded)
             except Exception as e:   # secondary lines are reported, never required
@@ -505,7 +544,7 @@ def main():
                 out["extra"]["seam_320x240"] = seam_latency(blob, torch, synth, Backend)
             except Exception as e:
                 out["extra"]["seam_320x240"] = {"error": str(e)}
-        if world == 1 and name == "mc30":   # the CPU baselines are timed on rank 0 of the 1-GPU headline run only
+        if args.full and world == 1 and name == "mc30":   # the CPU baselines are timed on rank 0 of the 1-GPU headline run only
             if args.cpu_port_frames > 0:
                 try:
                     out["cpu_baseline"] = cpu_baseline(blob, args, T, c["policy"])

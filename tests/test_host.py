@@ -258,6 +258,30 @@ def test_bench_self_launch_command_and_world_size_check():
     assert body.index("subprocess.call(launch_command") < body.index("import torch")   # spawn first, torch later
 
 
+def test_bench_full_is_opt_in_and_outputs_dump_as_float(tmp_path, monkeypatch):
+    """A plain bench run measures the headline only (--full opts into the rest), --steps below 1 is rejected, and
+    --dump-outputs writes the caller's (labels, confidences) as float64 / float32 .npy, a seeded sample above 64 MB."""
+    import bench
+    import torch
+    a = bench.parse_args(["--steps", "3", "--warmup", "1"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 1)
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    rec = torch.stack([torch.arange(40, dtype=torch.int32), torch.linspace(0, 1, 40).view(torch.int32)], dim=1)
+    labels, conf = rec[:, 0], rec[:, 1].view(torch.float32)          # stride-2 views, as classify_sharded returns them
+    bench.dump_outputs(str(tmp_path / "all"), labels, conf)
+    lab, cf = np.load(tmp_path / "all" / "labels.npy"), np.load(tmp_path / "all" / "confidence.npy")
+    assert lab.dtype == np.float64 and cf.dtype == np.float32
+    assert np.array_equal(lab, np.arange(40)) and np.array_equal(cf, conf.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20 * 10)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), labels, conf)
+    idx = np.load(tmp_path / "s1" / "index.npy")
+    assert len(idx) == 10 and np.array_equal(idx, np.load(tmp_path / "s2" / "index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "labels.npy"), idx)
+
+
 def test_pmc_traffic_is_tied_to_the_kernel_sources():
     import json
     import bench
