@@ -19,7 +19,7 @@ STATUS_NAMES = {0: "FAV_OK", 1: "FAV_ERR_INVALID_ARG", 2: "FAV_ERR_BAD_BLOB", 3:
                 4: "FAV_ERR_HIP", 5: "FAV_ERR_NO_DEVICE", 6: "FAV_ERR_UNSUPPORTED"}
 LAYOUT_NHWC_U8, LAYOUT_NHWC_F32 = 0, 1
 ARCH_RESNET18_CIFAR, ARCH_RESNET50, ARCH_VIT_B16, ARCH_VIT_TINY = 0, 1, 2, 3
-CONF_MAX_SOFTMAX, CONF_ENTROPY = 0, 1
+CONF_MAX_SOFTMAX, CONF_ENTROPY, CONF_MUTUAL_INFO = 0, 1, 2
 MATH_BF16, MATH_F32_EXACT = 0, 1
 K_STEM, K_CONV, K_MAXPOOL, K_AVGPOOL, K_DROPOUT, K_HEAD, K_COUNT = 0, 1, 2, 3, 4, 5, 6
 KERNEL_CLASS_NAMES = ("stem_im2col", "conv_igemm", "maxpool", "avgpool", "entry_dropout", "head")
@@ -61,6 +61,13 @@ class FavTailDesc(C.Structure):
                 ("drop", FavDropoutDesc), ("res_entry", C.c_int32), ("entry_site", C.c_int32)]
 
 
+class FavUncertainty(C.Structure):
+    """fav_uncertainty: one 72-byte record per frame (18 dwords; backend.unpack_uncertainty reads it as int32[n, 18])."""
+    _fields_ = [("label", C.c_int32), ("confidence", C.c_float), ("mean_prob", C.c_float), ("prob_std", C.c_float),
+                ("pred_entropy", C.c_float), ("expected_entropy", C.c_float), ("mutual_info", C.c_float),
+                ("agreement", C.c_float), ("top_label", C.c_int32 * 5), ("top_prob", C.c_float * 5)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -88,6 +95,8 @@ _SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_classify_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "fav_classify_uncertainty": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
@@ -114,6 +123,8 @@ _SIGNATURES = {
     "fav_op_vit_assemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "fav_op_head": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_head_uncertainty": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                          C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -26,7 +26,9 @@ from . import _lib, weights as _weights
 
 _ARCH = {"resnet18_cifar": _lib.ARCH_RESNET18_CIFAR, "resnet50": _lib.ARCH_RESNET50, "vit_b16": _lib.ARCH_VIT_B16,
          "vit_tiny": _lib.ARCH_VIT_TINY}
-_CONF = {"max_softmax": _lib.CONF_MAX_SOFTMAX, "entropy": _lib.CONF_ENTROPY}
+_CONF = {"max_softmax": _lib.CONF_MAX_SOFTMAX, "entropy": _lib.CONF_ENTROPY, "mutual_info": _lib.CONF_MUTUAL_INFO}
+#: dwords of one fav_uncertainty record (include/fav.h)
+UNCERTAINTY_DWORDS = 18
 _MATH = {"bf16": _lib.MATH_BF16, "f32_exact": _lib.MATH_F32_EXACT}
 
 
@@ -177,6 +179,40 @@ class Backend:
                                                  None, None, stream), self._h)
         return out
 
+    def classify_uncertainty(self, images, first_index: int = 0, out=None) -> dict:
+        """frames -> the uncertainty decomposition of the T samples (fav_classify_uncertainty; fields: include/fav.h
+        fav_uncertainty): a dict of ``label``, ``confidence``, ``mean_prob``, ``prob_std``, ``pred_entropy``,
+        ``expected_entropy``, ``mutual_info``, ``agreement`` ([n]), ``top_label``, ``top_prob`` ([n, 5]) - views of one
+        int32[n, 18] record buffer (``unpack_uncertainty``) - plus ``fail`` (uint8[n]) and ``score`` (fp32[n]).
+        torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out (the frames
+        are uploaded, the call is synchronous).  ``out``: a contiguous int32[n, 18] tensor on the frames' device to write
+        the records into (e.g. this rank's slot of an all-gather send buffer)."""
+        torch = self._torch
+        self._check_shape(images)
+        layout = self._layout_of(images)
+        n = int(images.shape[0])
+        host = isinstance(images, np.ndarray)
+        if host:
+            img = torch.from_numpy(np.ascontiguousarray(images)).to(f"cuda:{self.device}")
+        else:
+            if not images.is_cuda or images.device.index != self.device:
+                raise ValueError(f"frames must live on cuda:{self.device}")
+            img = images.contiguous()
+        dev = img.device
+        if out is None:
+            out = torch.empty((n, UNCERTAINTY_DWORDS), dtype=torch.int32, device=dev)
+        if out.dtype != torch.int32 or tuple(out.shape) != (n, UNCERTAINTY_DWORDS) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32[n, {UNCERTAINTY_DWORDS}] tensor on the frames' device")
+        fail = torch.empty(n, dtype=torch.uint8, device=dev)
+        score = torch.empty(n, dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self.lib.fav_classify_uncertainty(self._h, img.data_ptr(), n, layout, int(first_index), out.data_ptr(),
+                                                     fail.data_ptr(), score.data_ptr(), stream), self._h)
+        if host:
+            rec, fail, score = out.cpu().numpy(), fail.cpu().numpy(), score.cpu().numpy()   # synchronises the stream
+            return dict(unpack_uncertainty(rec), fail=fail, score=score)
+        return dict(unpack_uncertainty(out), fail=fail, score=score)
+
     def classify(self, images, first_index: int = 0):
         """The drop-in: frames -> (labels, confidences)."""
         labels, conf, _, _ = self.classify_detect(images, first_index)
@@ -275,6 +311,31 @@ class Backend:
         if rule_score is not None:
             metrics["rule_anomaly_score"] = rule_score
         return {"anomaly_score": round(s0, 6), "vision_status": status, "metrics": metrics}
+
+
+def unpack_uncertainty(records) -> dict:
+    """int32[n, 18] fav_uncertainty records (torch tensor on any device, or numpy) -> dict of per-field views:
+    ``label`` int32[n], ``confidence`` / ``mean_prob`` / ``prob_std`` / ``pred_entropy`` / ``expected_entropy`` /
+    ``mutual_info`` / ``agreement`` fp32[n] (bit-cast), ``top_label`` int32[n, 5], ``top_prob`` fp32[n, 5].  Nothing is
+    copied: the fields alias the record buffer."""
+    if records.ndim != 2 or int(records.shape[1]) != UNCERTAINTY_DWORDS:
+        raise ValueError(f"expected int32[n, {UNCERTAINTY_DWORDS}] records, got shape {tuple(records.shape)}")
+    if isinstance(records, np.ndarray):
+        if records.dtype != np.int32:
+            raise TypeError(f"records must be int32, got {records.dtype}")
+        f32 = np.float32
+    else:
+        import torch
+        if records.dtype != torch.int32:
+            raise TypeError(f"records must be int32, got {records.dtype}")
+        f32 = torch.float32
+    out = {"label": records[:, 0]}
+    for i, name in enumerate(("confidence", "mean_prob", "prob_std", "pred_entropy", "expected_entropy", "mutual_info",
+                              "agreement"), start=1):
+        out[name] = records[:, i].view(f32)
+    out["top_label"] = records[:, 8:13]
+    out["top_prob"] = records[:, 13:18].view(f32)
+    return out
 
 
 def anomaly_score_from_confidence(conf):

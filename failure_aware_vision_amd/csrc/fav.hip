@@ -828,12 +828,29 @@ const char* launch_entry_reduce(fav_handle* h, const void* x, void* y, const voi
     return nullptr;
 }
 
+// rec (one fav_uncertainty per frame) or conf_kind FAV_CONF_MUTUAL_INFO: head_unc_kernel; otherwise head_kernel
 const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C, int ld, float temperature, int kind,
-                        float tau, int* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride = 1) {
+                        float tau, int* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride = 1,
+                        fav_uncertainty* rec = nullptr) {
     if (C > 1024 || C < 1) return "head: num_classes must be in [1, 1024]";
     if (ld % 4 != 0 || ld < C) return "head: bad row stride";
     const float inv_temp = 1.0f / temperature;
     const float inv_lnC = C > 1 ? (float)(1.0 / std::log((double)C)) : 0.f;
+    if (rec || kind == FAV_CONF_MUTUAL_INFO) {
+        if (T < 1 || T > 4096) return "head: the uncertainty head takes 1 <= T <= 4096 samples";
+        const int K = std::min(C, T);       // largest mutual information of T samples over C classes: ln K
+        const float inv_lnK = K > 1 ? (float)(1.0 / std::log((double)K)) : 0.f;
+        // bytes: the logits, the second pass's p_t[label] reloads, the outputs
+        Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 4.0 * (double)T * n + (rec ? 72.0 : 8.0) * n);
+        const size_t lds = (size_t)T * 8;   // per-sample max and 1/sum
+        if (C <= 256)
+            hipLaunchKernelGGL((head_unc_kernel<1>), dim3(n), dim3(256), lds, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
+                               inv_lnK, labels, conf, fail, score, out_stride, (int*)rec);
+        else
+            hipLaunchKernelGGL((head_unc_kernel<4>), dim3(n), dim3(256), lds, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
+                               inv_lnK, labels, conf, fail, score, out_stride, (int*)rec);
+        return nullptr;
+    }
     Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 8.0 * n);
     if (C <= 256)
         hipLaunchKernelGGL((head_kernel<1>), dim3(n), dim3(256), 0, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
@@ -1719,11 +1736,22 @@ fav_status fav_create(const fav_config* cfg, fav_handle** out) {
     if (cfg->num_classes < 1 || cfg->num_classes > 1024 || cfg->max_batch < 1 || cfg->in_h < 8 || cfg->in_w < 8 ||
         cfg->n_samples < 1 || cfg->n_samples > 4096 || !(cfg->temperature > 0.f) || cfg->dropout_p < 0.f || cfg->dropout_p >= 1.f ||
         !(cfg->stdev[0] > 0.f && cfg->stdev[1] > 0.f && cfg->stdev[2] > 0.f) || cfg->math_mode < 0 || cfg->math_mode > 1 ||
-        cfg->conf_kind < 0 || cfg->conf_kind > 1 || cfg->n_members < 0 || cfg->n_members > 64 ||
+        cfg->conf_kind < 0 || cfg->conf_kind > 2 || cfg->n_members < 0 || cfg->n_members > 64 ||
         cfg->tail_min_rows < -1 || cfg->ens_grouped_max < -1 || cfg->vit_streams < 0 || cfg->vit_streams > 4 || cfg->stem_fused < -1 || cfg->stem_fused > 0 ||
         (cfg->n_members > 1 && cfg->site_mask != 0 && cfg->dropout_p > 0.f)) {   // ensemble members are deterministic
         g_create_error = "fav_create: config value out of range";
         return FAV_ERR_INVALID_ARG;
+    }
+    if (cfg->conf_kind == FAV_CONF_MUTUAL_INFO) {
+        // the samples the head averages (the T_eff / n_members rule of build_graph; the ViT path is a single pass)
+        const bool mc = !is_vit_arch(cfg->arch) && cfg->site_mask != 0 && std::lround((double)cfg->dropout_p * 256.0) > 0;
+        const int T = cfg->n_members > 1 ? cfg->n_members : (mc ? cfg->n_samples : 1);
+        if (T < 2 || cfg->num_classes < 2) {
+            g_create_error = fmt("fav_create: conf_kind FAV_CONF_MUTUAL_INFO (mutual information) needs at least 2 samples "
+                                 "(MC-Dropout with an active site, or n_members > 1) and 2 classes; this config has T=%d, "
+                                 "num_classes=%d", T, cfg->num_classes);
+            return FAV_ERR_INVALID_ARG;
+        }
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) {
@@ -1915,7 +1943,8 @@ void mark_last_use(fav_handle* h, hipStream_t s) {
     if (h->ev_last && hipEventRecord(h->ev_last, s) == hipSuccess) h->ev_last_set = true;
 }
 fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
-                              int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride);
+                              int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride,
+                              fav_uncertainty* rec = nullptr);
 }  // namespace
 
 fav_status fav_classify_ex(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
@@ -1950,9 +1979,27 @@ fav_status fav_classify_records(fav_handle* h, const void* images, int32_t n, in
     return st;
 }
 
+fav_status fav_classify_uncertainty(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
+                                    fav_uncertainty* records, uint8_t* fail, float* score, void* stream) {
+    static_assert(sizeof(fav_uncertainty) == 72, "fav_uncertainty is 18 dwords");
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!h->weights_loaded) { h->err = "fav_classify_uncertainty: no weights loaded"; return FAV_ERR_NO_WEIGHTS; }
+    if (!images || !records || ((uintptr_t)records & 7)) { h->err = "fav_classify_uncertainty: null or misaligned buffer"; return FAV_ERR_INVALID_ARG; }
+    if (n < 1 || n > h->cfg.max_batch) { h->err = fmt("fav_classify_uncertainty: n=%d outside [1, max_batch=%d]", n, h->cfg.max_batch); return FAV_ERR_INVALID_ARG; }
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) { h->err = "fav_classify_uncertainty: unknown layout"; return FAV_ERR_INVALID_ARG; }
+    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) { h->err = "fav_classify_uncertainty: first_image_index out of range"; return FAV_ERR_INVALID_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_last_use(h, s)) return st;
+    const fav_status st = classify_on_stream(h, images, n, layout, first_index, nullptr, nullptr, fail, score, s, 1, records);
+    mark_last_use(h, s);
+    return st;
+}
+
 namespace {
 fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
-                              int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride) {
+                              int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride,
+                              fav_uncertainty* rec) {
     h->ev_used = h->profiling ? h->ev_used : 0;
     if (h->vit) {
         for (auto& L : h->layers) { L.w = L.w_m[0]; L.b = L.b_m[0]; }
@@ -2063,7 +2110,7 @@ fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int3
     if (!h->vit) h->phase_out.back() = h->logits;
     const int T_head = h->n_members > 1 ? h->n_members : h->T_eff;
     if (const char* e = launch_head(h, h->logits, T_head, n, h->cfg.num_classes, h->cpad, h->cfg.temperature,
-                                    h->cfg.conf_kind, h->cfg.tau, labels, conf, fail, score, s, out_stride)) {
+                                    h->cfg.conf_kind, h->cfg.tau, labels, conf, fail, score, s, out_stride, rec)) {
         h->err = e;
         return FAV_ERR_INVALID_ARG;
     }
@@ -2228,7 +2275,18 @@ fav_status fav_op_entry_dropout(const void* x, void* out, int64_t elems, int32_t
 fav_status fav_op_head(const float* logits, int32_t T, int32_t n, int32_t C, int32_t ld, float temperature, int32_t kind,
                        float tau, int32_t* labels, float* conf, uint8_t* fail, float* score, void* stream) {
     if (!logits || !labels || !conf || T < 1 || n < 1 || !(temperature > 0.f)) return op_done("fav_op_head: bad argument");
+    if (kind == FAV_CONF_MUTUAL_INFO && (T < 2 || C < 2))
+        return op_done("fav_op_head: conf_kind 2 (mutual information) needs T >= 2 samples and num_classes >= 2");
     return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, labels, conf, fail, score, (hipStream_t)stream));
+}
+
+fav_status fav_op_head_uncertainty(const float* logits, int32_t T, int32_t n, int32_t C, int32_t ld, float temperature,
+                                   int32_t kind, float tau, fav_uncertainty* records, uint8_t* fail, float* score, void* stream) {
+    if (!logits || !records || ((uintptr_t)records & 7) || T < 1 || T > 4096 || n < 1 || kind < 0 || kind > 2 ||
+        !(temperature > 0.f))
+        return op_done("fav_op_head_uncertainty: bad argument (records non-NULL and 8-byte aligned, 1 <= T <= 4096, kind 0..2)");
+    return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, nullptr, nullptr, fail, score,
+                               (hipStream_t)stream, 1, records));
 }
 
 fav_status fav_op_layernorm(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t rows, int32_t D,

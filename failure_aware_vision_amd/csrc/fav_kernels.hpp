@@ -3232,6 +3232,197 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ log
     }
 }
 
+// ---------------------------------------------------------------------------
+// Uncertainty head: head_kernel's pbar, label and kind 0 / 1 confidence (same per-sample sequence, same wave-order
+// combine, hence the same bits) plus the decomposition of the T samples:
+//   H(pbar), (1/T) sum_t H(p_t), mutual information, vote share of the label (per-sample argmax of z_t, lowest index
+//   on ties), population std of p_t[label] (second pass: p_t[label] recomputed from the per-sample max and 1/sum kept
+//   in LDS, same operations as the first pass), top-5 of pbar (ties -> lowest index).
+// conf_kind 2: conf = 1 - MI / ln(min(C, T)) (inv_lnK = 1 / ln(min(C, T)), 0 when that is 1).
+// rec (may be NULL): one 18-dword record per frame, the layout of fav_uncertainty in include/fav.h.
+// labels / conf may be NULL; otherwise written with head_kernel's out_stride convention.
+// Dynamic LDS: 8 * T bytes (per-sample max and 1/sum).
+// ---------------------------------------------------------------------------
+template <int NV>
+__global__ __launch_bounds__(256) void head_unc_kernel(const float* __restrict__ logits, int T, int n, int C, int ld,
+                                                       float inv_temp, int conf_kind, float tau, float inv_lnC, float inv_lnK,
+                                                       int* __restrict__ labels, float* __restrict__ conf,
+                                                       uint8_t* __restrict__ fail, float* __restrict__ score, int out_stride,
+                                                       int* __restrict__ rec) {
+    static_assert(NV * 64 <= 256, "one float4 group of pbar per thread");
+    __shared__ __attribute__((aligned(16))) float part[4][NV * 256];
+    __shared__ int votes[NV * 256];
+    __shared__ float red_v[5][4];
+    __shared__ int red_i[5][4];
+    __shared__ float red_h[4], red_e[4], red_s[4];
+    __shared__ int out_rec[18];
+    extern __shared__ float smp[];          // [T] per-sample max, [T] per-sample 1/sum
+    const int img = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int c = tid; c < NV * 256; c += 256) votes[c] = 0;
+    __syncthreads();
+    float p[NV][4];
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[i][j] = 0.f;
+    float ent = 0.f;                        // sum of H(p_t) over this wave's samples, in sample order
+    for (int t = wave; t < T; t += 4) {
+        const float* row = logits + ((long long)t * n + img) * ld;
+        float z[NV][4];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = 4 * lane + 256 * i;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[i][j] = -INFINITY;
+            if (c + 3 < C) {
+                const float4 v = *(const float4*)(row + c);
+                z[i][0] = v.x * inv_temp; z[i][1] = v.y * inv_temp; z[i][2] = v.z * inv_temp; z[i][3] = v.w * inv_temp;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c + j < C) z[i][j] = row[c + j] * inv_temp;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) mx = fmaxf(mx, z[i][j]);
+        }
+        mx = wave_max(mx);
+        // this sample's vote: lowest class index whose z equals the maximum
+        int am = 0x7fffffff;
+#pragma unroll
+        for (int i = NV - 1; i >= 0; --i)
+#pragma unroll
+            for (int j = 3; j >= 0; --j)
+                if (z[i][j] == mx) am = 4 * lane + 256 * i + j;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) am = min(am, __shfl_xor(am, o, 64));
+        float s = 0.f, sd = 0.f;            // sd = sum e * (z - mx): H(p_t) = ln s - sd / s
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float d = z[i][j] - mx;
+                z[i][j] = expf(d);  // exp(-inf) = 0 for padded classes
+                s += z[i][j];
+                sd += z[i][j] > 0.f ? z[i][j] * d : 0.f;
+            }
+        s = wave_sum(s);
+        sd = wave_sum(sd);
+        const float inv = 1.0f / s;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p[i][j] += z[i][j] * inv;
+        ent += fmaxf(logf(s) - sd * inv, 0.f);
+        if (lane == 0) {
+            smp[t] = mx;
+            smp[T + t] = inv;
+            if (am < C) atomicAdd(&votes[am], 1);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        *(float4*)&part[wave][4 * lane + 256 * i] = make_float4(p[i][0], p[i][1], p[i][2], p[i][3]);
+    if (lane == 0) red_e[wave] = ent;
+    __syncthreads();
+    // thread tid owns classes 4*tid .. 4*tid + 3 (NV*256 floats per wave row = NV*64 float4 <= 256 threads)
+    const float inv_T = 1.0f / (float)T;
+    float pb[4] = {-1.f, -1.f, -1.f, -1.f};
+    float h = 0.f;
+    const int q = tid;
+    if (q < NV * 64) {
+        const float4 a = *(const float4*)&part[0][4 * q], b = *(const float4*)&part[1][4 * q];
+        const float4 c4 = *(const float4*)&part[2][4 * q], d = *(const float4*)&part[3][4 * q];
+        pb[0] = (((a.x + b.x) + c4.x) + d.x) * inv_T; pb[1] = (((a.y + b.y) + c4.y) + d.y) * inv_T;
+        pb[2] = (((a.z + b.z) + c4.z) + d.z) * inv_T; pb[3] = (((a.w + b.w) + c4.w) + d.w) * inv_T;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (4 * q + j >= C) pb[j] = -1.f;           // not a class: never selected
+            else if (pb[j] > 0.f) h -= pb[j] * logf(pb[j]);
+        }
+    }
+    h = wave_sum(h);
+    if (lane == 0) red_h[wave] = h;
+    // top-5 of pbar: five rounds of block arg-max, each excluding the classes already taken (rank 0 = the label)
+    int top_i[5];
+    float top_v[5];
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        float best = -1.f;
+        int besti = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (pb[j] > best) { best = pb[j]; besti = 4 * q + j; }   // j ascending: strict > keeps the lowest index
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(besti, o, 64);
+            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        }
+        if (lane == 0) { red_v[r][wave] = best; red_i[r][wave] = besti; }
+        __syncthreads();
+        float bv = red_v[r][0];
+        int bi = red_i[r][0];
+        for (int w = 1; w < 4; ++w)
+            if (red_v[r][w] > bv || (red_v[r][w] == bv && red_i[r][w] < bi)) { bv = red_v[r][w]; bi = red_i[r][w]; }
+        top_v[r] = bv; top_i[r] = bi;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * q + j == bi) pb[j] = -1.f;
+        if (r == 0) {
+            // second pass for prob_std: p_t[label] with the first pass's operations, (p_t - pbar[label])^2 summed per thread
+            float sq = 0.f;
+            for (int t = tid; t < T && bi < C; t += 256) {
+                const float zl = logits[((long long)t * n + img) * ld + bi] * inv_temp;
+                const float pt = expf(zl - smp[t]) * smp[T + t];
+                sq += (pt - bv) * (pt - bv);
+            }
+            sq = wave_sum(sq);
+            if (lane == 0) red_s[wave] = sq;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int bi = top_i[0];
+        const float bv = top_v[0];
+        float hh = red_h[0];
+        for (int w = 1; w < 4; ++w) hh += red_h[w];
+        // T = 1: pbar is p_0 bit for bit, so its entropy IS the expected entropy (and the mutual information exactly 0)
+        const float eh = T == 1 ? hh : (((red_e[0] + red_e[1]) + red_e[2]) + red_e[3]) * inv_T;
+        const float mi = fmaxf(hh - eh, 0.f);
+        const float sd = sqrtf((((red_s[0] + red_s[1]) + red_s[2]) + red_s[3]) * inv_T);
+        const float cf = conf_kind == 0 ? bv : (conf_kind == 1 ? 1.0f - hh * inv_lnC : 1.0f - mi * inv_lnK);
+        if (labels) labels[(long long)img * out_stride] = bi;
+        if (conf) conf[(long long)img * out_stride] = cf;
+        if (fail) fail[img] = cf < tau ? 1 : 0;
+        if (score) score[img] = fminf(fmaxf(1.0f - cf, 0.f), 1.f);
+        out_rec[0] = bi;
+        out_rec[1] = __float_as_int(cf);
+        out_rec[2] = __float_as_int(bv);
+        out_rec[3] = __float_as_int(sd);
+        out_rec[4] = __float_as_int(hh);
+        out_rec[5] = __float_as_int(eh);
+        out_rec[6] = __float_as_int(mi);
+        out_rec[7] = __float_as_int(bi < C ? (float)votes[bi] / (float)T : 0.f);
+    }
+    if (tid < 5) {
+        // rank tid of top-5 (selected with compile-time indices: no scratch); fewer than 5 classes leave label -1, prob 0
+        int ti = top_i[0];
+        float tv = top_v[0];
+#pragma unroll
+        for (int r = 1; r < 5; ++r)
+            if (tid == r) { ti = top_i[r]; tv = top_v[r]; }
+        const bool ok = ti < C;
+        out_rec[8 + tid] = ok ? ti : -1;
+        out_rec[13 + tid] = ok ? __float_as_int(tv) : 0;
+    }
+    if (rec) {
+        __syncthreads();
+        if (tid < 9) *(int2*)(rec + (long long)img * 18 + 2 * tid) = make_int2(out_rec[2 * tid], out_rec[2 * tid + 1]);
+    }
+}
+
 }  // namespace fav
 
 // ===========================================================================

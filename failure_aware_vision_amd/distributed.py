@@ -31,7 +31,7 @@ def unpack_records(rec):
     return rec[:, 0].contiguous(), rec[:, 1].contiguous().view(torch.float32)
 
 
-def classify_sharded(classifier, local_frames, n_total: int, rank: int, world: int, group=None):
+def classify_sharded(classifier, local_frames, n_total: int, rank: int, world: int, group=None, detail: bool = False):
     """Each rank classifies its own shard (global frame indices [start, stop)) and all ranks receive the full
     (labels[n_total], conf[n_total]).
 
@@ -45,7 +45,14 @@ def classify_sharded(classifier, local_frames, n_total: int, rank: int, world: i
     Lifetime of the results: on the direct path with equal shards (and with ``world == 1``) the two tensors are stride-2
     VIEWS of one freshly allocated [n, 2] int32 record buffer - no copy is made; call ``.contiguous()`` before handing a raw
     ``data_ptr()`` to something that assumes dense arrays.  Every call allocates its own buffers, so results stay valid
-    across later calls."""
+    across later calls.
+
+    ``detail=True``: the same exchange with the 72-byte uncertainty records (include/fav.h fav_uncertainty) in place of the
+    8-byte ones - ``Backend.classify_uncertainty`` writes them into this rank's slot of the send buffer - and the result is
+    ``unpack_uncertainty`` of the gathered int32[n_total, 18] records (a dict of per-field views).  A plain function
+    ``fn(frames, first_index=...) -> int32[n, 18]`` records is accepted there too."""
+    if detail:
+        return _classify_sharded_detail(classifier, local_frames, n_total, rank, world, group)
     import torch
     import torch.distributed as dist
     start, stop = shard_range(n_total, rank, world)
@@ -93,3 +100,54 @@ def classify_sharded(classifier, local_frames, n_total: int, rank: int, world: i
         s, e = shard_range(n_total, r, world)
         parts.append(recv[r * cap:r * cap + (e - s)])
     return unpack_records(torch.cat(parts, dim=0))
+
+
+def _classify_sharded_detail(classifier, local_frames, n_total: int, rank: int, world: int, group=None):
+    """classify_sharded(..., detail=True): one all-gather of int32[cap, 18] uncertainty records per rank."""
+    import torch
+    import torch.distributed as dist
+    from .backend import UNCERTAINTY_DWORDS as W, unpack_uncertainty
+    start, stop = shard_range(n_total, rank, world)
+    n_local = stop - start
+    if n_local > 0 and int(local_frames.shape[0]) != n_local:
+        raise ValueError(f"rank {rank} owns frames [{start},{stop}) but was handed {int(local_frames.shape[0])}")
+    cap = -(-n_total // world)  # every shard padded to the largest
+    if hasattr(classifier, "classify_uncertainty"):
+        # a Backend: host frames (or frames on another device) are uploaded to its GPU first
+        dev = torch.device(f"cuda:{classifier.device}")
+        if isinstance(local_frames, np.ndarray):
+            local_frames = torch.from_numpy(np.ascontiguousarray(local_frames))
+        local_frames = local_frames.to(dev)
+        send = torch.empty((cap, W), dtype=torch.int32, device=dev) if n_local == cap else \
+            torch.zeros((cap, W), dtype=torch.int32, device=dev)
+        if n_local > 0:
+            classifier.classify_uncertainty(local_frames, first_index=start, out=send[:n_local])
+    else:
+        if n_local > 0:
+            rec = classifier(local_frames, first_index=start)
+            rec = torch.from_numpy(np.ascontiguousarray(rec)) if isinstance(rec, np.ndarray) else rec
+            if rec.dtype != torch.int32 or tuple(rec.shape) != (n_local, W):
+                raise ValueError(f"the classifier must return int32[{n_local}, {W}] records, got {rec.dtype} {tuple(rec.shape)}")
+            dev = rec.device
+        else:
+            dev = local_frames.device if hasattr(local_frames, "device") and not isinstance(local_frames, np.ndarray) else "cpu"
+            rec = torch.zeros((0, W), dtype=torch.int32, device=dev)
+        send = torch.zeros((cap, W), dtype=torch.int32, device=dev)
+        send[:n_local] = rec
+    if world == 1:
+        return unpack_uncertainty(send[:n_local])
+    recv = torch.empty((world * cap, W), dtype=torch.int32, device=dev)
+    if dist.get_backend(group) == "gloo" and send.is_cuda:
+        # rehearsal only (several ranks sharing one GPU, where RCCL cannot run): the records cross the host
+        host = torch.empty((world * cap, W), dtype=torch.int32)
+        dist.all_gather_into_tensor(host, send.cpu(), group=group)
+        recv.copy_(host)
+    else:
+        dist.all_gather_into_tensor(recv, send, group=group)
+    if n_total == world * cap:                 # equal shards: the receive buffer IS the result
+        return unpack_uncertainty(recv)
+    parts = []
+    for r in range(world):
+        s, e = shard_range(n_total, r, world)
+        parts.append(recv[r * cap:r * cap + (e - s)])
+    return unpack_uncertainty(torch.cat(parts, dim=0))

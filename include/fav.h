@@ -53,7 +53,10 @@ typedef enum fav_layout { FAV_LAYOUT_NHWC_U8 = 0, FAV_LAYOUT_NHWC_F32 = 1 } fav_
  * no dropout sites, no ensemble; input a multiple of 16 with at most 256 tokens).  FAV_ARCH_VIT_TINY: a
  * two-layer, 128-wide miniature of it for the parity tests. */
 typedef enum fav_arch { FAV_ARCH_RESNET18_CIFAR = 0, FAV_ARCH_RESNET50 = 1, FAV_ARCH_VIT_B16 = 2, FAV_ARCH_VIT_TINY = 3 } fav_arch;
-typedef enum fav_conf_kind { FAV_CONF_MAX_SOFTMAX = 0, FAV_CONF_ENTROPY = 1 } fav_conf_kind;
+/* FAV_CONF_MUTUAL_INFO: conf = 1 - MI / ln(min(C, T)), the epistemic part of the samples' spread (fav_uncertainty below);
+ * fav_create accepts it only when the head averages T >= 2 samples (MC-Dropout with an active site and round(256 p) > 0,
+ * or n_members > 1) over num_classes >= 2. */
+typedef enum fav_conf_kind { FAV_CONF_MAX_SOFTMAX = 0, FAV_CONF_ENTROPY = 1, FAV_CONF_MUTUAL_INFO = 2 } fav_conf_kind;
 /* FAV_MATH_BF16: bf16 MFMA, fp32 accumulate (production).
  * FAV_MATH_F32_EXACT: same bf16 operands fed to the fp32-input MFMA, whose
  * result is a k-ordered fmaf chain; bit-reproducible against oracle/ (validation). */
@@ -135,6 +138,31 @@ fav_status fav_classify_ex(fav_handle* h, const void* images_dev, int32_t n, int
 fav_status fav_classify_records(fav_handle* h, const void* images_dev, int32_t n, int32_t layout,
                                 int64_t first_image_index, void* records_dev, uint8_t* fail_dev,
                                 float* score_dev, void* hip_stream);
+
+/* Uncertainty decomposition of one frame (72 bytes).  With z_t = fp32(logit_t * fp32(1/temperature)), p_t = softmax(z_t)
+ * and pbar = mean_t p_t, computed exactly as for fav_classify_ex (the T samples are the MC-Dropout samples, or the members
+ * of a deep ensemble; T = 1 for a single pass):
+ *   label            argmax pbar, lowest index on ties (bit-identical to fav_classify_ex's label)
+ *   confidence       the handle's conf_kind (kinds 0 / 1 bit-identical to fav_classify_ex's conf)
+ *   mean_prob        pbar[label] (equals confidence bit for bit under FAV_CONF_MAX_SOFTMAX)
+ *   prob_std         population std over the samples of p_t[label]
+ *   pred_entropy     H(pbar) in nats (what FAV_CONF_ENTROPY is derived from)
+ *   expected_entropy (1/T) sum_t H(p_t) in nats
+ *   mutual_info      max(pred_entropy - expected_entropy, 0)
+ *   agreement        #{t : argmax z_t == label} / T (per-sample argmax on z_t, lowest index on ties)
+ *   top_label/prob   classes by pbar, descending, lowest index first on ties; slots past num_classes: -1 / 0
+ * T = 1: expected_entropy = pred_entropy, mutual_info = 0, agreement = 1, prob_std = 0. */
+typedef struct fav_uncertainty {
+    int32_t label; float confidence; float mean_prob; float prob_std;
+    float pred_entropy; float expected_entropy; float mutual_info; float agreement;
+    int32_t top_label[5]; float top_prob[5];
+} fav_uncertainty;   /* 72 bytes */
+
+/* Same schedule as fav_classify_ex; the head writes one fav_uncertainty per frame to records_dev[n] (non-NULL, 8-byte
+ * aligned device pointer, e.g. a rank's slot of an all-gather buffer).  fail_dev / score_dev may be NULL. */
+fav_status fav_classify_uncertainty(fav_handle* h, const void* images_dev, int32_t n, int32_t layout,
+                                    int64_t first_image_index, fav_uncertainty* records_dev,
+                                    uint8_t* fail_dev, float* score_dev, void* hip_stream);
 
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
@@ -239,6 +267,12 @@ fav_status fav_op_entry_reduce(const void* x, void* y, const void* wa, const flo
 fav_status fav_op_head(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld,
                        float temperature, int32_t conf_kind, float tau,
                        int32_t* labels, float* conf, uint8_t* fail, float* score, void* hip_stream);
+/* logits fp32 [T][n][ld] -> records[n] (fav_uncertainty, 8-byte aligned), fail / score if non-NULL.  T <= 4096,
+ * num_classes <= 1024; conf_kind 0, 1 or 2 (kind 2 at T = 1 or num_classes = 1: conf = 1).  fav_op_head with conf_kind 2
+ * runs the same kernel (and needs T >= 2, num_classes >= 2). */
+fav_status fav_op_head_uncertainty(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld,
+                                   float temperature, int32_t conf_kind, float tau, fav_uncertainty* records,
+                                   uint8_t* fail, float* score, void* hip_stream);
 
 /* ---- ViT building blocks (BASELINE configs[4]); linear layers go through fav_op_conv2d with kh = kw = 1.
  * LayerNorm over rows of D bf16 values (row r at x + r*ldx elements; D % 4 == 0, D <= 1024), fp32 statistics,
