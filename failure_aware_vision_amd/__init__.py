@@ -6,5 +6,6 @@ library; constructing a Backend does, and raises if it (or a gfx950 GPU) is
 missing — there is no CPU fallback.
 """
 from .backend import Backend, anomaly_score_from_confidence, unpack_uncertainty  # noqa: F401
+from .conformal import Conformal, calibrate_qhat, unpack_sets  # noqa: F401
 from .distributed import classify_sharded, shard_range  # noqa: F401
 from . import synth, weights  # noqa: F401

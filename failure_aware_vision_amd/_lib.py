@@ -68,6 +68,21 @@ class FavUncertainty(C.Structure):
                 ("agreement", C.c_float), ("top_label", C.c_int32 * 5), ("top_prob", C.c_float * 5)]
 
 
+CP_LAC, CP_APS = 0, 1
+
+
+class FavConformal(C.Structure):
+    """fav_conformal: the split-conformal score and its calibrated threshold (32 bytes)."""
+    _fields_ = [("struct_size", C.c_uint32), ("score_kind", C.c_int32), ("randomized", C.c_int32), ("k_reg", C.c_int32),
+                ("lambda_", C.c_float), ("qhat", C.c_float), ("seed", C.c_uint64)]
+
+
+class FavPredSet(C.Structure):
+    """fav_pred_set: one 160-byte prediction-set record per frame (40 dwords; conformal.unpack_sets reads it as int32[n, 40])."""
+    _fields_ = [("label", C.c_int32), ("confidence", C.c_float), ("set_size", C.c_int32), ("set_mass", C.c_float),
+                ("u", C.c_float), ("reserved", C.c_int32 * 3), ("member", C.c_uint32 * 32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -97,6 +112,10 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_void_p]),
     "fav_classify_uncertainty": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "fav_classify_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(FavConformal),
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_conformal_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(FavConformal),
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
@@ -125,6 +144,9 @@ _SIGNATURES = {
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_op_head_uncertainty": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_head_sets": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float,
+                                   C.c_int64, C.POINTER(FavConformal), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

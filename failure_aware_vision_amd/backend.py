@@ -19,6 +19,7 @@ only for device buffers and the current stream.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -212,6 +213,82 @@ class Backend:
             rec, fail, score = out.cpu().numpy(), fail.cpu().numpy(), score.cpu().numpy()   # synchronises the stream
             return dict(unpack_uncertainty(rec), fail=fail, score=score)
         return dict(unpack_uncertainty(out), fail=fail, score=score)
+
+    # -- conformal prediction sets (conformal.py; include/fav.h fav_classify_sets) ---------------------------------------
+    def _frames_on_device(self, images):
+        """-> (frames on this Backend's GPU, True when they came from the host)."""
+        if isinstance(images, np.ndarray):
+            return self._torch.from_numpy(np.ascontiguousarray(images)).to(f"cuda:{self.device}"), True
+        if not images.is_cuda or images.device.index != self.device:
+            raise ValueError(f"frames must live on cuda:{self.device}")
+        return images.contiguous(), False
+
+    def conformal_scores(self, images, labels, cp, first_index: int = 0):
+        """Calibration scores s(y) of the true classes ``labels`` (int[n]) under ``cp`` (a ``conformal.Conformal``; its qhat
+        is not used), fp32[n], NaN where a label lies outside [0, num_classes).  Frame i has global index first_index + i
+        (the key of a randomized score's draw); batches of max_batch frames.  torch CUDA frames in -> CUDA tensor out,
+        asynchronous on the current stream; numpy in -> numpy out, synchronous."""
+        torch = self._torch
+        self._check_shape(images)
+        layout = self._layout_of(images)
+        n = int(images.shape[0])
+        if int(np.shape(labels)[0] if isinstance(labels, np.ndarray) else labels.shape[0]) != n:
+            raise ValueError("one label per frame")
+        img, host = self._frames_on_device(images)
+        dev = img.device
+        lab = (torch.from_numpy(np.asarray(labels)) if isinstance(labels, np.ndarray) else labels).to(dev, torch.int32).contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        c = cp.to_c()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        mb = int(self.cfg.max_batch)
+        for b in range(0, n, mb):
+            e = min(n, b + mb)
+            _lib.check(self.lib.fav_conformal_scores(self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b,
+                                                     C.byref(c), lab[b:e].data_ptr(), out[b:e].data_ptr(), stream), self._h)
+        return out.cpu().numpy() if host else out
+
+    def calibrate_conformal(self, images, labels, alpha: float, method: str = "aps", randomized: bool = True,
+                            lam: float = 0.0, k_reg: int = 0, first_index: int = 0, seed: int = 0):
+        """Split-conformal calibration on held-out labelled frames -> a ``conformal.Conformal`` with ``qhat`` set, so that
+        ``classify_sets`` covers the true class with probability >= 1 - alpha.  ``method``: "lac", "aps" or "raps"
+        (APS with ``lam`` > 0 and ``k_reg``); ``randomized`` (APS / RAPS only) draws u per frame from ``seed``."""
+        from .conformal import Conformal, calibrate_qhat
+        if method not in ("lac", "aps", "raps"):
+            raise ValueError(f"method must be 'lac', 'aps' or 'raps', got {method!r}")
+        kind = "lac" if method == "lac" else "aps"
+        cp = Conformal(kind=kind, randomized=bool(randomized) and kind == "aps", lam=float(lam), k_reg=int(k_reg), seed=int(seed))
+        s = self.conformal_scores(images, labels, cp, first_index=first_index)
+        s = s if isinstance(s, np.ndarray) else s.cpu().numpy()
+        return dataclasses.replace(cp, qhat=calibrate_qhat(s, alpha))
+
+    def classify_sets(self, images, cp, first_index: int = 0, out=None) -> dict:
+        """frames -> their conformal prediction sets under ``cp`` (fav_classify_sets): ``unpack_sets`` of one int32[n, 40]
+        record buffer (``label``, ``confidence``, ``set_size``, ``set_mass``, ``u``, ``members`` bool[n, num_classes])
+        plus ``fail`` (uint8[n], conf < tau), ``score`` (fp32[n]) and ``ambiguous`` (set_size != 1: the set-valued
+        failure flag).  torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy
+        out, synchronous.  ``out``: a contiguous int32[n, 40] tensor on the frames' device to write the records into
+        (e.g. this rank's slot of an all-gather send buffer)."""
+        from .conformal import PRED_SET_DWORDS as W, unpack_sets
+        torch = self._torch
+        self._check_shape(images)
+        layout = self._layout_of(images)
+        n = int(images.shape[0])
+        img, host = self._frames_on_device(images)
+        dev = img.device
+        if out is None:
+            out = torch.empty((n, W), dtype=torch.int32, device=dev)
+        if out.dtype != torch.int32 or tuple(out.shape) != (n, W) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32[n, {W}] tensor on the frames' device")
+        fail = torch.empty(n, dtype=torch.uint8, device=dev)
+        score = torch.empty(n, dtype=torch.float32, device=dev)
+        c = cp.to_c()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self.lib.fav_classify_sets(self._h, img.data_ptr(), n, layout, int(first_index), C.byref(c),
+                                              out.data_ptr(), fail.data_ptr(), score.data_ptr(), stream), self._h)
+        if host:
+            out, fail, score = out.cpu().numpy(), fail.cpu().numpy(), score.cpu().numpy()   # synchronises the stream
+        r = unpack_sets(out, self.cfg.num_classes)
+        return dict(r, fail=fail, score=score, ambiguous=r["set_size"] != 1)
 
     def classify(self, images, first_index: int = 0):
         """The drop-in: frames -> (labels, confidences)."""

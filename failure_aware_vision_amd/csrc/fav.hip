@@ -828,14 +828,61 @@ const char* launch_entry_reduce(fav_handle* h, const void* x, void* y, const voi
     return nullptr;
 }
 
-// rec (one fav_uncertainty per frame) or conf_kind FAV_CONF_MUTUAL_INFO: head_unc_kernel; otherwise head_kernel
+// The conformal prediction-set head's arguments (fav_classify_sets / fav_conformal_scores / fav_op_head_sets): cp checked
+// by check_conformal; rec and / or (true_labels, true_scores).
+struct HeadSets {
+    const fav_conformal* cp;
+    int64_t first_index;
+    const int32_t* true_labels;
+    float* true_scores;
+    fav_pred_set* rec;
+};
+
+const char* check_conformal(const fav_conformal* cp) {
+    if (!cp || cp->struct_size != sizeof(fav_conformal)) return "conformal: cp is NULL or its struct_size is wrong";
+    if (cp->score_kind != FAV_CP_LAC && cp->score_kind != FAV_CP_APS) return "conformal: unknown score_kind";
+    if (std::isnan(cp->qhat)) return "conformal: qhat is NaN";
+    if (!(cp->lambda >= 0.f) || !std::isfinite(cp->lambda)) return "conformal: lambda must be finite and >= 0";
+    if (cp->k_reg < 0) return "conformal: k_reg must be >= 0";
+    if (cp->randomized != 0 && cp->randomized != 1) return "conformal: randomized must be 0 or 1";
+    if (cp->score_kind == FAV_CP_LAC && (cp->randomized || cp->lambda != 0.f))
+        return "conformal: FAV_CP_LAC takes neither randomized nor lambda";
+    return nullptr;
+}
+
+// rec (one fav_uncertainty per frame) or conf_kind FAV_CONF_MUTUAL_INFO: head_unc_kernel; sets: head_sets_kernel;
+// otherwise head_kernel
 const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C, int ld, float temperature, int kind,
                         float tau, int* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride = 1,
-                        fav_uncertainty* rec = nullptr) {
+                        fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr) {
     if (C > 1024 || C < 1) return "head: num_classes must be in [1, 1024]";
     if (ld % 4 != 0 || ld < C) return "head: bad row stride";
     const float inv_temp = 1.0f / temperature;
     const float inv_lnC = C > 1 ? (float)(1.0 / std::log((double)C)) : 0.f;
+    if (sets) {
+        if (const char* e = check_conformal(sets->cp)) return e;
+        if (!sets->rec && !sets->true_labels) return "head: the sets head needs records or calibration labels";
+        if (!sets->true_labels != !sets->true_scores) return "head: true_labels and true_scores go together";
+        if ((uintptr_t)sets->rec & 7) return "head: prediction-set records must be 8-byte aligned";
+        if (sets->first_index < 0 || sets->first_index + n > 0xFFFFFFFFll) return "head: first_image_index out of range";
+        const int K = std::min(C, T);
+        const float inv_lnK = K > 1 ? (float)(1.0 / std::log((double)K)) : 0.f;
+        SetsParams p;
+        p.score_kind = sets->cp->score_kind; p.randomized = sets->cp->randomized; p.k_reg = sets->cp->k_reg;
+        p.lambda = sets->cp->lambda; p.qhat = sets->cp->qhat;
+        p.seed_lo = (uint32_t)(sets->cp->seed & 0xFFFFFFFFull); p.seed_hi = (uint32_t)(sets->cp->seed >> 32);
+        p.first_index = sets->first_index;
+        // bytes: the logits, the labels and scores of a calibration call, the outputs
+        Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + (sets->true_labels ? 8.0 : 0.0) * n +
+                                       (sets->rec ? 160.0 : 0.0) * n + (fail ? 1.0 : 0.0) * n + (score ? 4.0 : 0.0) * n);
+        if (C <= 256)
+            hipLaunchKernelGGL((head_sets_kernel<1>), dim3(n), dim3(256), 0, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
+                               inv_lnK, p, sets->true_labels, sets->true_scores, (int*)sets->rec, fail, score);
+        else
+            hipLaunchKernelGGL((head_sets_kernel<4>), dim3(n), dim3(256), 0, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
+                               inv_lnK, p, sets->true_labels, sets->true_scores, (int*)sets->rec, fail, score);
+        return nullptr;
+    }
     if (rec || kind == FAV_CONF_MUTUAL_INFO) {
         if (T < 1 || T > 4096) return "head: the uncertainty head takes 1 <= T <= 4096 samples";
         const int K = std::min(C, T);       // largest mutual information of T samples over C classes: ln K
@@ -1944,7 +1991,7 @@ void mark_last_use(fav_handle* h, hipStream_t s) {
 }
 fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                               int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride,
-                              fav_uncertainty* rec = nullptr);
+                              fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr);
 }  // namespace
 
 fav_status fav_classify_ex(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
@@ -1997,9 +2044,46 @@ fav_status fav_classify_uncertainty(fav_handle* h, const void* images, int32_t n
 }
 
 namespace {
+// the argument checks of fav_classify_sets / fav_conformal_scores, then the fav_classify_ex schedule with the sets head
+fav_status classify_sets_common(const char* who, fav_handle* h, const void* images, int32_t n, int32_t layout,
+                                int64_t first_index, const HeadSets& hs, uint8_t* fail, float* score, void* stream) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", who); return FAV_ERR_NO_WEIGHTS; }
+    if (const char* e = check_conformal(hs.cp)) { h->err = fmt("%s: %s", who, e); return FAV_ERR_INVALID_ARG; }
+    if (!images || (!hs.rec && !hs.true_scores) || (hs.true_scores && !hs.true_labels) || ((uintptr_t)hs.rec & 7)) {
+        h->err = fmt("%s: null or misaligned buffer", who);
+        return FAV_ERR_INVALID_ARG;
+    }
+    if (n < 1 || n > h->cfg.max_batch) { h->err = fmt("%s: n=%d outside [1, max_batch=%d]", who, n, h->cfg.max_batch); return FAV_ERR_INVALID_ARG; }
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) { h->err = fmt("%s: unknown layout", who); return FAV_ERR_INVALID_ARG; }
+    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) { h->err = fmt("%s: first_image_index out of range", who); return FAV_ERR_INVALID_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_last_use(h, s)) return st;
+    const fav_status st = classify_on_stream(h, images, n, layout, first_index, nullptr, nullptr, fail, score, s, 1, nullptr, &hs);
+    mark_last_use(h, s);
+    return st;
+}
+}  // namespace
+
+fav_status fav_classify_sets(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
+                             const fav_conformal* cp, fav_pred_set* records, uint8_t* fail, float* score, void* stream) {
+    static_assert(sizeof(fav_pred_set) == 160, "fav_pred_set is 40 dwords");
+    static_assert(sizeof(fav_conformal) == 32, "fav_conformal is 32 bytes");
+    const HeadSets hs{cp, first_index, nullptr, nullptr, records};
+    return classify_sets_common("fav_classify_sets", h, images, n, layout, first_index, hs, fail, score, stream);
+}
+
+fav_status fav_conformal_scores(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
+                                const fav_conformal* cp, const int32_t* labels, float* scores, void* stream) {
+    const HeadSets hs{cp, first_index, labels, scores, nullptr};
+    return classify_sets_common("fav_conformal_scores", h, images, n, layout, first_index, hs, nullptr, nullptr, stream);
+}
+
+namespace {
 fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                               int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride,
-                              fav_uncertainty* rec) {
+                              fav_uncertainty* rec, const HeadSets* sets) {
     h->ev_used = h->profiling ? h->ev_used : 0;
     if (h->vit) {
         for (auto& L : h->layers) { L.w = L.w_m[0]; L.b = L.b_m[0]; }
@@ -2110,7 +2194,7 @@ fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int3
     if (!h->vit) h->phase_out.back() = h->logits;
     const int T_head = h->n_members > 1 ? h->n_members : h->T_eff;
     if (const char* e = launch_head(h, h->logits, T_head, n, h->cfg.num_classes, h->cpad, h->cfg.temperature,
-                                    h->cfg.conf_kind, h->cfg.tau, labels, conf, fail, score, s, out_stride, rec)) {
+                                    h->cfg.conf_kind, h->cfg.tau, labels, conf, fail, score, s, out_stride, rec, sets)) {
         h->err = e;
         return FAV_ERR_INVALID_ARG;
     }
@@ -2287,6 +2371,16 @@ fav_status fav_op_head_uncertainty(const float* logits, int32_t T, int32_t n, in
         return op_done("fav_op_head_uncertainty: bad argument (records non-NULL and 8-byte aligned, 1 <= T <= 4096, kind 0..2)");
     return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, nullptr, nullptr, fail, score,
                                (hipStream_t)stream, 1, records));
+}
+
+fav_status fav_op_head_sets(const float* logits, int32_t T, int32_t n, int32_t C, int32_t ld, float temperature, int32_t kind,
+                            float tau, int64_t first_index, const fav_conformal* cp, const int32_t* true_labels,
+                            float* true_scores, fav_pred_set* records, uint8_t* fail, float* score, void* stream) {
+    if (!logits || T < 1 || n < 1 || kind < 0 || kind > 2 || !(temperature > 0.f))
+        return op_done("fav_op_head_sets: bad argument (logits non-NULL, T >= 1, n >= 1, kind 0..2, temperature > 0)");
+    const HeadSets hs{cp, first_index, true_labels, true_scores, records};
+    return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, nullptr, nullptr, fail, score,
+                               (hipStream_t)stream, 1, nullptr, &hs));
 }
 
 fav_status fav_op_layernorm(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t rows, int32_t D,

@@ -3423,6 +3423,240 @@ __global__ __launch_bounds__(256) void head_unc_kernel(const float* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------
+// Conformal prediction-set head: head_unc_kernel's pbar, label and confidence (same
+// per-sample sequence, same wave-order combine, hence the same bits for kinds 0 / 1 / 2), then
+//   sort     the classes by pbar descending, lowest index first on ties: a bitonic sort of NV*256 64-bit keys
+//            (~float_bits(pbar) << 32) | class (pbar >= 0, so the bits order like the values; padding classes get
+//            all-ones high bits and sort last).  Thread q holds sorted positions 4q .. 4q+3; partners 1, 2 apart are in
+//            its registers, 4 .. 128 apart in its wave (shuffles), 256 / 512 apart (NV = 4 only) meet through LDS
+//   scan     A(r) = mass ahead of rank r, one running fp32 sum in rank order (A(0) = 0, A(r+1) = A(r) + pbar_(r))
+//   score    LAC: 1 - pbar[c];  APS / RAPS: fmaf(u, pbar[c], A(rank c)) + lambda * max(0, rank c + 1 - k_reg)
+//   member   s(c) <= qhat, per class; true_scores[img] = s(true_labels[img]) (NaN outside [0, C))
+// u: 1, or with randomized one Philox4x32-10 draw per frame, counter (0, global frame, 0, 0xC0F0), u = (x0 >> 8) 2^-24.
+// rec (may be NULL): one 40-dword record per frame, the layout of fav_pred_set in include/fav.h.
+// ---------------------------------------------------------------------------
+struct SetsParams {
+    int score_kind;         // 0: LAC, 1: APS / RAPS
+    int randomized;
+    int k_reg;
+    float lambda;
+    float qhat;
+    uint32_t seed_lo, seed_hi;
+    long long first_index;  // global index of frame 0 (the Philox counter)
+};
+
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
+    const int lo = __shfl_xor((int)(uint32_t)v, m, 64), hi = __shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+    return ((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void head_sets_kernel(const float* __restrict__ logits, int T, int n, int C, int ld,
+                                                        float inv_temp, int conf_kind, float tau, float inv_lnC, float inv_lnK,
+                                                        SetsParams cp, const int* __restrict__ true_labels,
+                                                        float* __restrict__ true_scores, int* __restrict__ rec,
+                                                        uint8_t* __restrict__ fail, float* __restrict__ score) {
+    static_assert(NV == 1 || NV == 4, "sort width 256 or 1024");
+    constexpr int N = NV * 256;             // sort width
+    // part: the four waves' pbar partials; after the combine, rows 0-1 carry the cross-wave sort exchange (NV = 4), row 2
+    // the sorted pbar.  ahead: the mass ahead A by rank (an array of its own, so the scan's loads can run ahead of its
+    // stores)
+    __shared__ __attribute__((aligned(16))) float part[4][N];
+    __shared__ __attribute__((aligned(16))) float ahead[N];
+    __shared__ float red_h[4], red_e[4], red_m[4];
+    __shared__ int out_rec[40];             // the record: 8 header dwords, then the 32 membership words
+    __shared__ int set_n;
+    const int img = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 32) out_rec[8 + tid] = 0;
+    if (tid == 0) set_n = 0;
+    float p[NV][4];
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[i][j] = 0.f;
+    float ent = 0.f;                        // sum of H(p_t) over this wave's samples, in sample order (conf_kind 2)
+    for (int t = wave; t < T; t += 4) {
+        const float* row = logits + ((long long)t * n + img) * ld;
+        float z[NV][4];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = 4 * lane + 256 * i;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[i][j] = -INFINITY;
+            if (c + 3 < C) {
+                const float4 v = *(const float4*)(row + c);
+                z[i][0] = v.x * inv_temp; z[i][1] = v.y * inv_temp; z[i][2] = v.z * inv_temp; z[i][3] = v.w * inv_temp;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c + j < C) z[i][j] = row[c + j] * inv_temp;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) mx = fmaxf(mx, z[i][j]);
+        }
+        mx = wave_max(mx);
+        float s = 0.f, sd = 0.f;            // sd = sum e * (z - mx): H(p_t) = ln s - sd / s
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float d = z[i][j] - mx;
+                z[i][j] = expf(d);  // exp(-inf) = 0 for padded classes
+                s += z[i][j];
+                sd += z[i][j] > 0.f ? z[i][j] * d : 0.f;
+            }
+        s = wave_sum(s);
+        const float inv = 1.0f / s;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p[i][j] += z[i][j] * inv;
+        if (conf_kind == 2) {
+            sd = wave_sum(sd);
+            ent += fmaxf(logf(s) - sd * inv, 0.f);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        *(float4*)&part[wave][4 * lane + 256 * i] = make_float4(p[i][0], p[i][1], p[i][2], p[i][3]);
+    if (lane == 0) red_e[wave] = ent;
+    __syncthreads();
+    // thread tid owns classes 4*tid .. 4*tid + 3 (threads tid >= NV*64 own none)
+    const float inv_T = 1.0f / (float)T;
+    float h = 0.f;
+    unsigned long long key[4];
+    if (tid < NV * 64) {
+        const float4 a = *(const float4*)&part[0][4 * tid], b = *(const float4*)&part[1][4 * tid];
+        const float4 c4 = *(const float4*)&part[2][4 * tid], d = *(const float4*)&part[3][4 * tid];
+        const float pb[4] = {(((a.x + b.x) + c4.x) + d.x) * inv_T, (((a.y + b.y) + c4.y) + d.y) * inv_T,
+                             (((a.z + b.z) + c4.z) + d.z) * inv_T, (((a.w + b.w) + c4.w) + d.w) * inv_T};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int cls = 4 * tid + j;
+            if (cls < C && pb[j] > 0.f) h -= pb[j] * logf(pb[j]);
+            key[j] = ((unsigned long long)(cls < C ? ~__float_as_uint(pb[j]) : 0xFFFFFFFFu) << 32) | (uint32_t)cls;
+        }
+    }
+    h = wave_sum(h);
+    if (lane == 0) red_h[wave] = h;
+    // bitonic sort, ascending keys; element e = 4 * tid + j
+    if (NV == 4 || wave == 0) {
+        unsigned long long* kx = (unsigned long long*)&part[0][0];
+#pragma unroll
+        for (int lk = 1; lk <= (NV == 4 ? 10 : 8); ++lk) {          // affine loops: fully unrolled, every index constant
+#pragma unroll
+            for (int lj = lk - 1; lj >= 0; --lj) {
+                const int k = 1 << lk, jj = 1 << lj;
+                unsigned long long o[4];
+                if (jj >= 256) {
+                    __syncthreads();
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) kx[4 * tid + j] = key[j];
+                    __syncthreads();
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[j] = kx[(4 * tid + j) ^ jj];
+                } else if (jj >= 4) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[j] = shfl_xor_u64(key[j], jj >> 2);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[j] = key[j ^ jj];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int e = 4 * tid + j;
+                    const bool take_min = ((e & jj) == 0) == ((e & k) == 0);
+                    const bool lt = key[j] < o[j];
+                    key[j] = (take_min == lt) ? key[j] : o[j];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    float v[4];
+    int cl[4];
+    if (tid < NV * 64) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = __uint_as_float(~(uint32_t)(key[j] >> 32));     // padding: 0
+            cl[j] = (int)(uint32_t)key[j];
+        }
+        *(float4*)&part[2][4 * tid] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        // the mass ahead: one running sum in rank order (so A(r+1) >= fl(A(r) + u pbar_(r)) and every score is
+        // non-decreasing in rank)
+        float acc = 0.f;
+        const int nq = (C + 3) >> 2;
+#pragma unroll 8
+        for (int q4 = 0; q4 < nq; ++q4) {
+            const float4 x = *(const float4*)&part[2][4 * q4];
+            float4 a;
+            a.x = acc; acc += x.x;
+            a.y = acc; acc += x.y;
+            a.z = acc; acc += x.z;
+            a.w = acc; acc += x.w;
+            *(float4*)&ahead[4 * q4] = a;
+        }
+    }
+    float u = 1.f;
+    if (cp.randomized) {
+        const uint4 r = philox4x32_10(make_uint4(0u, (uint32_t)(cp.first_index + img), 0u, 0xC0F0u), cp.seed_lo, cp.seed_hi);
+        u = (float)(r.x >> 8) * 0x1p-24f;
+    }
+    __syncthreads();
+    const int y = true_labels ? true_labels[img] : -1;
+    float mass = 0.f;                       // pbar summed over this thread's members, in rank order
+    if (tid < NV * 64) {
+        int cnt = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = 4 * tid + j;
+            if (cl[j] < C) {
+                const float sc = cp.score_kind == 0 ? 1.0f - v[j]
+                                                    : fmaf(u, v[j], ahead[r]) + cp.lambda * (float)max(0, r + 1 - cp.k_reg);
+                if (sc <= cp.qhat) {
+                    atomicOr((uint32_t*)&out_rec[8 + (cl[j] >> 5)], 1u << (cl[j] & 31));
+                    mass += v[j];
+                    ++cnt;
+                }
+                if (cl[j] == y) true_scores[img] = sc;
+            }
+        }
+        if (cnt) atomicAdd(&set_n, cnt);
+    }
+    mass = wave_sum(mass);
+    if (lane == 0) red_m[wave] = mass;
+    __syncthreads();
+    if (tid == 0) {
+        const int bi = cl[0];               // sorted position 0: argmax pbar, lowest index on ties
+        const float bv = v[0];
+        float hh = red_h[0];
+        for (int w = 1; w < 4; ++w) hh += red_h[w];
+        // T = 1: pbar is p_0 bit for bit, so its entropy IS the expected entropy (and the mutual information exactly 0)
+        const float eh = T == 1 ? hh : (((red_e[0] + red_e[1]) + red_e[2]) + red_e[3]) * inv_T;
+        const float mi = fmaxf(hh - eh, 0.f);
+        const float cf = conf_kind == 0 ? bv : (conf_kind == 1 ? 1.0f - hh * inv_lnC : 1.0f - mi * inv_lnK);
+        if (fail) fail[img] = cf < tau ? 1 : 0;
+        if (score) score[img] = fminf(fmaxf(1.0f - cf, 0.f), 1.f);
+        if (true_labels && (y < 0 || y >= C)) true_scores[img] = __int_as_float(0x7fc00000);
+        out_rec[0] = bi;
+        out_rec[1] = __float_as_int(cf);
+        out_rec[2] = set_n;
+        out_rec[3] = __float_as_int(((red_m[0] + red_m[1]) + red_m[2]) + red_m[3]);
+        out_rec[4] = __float_as_int(cp.score_kind == 0 ? 0.f : u);
+        out_rec[5] = out_rec[6] = out_rec[7] = 0;
+    }
+    if (rec) {
+        __syncthreads();
+        if (tid < 20) *(int2*)(rec + (long long)img * 40 + 2 * tid) = make_int2(out_rec[2 * tid], out_rec[2 * tid + 1]);
+    }
+}
+
 }  // namespace fav
 
 // ===========================================================================

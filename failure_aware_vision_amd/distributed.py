@@ -31,7 +31,8 @@ def unpack_records(rec):
     return rec[:, 0].contiguous(), rec[:, 1].contiguous().view(torch.float32)
 
 
-def classify_sharded(classifier, local_frames, n_total: int, rank: int, world: int, group=None, detail: bool = False):
+def classify_sharded(classifier, local_frames, n_total: int, rank: int, world: int, group=None, detail: bool = False,
+                     sets=None):
     """Each rank classifies its own shard (global frame indices [start, stop)) and all ranks receive the full
     (labels[n_total], conf[n_total]).
 
@@ -50,7 +51,22 @@ def classify_sharded(classifier, local_frames, n_total: int, rank: int, world: i
     ``detail=True``: the same exchange with the 72-byte uncertainty records (include/fav.h fav_uncertainty) in place of the
     8-byte ones - ``Backend.classify_uncertainty`` writes them into this rank's slot of the send buffer - and the result is
     ``unpack_uncertainty`` of the gathered int32[n_total, 18] records (a dict of per-field views).  A plain function
-    ``fn(frames, first_index=...) -> int32[n, 18]`` records is accepted there too."""
+    ``fn(frames, first_index=...) -> int32[n, 18]`` records is accepted there too.
+
+    ``sets=cp`` (a ``conformal.Conformal``): the same exchange with the 160-byte prediction-set records (include/fav.h
+    fav_pred_set) - ``Backend.classify_sets`` writes them into this rank's slot - and the result is ``unpack_sets`` of the
+    gathered int32[n_total, 40] records.  A plain function ``fn(frames, first_index=...) -> int32[n, 40]`` records is
+    accepted there too.  The randomized draw is keyed by the global frame index, so the gathered sets are those of one
+    rank classifying every frame."""
+    if sets is not None:
+        from .conformal import PRED_SET_DWORDS, unpack_sets
+        num_classes = int(classifier.cfg.num_classes) if hasattr(classifier, "classify_sets") else 1024
+        method = None
+        if hasattr(classifier, "classify_sets"):
+            method = lambda frames, first_index=0, out=None: classifier.classify_sets(frames, sets, first_index=first_index,  # noqa: E731
+                                                                                    out=out)
+        return _gather_records(classifier, method, local_frames, n_total, rank, world, group, PRED_SET_DWORDS,
+                               lambda rec: unpack_sets(rec, num_classes))
     if detail:
         return _classify_sharded_detail(classifier, local_frames, n_total, rank, world, group)
     import torch
@@ -104,15 +120,24 @@ def classify_sharded(classifier, local_frames, n_total: int, rank: int, world: i
 
 def _classify_sharded_detail(classifier, local_frames, n_total: int, rank: int, world: int, group=None):
     """classify_sharded(..., detail=True): one all-gather of int32[cap, 18] uncertainty records per rank."""
+    from .backend import UNCERTAINTY_DWORDS, unpack_uncertainty
+    method = classifier.classify_uncertainty if hasattr(classifier, "classify_uncertainty") else None
+    return _gather_records(classifier, method, local_frames, n_total, rank, world, group, UNCERTAINTY_DWORDS,
+                           unpack_uncertainty)
+
+
+def _gather_records(classifier, method, local_frames, n_total: int, rank: int, world: int, group, W: int, unpack):
+    """One all-gather of int32[cap, W] records per rank.  ``method(frames, first_index=, out=)``: the Backend method that
+    writes the records into this rank's slot of the send buffer (None: ``classifier`` is a plain function returning
+    int32[n, W] records); ``unpack``: records -> the result dict."""
     import torch
     import torch.distributed as dist
-    from .backend import UNCERTAINTY_DWORDS as W, unpack_uncertainty
     start, stop = shard_range(n_total, rank, world)
     n_local = stop - start
     if n_local > 0 and int(local_frames.shape[0]) != n_local:
         raise ValueError(f"rank {rank} owns frames [{start},{stop}) but was handed {int(local_frames.shape[0])}")
     cap = -(-n_total // world)  # every shard padded to the largest
-    if hasattr(classifier, "classify_uncertainty"):
+    if method is not None:
         # a Backend: host frames (or frames on another device) are uploaded to its GPU first
         dev = torch.device(f"cuda:{classifier.device}")
         if isinstance(local_frames, np.ndarray):
@@ -121,7 +146,7 @@ def _classify_sharded_detail(classifier, local_frames, n_total: int, rank: int, 
         send = torch.empty((cap, W), dtype=torch.int32, device=dev) if n_local == cap else \
             torch.zeros((cap, W), dtype=torch.int32, device=dev)
         if n_local > 0:
-            classifier.classify_uncertainty(local_frames, first_index=start, out=send[:n_local])
+            method(local_frames, first_index=start, out=send[:n_local])
     else:
         if n_local > 0:
             rec = classifier(local_frames, first_index=start)
@@ -135,7 +160,7 @@ def _classify_sharded_detail(classifier, local_frames, n_total: int, rank: int, 
         send = torch.zeros((cap, W), dtype=torch.int32, device=dev)
         send[:n_local] = rec
     if world == 1:
-        return unpack_uncertainty(send[:n_local])
+        return unpack(send[:n_local])
     recv = torch.empty((world * cap, W), dtype=torch.int32, device=dev)
     if dist.get_backend(group) == "gloo" and send.is_cuda:
         # rehearsal only (several ranks sharing one GPU, where RCCL cannot run): the records cross the host
@@ -145,9 +170,9 @@ def _classify_sharded_detail(classifier, local_frames, n_total: int, rank: int, 
     else:
         dist.all_gather_into_tensor(recv, send, group=group)
     if n_total == world * cap:                 # equal shards: the receive buffer IS the result
-        return unpack_uncertainty(recv)
+        return unpack(recv)
     parts = []
     for r in range(world):
         s, e = shard_range(n_total, r, world)
         parts.append(recv[r * cap:r * cap + (e - s)])
-    return unpack_uncertainty(torch.cat(parts, dim=0))
+    return unpack(torch.cat(parts, dim=0))

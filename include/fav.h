@@ -164,6 +164,49 @@ fav_status fav_classify_uncertainty(fav_handle* h, const void* images_dev, int32
                                     int64_t first_image_index, fav_uncertainty* records_dev,
                                     uint8_t* fail_dev, float* score_dev, void* hip_stream);
 
+/* Split-conformal prediction sets.  From pbar exactly as fav_classify_ex computes it,
+ * the classes are ranked by pbar descending, lowest index first on ties (rank 0 = the label); A(c) is the mass ahead
+ * of class c, one fp32 running sum of pbar in rank order (A = 0 at rank 0).  Score of class c:
+ *   FAV_CP_LAC  s(c) = 1.0f - pbar[c]
+ *   FAV_CP_APS  s(c) = fmaf(u, pbar[c], A(c)) + lambda * (float)max(0, rank(c) + 1 - k_reg)
+ *               (lambda = 0: APS; lambda > 0: RAPS).  u = 1, or with randomized != 0 one draw per frame:
+ *               Philox4x32-10, key = seed, counter = (0, global frame index, 0, 0xC0F0), u = (x0 >> 8) * 2^-24.
+ * Class c is in the set iff s(c) <= qhat (qhat = +inf: every class; an empty set is legal).  The calibration score of
+ * a frame with true class y is s(y), the value the membership test compares; qhat comes from calibration
+ * (the ceil((n+1)(1-alpha))-th smallest score of n held-out frames).  The set then holds the true class with
+ * probability >= 1 - alpha on exchangeable frames.
+ * fav_conformal is rejected (FAV_ERR_INVALID_ARG) when struct_size != sizeof(fav_conformal), qhat is NaN, lambda is
+ * negative or not finite, k_reg < 0, or LAC is combined with randomized != 0 or lambda != 0. */
+typedef enum fav_cp_score { FAV_CP_LAC = 0, FAV_CP_APS = 1 } fav_cp_score;
+typedef struct fav_conformal {
+    uint32_t struct_size; int32_t score_kind; int32_t randomized; int32_t k_reg;
+    float lambda; float qhat; uint64_t seed;
+} fav_conformal;   /* 32 bytes */
+
+/* One frame's prediction set (160 bytes).
+ *   label / confidence  bit-identical to fav_classify_ex's (the handle's conf_kind)
+ *   set_size            number of classes in the set
+ *   set_mass            fp32 sum of pbar over the set (each thread's 4 ranks in order, wave butterfly, waves in order)
+ *   u                   the draw used: 1 when not randomized, 0 under FAV_CP_LAC
+ *   member              bit c % 32 of word c / 32 set: class c is in the set (bits of classes >= num_classes are 0) */
+typedef struct fav_pred_set {
+    int32_t label; float confidence; int32_t set_size; float set_mass;
+    float u; int32_t reserved[3];
+    uint32_t member[32];
+} fav_pred_set;   /* 160 bytes */
+
+/* Same schedule as fav_classify_ex; the head writes one fav_pred_set per frame to records_dev[n] (non-NULL, 8-byte
+ * aligned device pointer, e.g. a rank's slot of an all-gather buffer).  fail_dev / score_dev (conf < tau, as
+ * fav_classify_ex) may be NULL. */
+fav_status fav_classify_sets(fav_handle* h, const void* images_dev, int32_t n, int32_t layout,
+                             int64_t first_image_index, const fav_conformal* cp, fav_pred_set* records_dev,
+                             uint8_t* fail_dev, float* score_dev, void* hip_stream);
+/* Calibration: scores_dev[i] = s(labels_dev[i]) for frame i under cp (cp->qhat is not used and may be +inf);
+ * NaN where the label lies outside [0, num_classes). */
+fav_status fav_conformal_scores(fav_handle* h, const void* images_dev, int32_t n, int32_t layout,
+                                int64_t first_image_index, const fav_conformal* cp, const int32_t* labels_dev,
+                                float* scores_dev, void* hip_stream);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -273,6 +316,15 @@ fav_status fav_op_head(const float* logits, int32_t T, int32_t n, int32_t num_cl
 fav_status fav_op_head_uncertainty(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld,
                                    float temperature, int32_t conf_kind, float tau, fav_uncertainty* records,
                                    uint8_t* fail, float* score, void* hip_stream);
+
+/* logits fp32 [T][n][ld] -> the prediction sets of fav_classify_sets under cp.  records (8-byte aligned) may be NULL
+ * when true_labels is given; true_labels / true_scores (both or neither): the calibration scores of
+ * fav_conformal_scores.  fail / score may be NULL.  num_classes <= 1024; conf_kind 0, 1 or 2; first_image_index is
+ * the global index of frame 0 (the Philox counter of a randomized cp). */
+fav_status fav_op_head_sets(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld,
+                            float temperature, int32_t conf_kind, float tau, int64_t first_image_index,
+                            const fav_conformal* cp, const int32_t* true_labels, float* true_scores,
+                            fav_pred_set* records, uint8_t* fail, float* score, void* hip_stream);
 
 /* ---- ViT building blocks (BASELINE configs[4]); linear layers go through fav_op_conv2d with kh = kw = 1.
  * LayerNorm over rows of D bf16 values (row r at x + r*ldx elements; D % 4 == 0, D <= 1024), fp32 statistics,
