@@ -13,6 +13,8 @@ from oracle import fav_oracle as O
 
 torch = pytest.importorskip("torch")
 F = torch.nn.functional
+import vit_ref  # noqa: E402
+from vit_ref import torch_vit_logits  # noqa: E402
 
 
 def test_exact_exp_and_gelu_are_accurate():
@@ -40,30 +42,6 @@ def test_layernorm_and_softmax_vs_torch():
     assert np.abs(p - torch.softmax(torch.from_numpy(s).double() / 8, -1).numpy()).max() < 3e-6
 
 
-def torch_vit_logits(model, xn):
-    """fp64 torch restatement of the same encoder (no bf16 rounding): what the oracle approximates."""
-    c, Ls = O.VIT_CFG[model.arch], model.layers
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).double()
-    b, hh, ww, _ = xn.shape
-    p, d, heads = c["patch"], c["dim"], c["heads"]
-    x = F.conv2d(t(xn).permute(0, 3, 1, 2), t(Ls[0].w).permute(0, 3, 1, 2), t(Ls[0].b), stride=p)    # [b, d, gh, gw]
-    x = x.flatten(2).transpose(1, 2)
-    pos = t(Ls[1].w).reshape(-1, d)
-    x = torch.cat([pos[:1].expand(b, 1, d), x + pos[1:]], 1)
-    li = 2
-    for _ in range(c["depth"]):
-        ln1, qkv, proj, ln2, fc1, fc2 = Ls[li:li + 6]
-        li += 6
-        y = F.layer_norm(x, (d,), t(ln1.w), t(ln1.b), 1e-6)
-        q, k, v = F.linear(y, t(qkv.w).reshape(3 * d, d), t(qkv.b)).reshape(b, -1, 3, heads, 64).permute(2, 0, 3, 1, 4)
-        a = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(b, -1, d)
-        x = x + F.linear(a, t(proj.w).reshape(d, d), t(proj.b))
-        y = F.layer_norm(x, (d,), t(ln2.w), t(ln2.b), 1e-6)
-        x = x + F.linear(F.gelu(F.linear(y, t(fc1.w).reshape(-1, d), t(fc1.b))), t(fc2.w).reshape(d, -1), t(fc2.b))
-    y = F.layer_norm(x[:, 0], (d,), t(Ls[li].w), t(Ls[li].b), 1e-6)
-    return F.linear(y, t(Ls[li + 1].w).reshape(-1, d), t(Ls[li + 1].b)).numpy()
-
-
 @pytest.mark.parametrize("exact", [False, True, "mfma"])
 def test_vit_tiny_oracle_vs_torch(exact):
     blob, info = weights.make_synthetic_vit("vit_tiny", seed=3)
@@ -81,6 +59,28 @@ def test_vit_tiny_oracle_vs_torch(exact):
     assert np.array_equal(labels[clear], pr.argmax(1)[clear])
     ent = 1.0 + (pr * np.log(np.maximum(pr, 1e-300))).sum(1) / np.log(pr.shape[1])
     assert np.abs(conf - ent).max() < 0.02
+
+
+def test_vit_b16_oracle_vs_float64():
+    """The production-mode oracle (= the device's bits, tests/test_gpu_vit.py) of the full ViT-B/16 - 12 layers, 768 wide, 12 heads -
+    at 64x64 (17 tokens) against the float64 restatement of tests/vit_ref.py, on clean and Gaussian-corrupted frames.  Measured:
+    rel. RMS 0.0080 of the logits' spread, max abs 0.16 (spread ~5), entropy confidence within 0.0061; the bounds are ~2.5x that."""
+    blob, _ = weights.make_synthetic_vit("vit_b16", seed=1, in_hw=(64, 64))
+    u8 = synth.synthetic_frames_u8(4, 64, 64, seed=21)
+    frames = np.concatenate([u8.astype(np.float32) / np.float32(255.0), synth.gaussian_noise_f32(u8, 3, seed=3)])
+    cfg = O.ClassifyConfig(exact="mfma", temperature=1.5, conf_kind=O.CONF_ENTROPY)
+    labels, conf, lg, _ = O.classify(O.parse_blob(blob), frames, cfg, return_logits=True)
+    ref = vit_ref.classify(blob, frames)
+    err = lg[0].astype(np.float64) - ref
+    assert np.sqrt(np.mean(err ** 2)) < 0.02 * ref.std()
+    assert np.abs(err).max() < 0.4
+    hd = vit_ref.head(ref, 1.5)
+    clear = hd["gap"] > 0.01
+    assert clear.sum() >= 6
+    assert np.array_equal(labels[clear], hd["label"][clear])
+    assert np.abs(conf - hd["confidence"]).max() < 0.015
+    # negative control: the same confidences are far from what temperature 1.0 would give
+    assert np.abs(conf - vit_ref.head(ref, 1.0)["confidence"]).max() > 0.015
 
 
 def test_vit_checkpoints_are_machine_independent():
