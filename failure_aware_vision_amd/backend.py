@@ -131,31 +131,54 @@ class Backend:
         if images.ndim != 4 or images.shape[1] != self.cfg.in_h or images.shape[2] != self.cfg.in_w or images.shape[3] != 3:
             raise ValueError(f"expected frames of shape (n, {self.cfg.in_h}, {self.cfg.in_w}, 3), got {tuple(images.shape)}")
 
+    def _frames_on_device(self, images, refuse_host: str | None = None):
+        """-> (frames on this Backend's GPU, True when they came from the host).  refuse_host: the message with which
+        host frames are refused like frames on another device."""
+        if isinstance(images, np.ndarray) and refuse_host is None:
+            return self._torch.from_numpy(np.ascontiguousarray(images)).to(f"cuda:{self.device}"), True
+        if isinstance(images, np.ndarray) or not images.is_cuda or images.device.index != self.device:
+            raise ValueError(refuse_host or f"frames must live on cuda:{self.device}")
+        return images.contiguous(), False
+
+    def _classify_args(self, images, keep_host: bool = False, refuse_host: str | None = None):
+        """The prelude of every classify method -> (frames, from the host?, n, layout, stream).  The frames are on this
+        Backend's GPU and the stream is its current one, except with keep_host, where host frames stay a contiguous numpy
+        array and the stream is None."""
+        self._check_shape(images)
+        layout = self._layout_of(images)
+        n = int(images.shape[0])
+        if keep_host and isinstance(images, np.ndarray):
+            return np.ascontiguousarray(images), True, n, layout, None
+        img, host = self._frames_on_device(images, refuse_host)
+        return img, host, n, layout, self._torch.cuda.current_stream(img.device).cuda_stream
+
+    def _records_out(self, out, n: int, width: int, dev):
+        """-> ``out``, or a new buffer when it is None: a contiguous int32[n, width] tensor on the frames' device."""
+        torch = self._torch
+        if out is None:
+            return torch.empty((n, width), dtype=torch.int32, device=dev)
+        if out.dtype != torch.int32 or tuple(out.shape) != (n, width) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32[n, {width}] tensor on the frames' device")
+        return out
+
     def classify_detect(self, images, first_index: int = 0):
         """-> (labels int32[n], confidences fp32[n], fail uint8[n], anomaly_score fp32[n]).
         torch CUDA tensors in -> torch CUDA tensors out (asynchronous on the current
         stream); numpy in -> numpy out (synchronous)."""
         torch = self._torch
-        self._check_shape(images)
-        layout = self._layout_of(images)
-        n = int(images.shape[0])
-        if isinstance(images, np.ndarray):
-            img = np.ascontiguousarray(images)
+        img, host, n, layout, stream = self._classify_args(images, keep_host=True)
+        if host:
             labels = np.empty(n, np.int32); conf = np.empty(n, np.float32)
             fail = np.empty(n, np.uint8); score = np.empty(n, np.float32)
             _lib.check(self.lib.fav_classify_host(self._h, img.ctypes.data, n, layout, int(first_index),
                                                   labels.ctypes.data, conf.ctypes.data, fail.ctypes.data,
                                                   score.ctypes.data), self._h)
             return labels, conf, fail, score
-        if not images.is_cuda or images.device.index != self.device:
-            raise ValueError(f"frames must live on cuda:{self.device}")
-        img = images.contiguous()
         dev = img.device
         labels = torch.empty(n, dtype=torch.int32, device=dev)
         conf = torch.empty(n, dtype=torch.float32, device=dev)
         fail = torch.empty(n, dtype=torch.uint8, device=dev)
         score = torch.empty(n, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(self.lib.fav_classify_ex(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
                                             conf.data_ptr(), fail.data_ptr(), score.data_ptr(), stream), self._h)
         return labels, conf, fail, score
@@ -164,18 +187,8 @@ class Backend:
         """frames (CUDA tensor) -> int32[n, 2] CUDA tensor of packed (label, confidence bits) records, written by the
         confidence head itself (fav_classify_records).  ``out``: a contiguous int32[n, 2] view to write into - e.g. this
         rank's slot of an all-gather send buffer (distributed.classify_sharded), so nothing is packed or copied."""
-        torch = self._torch
-        self._check_shape(images)
-        layout = self._layout_of(images)
-        n = int(images.shape[0])
-        if isinstance(images, np.ndarray) or not images.is_cuda or images.device.index != self.device:
-            raise ValueError(f"classify_records takes frames on cuda:{self.device}")
-        img = images.contiguous()
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.int32, device=img.device)
-        if out.dtype != torch.int32 or tuple(out.shape) != (n, 2) or not out.is_contiguous() or out.device != img.device:
-            raise ValueError("out must be a contiguous int32[n, 2] tensor on the frames' device")
-        stream = torch.cuda.current_stream(img.device).cuda_stream
+        img, _, n, layout, stream = self._classify_args(images, refuse_host=f"classify_records takes frames on cuda:{self.device}")
+        out = self._records_out(out, n, 2, img.device)
         _lib.check(self.lib.fav_classify_records(self._h, img.data_ptr(), n, layout, int(first_index), out.data_ptr(),
                                                  None, None, stream), self._h)
         return out
@@ -189,57 +202,31 @@ class Backend:
         are uploaded, the call is synchronous).  ``out``: a contiguous int32[n, 18] tensor on the frames' device to write
         the records into (e.g. this rank's slot of an all-gather send buffer)."""
         torch = self._torch
-        self._check_shape(images)
-        layout = self._layout_of(images)
-        n = int(images.shape[0])
-        host = isinstance(images, np.ndarray)
-        if host:
-            img = torch.from_numpy(np.ascontiguousarray(images)).to(f"cuda:{self.device}")
-        else:
-            if not images.is_cuda or images.device.index != self.device:
-                raise ValueError(f"frames must live on cuda:{self.device}")
-            img = images.contiguous()
+        img, host, n, layout, stream = self._classify_args(images)
         dev = img.device
-        if out is None:
-            out = torch.empty((n, UNCERTAINTY_DWORDS), dtype=torch.int32, device=dev)
-        if out.dtype != torch.int32 or tuple(out.shape) != (n, UNCERTAINTY_DWORDS) or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32[n, {UNCERTAINTY_DWORDS}] tensor on the frames' device")
+        out = self._records_out(out, n, UNCERTAINTY_DWORDS, dev)
         fail = torch.empty(n, dtype=torch.uint8, device=dev)
         score = torch.empty(n, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(self.lib.fav_classify_uncertainty(self._h, img.data_ptr(), n, layout, int(first_index), out.data_ptr(),
                                                      fail.data_ptr(), score.data_ptr(), stream), self._h)
         if host:
-            rec, fail, score = out.cpu().numpy(), fail.cpu().numpy(), score.cpu().numpy()   # synchronises the stream
-            return dict(unpack_uncertainty(rec), fail=fail, score=score)
+            out, fail, score = out.cpu().numpy(), fail.cpu().numpy(), score.cpu().numpy()   # synchronises the stream
         return dict(unpack_uncertainty(out), fail=fail, score=score)
 
     # -- conformal prediction sets (conformal.py; include/fav.h fav_classify_sets) ---------------------------------------
-    def _frames_on_device(self, images):
-        """-> (frames on this Backend's GPU, True when they came from the host)."""
-        if isinstance(images, np.ndarray):
-            return self._torch.from_numpy(np.ascontiguousarray(images)).to(f"cuda:{self.device}"), True
-        if not images.is_cuda or images.device.index != self.device:
-            raise ValueError(f"frames must live on cuda:{self.device}")
-        return images.contiguous(), False
-
     def conformal_scores(self, images, labels, cp, first_index: int = 0):
         """Calibration scores s(y) of the true classes ``labels`` (int[n]) under ``cp`` (a ``conformal.Conformal``; its qhat
         is not used), fp32[n], NaN where a label lies outside [0, num_classes).  Frame i has global index first_index + i
         (the key of a randomized score's draw); batches of max_batch frames.  torch CUDA frames in -> CUDA tensor out,
         asynchronous on the current stream; numpy in -> numpy out, synchronous."""
         torch = self._torch
-        self._check_shape(images)
-        layout = self._layout_of(images)
-        n = int(images.shape[0])
+        img, host, n, layout, stream = self._classify_args(images)
         if int(np.shape(labels)[0] if isinstance(labels, np.ndarray) else labels.shape[0]) != n:
             raise ValueError("one label per frame")
-        img, host = self._frames_on_device(images)
         dev = img.device
         lab = (torch.from_numpy(np.asarray(labels)) if isinstance(labels, np.ndarray) else labels).to(dev, torch.int32).contiguous()
         out = torch.empty(n, dtype=torch.float32, device=dev)
         c = cp.to_c()
-        stream = torch.cuda.current_stream(dev).cuda_stream
         mb = int(self.cfg.max_batch)
         for b in range(0, n, mb):
             e = min(n, b + mb)
@@ -268,21 +255,14 @@ class Backend:
         failure flag).  torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy
         out, synchronous.  ``out``: a contiguous int32[n, 40] tensor on the frames' device to write the records into
         (e.g. this rank's slot of an all-gather send buffer)."""
-        from .conformal import PRED_SET_DWORDS as W, unpack_sets
+        from .conformal import PRED_SET_DWORDS, unpack_sets
         torch = self._torch
-        self._check_shape(images)
-        layout = self._layout_of(images)
-        n = int(images.shape[0])
-        img, host = self._frames_on_device(images)
+        img, host, n, layout, stream = self._classify_args(images)
         dev = img.device
-        if out is None:
-            out = torch.empty((n, W), dtype=torch.int32, device=dev)
-        if out.dtype != torch.int32 or tuple(out.shape) != (n, W) or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32[n, {W}] tensor on the frames' device")
+        out = self._records_out(out, n, PRED_SET_DWORDS, dev)
         fail = torch.empty(n, dtype=torch.uint8, device=dev)
         score = torch.empty(n, dtype=torch.float32, device=dev)
         c = cp.to_c()
-        stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(self.lib.fav_classify_sets(self._h, img.data_ptr(), n, layout, int(first_index), C.byref(c),
                                               out.data_ptr(), fail.data_ptr(), score.data_ptr(), stream), self._h)
         if host:

@@ -859,14 +859,24 @@ const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C,
     if (ld % 4 != 0 || ld < C) return "head: bad row stride";
     const float inv_temp = 1.0f / temperature;
     const float inv_lnC = C > 1 ? (float)(1.0 / std::log((double)C)) : 0.f;
+    const int K = std::min(C, T);           // largest mutual information of T samples over C classes: ln K
+    const float inv_lnK = K > 1 ? (float)(1.0 / std::log((double)K)) : 0.f;
+    // one block per frame; the instantiation by the class count (NV = 1: up to 256 classes, 4: up to 1024)
+#define FAV_LAUNCH_HEAD(KERNEL, LDS, ...)                                                                                   \
+    do {                                                                                                                    \
+        if (C <= 256)                                                                                                       \
+            hipLaunchKernelGGL((KERNEL<1>), dim3(n), dim3(256), LDS, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,  \
+                               __VA_ARGS__);                                                                                \
+        else                                                                                                                \
+            hipLaunchKernelGGL((KERNEL<4>), dim3(n), dim3(256), LDS, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,  \
+                               __VA_ARGS__);                                                                                \
+    } while (0)
     if (sets) {
         if (const char* e = check_conformal(sets->cp)) return e;
         if (!sets->rec && !sets->true_labels) return "head: the sets head needs records or calibration labels";
         if (!sets->true_labels != !sets->true_scores) return "head: true_labels and true_scores go together";
         if ((uintptr_t)sets->rec & 7) return "head: prediction-set records must be 8-byte aligned";
         if (sets->first_index < 0 || sets->first_index + n > 0xFFFFFFFFll) return "head: first_image_index out of range";
-        const int K = std::min(C, T);
-        const float inv_lnK = K > 1 ? (float)(1.0 / std::log((double)K)) : 0.f;
         SetsParams p;
         p.score_kind = sets->cp->score_kind; p.randomized = sets->cp->randomized; p.k_reg = sets->cp->k_reg;
         p.lambda = sets->cp->lambda; p.qhat = sets->cp->qhat;
@@ -875,36 +885,18 @@ const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C,
         // bytes: the logits, the labels and scores of a calibration call, the outputs
         Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + (sets->true_labels ? 8.0 : 0.0) * n +
                                        (sets->rec ? 160.0 : 0.0) * n + (fail ? 1.0 : 0.0) * n + (score ? 4.0 : 0.0) * n);
-        if (C <= 256)
-            hipLaunchKernelGGL((head_sets_kernel<1>), dim3(n), dim3(256), 0, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
-                               inv_lnK, p, sets->true_labels, sets->true_scores, (int*)sets->rec, fail, score);
-        else
-            hipLaunchKernelGGL((head_sets_kernel<4>), dim3(n), dim3(256), 0, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
-                               inv_lnK, p, sets->true_labels, sets->true_scores, (int*)sets->rec, fail, score);
-        return nullptr;
-    }
-    if (rec || kind == FAV_CONF_MUTUAL_INFO) {
+        FAV_LAUNCH_HEAD(head_sets_kernel, 0, inv_lnK, p, sets->true_labels, sets->true_scores, (int*)sets->rec, fail, score);
+    } else if (rec || kind == FAV_CONF_MUTUAL_INFO) {
         if (T < 1 || T > 4096) return "head: the uncertainty head takes 1 <= T <= 4096 samples";
-        const int K = std::min(C, T);       // largest mutual information of T samples over C classes: ln K
-        const float inv_lnK = K > 1 ? (float)(1.0 / std::log((double)K)) : 0.f;
         // bytes: the logits, the second pass's p_t[label] reloads, the outputs
         Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 4.0 * (double)T * n + (rec ? 72.0 : 8.0) * n);
-        const size_t lds = (size_t)T * 8;   // per-sample max and 1/sum
-        if (C <= 256)
-            hipLaunchKernelGGL((head_unc_kernel<1>), dim3(n), dim3(256), lds, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
-                               inv_lnK, labels, conf, fail, score, out_stride, (int*)rec);
-        else
-            hipLaunchKernelGGL((head_unc_kernel<4>), dim3(n), dim3(256), lds, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
-                               inv_lnK, labels, conf, fail, score, out_stride, (int*)rec);
-        return nullptr;
+        // dynamic LDS: per-sample max and 1/sum
+        FAV_LAUNCH_HEAD(head_unc_kernel, (size_t)T * 8, inv_lnK, labels, conf, fail, score, out_stride, (int*)rec);
+    } else {
+        Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 8.0 * n);
+        FAV_LAUNCH_HEAD(head_kernel, 0, labels, conf, fail, score, out_stride);
     }
-    Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 8.0 * n);
-    if (C <= 256)
-        hipLaunchKernelGGL((head_kernel<1>), dim3(n), dim3(256), 0, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
-                           labels, conf, fail, score, out_stride);
-    else
-        hipLaunchKernelGGL((head_kernel<4>), dim3(n), dim3(256), 0, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,
-                           labels, conf, fail, score, out_stride);
+#undef FAV_LAUNCH_HEAD
     return nullptr;
 }
 
@@ -1992,92 +1984,66 @@ void mark_last_use(fav_handle* h, hipStream_t s) {
 fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                               int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride,
                               fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr);
-}  // namespace
 
-fav_status fav_classify_ex(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
-                           int32_t* labels, float* conf, uint8_t* fail, float* score, void* stream) {
-    if (!h) return FAV_ERR_INVALID_ARG;
-    if (!h->weights_loaded) { h->err = "fav_classify: no weights loaded"; return FAV_ERR_NO_WEIGHTS; }
-    if (!images || !labels || !conf) { h->err = "fav_classify: null buffer"; return FAV_ERR_INVALID_ARG; }
-    if (n < 1 || n > h->cfg.max_batch) { h->err = fmt("fav_classify: n=%d outside [1, max_batch=%d]", n, h->cfg.max_batch); return FAV_ERR_INVALID_ARG; }
-    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) { h->err = "fav_classify: unknown layout"; return FAV_ERR_INVALID_ARG; }
-    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) { h->err = "fav_classify: first_image_index out of range"; return FAV_ERR_INVALID_ARG; }
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (fav_status st = wait_last_use(h, s)) return st;
-    const fav_status st = classify_on_stream(h, images, n, layout, first_index, labels, conf, fail, score, s, 1);
-    mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
-    return st;
-}
-
-fav_status fav_classify_records(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
-                                void* records, uint8_t* fail, float* score, void* stream) {
-    if (!h) return FAV_ERR_INVALID_ARG;
-    if (!h->weights_loaded) { h->err = "fav_classify_records: no weights loaded"; return FAV_ERR_NO_WEIGHTS; }
-    if (!images || !records || ((uintptr_t)records & 7)) { h->err = "fav_classify_records: null or misaligned buffer"; return FAV_ERR_INVALID_ARG; }
-    if (n < 1 || n > h->cfg.max_batch) { h->err = fmt("fav_classify_records: n=%d outside [1, max_batch=%d]", n, h->cfg.max_batch); return FAV_ERR_INVALID_ARG; }
-    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) { h->err = "fav_classify_records: unknown layout"; return FAV_ERR_INVALID_ARG; }
-    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) { h->err = "fav_classify_records: first_image_index out of range"; return FAV_ERR_INVALID_ARG; }
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (fav_status st = wait_last_use(h, s)) return st;
-    const fav_status st = classify_on_stream(h, images, n, layout, first_index, (int32_t*)records, (float*)records + 1, fail, score, s, 2);
-    mark_last_use(h, s);
-    return st;
-}
-
-fav_status fav_classify_uncertainty(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
-                                    fav_uncertainty* records, uint8_t* fail, float* score, void* stream) {
-    static_assert(sizeof(fav_uncertainty) == 72, "fav_uncertainty is 18 dwords");
-    if (!h) return FAV_ERR_INVALID_ARG;
-    if (!h->weights_loaded) { h->err = "fav_classify_uncertainty: no weights loaded"; return FAV_ERR_NO_WEIGHTS; }
-    if (!images || !records || ((uintptr_t)records & 7)) { h->err = "fav_classify_uncertainty: null or misaligned buffer"; return FAV_ERR_INVALID_ARG; }
-    if (n < 1 || n > h->cfg.max_batch) { h->err = fmt("fav_classify_uncertainty: n=%d outside [1, max_batch=%d]", n, h->cfg.max_batch); return FAV_ERR_INVALID_ARG; }
-    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) { h->err = "fav_classify_uncertainty: unknown layout"; return FAV_ERR_INVALID_ARG; }
-    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) { h->err = "fav_classify_uncertainty: first_image_index out of range"; return FAV_ERR_INVALID_ARG; }
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (fav_status st = wait_last_use(h, s)) return st;
-    const fav_status st = classify_on_stream(h, images, n, layout, first_index, nullptr, nullptr, fail, score, s, 1, records);
-    mark_last_use(h, s);
-    return st;
-}
-
-namespace {
-// the argument checks of fav_classify_sets / fav_conformal_scores, then the fav_classify_ex schedule with the sets head
-fav_status classify_sets_common(const char* who, fav_handle* h, const void* images, int32_t n, int32_t layout,
-                                int64_t first_index, const HeadSets& hs, uint8_t* fail, float* score, void* stream) {
+// The gate of every classify entry point: the argument checks, then classify_on_stream behind the previous user of the
+// handle's buffers.  who: the public name the messages carry; bad: the entry point's own complaint about its buffers and
+// parameters (NULL: none), reported after the handle and weights checks and before those on n, layout and first_index.
+fav_status classify_gate(const char* who, fav_handle* h, const char* bad, const void* images, int32_t n, int32_t layout,
+                         int64_t first_index, int32_t* labels, float* conf, uint8_t* fail, float* score, void* stream,
+                         int out_stride, fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr) {
     if (!h) return FAV_ERR_INVALID_ARG;
     if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", who); return FAV_ERR_NO_WEIGHTS; }
-    if (const char* e = check_conformal(hs.cp)) { h->err = fmt("%s: %s", who, e); return FAV_ERR_INVALID_ARG; }
-    if (!images || (!hs.rec && !hs.true_scores) || (hs.true_scores && !hs.true_labels) || ((uintptr_t)hs.rec & 7)) {
-        h->err = fmt("%s: null or misaligned buffer", who);
-        return FAV_ERR_INVALID_ARG;
-    }
+    if (bad) { h->err = fmt("%s: %s", who, bad); return FAV_ERR_INVALID_ARG; }
     if (n < 1 || n > h->cfg.max_batch) { h->err = fmt("%s: n=%d outside [1, max_batch=%d]", who, n, h->cfg.max_batch); return FAV_ERR_INVALID_ARG; }
     if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) { h->err = fmt("%s: unknown layout", who); return FAV_ERR_INVALID_ARG; }
     if (first_index < 0 || first_index + n > 0xFFFFFFFFll) { h->err = fmt("%s: first_image_index out of range", who); return FAV_ERR_INVALID_ARG; }
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (fav_status st = wait_last_use(h, s)) return st;
-    const fav_status st = classify_on_stream(h, images, n, layout, first_index, nullptr, nullptr, fail, score, s, 1, nullptr, &hs);
-    mark_last_use(h, s);
+    const fav_status st = classify_on_stream(h, images, n, layout, first_index, labels, conf, fail, score, s, out_stride, rec, sets);
+    mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
     return st;
 }
+const char* const kBadRecords = "null or misaligned buffer";
+const char* bad_sets_args(const void* images, const HeadSets& hs) {
+    if (const char* e = check_conformal(hs.cp)) return e;
+    return !images || (!hs.rec && !hs.true_scores) || (hs.true_scores && !hs.true_labels) || ((uintptr_t)hs.rec & 7) ? kBadRecords : nullptr;
+}
 }  // namespace
+
+fav_status fav_classify_ex(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
+                           int32_t* labels, float* conf, uint8_t* fail, float* score, void* stream) {
+    return classify_gate("fav_classify", h, !images || !labels || !conf ? "null buffer" : nullptr, images, n, layout, first_index,
+                         labels, conf, fail, score, stream, 1);
+}
+
+fav_status fav_classify_records(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
+                                void* records, uint8_t* fail, float* score, void* stream) {
+    return classify_gate("fav_classify_records", h, !images || !records || ((uintptr_t)records & 7) ? kBadRecords : nullptr, images, n,
+                         layout, first_index, (int32_t*)records, (float*)records + 1, fail, score, stream, 2);
+}
+
+fav_status fav_classify_uncertainty(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
+                                    fav_uncertainty* records, uint8_t* fail, float* score, void* stream) {
+    static_assert(sizeof(fav_uncertainty) == 72, "fav_uncertainty is 18 dwords");
+    return classify_gate("fav_classify_uncertainty", h, !images || !records || ((uintptr_t)records & 7) ? kBadRecords : nullptr, images,
+                         n, layout, first_index, nullptr, nullptr, fail, score, stream, 1, records);
+}
 
 fav_status fav_classify_sets(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                              const fav_conformal* cp, fav_pred_set* records, uint8_t* fail, float* score, void* stream) {
     static_assert(sizeof(fav_pred_set) == 160, "fav_pred_set is 40 dwords");
     static_assert(sizeof(fav_conformal) == 32, "fav_conformal is 32 bytes");
     const HeadSets hs{cp, first_index, nullptr, nullptr, records};
-    return classify_sets_common("fav_classify_sets", h, images, n, layout, first_index, hs, fail, score, stream);
+    return classify_gate("fav_classify_sets", h, bad_sets_args(images, hs), images, n, layout, first_index, nullptr, nullptr, fail,
+                         score, stream, 1, nullptr, &hs);
 }
 
 fav_status fav_conformal_scores(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                                 const fav_conformal* cp, const int32_t* labels, float* scores, void* stream) {
     const HeadSets hs{cp, first_index, labels, scores, nullptr};
-    return classify_sets_common("fav_conformal_scores", h, images, n, layout, first_index, hs, nullptr, nullptr, stream);
+    return classify_gate("fav_conformal_scores", h, bad_sets_args(images, hs), images, n, layout, first_index, nullptr, nullptr,
+                         nullptr, nullptr, stream, 1, nullptr, &hs);
 }
 
 namespace {

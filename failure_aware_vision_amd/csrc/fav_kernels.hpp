@@ -3113,12 +3113,15 @@ __global__ __launch_bounds__(512, 4) void attention_kernel(const uint16_t* __res
 }
 
 // ---------------------------------------------------------------------------
-// Confidence head: logits [T][n][ld] fp32 -> pbar = mean_t softmax(z_t * inv_temp),
-// label = argmax (lowest index on ties), conf = max pbar or 1 - H(pbar)/ln C,
-// fail = conf < tau, score = clamp(1 - conf).
+// Confidence heads: logits [T][n][ld] fp32 -> pbar = mean_t softmax(z_t * inv_temp),
+// label = argmax (lowest index on ties), conf = max pbar, 1 - H(pbar)/ln C or
+// 1 - MI/ln min(C, T), fail = conf < tau, score = clamp(1 - conf).
 // One block (4 waves) per frame; wave w takes samples t = w, w+4, ...; a lane
 // owns classes {4*lane + 256*i + (0..3)} (coalesced float4 loads); all
 // reductions are wavefront shuffles, waves meet once through LDS.
+// head_kernel, head_unc_kernel and head_sets_kernel all compute pbar, label and
+// confidence with the head core below (head_load_row .. head_finish): one
+// sequence of fp32 operations, so the three give the same bits.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -3129,6 +3132,129 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+// arg-max that prefers the lowest index among equal values: across a wave, then over the four waves' winners in LDS
+__device__ __forceinline__ void argmax_take(float& best, int& besti, float ov, int oi) {
+    if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+}
+__device__ __forceinline__ void wave_argmax(float& best, int& besti) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) argmax_take(best, besti, __shfl_xor(best, o, 64), __shfl_xor(besti, o, 64));
+}
+__device__ __forceinline__ void argmax_of_waves(const float* rv, const int* ri, float& bv, int& bi) {
+    bv = rv[0]; bi = ri[0];
+    for (int w = 1; w < 4; ++w) argmax_take(bv, bi, rv[w], ri[w]);
+}
+__device__ __forceinline__ float sum_of_waves(const float* r) { return ((r[0] + r[1]) + r[2]) + r[3]; }
+
+// One sample's row -> this lane's z = logit * inv_temp (-inf past class C); returns the row's maximum.
+template <int NV>
+__device__ __forceinline__ float head_load_row(const float* row, int C, float inv_temp, int lane, float (&z)[NV][4]) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = 4 * lane + 256 * i;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[i][j] = -INFINITY;
+        if (c + 3 < C) {
+            const float4 v = *(const float4*)(row + c);
+            z[i][0] = v.x * inv_temp; z[i][1] = v.y * inv_temp; z[i][2] = v.z * inv_temp; z[i][3] = v.w * inv_temp;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c + j < C) z[i][j] = row[c + j] * inv_temp;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) mx = fmaxf(mx, z[i][j]);
+    }
+    return wave_max(mx);
+}
+
+// p += softmax(z) of one sample (z becomes exp(z - mx)).  ENT: sd = this lane's sum e * (z - mx), for head_sample_entropy.
+struct SoftmaxTerms { float s, inv, sd; };  // sum of exp over the row, its reciprocal, sd
+template <bool ENT, int NV>
+__device__ __forceinline__ SoftmaxTerms head_accumulate(float (&z)[NV][4], float mx, float (&p)[NV][4]) {
+    float s = 0.f, sd = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float d = z[i][j] - mx;
+            z[i][j] = expf(d);  // exp(-inf) = 0 for padded classes
+            s += z[i][j];
+            if (ENT) sd += z[i][j] > 0.f ? z[i][j] * d : 0.f;
+        }
+    s = wave_sum(s);
+    const float inv = 1.0f / s;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[i][j] += z[i][j] * inv;
+    return {s, inv, sd};
+}
+// H(p_t) = ln s - (sum e * (z - mx)) / s
+__device__ __forceinline__ float head_sample_entropy(const SoftmaxTerms& st) {
+    return fmaxf(logf(st.s) - wave_sum(st.sd) * st.inv, 0.f);
+}
+
+// The waves meet: their partial sums p go through part (one barrier), thread tid < NV*64 gets pb[0..3] = pbar of classes
+// 4*tid .. 4*tid+3 (0 past class C, the padding; -1 in threads that own no classes), and red_h[wave] the
+// wave's share of H(pbar).  part is free again once every thread has returned.
+template <int NV>
+__device__ __forceinline__ void head_combine(float (&part)[4][NV * 256], const float (&p)[NV][4], int tid, int C, float inv_T,
+                                             float (&pb)[4], float* red_h) {
+    static_assert(NV * 64 <= 256, "one float4 group of pbar per thread");
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        *(float4*)&part[wave][4 * lane + 256 * i] = make_float4(p[i][0], p[i][1], p[i][2], p[i][3]);
+    __syncthreads();
+    float h = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pb[j] = -1.f;
+    if (tid < NV * 64) {
+        const float4 a = *(const float4*)&part[0][4 * tid], b = *(const float4*)&part[1][4 * tid];
+        const float4 c4 = *(const float4*)&part[2][4 * tid], d = *(const float4*)&part[3][4 * tid];
+        pb[0] = (((a.x + b.x) + c4.x) + d.x) * inv_T; pb[1] = (((a.y + b.y) + c4.y) + d.y) * inv_T;
+        pb[2] = (((a.z + b.z) + c4.z) + d.z) * inv_T; pb[3] = (((a.w + b.w) + c4.w) + d.w) * inv_T;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * tid + j < C && pb[j] > 0.f) h -= pb[j] * logf(pb[j]);
+    }
+    h = wave_sum(h);
+    if (lane == 0) red_h[wave] = h;
+}
+// pb past class C -> -1, below every probability: never selected by an arg-max
+__device__ __forceinline__ void head_mask_classes(float (&pb)[4], int tid, int C) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (4 * tid + j >= C) pb[j] = -1.f;
+}
+// this thread's best of its four pbar (j ascending and a strict >: the lowest index wins)
+__device__ __forceinline__ void head_thread_argmax(const float (&pb)[4], int tid, float& best, int& besti) {
+    best = -1.f; besti = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (pb[j] > best) { best = pb[j]; besti = 4 * tid + j; }
+}
+
+// H(pbar), the expected entropy (1/T) sum_t H(p_t) from the waves' sums red_e, and their difference, the mutual information
+struct HeadEntropies { float hh, eh, mi; };
+__device__ __forceinline__ HeadEntropies head_entropies(const float* red_h, const float* red_e, int T, float inv_T) {
+    const float hh = sum_of_waves(red_h);
+    // T = 1: pbar is p_0 bit for bit, so its entropy IS the expected entropy (and the mutual information exactly 0)
+    const float eh = T == 1 ? hh : sum_of_waves(red_e) * inv_T;
+    return {hh, eh, fmaxf(hh - eh, 0.f)};
+}
+// The finish (one thread): confidence by conf_kind, fail and score (either may be NULL); returns the confidence.
+// MI = false (head_kernel, which is never launched with conf_kind 2) leaves mi and inv_lnK unused.
+template <bool MI>
+__device__ __forceinline__ float head_finish(int conf_kind, float bv, float hh, float inv_lnC, float mi, float inv_lnK, float tau,
+                                             int img, uint8_t* __restrict__ fail, float* __restrict__ score) {
+    const float cf = conf_kind == 0 ? bv : (!MI || conf_kind == 1 ? 1.0f - hh * inv_lnC : 1.0f - mi * inv_lnK);
+    if (fail) fail[img] = cf < tau ? 1 : 0;
+    if (score) score[img] = fminf(fmaxf(1.0f - cf, 0.f), 1.f);
+    return cf;
 }
 
 template <int NV>  // float4 groups per lane: supports num_classes <= 256 * NV
@@ -3144,97 +3270,32 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ log
     __shared__ float red_h[4];
     const int img = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float p[NV][4];
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) p[i][j] = 0.f;
+    float p[NV][4] = {};
     for (int t = wave; t < T; t += 4) {
-        const float* row = logits + ((long long)t * n + img) * ld;
         float z[NV][4];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = 4 * lane + 256 * i;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[i][j] = -INFINITY;
-            if (c + 3 < C) {
-                const float4 v = *(const float4*)(row + c);
-                z[i][0] = v.x * inv_temp; z[i][1] = v.y * inv_temp; z[i][2] = v.z * inv_temp; z[i][3] = v.w * inv_temp;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (c + j < C) z[i][j] = row[c + j] * inv_temp;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) mx = fmaxf(mx, z[i][j]);
-        }
-        mx = wave_max(mx);
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                z[i][j] = expf(z[i][j] - mx);  // exp(-inf) = 0 for padded classes
-                s += z[i][j];
-            }
-        s = wave_sum(s);
-        const float inv = 1.0f / s;
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[i][j] += z[i][j] * inv;
+        const float mx = head_load_row(logits + ((long long)t * n + img) * ld, C, inv_temp, lane, z);
+        head_accumulate<false>(z, mx, p);
     }
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-        *(float4*)&part[wave][4 * lane + 256 * i] = make_float4(p[i][0], p[i][1], p[i][2], p[i][3]);
-    __syncthreads();
-    // thread tid owns classes 4*tid + 1024*i'  (NV*256 floats per wave row = NV*64 float4)
-    const float inv_T = 1.0f / (float)T;
-    float best = -1.f;
-    int besti = 0x7fffffff;
-    float h = 0.f;
-    for (int q = tid; q < NV * 64; q += 256) {
-        const float4 a = *(const float4*)&part[0][4 * q], b = *(const float4*)&part[1][4 * q];
-        const float4 c4 = *(const float4*)&part[2][4 * q], d = *(const float4*)&part[3][4 * q];
-        const float pb[4] = {(((a.x + b.x) + c4.x) + d.x) * inv_T, (((a.y + b.y) + c4.y) + d.y) * inv_T,
-                             (((a.z + b.z) + c4.z) + d.z) * inv_T, (((a.w + b.w) + c4.w) + d.w) * inv_T};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int cls = 4 * q + j;
-            if (cls < C) {
-                if (pb[j] > best) { best = pb[j]; besti = cls; }
-                if (pb[j] > 0.f) h -= pb[j] * logf(pb[j]);
-            }
-        }
-    }
-    // wave argmax (ties -> lowest index), wave entropy sum
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(besti, o, 64);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-    }
-    h = wave_sum(h);
-    if (lane == 0) { red_v[wave] = best; red_i[wave] = besti; red_h[wave] = h; }
+    float pb[4], best;
+    int besti;
+    head_combine<NV>(part, p, tid, C, 1.0f / (float)T, pb, red_h);
+    head_mask_classes(pb, tid, C);
+    head_thread_argmax(pb, tid, best, besti);
+    wave_argmax(best, besti);
+    if (lane == 0) { red_v[wave] = best; red_i[wave] = besti; }
     __syncthreads();
     if (tid == 0) {
-        float bv = red_v[0]; int bi = red_i[0]; float hh = red_h[0];
-        for (int w = 1; w < 4; ++w) {
-            if (red_v[w] > bv || (red_v[w] == bv && red_i[w] < bi)) { bv = red_v[w]; bi = red_i[w]; }
-            hh += red_h[w];
-        }
-        const float cf = conf_kind == 0 ? bv : 1.0f - hh * inv_lnC;
+        float bv;
+        int bi;
+        argmax_of_waves(red_v, red_i, bv, bi);
         labels[(long long)img * out_stride] = bi;
-        conf[(long long)img * out_stride] = cf;
-        if (fail) fail[img] = cf < tau ? 1 : 0;
-        if (score) score[img] = fminf(fmaxf(1.0f - cf, 0.f), 1.f);
+        conf[(long long)img * out_stride] = head_finish<false>(conf_kind, bv, sum_of_waves(red_h), inv_lnC, 0.f, 0.f, tau, img, fail, score);
     }
 }
 
 // ---------------------------------------------------------------------------
-// Uncertainty head: head_kernel's pbar, label and kind 0 / 1 confidence (same per-sample sequence, same wave-order
-// combine, hence the same bits) plus the decomposition of the T samples:
+// Uncertainty head: the head core's pbar, label and confidence plus the decomposition of the T samples (DESIGN.md
+// section 2, item 5):
 //   H(pbar), (1/T) sum_t H(p_t), mutual information, vote share of the label (per-sample argmax of z_t, lowest index
 //   on ties), population std of p_t[label] (second pass: p_t[label] recomputed from the per-sample max and 1/sum kept
 //   in LDS, same operations as the first pass), top-5 of pbar (ties -> lowest index).
@@ -3249,7 +3310,6 @@ __global__ __launch_bounds__(256) void head_unc_kernel(const float* __restrict__
                                                        int* __restrict__ labels, float* __restrict__ conf,
                                                        uint8_t* __restrict__ fail, float* __restrict__ score, int out_stride,
                                                        int* __restrict__ rec) {
-    static_assert(NV * 64 <= 256, "one float4 group of pbar per thread");
     __shared__ __attribute__((aligned(16))) float part[4][NV * 256];
     __shared__ int votes[NV * 256];
     __shared__ float red_v[5][4];
@@ -3261,33 +3321,11 @@ __global__ __launch_bounds__(256) void head_unc_kernel(const float* __restrict__
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int c = tid; c < NV * 256; c += 256) votes[c] = 0;
     __syncthreads();
-    float p[NV][4];
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) p[i][j] = 0.f;
+    float p[NV][4] = {};
     float ent = 0.f;                        // sum of H(p_t) over this wave's samples, in sample order
     for (int t = wave; t < T; t += 4) {
-        const float* row = logits + ((long long)t * n + img) * ld;
         float z[NV][4];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = 4 * lane + 256 * i;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[i][j] = -INFINITY;
-            if (c + 3 < C) {
-                const float4 v = *(const float4*)(row + c);
-                z[i][0] = v.x * inv_temp; z[i][1] = v.y * inv_temp; z[i][2] = v.z * inv_temp; z[i][3] = v.w * inv_temp;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (c + j < C) z[i][j] = row[c + j] * inv_temp;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) mx = fmaxf(mx, z[i][j]);
-        }
-        mx = wave_max(mx);
+        const float mx = head_load_row(logits + ((long long)t * n + img) * ld, C, inv_temp, lane, z);
         // this sample's vote: lowest class index whose z equals the maximum
         int am = 0x7fffffff;
 #pragma unroll
@@ -3297,79 +3335,35 @@ __global__ __launch_bounds__(256) void head_unc_kernel(const float* __restrict__
                 if (z[i][j] == mx) am = 4 * lane + 256 * i + j;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) am = min(am, __shfl_xor(am, o, 64));
-        float s = 0.f, sd = 0.f;            // sd = sum e * (z - mx): H(p_t) = ln s - sd / s
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float d = z[i][j] - mx;
-                z[i][j] = expf(d);  // exp(-inf) = 0 for padded classes
-                s += z[i][j];
-                sd += z[i][j] > 0.f ? z[i][j] * d : 0.f;
-            }
-        s = wave_sum(s);
-        sd = wave_sum(sd);
-        const float inv = 1.0f / s;
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[i][j] += z[i][j] * inv;
-        ent += fmaxf(logf(s) - sd * inv, 0.f);
+        const SoftmaxTerms st = head_accumulate<true>(z, mx, p);
+        ent += head_sample_entropy(st);
         if (lane == 0) {
             smp[t] = mx;
-            smp[T + t] = inv;
+            smp[T + t] = st.inv;
             if (am < C) atomicAdd(&votes[am], 1);
         }
     }
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-        *(float4*)&part[wave][4 * lane + 256 * i] = make_float4(p[i][0], p[i][1], p[i][2], p[i][3]);
     if (lane == 0) red_e[wave] = ent;
-    __syncthreads();
-    // thread tid owns classes 4*tid .. 4*tid + 3 (NV*256 floats per wave row = NV*64 float4 <= 256 threads)
     const float inv_T = 1.0f / (float)T;
-    float pb[4] = {-1.f, -1.f, -1.f, -1.f};
-    float h = 0.f;
-    const int q = tid;
-    if (q < NV * 64) {
-        const float4 a = *(const float4*)&part[0][4 * q], b = *(const float4*)&part[1][4 * q];
-        const float4 c4 = *(const float4*)&part[2][4 * q], d = *(const float4*)&part[3][4 * q];
-        pb[0] = (((a.x + b.x) + c4.x) + d.x) * inv_T; pb[1] = (((a.y + b.y) + c4.y) + d.y) * inv_T;
-        pb[2] = (((a.z + b.z) + c4.z) + d.z) * inv_T; pb[3] = (((a.w + b.w) + c4.w) + d.w) * inv_T;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (4 * q + j >= C) pb[j] = -1.f;           // not a class: never selected
-            else if (pb[j] > 0.f) h -= pb[j] * logf(pb[j]);
-        }
-    }
-    h = wave_sum(h);
-    if (lane == 0) red_h[wave] = h;
+    float pb[4];
+    head_combine<NV>(part, p, tid, C, inv_T, pb, red_h);
+    head_mask_classes(pb, tid, C);
     // top-5 of pbar: five rounds of block arg-max, each excluding the classes already taken (rank 0 = the label)
     int top_i[5];
     float top_v[5];
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
-        float best = -1.f;
-        int besti = 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (pb[j] > best) { best = pb[j]; besti = 4 * q + j; }   // j ascending: strict > keeps the lowest index
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(besti, o, 64);
-            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-        }
+        float best, bv;
+        int besti, bi;
+        head_thread_argmax(pb, tid, best, besti);
+        wave_argmax(best, besti);
         if (lane == 0) { red_v[r][wave] = best; red_i[r][wave] = besti; }
         __syncthreads();
-        float bv = red_v[r][0];
-        int bi = red_i[r][0];
-        for (int w = 1; w < 4; ++w)
-            if (red_v[r][w] > bv || (red_v[r][w] == bv && red_i[r][w] < bi)) { bv = red_v[r][w]; bi = red_i[r][w]; }
+        argmax_of_waves(red_v[r], red_i[r], bv, bi);
         top_v[r] = bv; top_i[r] = bi;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (4 * q + j == bi) pb[j] = -1.f;
+            if (4 * tid + j == bi) pb[j] = -1.f;
         if (r == 0) {
             // second pass for prob_std: p_t[label] with the first pass's operations, (p_t - pbar[label])^2 summed per thread
             float sq = 0.f;
@@ -3386,24 +3380,18 @@ __global__ __launch_bounds__(256) void head_unc_kernel(const float* __restrict__
     if (tid == 0) {
         const int bi = top_i[0];
         const float bv = top_v[0];
-        float hh = red_h[0];
-        for (int w = 1; w < 4; ++w) hh += red_h[w];
-        // T = 1: pbar is p_0 bit for bit, so its entropy IS the expected entropy (and the mutual information exactly 0)
-        const float eh = T == 1 ? hh : (((red_e[0] + red_e[1]) + red_e[2]) + red_e[3]) * inv_T;
-        const float mi = fmaxf(hh - eh, 0.f);
-        const float sd = sqrtf((((red_s[0] + red_s[1]) + red_s[2]) + red_s[3]) * inv_T);
-        const float cf = conf_kind == 0 ? bv : (conf_kind == 1 ? 1.0f - hh * inv_lnC : 1.0f - mi * inv_lnK);
+        const HeadEntropies en = head_entropies(red_h, red_e, T, inv_T);
+        const float sd = sqrtf(sum_of_waves(red_s) * inv_T);
+        const float cf = head_finish<true>(conf_kind, bv, en.hh, inv_lnC, en.mi, inv_lnK, tau, img, fail, score);
         if (labels) labels[(long long)img * out_stride] = bi;
         if (conf) conf[(long long)img * out_stride] = cf;
-        if (fail) fail[img] = cf < tau ? 1 : 0;
-        if (score) score[img] = fminf(fmaxf(1.0f - cf, 0.f), 1.f);
         out_rec[0] = bi;
         out_rec[1] = __float_as_int(cf);
         out_rec[2] = __float_as_int(bv);
         out_rec[3] = __float_as_int(sd);
-        out_rec[4] = __float_as_int(hh);
-        out_rec[5] = __float_as_int(eh);
-        out_rec[6] = __float_as_int(mi);
+        out_rec[4] = __float_as_int(en.hh);
+        out_rec[5] = __float_as_int(en.eh);
+        out_rec[6] = __float_as_int(en.mi);
         out_rec[7] = __float_as_int(bi < C ? (float)votes[bi] / (float)T : 0.f);
     }
     if (tid < 5) {
@@ -3424,8 +3412,8 @@ __global__ __launch_bounds__(256) void head_unc_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------
-// Conformal prediction-set head: head_unc_kernel's pbar, label and confidence (same
-// per-sample sequence, same wave-order combine, hence the same bits for kinds 0 / 1 / 2), then
+// Conformal prediction-set head: the head core's pbar, label and confidence (kinds
+// 0 / 1 / 2; the per-sample entropies only under kind 2), then
 //   sort     the classes by pbar descending, lowest index first on ties: a bitonic sort of NV*256 64-bit keys
 //            (~float_bits(pbar) << 32) | class (pbar >= 0, so the bits order like the values; padding classes get
 //            all-ones high bits and sort last).  Thread q holds sorted positions 4q .. 4q+3; partners 1, 2 apart are in
@@ -3471,77 +3459,27 @@ __global__ __launch_bounds__(256) void head_sets_kernel(const float* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < 32) out_rec[8 + tid] = 0;
     if (tid == 0) set_n = 0;
-    float p[NV][4];
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) p[i][j] = 0.f;
+    float p[NV][4] = {};
     float ent = 0.f;                        // sum of H(p_t) over this wave's samples, in sample order (conf_kind 2)
     for (int t = wave; t < T; t += 4) {
-        const float* row = logits + ((long long)t * n + img) * ld;
         float z[NV][4];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = 4 * lane + 256 * i;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[i][j] = -INFINITY;
-            if (c + 3 < C) {
-                const float4 v = *(const float4*)(row + c);
-                z[i][0] = v.x * inv_temp; z[i][1] = v.y * inv_temp; z[i][2] = v.z * inv_temp; z[i][3] = v.w * inv_temp;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (c + j < C) z[i][j] = row[c + j] * inv_temp;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) mx = fmaxf(mx, z[i][j]);
-        }
-        mx = wave_max(mx);
-        float s = 0.f, sd = 0.f;            // sd = sum e * (z - mx): H(p_t) = ln s - sd / s
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float d = z[i][j] - mx;
-                z[i][j] = expf(d);  // exp(-inf) = 0 for padded classes
-                s += z[i][j];
-                sd += z[i][j] > 0.f ? z[i][j] * d : 0.f;
-            }
-        s = wave_sum(s);
-        const float inv = 1.0f / s;
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[i][j] += z[i][j] * inv;
-        if (conf_kind == 2) {
-            sd = wave_sum(sd);
-            ent += fmaxf(logf(s) - sd * inv, 0.f);
-        }
+        const float mx = head_load_row(logits + ((long long)t * n + img) * ld, C, inv_temp, lane, z);
+        const SoftmaxTerms st = head_accumulate<true>(z, mx, p);
+        if (conf_kind == 2) ent += head_sample_entropy(st);
     }
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-        *(float4*)&part[wave][4 * lane + 256 * i] = make_float4(p[i][0], p[i][1], p[i][2], p[i][3]);
     if (lane == 0) red_e[wave] = ent;
-    __syncthreads();
-    // thread tid owns classes 4*tid .. 4*tid + 3 (threads tid >= NV*64 own none)
     const float inv_T = 1.0f / (float)T;
-    float h = 0.f;
+    float pb[4];
+    head_combine<NV>(part, p, tid, C, inv_T, pb, red_h);
+    // thread tid owns classes 4*tid .. 4*tid + 3 (threads tid >= NV*64 own none)
     unsigned long long key[4];
     if (tid < NV * 64) {
-        const float4 a = *(const float4*)&part[0][4 * tid], b = *(const float4*)&part[1][4 * tid];
-        const float4 c4 = *(const float4*)&part[2][4 * tid], d = *(const float4*)&part[3][4 * tid];
-        const float pb[4] = {(((a.x + b.x) + c4.x) + d.x) * inv_T, (((a.y + b.y) + c4.y) + d.y) * inv_T,
-                             (((a.z + b.z) + c4.z) + d.z) * inv_T, (((a.w + b.w) + c4.w) + d.w) * inv_T};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int cls = 4 * tid + j;
-            if (cls < C && pb[j] > 0.f) h -= pb[j] * logf(pb[j]);
             key[j] = ((unsigned long long)(cls < C ? ~__float_as_uint(pb[j]) : 0xFFFFFFFFu) << 32) | (uint32_t)cls;
         }
     }
-    h = wave_sum(h);
-    if (lane == 0) red_h[wave] = h;
     // bitonic sort, ascending keys; element e = 4 * tid + j
     if (NV == 4 || wave == 0) {
         unsigned long long* kx = (unsigned long long*)&part[0][0];
@@ -3635,19 +3573,13 @@ __global__ __launch_bounds__(256) void head_sets_kernel(const float* __restrict_
     if (tid == 0) {
         const int bi = cl[0];               // sorted position 0: argmax pbar, lowest index on ties
         const float bv = v[0];
-        float hh = red_h[0];
-        for (int w = 1; w < 4; ++w) hh += red_h[w];
-        // T = 1: pbar is p_0 bit for bit, so its entropy IS the expected entropy (and the mutual information exactly 0)
-        const float eh = T == 1 ? hh : (((red_e[0] + red_e[1]) + red_e[2]) + red_e[3]) * inv_T;
-        const float mi = fmaxf(hh - eh, 0.f);
-        const float cf = conf_kind == 0 ? bv : (conf_kind == 1 ? 1.0f - hh * inv_lnC : 1.0f - mi * inv_lnK);
-        if (fail) fail[img] = cf < tau ? 1 : 0;
-        if (score) score[img] = fminf(fmaxf(1.0f - cf, 0.f), 1.f);
+        const HeadEntropies en = head_entropies(red_h, red_e, T, inv_T);
+        const float cf = head_finish<true>(conf_kind, bv, en.hh, inv_lnC, en.mi, inv_lnK, tau, img, fail, score);
         if (true_labels && (y < 0 || y >= C)) true_scores[img] = __int_as_float(0x7fc00000);
         out_rec[0] = bi;
         out_rec[1] = __float_as_int(cf);
         out_rec[2] = set_n;
-        out_rec[3] = __float_as_int(((red_m[0] + red_m[1]) + red_m[2]) + red_m[3]);
+        out_rec[3] = __float_as_int(sum_of_waves(red_m));
         out_rec[4] = __float_as_int(cp.score_kind == 0 ? 0.f : u);
         out_rec[5] = out_rec[6] = out_rec[7] = 0;
     }
