@@ -83,6 +83,14 @@ class FavPredSet(C.Structure):
                 ("u", C.c_float), ("reserved", C.c_int32 * 3), ("member", C.c_uint32 * 32)]
 
 
+SWEEP_MAX_TEMPS = 32
+
+
+class FavCalibCell(C.Structure):
+    """fav_calib_cell: one 16-byte cell per (frame, temperature) of a sweep (calibration.unpack_cells reads int32[n, K, 4])."""
+    _fields_ = [("label", C.c_int32), ("confidence", C.c_float), ("nll", C.c_float), ("brier", C.c_float)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -116,6 +124,10 @@ _SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_conformal_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(FavConformal),
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_classify_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_float),
+                                     C.c_int32, C.c_void_p, C.c_void_p]),
+    "fav_set_temperature": (C.c_int, [C.c_void_p, C.c_float]),
+    "fav_set_tau": (C.c_int, [C.c_void_p, C.c_float]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
@@ -147,6 +159,8 @@ _SIGNATURES = {
     "fav_op_head_sets": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float,
                                    C.c_int64, C.POINTER(FavConformal), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "fav_op_head_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

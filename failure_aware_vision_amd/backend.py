@@ -270,6 +270,124 @@ class Backend:
         r = unpack_sets(out, self.cfg.num_classes)
         return dict(r, fail=fail, score=score, ambiguous=r["set_size"] != 1)
 
+    # -- temperature / tau calibration (calibration.py; include/fav.h fav_classify_sweep) --------------------------------
+    def _labels_on(self, labels, n: int, dev):
+        torch = self._torch
+        if int(np.shape(labels)[0] if isinstance(labels, np.ndarray) else labels.shape[0]) != n:
+            raise ValueError("one label per frame")
+        return (torch.from_numpy(np.asarray(labels)) if isinstance(labels, np.ndarray) else labels).to(dev, torch.int32).contiguous()
+
+    @staticmethod
+    def _temps_c(temperatures):
+        t = np.ascontiguousarray(np.asarray(temperatures, np.float32).ravel())
+        if not 1 <= t.size <= _lib.SWEEP_MAX_TEMPS:
+            raise ValueError(f"between 1 and {_lib.SWEEP_MAX_TEMPS} temperatures per sweep, got {t.size}")
+        return t, t.ctypes.data_as(C.POINTER(C.c_float))
+
+    def _sweep_logits(self, lg, lab, temps):
+        """The sweep head alone (fav_op_head_sweep) on fp32 logits [T, n, ld] kept on the device, of which the first
+        num_classes columns count -> int32[n, K, 4] cells."""
+        torch = self._torch
+        t, tp = self._temps_c(temps)
+        T, n, ld = (int(x) for x in lg.shape)
+        cells = torch.empty((n, t.size, 4), dtype=torch.int32, device=lg.device)
+        _lib.check(self.lib.fav_op_head_sweep(lg.data_ptr(), T, n, self.cfg.num_classes, ld, tp, t.size, self.cfg.conf_kind,
+                                              lab.data_ptr(), cells.data_ptr(), torch.cuda.current_stream(lg.device).cuda_stream))
+        return cells
+
+    def calibration_sweep(self, images, labels, temperatures, first_index: int = 0, _keep_logits=None):
+        """The confidence head at every one of ``temperatures`` (1 to 32 of them) in one launch per batch
+        (fav_classify_sweep): int32[n, K, 4] cells, ``calibration.unpack_cells`` -> label, confidence, nll, brier per
+        (frame, temperature), ``labels`` (int[n]) being the frames' true classes.  The handle's own temperature is not
+        used.  Batches of max_batch frames; torch CUDA frames in -> CUDA tensor out, asynchronous on the current stream;
+        numpy in -> numpy out, synchronous."""
+        torch = self._torch
+        img, host, n, layout, stream = self._classify_args(images)
+        dev = img.device
+        lab = self._labels_on(labels, n, dev)
+        t, tp = self._temps_c(temperatures)
+        cells = torch.empty((n, t.size, 4), dtype=torch.int32, device=dev)
+        mb = int(self.cfg.max_batch)
+        for b in range(0, n, mb):
+            e = min(n, b + mb)
+            _lib.check(self.lib.fav_classify_sweep(self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b,
+                                                   lab[b:e].data_ptr(), tp, t.size, cells[b:e].data_ptr(), stream), self._h)
+            if _keep_logits is not None:
+                lg = self.logits()                                  # [T, e - b, C], this batch's
+                ld = (lg.shape[2] + 3) // 4 * 4                     # the head reads rows of a multiple of 4 floats
+                if ld != lg.shape[2]:
+                    lg = torch.nn.functional.pad(lg, (0, ld - lg.shape[2]))
+                _keep_logits.append((lg, lab[b:e]))
+        return cells.cpu().numpy() if host else cells
+
+    def calibrate_temperature(self, images, labels, lo: float = 0.25, hi: float = 8.0, rtol: float = 1e-3,
+                              first_index: int = 0, logits_budget_bytes: int = 8 << 30):
+        """Fit the softmax temperature on held-out labelled frames by minimum mean NLL (``calibration.fit_temperature``)
+        -> a ``TemperatureFit`` (temperature, nll, at_bound, rounds).  ONE forward pass per batch: the first grid runs
+        through fav_classify_sweep, its logits stay on the device, and the finer grids run the sweep head alone on them
+        (fav_op_head_sweep).  A calibration set whose logits exceed ``logits_budget_bytes`` is refused.  The handle is
+        not changed: see ``set_temperature`` / ``apply``."""
+        from .calibration import fit_temperature, unpack_cells
+        n = int(images.shape[0])
+        need = 4 * self.T * n * ((int(self.cfg.num_classes) + 3) // 4 * 4)
+        if need > int(logits_budget_bytes):
+            raise ValueError(f"calibrate_temperature keeps the calibration set's logits on the device: {self.T} samples x {n} "
+                             f"frames x {self.cfg.num_classes} classes = {need} bytes ({need / 2**30:.2f} GiB) exceed "
+                             f"logits_budget_bytes = {int(logits_budget_bytes)}; calibrate on fewer frames")
+        kept = []
+
+        def sum_nll(cells):
+            c = cells if isinstance(cells, np.ndarray) else cells.cpu().numpy()
+            return unpack_cells(c)["nll"].astype(np.float64).sum(axis=0)
+
+        def nll_of(temps):
+            if not kept:
+                return sum_nll(self.calibration_sweep(images, labels, temps, first_index, _keep_logits=kept)) / n
+            return sum(sum_nll(self._sweep_logits(lg, lab, temps)) for lg, lab in kept) / n
+        return fit_temperature(nll_of, lo=lo, hi=hi, rtol=rtol)
+
+    def _detect_batched(self, images, first_index: int = 0):
+        """classify_detect over batches of max_batch frames -> numpy (labels, conf)."""
+        n, mb = int(images.shape[0]), int(self.cfg.max_batch)
+        out_l, out_c = [], []
+        for b in range(0, n, mb):
+            l, c, _, _ = self.classify_detect(images[b:min(n, b + mb)], int(first_index) + b)
+            out_l.append(l if isinstance(l, np.ndarray) else l.cpu().numpy())
+            out_c.append(c if isinstance(c, np.ndarray) else c.cpu().numpy())
+        return np.concatenate(out_l), np.concatenate(out_c)
+
+    def calibrate_tau(self, images, labels, target_risk: float, delta: float | None = None, first_index: int = 0) -> dict:
+        """The failure threshold for a target selective risk at the handle's CURRENT temperature (calibrate that first):
+        classify the held-out frames, then ``calibration.tau_for_risk`` -> dict tau, coverage, risk, bound.  ``delta``:
+        the guarantee's failure probability (None: the empirical risk decides).  The handle is not changed."""
+        from .calibration import tau_for_risk
+        pred, conf = self._detect_batched(images, first_index)
+        lab = labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()
+        return tau_for_risk(conf, pred == np.asarray(lab).ravel(), target_risk, delta)
+
+    def calibration_report(self, images, labels, first_index: int = 0) -> dict:
+        """What the confidence is worth on labelled frames at the current temperature (a one-temperature sweep):
+        accuracy, mean_confidence, nll, brier, ece, mce, aurc."""
+        from .calibration import report_from_cells
+        cells = self.calibration_sweep(images, labels, [self.cfg.temperature], first_index)
+        lab = labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()
+        return report_from_cells(cells if isinstance(cells, np.ndarray) else cells.cpu().numpy(), lab)
+
+    def set_temperature(self, temperature: float):
+        """Softmax temperature of the calls made from now on (finite, > 0); calls already enqueued keep the old one."""
+        _lib.check(self.lib.fav_set_temperature(self._h, float(temperature)), self._h)
+        self.cfg.temperature = float(temperature)
+
+    def set_tau(self, tau: float):
+        """Failure threshold (fail = conf < tau) of the calls made from now on; not NaN."""
+        _lib.check(self.lib.fav_set_tau(self._h, float(tau)), self._h)
+        self.cfg.tau = float(tau)
+
+    def apply(self, cal):
+        """Adopt a ``calibration.Calibration``: its temperature and tau."""
+        self.set_temperature(cal.temperature)
+        self.set_tau(cal.tau)
+
     def classify(self, images, first_index: int = 0):
         """The drop-in: frames -> (labels, confidences)."""
         labels, conf, _, _ = self.classify_detect(images, first_index)

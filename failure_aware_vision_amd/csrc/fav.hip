@@ -850,11 +850,38 @@ const char* check_conformal(const fav_conformal* cp) {
     return nullptr;
 }
 
+// The temperature-sweep head's arguments (fav_classify_sweep / fav_op_head_sweep): K temperatures on the host, the frames'
+// true labels and the [n][K] cells on the device.
+struct HeadSweep {
+    const float* temps;
+    int32_t K;
+    const int32_t* true_labels;
+    fav_calib_cell* cells;
+};
+
+// Everything about a sweep that can be wrong without looking at the device (NULL: nothing).  T < 0: not known yet (the
+// classify entry point checks the handle's configuration instead).
+const char* check_sweep(const HeadSweep& sw, int C, int T, int kind) {
+    if (sw.K < 1 || sw.K > FAV_SWEEP_MAX_TEMPS) return "sweep: K must be in [1, 32] (FAV_SWEEP_MAX_TEMPS)";
+    if (!sw.temps) return "sweep: temperatures are NULL";
+    for (int k = 0; k < sw.K; ++k)
+        if (!std::isfinite(sw.temps[k]) || !(sw.temps[k] > 0.f)) return "sweep: every temperature must be finite and > 0";
+    if (!sw.cells || ((uintptr_t)sw.cells & 7)) return "sweep: cells must be non-NULL and 8-byte aligned";
+    if (!sw.true_labels) return "sweep: true labels are NULL";
+    if (C > 1024 || C < 1) return "head: num_classes must be in [1, 1024]";
+    if (kind < 0 || kind > 2) return "sweep: conf_kind must be 0, 1 or 2";
+    if (kind == FAV_CONF_MUTUAL_INFO && ((T >= 0 && T < 2) || C < 2))
+        return "sweep: conf_kind 2 (mutual information) needs T >= 2 samples and num_classes >= 2";
+    return nullptr;
+}
+
 // rec (one fav_uncertainty per frame) or conf_kind FAV_CONF_MUTUAL_INFO: head_unc_kernel; sets: head_sets_kernel;
-// otherwise head_kernel
+// sweep: head_sweep_kernel (temperature, tau, labels .. score are then not used); otherwise head_kernel
 const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C, int ld, float temperature, int kind,
                         float tau, int* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride = 1,
-                        fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr) {
+                        fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr, const HeadSweep* sweep = nullptr) {
+    if (sweep)
+        if (const char* e = check_sweep(*sweep, C, T, kind)) return e;
     if (C > 1024 || C < 1) return "head: num_classes must be in [1, 1024]";
     if (ld % 4 != 0 || ld < C) return "head: bad row stride";
     const float inv_temp = 1.0f / temperature;
@@ -871,7 +898,33 @@ const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C,
             hipLaunchKernelGGL((KERNEL<4>), dim3(n), dim3(256), LDS, s, logits, T, n, C, ld, inv_temp, kind, tau, inv_lnC,  \
                                __VA_ARGS__);                                                                                \
     } while (0)
-    if (sets) {
+    if (sweep) {
+        if (T < 1 || T > 4096) return "head: the sweep head takes 1 <= T <= 4096 samples";
+        SweepParams p;
+        for (int k = 0; k < kSweepMaxTemps; ++k) p.inv_temp[k] = 1.0f / sweep->temps[std::min(k, sweep->K - 1)];
+        p.K = sweep->K;
+        // dynamic LDS: as many of the frame's rows as fit beside the kernel's 16.4 KB of static LDS
+        const int kSweepLds = 140 * 1024;
+        const int row_bytes = ((C + 3) & ~3) * 4;
+        p.t_lds = std::min(T, kSweepLds / row_bytes);
+        const size_t lds = (size_t)p.t_lds * row_bytes;
+        // bytes: the logits once, the labels, the cells
+        Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 4.0 * n + 16.0 * n * sweep->K);
+#define FAV_LAUNCH_SWEEP(NV_)                                                                                               \
+    do {                                                                                                                    \
+        static DeviceFlags attr_set;   /* hipFuncSetAttribute applies to the CURRENT device only */                         \
+        if (!attr_set.test_current()) {                                                                                     \
+            if (hipFuncSetAttribute((const void*)head_sweep_kernel<NV_>, hipFuncAttributeMaxDynamicSharedMemorySize,        \
+                                    kSweepLds) != hipSuccess)                                                               \
+                return "head: cannot reserve LDS for the sweep head";                                                       \
+            attr_set.set_current();                                                                                         \
+        }                                                                                                                   \
+        hipLaunchKernelGGL((head_sweep_kernel<NV_>), dim3(n), dim3(256), lds, s, logits, T, n, C, ld, kind, inv_lnC,        \
+                           inv_lnK, p, sweep->true_labels, (int*)sweep->cells);                                             \
+    } while (0)
+        if (C <= 256) FAV_LAUNCH_SWEEP(1); else FAV_LAUNCH_SWEEP(4);
+#undef FAV_LAUNCH_SWEEP
+    } else if (sets) {
         if (const char* e = check_conformal(sets->cp)) return e;
         if (!sets->rec && !sets->true_labels) return "head: the sets head needs records or calibration labels";
         if (!sets->true_labels != !sets->true_scores) return "head: true_labels and true_scores go together";
@@ -1983,14 +2036,15 @@ void mark_last_use(fav_handle* h, hipStream_t s) {
 }
 fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                               int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride,
-                              fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr);
+                              fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr, const HeadSweep* sweep = nullptr);
 
 // The gate of every classify entry point: the argument checks, then classify_on_stream behind the previous user of the
 // handle's buffers.  who: the public name the messages carry; bad: the entry point's own complaint about its buffers and
 // parameters (NULL: none), reported after the handle and weights checks and before those on n, layout and first_index.
 fav_status classify_gate(const char* who, fav_handle* h, const char* bad, const void* images, int32_t n, int32_t layout,
                          int64_t first_index, int32_t* labels, float* conf, uint8_t* fail, float* score, void* stream,
-                         int out_stride, fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr) {
+                         int out_stride, fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr,
+                         const HeadSweep* sweep = nullptr) {
     if (!h) return FAV_ERR_INVALID_ARG;
     if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", who); return FAV_ERR_NO_WEIGHTS; }
     if (bad) { h->err = fmt("%s: %s", who, bad); return FAV_ERR_INVALID_ARG; }
@@ -2000,7 +2054,7 @@ fav_status classify_gate(const char* who, fav_handle* h, const char* bad, const 
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (fav_status st = wait_last_use(h, s)) return st;
-    const fav_status st = classify_on_stream(h, images, n, layout, first_index, labels, conf, fail, score, s, out_stride, rec, sets);
+    const fav_status st = classify_on_stream(h, images, n, layout, first_index, labels, conf, fail, score, s, out_stride, rec, sets, sweep);
     mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
     return st;
 }
@@ -2046,10 +2100,38 @@ fav_status fav_conformal_scores(fav_handle* h, const void* images, int32_t n, in
                          nullptr, nullptr, stream, 1, nullptr, &hs);
 }
 
+fav_status fav_classify_sweep(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
+                              const int32_t* true_labels, const float* temps, int32_t K, fav_calib_cell* cells, void* stream) {
+    static_assert(sizeof(fav_calib_cell) == 16, "fav_calib_cell is 4 dwords");
+    if (!h) return FAV_ERR_INVALID_ARG;
+    const HeadSweep sw{temps, K, true_labels, cells};
+    // the handle's conf_kind was checked against its sample count by fav_create
+    const char* bad = check_sweep(sw, h->cfg.num_classes, -1, h->cfg.conf_kind);
+    return classify_gate("fav_classify_sweep", h, bad ? bad : (!images ? "null buffer" : nullptr), images, n, layout, first_index,
+                         nullptr, nullptr, nullptr, nullptr, stream, 1, nullptr, nullptr, &sw);
+}
+
+fav_status fav_set_temperature(fav_handle* h, float temperature) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!std::isfinite(temperature) || !(temperature > 0.f)) {
+        h->err = fmt("fav_set_temperature: temperature %g is not finite and > 0", (double)temperature);
+        return FAV_ERR_INVALID_ARG;
+    }
+    h->cfg.temperature = temperature;   // read on the host when a head is launched: enqueued calls carry their own copy
+    return FAV_OK;
+}
+
+fav_status fav_set_tau(fav_handle* h, float tau) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (std::isnan(tau)) { h->err = "fav_set_tau: tau is NaN"; return FAV_ERR_INVALID_ARG; }
+    h->cfg.tau = tau;
+    return FAV_OK;
+}
+
 namespace {
 fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                               int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride,
-                              fav_uncertainty* rec, const HeadSets* sets) {
+                              fav_uncertainty* rec, const HeadSets* sets, const HeadSweep* sweep) {
     h->ev_used = h->profiling ? h->ev_used : 0;
     if (h->vit) {
         for (auto& L : h->layers) { L.w = L.w_m[0]; L.b = L.b_m[0]; }
@@ -2160,7 +2242,7 @@ fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int3
     if (!h->vit) h->phase_out.back() = h->logits;
     const int T_head = h->n_members > 1 ? h->n_members : h->T_eff;
     if (const char* e = launch_head(h, h->logits, T_head, n, h->cfg.num_classes, h->cpad, h->cfg.temperature,
-                                    h->cfg.conf_kind, h->cfg.tau, labels, conf, fail, score, s, out_stride, rec, sets)) {
+                                    h->cfg.conf_kind, h->cfg.tau, labels, conf, fail, score, s, out_stride, rec, sets, sweep)) {
         h->err = e;
         return FAV_ERR_INVALID_ARG;
     }
@@ -2347,6 +2429,15 @@ fav_status fav_op_head_sets(const float* logits, int32_t T, int32_t n, int32_t C
     const HeadSets hs{cp, first_index, true_labels, true_scores, records};
     return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, nullptr, nullptr, fail, score,
                                (hipStream_t)stream, 1, nullptr, &hs));
+}
+
+fav_status fav_op_head_sweep(const float* logits, int32_t T, int32_t n, int32_t C, int32_t ld, const float* temps, int32_t K,
+                             int32_t kind, const int32_t* true_labels, fav_calib_cell* cells, void* stream) {
+    const HeadSweep sw{temps, K, true_labels, cells};
+    if (const char* e = check_sweep(sw, C, T, kind)) return op_done(fmt("fav_op_head_sweep: %s", e).c_str());
+    if (!logits || T < 1 || n < 1) return op_done("fav_op_head_sweep: bad argument (logits non-NULL, T >= 1, n >= 1)");
+    return op_done(launch_head(nullptr, logits, T, n, C, ld, 1.0f, kind, 0.f, nullptr, nullptr, nullptr, nullptr,
+                               (hipStream_t)stream, 1, nullptr, nullptr, &sw));
 }
 
 fav_status fav_op_layernorm(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t rows, int32_t D,

@@ -7,6 +7,7 @@
 // implement is the one stated in oracle/fav_oracle.py and DESIGN.md §3.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 
 // Phase stamps (per-block clocks written through ConvParams / TailParams / GemmSkParams::dbg) exist in the experiments build only
@@ -3586,6 +3587,139 @@ __global__ __launch_bounds__(256) void head_sets_kernel(const float* __restrict_
     if (rec) {
         __syncthreads();
         if (tid < 20) *(int2*)(rec + (long long)img * 40 + 2 * tid) = make_int2(out_rec[2 * tid], out_rec[2 * tid + 1]);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Temperature-sweep head: the head core at K <= 32 temperatures in ONE launch, so a
+// frame's logits come from HBM once, not K times.  For temperature k it writes the 4-dword cell (n, K) -> cells[img][k]
+// (fav_calib_cell in include/fav.h):
+//   label, confidence   the head core's, bit-identical to head_kernel / head_unc_kernel at inv_temp[k]
+//   nll                 -logf(fmaxf(pbar[y], FLT_MIN)), y = true_labels[img]
+//   brier               sum_{c < C} (pbar[c] - [c == y])^2: a thread's 4 classes in order, wave butterfly, waves 0-3 in
+//                       order
+//   y outside [0, C): nll = brier = NaN, label / confidence still written.
+// Schedule.  The block first copies its frame's rows into LDS (rows[t][Cp], Cp = C rounded up to 4; a lane stores exactly
+// the classes head_load_row later makes it read, so no barrier separates the copy from the reads).  The temperatures then
+// go in groups of G = kSweepGroup: one pass over the T rows feeds G sets of accumulators (G independent exp chains per
+// row also give the one wave a SIMD holds something to overlap), and every pass reads the rows from LDS.  Rows
+// t >= t_lds - those past the dynamic LDS the launch could reserve - are re-read from global memory in every pass,
+// i.e. from L2 / MALL (a frame's whole [T][C] is at most 16 MB at T = 4096).  The result of a temperature does not
+// depend on its group: each (temperature, sample) runs the head core's own sequence, and the waves meet per temperature.
+// Budget (NV = 4): static LDS 16 KB (part) + 0.4 KB; dynamic LDS t_lds * Cp * 4 B <= 140 KB (T = 30, C = 1000: 117 KB,
+// one block per CU - as many blocks as the heads it replaces put on a CU at n <= 256); accumulators G * NV * 4 = 64
+// VGPRs of 512 available at 4 waves per CU; no scratch (profiles/sweep_resource_usage.txt).
+// ---------------------------------------------------------------------------
+constexpr int kSweepMaxTemps = 32;
+constexpr int kSweepGroup = 4;
+struct SweepParams {
+    float inv_temp[kSweepMaxTemps];
+    int K;
+    int t_lds;              // rows [0, t_lds) of a frame are staged in LDS
+};
+
+// One row at the group's temperatures: p[g] += softmax(row * it[g]), ent[g] += H of it (conf_kind 2 only)
+template <int NV, int G>
+__device__ __forceinline__ void sweep_row(const float* row, int C, const float (&it)[G], int ng, int conf_kind, int lane,
+                                          float (&p)[G][NV][4], float (&ent)[G]) {
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+        if (g < ng) {
+            float z[NV][4];
+            const float mx = head_load_row(row, C, it[g], lane, z);
+            const SoftmaxTerms st = head_accumulate<true>(z, mx, p[g]);
+            if (conf_kind == 2) ent[g] += head_sample_entropy(st);
+        }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void head_sweep_kernel(const float* __restrict__ logits, int T, int n, int C, int ld,
+                                                         int conf_kind, float inv_lnC, float inv_lnK, SweepParams sp,
+                                                         const int* __restrict__ true_labels, int* __restrict__ cells) {
+    constexpr int G = kSweepGroup;
+    __shared__ __attribute__((aligned(16))) float part[4][NV * 256];
+    __shared__ float red_v[G][4], red_h[G][4], red_e[G][4], red_b[G][4];
+    __shared__ int red_i[G][4];
+    __shared__ float p_true[G];
+    extern __shared__ __attribute__((aligned(16))) float rows[];   // [t_lds][Cp]
+    const int img = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int Cp = (C + 3) & ~3;
+    const int t_lds = min(T, sp.t_lds);
+    // stage: wave w copies the rows it will read (t = w, w + 4, ...), every lane its own classes
+#pragma unroll 2
+    for (int t = wave; t < t_lds; t += 4) {
+        const float* src = logits + ((long long)t * n + img) * ld;
+        float* dst = rows + t * Cp;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = 4 * lane + 256 * i;
+            if (c + 3 < C) {
+                *(float4*)(dst + c) = *(const float4*)(src + c);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c + j < C) dst[c + j] = src[c + j];
+            }
+        }
+    }
+    const int y = true_labels[img];
+    const bool y_ok = y >= 0 && y < C;
+    const float inv_T = 1.0f / (float)T;
+    for (int k0 = 0; k0 < sp.K; k0 += G) {
+        const int ng = min(G, sp.K - k0);
+        float it[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) it[g] = sp.inv_temp[min(k0 + g, kSweepMaxTemps - 1)];
+        float p[G][NV][4] = {};
+        float ent[G] = {};                  // sum of H(p_t) over this wave's samples, in sample order (conf_kind 2)
+        for (int t = wave; t < T; t += 4) {
+            if (t < t_lds)
+                sweep_row<NV, G>(rows + t * Cp, C, it, ng, conf_kind, lane, p, ent);
+            else
+                sweep_row<NV, G>(logits + ((long long)t * n + img) * ld, C, it, ng, conf_kind, lane, p, ent);
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if (g < ng) {                   // block-uniform: the barriers below are reached by every thread or by none
+                if (lane == 0) red_e[g][wave] = ent[g];
+                float pb[4], best;
+                int besti;
+                head_combine<NV>(part, p[g], tid, C, inv_T, pb, red_h[g]);
+                float b = 0.f;
+                if (tid < NV * 64) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int c = 4 * tid + j;
+                        if (c < C) {
+                            const float d = pb[j] - (c == y ? 1.0f : 0.0f);
+                            b += d * d;
+                            if (c == y) p_true[g] = pb[j];
+                        }
+                    }
+                }
+                b = wave_sum(b);
+                if (lane == 0) red_b[g][wave] = b;
+                head_mask_classes(pb, tid, C);
+                head_thread_argmax(pb, tid, best, besti);
+                wave_argmax(best, besti);
+                if (lane == 0) { red_v[g][wave] = best; red_i[g][wave] = besti; }
+                __syncthreads();            // also frees part for the next temperature's combine
+                if (tid == 0) {
+                    float bv;
+                    int bi;
+                    argmax_of_waves(red_v[g], red_i[g], bv, bi);
+                    const HeadEntropies en = head_entropies(red_h[g], red_e[g], T, inv_T);
+                    const float cf = head_finish<true>(conf_kind, bv, en.hh, inv_lnC, en.mi, inv_lnK, 0.f, img, nullptr, nullptr);
+                    const float nan = __int_as_float(0x7fc00000);
+                    const float nll = y_ok ? -logf(fmaxf(p_true[g], FLT_MIN)) : nan;
+                    const float brier = y_ok ? sum_of_waves(red_b[g]) : nan;
+                    int* cell = cells + ((long long)img * sp.K + k0 + g) * 4;
+                    *(int2*)cell = make_int2(bi, __float_as_int(cf));
+                    *(int2*)(cell + 2) = make_int2(__float_as_int(nll), __float_as_int(brier));
+                }
+            }
+        __syncthreads();                    // the group's red_* and p_true are read before the next group writes them
     }
 }
 

@@ -207,6 +207,29 @@ fav_status fav_conformal_scores(fav_handle* h, const void* images_dev, int32_t n
                                 int64_t first_image_index, const fav_conformal* cp, const int32_t* labels_dev,
                                 float* scores_dev, void* hip_stream);
 
+/* Temperature sweep: the confidence head at K trial temperatures in one launch, on
+ * held-out frames whose true classes are known.  Cell (frame i, temperature k), with pbar computed exactly as
+ * fav_classify_ex computes it at temperature temps[k] (inv_temp = 1.0f / temps[k]) and y = true_labels[i]:
+ *   label, confidence   bit-identical to fav_classify_ex's at that temperature (the handle's conf_kind)
+ *   nll                 -logf(fmaxf(pbar[y], FLT_MIN)): at most 87.34, never +inf
+ *   brier               sum over c < num_classes of (pbar[c] - [c == y])^2, fp32, in a fixed order
+ * y outside [0, num_classes): nll and brier are NaN, label and confidence are still written.  The mean of nll over the
+ * frames is what a temperature is fitted on; label / confidence feed the reliability and risk-coverage metrics. */
+#define FAV_SWEEP_MAX_TEMPS 32
+typedef struct fav_calib_cell { int32_t label; float confidence; float nll; float brier; } fav_calib_cell;   /* 16 bytes */
+
+/* The forward pass of fav_classify_ex, then the sweep head instead of the plain one: cells_dev[n][K] (non-NULL, 8-byte
+ * aligned device pointer), true_labels_dev[n] (device), temps_host: K host floats, 1 <= K <= FAV_SWEEP_MAX_TEMPS, all
+ * finite and > 0 (read before the call returns).  The handle's own temperature and tau are not used.  fav_get_logits
+ * afterwards returns this call's logits. */
+fav_status fav_classify_sweep(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
+                              const int32_t* true_labels_dev, const float* temps_host, int32_t K,
+                              fav_calib_cell* cells_dev, void* hip_stream);
+/* The handle's temperature (finite, > 0) and failure threshold tau (not NaN): they take effect for calls enqueued after
+ * the setter returns; calls already enqueued keep the old value.  A rejected value leaves the handle as it was. */
+fav_status fav_set_temperature(fav_handle* h, float temperature);
+fav_status fav_set_tau(fav_handle* h, float tau);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -325,6 +348,13 @@ fav_status fav_op_head_sets(const float* logits, int32_t T, int32_t n, int32_t n
                             float temperature, int32_t conf_kind, float tau, int64_t first_image_index,
                             const fav_conformal* cp, const int32_t* true_labels, float* true_scores,
                             fav_pred_set* records, uint8_t* fail, float* score, void* hip_stream);
+
+/* logits fp32 [T][n][ld] (device) -> cells[n][K] (fav_calib_cell, 8-byte aligned) at the K temperatures temps_host
+ * (host floats, 1 <= K <= FAV_SWEEP_MAX_TEMPS, all finite and > 0), one launch that reads the logits once.  T <= 4096,
+ * num_classes <= 1024; conf_kind 0, 1 or 2 (kind 2 needs T >= 2 and num_classes >= 2, as for fav_op_head). */
+fav_status fav_op_head_sweep(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld,
+                             const float* temps_host, int32_t K, int32_t conf_kind, const int32_t* true_labels_dev,
+                             fav_calib_cell* cells_dev, void* hip_stream);
 
 /* ---- ViT building blocks (BASELINE configs[4]); linear layers go through fav_op_conv2d with kh = kw = 1.
  * LayerNorm over rows of D bf16 values (row r at x + r*ldx elements; D % 4 == 0, D <= 1024), fp32 statistics,
