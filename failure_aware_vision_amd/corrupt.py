@@ -3,7 +3,8 @@
 (normal / frozen / blank / corrupted), ``set_noise``, ``set_brightness``, ``get_vision_status``,
 plus ``apply(frames)`` which actually produces the corrupted frames on the GPU
 (``fav_op_corrupt``) — what the browser canvas does in the reference (app.js:782-857) — and
-``gaussian(frames, severity)`` for ImageNet-C style noise.  Deterministic in (seed, frame index).
+``gaussian(frames, severity)`` for ImageNet-C style noise.  Deterministic in (seed, frame index);
+the generator keeps the low 32 bits of the frame index, so frame 2**32 + k repeats frame k.
 """
 from __future__ import annotations
 

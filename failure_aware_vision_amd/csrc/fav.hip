@@ -2470,6 +2470,9 @@ fav_status fav_op_signal_stats(const uint8_t* frames, int32_t n, int32_t H, int3
     static_assert(sizeof(fav_signal_stats) == sizeof(SignalStats), "fav_signal_stats layout");
     if (!frames || !stats || n < 1 || H < 3 || W < 4 || W % 4 != 0 || (long long)H * W > 150000)
         return op_done("fav_op_signal_stats: bad argument (need W % 4 == 0, 3 <= H, H*W <= 150000)");
+    // the kernel reads frames and prev_gray, and writes last_gray, four pixels a dword; the records hold doubles
+    if (((uintptr_t)frames | (uintptr_t)prev_gray | (uintptr_t)last_gray) % 4 != 0 || (uintptr_t)stats % 8 != 0)
+        return op_done("fav_op_signal_stats: frames, prev_gray and last_gray must be 4-byte aligned, stats 8-byte aligned");
     const size_t lds = (((size_t)H * W + 15) & ~(size_t)15) + 1024 * 4 + 16 * 8;
     if (hipFuncSetAttribute((const void*)signal_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return op_done("fav_op_signal_stats: cannot reserve LDS for the gray plane");

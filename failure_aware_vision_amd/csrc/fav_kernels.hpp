@@ -3851,6 +3851,7 @@ __global__ __launch_bounds__(256) void signal_stats_kernel(const uint8_t* __rest
 //               bars of height 2..14 blended towards (255, 0, 170) with alpha 0.4..0.9        (app.js:835-850)
 //   gaussian  : fp32 out = clamp(p/255 + sigma * N(0,1)), Box-Muller on Philox uniforms
 // Philox4x32-10, key = seed, counter = (pixel or pair index, global frame, stream, 0).
+// The global frame enters the counter as the low 32 bits of first_index + f: frame 2^32 + k draws what frame k draws.
 // ===========================================================================
 namespace fav {
 

@@ -385,7 +385,9 @@ fav_status fav_op_vit_assemble(const void* emb, const float* pos, void* x, int32
  * (ksize 1, reflect-101) variance, mean brightness, mean |gray - previous gray|, 256-bin
  * histogram entropy.  frames_bgr: [n][H][W][3] uint8 on the device, consecutive frames of
  * one stream; prev_gray: gray plane preceding frame 0 (NULL = none); last_gray_out: receives
- * the gray plane of frame n-1 (NULL = not wanted).  W % 4 == 0, H*W <= 150000. */
+ * the gray plane of frame n-1 (NULL = not wanted).  W % 4 == 0, H >= 3, H*W <= 150000.
+ * The kernel moves four pixels per dword: frames_bgr, prev_gray and last_gray_out must be
+ * 4-byte aligned and stats_dev 8-byte aligned, else FAV_ERR_INVALID_ARG and nothing is launched. */
 typedef struct fav_signal_stats {
     double lap_var, mean, mean_diff;
     float entropy;

@@ -17,7 +17,9 @@ def u01(x):
 def corrupt(frames, mode, level, gain, sigma, seed, first_index):
     n, H, W, _ = frames.shape
     px = np.arange(H * W, dtype=np.uint32)[None, :]
-    fr = (np.arange(n, dtype=np.uint32) + np.uint32(first_index))[:, None]
+    # the kernel's frame counter is the low 32 bits of first_index + f: it wraps at 2**32
+    fr = np.arange(n, dtype=np.uint64) + np.uint64(int(first_index) & 0xFFFFFFFF)
+    fr = (fr & np.uint64(0xFFFFFFFF)).astype(np.uint32)[:, None]
     k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
     c = frames.reshape(n, H * W, 3).astype(f32)
     if mode == 3:

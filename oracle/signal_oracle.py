@@ -50,30 +50,38 @@ class SignalOracle:
 
     def analyze_frame(self, frame):
         _, lap_var, mean, mean_diff, entropy, _ = self.raw(frame)
-        blur = max(0.0, min(1.0, 1.0 - lap_var / 500.0))
-        bright = max(0.0, min(1.0, abs(mean - 128.0) / 128.0))
-        if mean_diff is not None:
-            self.frozen = self.frozen + 1 if mean_diff < 1.0 else 0
-            freeze = 1.0 if self.frozen >= 5 else (0.3 * (self.frozen / 5) if self.frozen > 0 else 0.0)
-        else:
-            freeze, mean_diff = 0.0, 10.0
-        if entropy < 4.0:
-            ent = max(0.0, min(1.0, (4.0 - entropy) / 4.0))
-        elif entropy > 7.0:
-            ent = max(0.0, min(1.0, (entropy - 7.0) / 1.5))
-        else:
-            ent = 0.0
-        score = max(0.0, min(1.0, self.W[0] * blur + self.W[1] * bright + self.W[2] * freeze + self.W[3] * ent))
-        if mean < 15 or mean > 245:
-            status = "VISION_BLANK"
-        elif self.frozen >= 5:
-            status = "VISION_FROZEN"
-        elif entropy < 2.0 or entropy > 7.5:
-            status = "VISION_CORRUPTED"
-        else:
-            status = "VISION_OK"
-        return {"anomaly_score": round(score, 6), "vision_status": status,
-                "metrics": {"blur": round(blur, 4), "brightness": round(bright, 4), "freeze": round(freeze, 4),
-                            "entropy": round(ent, 4),
-                            "raw": {"laplacian_var": round(lap_var, 2), "mean_brightness": round(mean, 1),
-                                    "frame_diff": round(mean_diff, 2), "entropy": round(entropy, 3)}}}
+        res, self.frozen = score(lap_var, mean, mean_diff, entropy, self.frozen)
+        return res
+
+
+def score(lap_var, mean, mean_diff, entropy, frozen):
+    """The scalar half of analyze_frame (signal_analyzer.py:66-143,145-171) on the raw numbers; mean_diff None = first
+    frame.  Returns (result dict, new frozen run)."""
+    blur = max(0.0, min(1.0, 1.0 - lap_var / 500.0))
+    bright = max(0.0, min(1.0, abs(mean - 128.0) / 128.0))
+    if mean_diff is not None:
+        frozen = frozen + 1 if mean_diff < 1.0 else 0
+        freeze = 1.0 if frozen >= 5 else (0.3 * (frozen / 5) if frozen > 0 else 0.0)
+    else:
+        freeze, mean_diff = 0.0, 10.0
+    if entropy < 4.0:
+        ent = max(0.0, min(1.0, (4.0 - entropy) / 4.0))
+    elif entropy > 7.0:
+        ent = max(0.0, min(1.0, (entropy - 7.0) / 1.5))
+    else:
+        ent = 0.0
+    w = SignalOracle.W
+    total = max(0.0, min(1.0, w[0] * blur + w[1] * bright + w[2] * freeze + w[3] * ent))
+    if mean < 15 or mean > 245:
+        status = "VISION_BLANK"
+    elif frozen >= 5:
+        status = "VISION_FROZEN"
+    elif entropy < 2.0 or entropy > 7.5:
+        status = "VISION_CORRUPTED"
+    else:
+        status = "VISION_OK"
+    return {"anomaly_score": round(total, 6), "vision_status": status,
+            "metrics": {"blur": round(blur, 4), "brightness": round(bright, 4), "freeze": round(freeze, 4),
+                        "entropy": round(ent, 4),
+                        "raw": {"laplacian_var": round(lap_var, 2), "mean_brightness": round(mean, 1),
+                                "frame_diff": round(mean_diff, 2), "entropy": round(entropy, 3)}}}, frozen
