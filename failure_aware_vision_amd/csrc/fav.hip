@@ -3,7 +3,8 @@
 //
 // Host side of the hot path: a static schedule of kernel launches on ONE HIP
 // stream (handle is single-caller, like the reference's per-connection scorer,
-// platform/backend/main.py:110-118), a workspace arena allocated once, and
+// platform/backend/main.py:110-118; an ensemble's members and a ViT batch's parts
+// fork from it and join it), a workspace arena allocated once, and
 // Infinity-Cache-sized passes: frames go through the high-resolution stages in
 // chunks small enough that producer->consumer activations stay in the 256 MiB
 // L3, then through the low-resolution stages in larger chunks that fill the
@@ -74,10 +75,8 @@ inline bool is_vit_arch(int arch) { return arch == 2 || arch == 3; }
 struct Layer {  // one convolution / fc
     int cout, cin, kh, kw, stride, pad;
     int cout_pad, k;         // device layout: w[cout_pad][k], bias[cout_pad]
-    uint16_t* w = nullptr;          // weights / bias of the member being run
-    float* b = nullptr;
     std::vector<uint16_t*> w_m;     // per ensemble member: w_slab + member * w_stride (one allocation, so that a grouped
-    std::vector<float*> b_m;        // launch reaches member g's weights at a constant stride)
+    std::vector<float*> b_m;        // launch reaches member g's weights at a constant stride); a single model is member 0
     void *w_slab = nullptr, *b_slab = nullptr;
     size_t w_stride = 0, b_stride = 0;
 };
@@ -109,6 +108,28 @@ struct Phase {
     bool low_res;            // belongs to the low-resolution group (chunk_b)
     int chunk;
 };
+const int kMaxPhases = 4;    // build_graph: prefix and suffix, each split at most once (at the low-resolution group)
+
+// What a grouped launch adds to a launch: every op of the schedule is ONE launch over all members - block row blockIdx.y is
+// member y, whose tensors lie at a constant byte stride behind member 0's (the workspaces and the weights are slabs).
+// run_chunks builds it per op and hands it to the launcher; default-constructed: one member, no strides.
+struct Group { int n = 1; long long x = 0, w = 0, b = 0, res = 0, y = 0, wb = 0, bb = 0, wa = 0, ba = 0, y2 = 0; };
+
+// Where run_chunks launches: a stream, a workspace, a member's weights.  Every handle has at least one lane: a single model
+// is lane 0 on the caller's stream; an ensemble has one lane per member on the member's own stream, and a grouped call runs
+// lane 0 on the caller's stream with groups = n_members.  The buffers are views: the handle owns (and frees) the slabs.
+struct Lane {
+    hipStream_t stream = nullptr;   // the member's own stream (an ensemble); a call on the caller's stream fills in its copy
+    hipEvent_t done = nullptr;      // with `stream`: the member's join
+    void* act[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    void* a1 = nullptr;
+    void* phase_out[kMaxPhases] = {nullptr, nullptr, nullptr, nullptr};   // all but the last phase's, which writes the logits
+    int member = 0;                 // whose weights, and whose slot of the logits
+    int groups = 1;                 // > 1: every op one launch over this many members, from this lane's at a constant stride
+};
+
+// The frames of one call
+struct Frames { const void* images; int layout; int n; long long first_index; };
 
 }  // namespace
 
@@ -122,34 +143,21 @@ struct fav_handle {
     bool weights_loaded = false;
     std::vector<char> member_loaded;   // deep ensemble (BASELINE configs[3]): one checkpoint per member
     int n_members = 1;
-    // workspace
+    // workspace: the slabs (n_members equal parts each for an ensemble, so that a grouped launch finds member g's tensors at a
+    // constant stride); the lanes hold views into them
     void* act[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t act_bytes = 0;
-    // two-stream pipeline over the last two phases: the low-resolution,
-    // MFMA-bound phase of chunk c runs on stream_b while the high-resolution, HBM-bound
-    // phase of chunk c+1 runs on stream_a.  The second phase has its own rotating set.
-    void* act2[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t act2_bytes = 0;
-    int pipe_first = -1;            // index of the first phase of the pipelined pair (-1: none)
-    hipStream_t stream_a = nullptr, stream_b = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join_a = nullptr, ev_join_b = nullptr;
-    std::vector<hipEvent_t> ev_chunk;
+    hipEvent_t ev_fork = nullptr;   // ViT: the fork of a split batch
     void* a1 = nullptr;
     size_t a1_bytes = 0;
-    // deep ensemble (BASELINE configs[3]): the members are independent networks over the same frames, so each runs on
-    // its own stream with its own rotating buffers (member 0: the handle's) and the head waits for all of them - at
-    // the per-GPU share of 32 frames a single member leaves most CUs idle in layers 3-4.  FAV_ENS_STREAMS=0: serial.
-    struct MemberWs { void* act[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; void* a1 = nullptr; std::vector<void*> phase_out;
-                      hipStream_t stream = nullptr; hipEvent_t done = nullptr; };
-    std::vector<MemberWs> mws;
+    // One lane per member (a single model: lane 0, no stream of its own).  Deep ensemble (BASELINE configs[3]): the members are
+    // independent networks over the same frames, so each runs on its own stream with its own rotating buffers and the head
+    // waits for all of them - at the per-GPU share of 32 frames a single member leaves most CUs idle in layers 3-4 - unless
+    // the call is grouped (will_group).  (The members one after another on the caller's stream: 4 290 against 7 580 frames/s
+    // at 32 frames per call; the code is gone, its record is tools/experiments/ensemble_serial_members.diff.)
+    std::vector<Lane> lanes;
     hipEvent_t ev_members = nullptr;
-    // Grouped launches (default: every call; fav_config.ens_grouped_max limits the frames per call or switches them off): every op of
-    // the schedule is ONE launch over all members - block row blockIdx.y is member y, whose tensors lie at a constant byte
-    // stride behind member 0's (the workspaces and the weights are slabs).  `grp` is what the launchers add to a launch.
-    struct Group { int n = 1; long long x = 0, w = 0, b = 0, res = 0, y = 0, wb = 0, bb = 0, wa = 0, ba = 0, y2 = 0; };
-    Group grp;
-    bool can_group = false;
-    int group_max_frames = 0;
+    bool plan_has_mc = false, plan_stem_fused = false;   // build_graph: what will_group asks about the schedule
     std::vector<hipStream_t> vit_streams;   // ViT: parts of the batch side by side
     std::vector<hipEvent_t> vit_done;
     // chained stream-K GEMM (gemm_streamk_kernel): one workspace per stream the encoder may run on (slot 0: the caller's)
@@ -157,7 +165,7 @@ struct fav_handle {
     SkWs sk[5];
     int sk_slot = 0;                        // the slot run_vit's launches use
     bool plan_no_fuse = false;      // fav_plan_schedule: build the layer-by-layer schedule (the fused one's reference)
-    std::vector<void*> phase_out;   // output tensor of each phase
+    std::vector<void*> phase_out;   // output slab of each phase but the last (whose output is the logits)
     float* logits = nullptr;        // [T][max_batch][cpad]
     int cpad = 0;
     int last_T = 0, last_n = 0;
@@ -170,7 +178,7 @@ struct fav_handle {
     // stream and host_stream, or two torch streams) are then ordered on the device instead of racing on the activations.
     hipEvent_t ev_last = nullptr;
     bool ev_last_set = false;
-    // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w / b), fixed buffers
+    // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     int vit_ntok = 0;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -300,14 +308,13 @@ bool proj_enabled() {
     return FAV_KNOB("FAV_PROJ", 1) != 0;
 }
 
-bool launch_proj(fav_handle* h, const fav_conv_desc& d, hipStream_t s) {
+bool launch_proj(fav_handle* h, const fav_conv_desc& d, const Group& G, hipStream_t s) {
     const bool wide = d.Cin == 512 && d.Cout == 1024;       // layer 3's shortcut: 8 waves x 32 pixels, one block per CU
     if (!proj_enabled() || d.kh != 1 || d.kw != 1 || d.pad != 0 || !((d.Cin == 256 && d.Cout == 512) || wide) || d.res || d.drop.site >= 0 ||
         d.out_f32 || d.relu != 0 || d.math_mode != FAV_MATH_BF16 || (d.stride != 1 && d.stride != 2)) return false;
     const int Ho = conv_out(d.H, 1, d.stride, 0), Wo = conv_out(d.W, 1, d.stride, 0);
     const long long M = (long long)d.n_frames * Ho * Wo;
-    const int groups = h ? h->grp.n : 1;               // a grouped launch is as large as all its members together
-    if (M * groups < (wide ? 512 * 256 : 4096) || M > 0x7fffffffLL || (long long)d.H * d.W * d.Cin * 2 * 4 >= 0x40000000LL) return false;
+    if (M * G.n < (wide ? 512 * 256 : 4096) || M > 0x7fffffffLL || (long long)d.H * d.W * d.Cin * 2 * 4 >= 0x40000000LL) return false;
     TailParams p;
     memset(&p, 0, sizeof p);
     p.t1 = (const uint16_t*)d.x; p.wc = (const uint16_t*)d.w; p.bias_c = d.bias; p.y = (uint16_t*)d.y;
@@ -321,7 +328,6 @@ bool launch_proj(fav_handle* h, const fav_conv_desc& d, hipStream_t s) {
     p.div_hw = fastdiv_make((uint32_t)p.HW);
     p.div_w = fastdiv_make((uint32_t)Wo);
     p.dbg = nullptr;
-    const fav_handle::Group G = h ? h->grp : fav_handle::Group{};
     p.g_t1 = G.x; p.g_wc = G.w; p.g_bc = G.b; p.g_y = G.y;
     const int lds = p.zero_off + 256;
     auto kern = bottleneck_tail_kernel<256, 0, false, 2, 4, true, 32, 512, false, false>;
@@ -341,14 +347,14 @@ bool launch_proj(fav_handle* h, const fav_conv_desc& d, hipStream_t s) {
 }
 
 
-const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int ldy, hipStream_t s) {
+const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int ldy, const Group& G, hipStream_t s) {
     if (d.Cin % 64 != 0) return "conv: Cin must be a multiple of 64";
     if (cout_pad % 64 != 0) return "conv: padded Cout must be a multiple of 64";
     // the bf16 epilogues store whole 16-byte groups of channels and range-check rows only: padded columns would land in
     // the next pixel's first channels.  Only the fp32 (logit) output, whose row pitch is the padded width, may be padded.
     if (!d.out_f32 && cout_pad != d.Cout) return "conv: a bf16 output needs Cout to be a multiple of 64 (no column padding)";
     if (d.out_f32 && ldy < cout_pad) return "conv: the fp32 output's row pitch must cover the padded Cout";
-    if (cout_pad == d.Cout && ldy == d.Cout && launch_proj(h, d, s)) return nullptr;
+    if (cout_pad == d.Cout && ldy == d.Cout && launch_proj(h, d, G, s)) return nullptr;
     ConvParams p;
     p.x = (const uint16_t*)d.x; p.w = (const uint16_t*)d.w; p.bias = d.bias; p.res = (const uint16_t*)d.res; p.y = d.y;
     p.H = d.H; p.W = d.W; p.Cin = d.Cin;
@@ -367,7 +373,6 @@ const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int
     p.div_w = fastdiv_make((uint32_t)p.Wo);
     if (p.drop.site >= 0 && (p.drop.v0 < 0 || p.drop.v0 + d.n_frames > 0x7fffffffLL)) return "conv: virtual frame index out of range";
     p.dbg = nullptr;
-    const fav_handle::Group G = h ? h->grp : fav_handle::Group{};
     p.g_x = G.x; p.g_w = G.w; p.g_bias = G.b; p.g_res = G.res; p.g_y = G.y;
     if (d.out_f32 && p.drop.site >= 0) return "conv: dropout on fp32 output unsupported";
     // the ViT encoder's GEMMs (M = 197 rows per frame, K = 768 / 3072): the 256 x 256 tile from 50 of them up (measured, round 4,
@@ -580,7 +585,7 @@ bool tail_enabled() {
     return FAV_KNOB("FAV_FUSE", 1) != 0;
 }
 
-const char* launch_tail(fav_handle* h, const fav_tail_desc& d, hipStream_t s) {
+const char* launch_tail(fav_handle* h, const fav_tail_desc& d, const Group& G, hipStream_t s) {
     const bool has3x3 = d.wb != nullptr;
     const int nred = d.wa ? d.Nred : 0;
     TailGeom g;
@@ -599,7 +604,6 @@ const char* launch_tail(fav_handle* h, const fav_tail_desc& d, hipStream_t s) {
     p.div_hw = fastdiv_make((uint32_t)p.HW);
     p.div_w = fastdiv_make((uint32_t)d.W);
     if (p.drop.site >= 0 && (p.drop.v0 < 0 || p.drop.v0 + d.n_frames > 0x7fffffffLL)) return "bottleneck tail: virtual frame index out of range";
-    const fav_handle::Group G = h ? h->grp : fav_handle::Group{};
     p.g_t1 = G.x; p.g_res = G.res; p.g_y = G.y; p.g_t1n = G.y2;
     p.g_wb = G.wb; p.g_bb = G.bb; p.g_wc = G.w; p.g_bc = G.b; p.g_wa = G.wa; p.g_ba = G.ba;
     p.site_e = d.entry_site;
@@ -762,7 +766,7 @@ void launch_maxpool(fav_handle* h, const void* x, void* y, int n, int H, int W, 
 
 // normalise + 7x7/2 conv (64 channels, weights [64][192]) + bias + ReLU + 3x3/2 max pool, frames -> [n][Hp][Wp][64] bf16
 const char* launch_stem_pool(fav_handle* h, const void* images, int layout, int n, int H, int W, const void* w, const float* bias,
-                             const float* mean, const float* istd, void* out, hipStream_t s) {
+                             const float* mean, const float* istd, void* out, const Group& G, hipStream_t s) {
     if (n < 1 || H < 1 || W < 1) return "stem: empty input";
     if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return "stem: unknown layout";
     StemPoolParams p;
@@ -775,7 +779,6 @@ const char* launch_stem_pool(fav_handle* h, const void* images, int layout, int 
     p.tiles_y = (p.Hp + 7) / 8; p.tiles_x = (p.Wp + 7) / 8;
     p.tiles = (long long)n * p.tiles_y * p.tiles_x;
     p.m0 = mean[0]; p.m1 = mean[1]; p.m2 = mean[2]; p.i0 = istd[0]; p.i1 = istd[1]; p.i2 = istd[2];
-    const fav_handle::Group G = h ? h->grp : fav_handle::Group{};
     p.g_w = G.w; p.g_bias = G.b; p.g_out = G.y;
     const double M = (double)n * p.Hc * p.Wc;
     Prof pr(h, s, FAV_K_CONV, 2.0 * M * 64 * 192 * G.n,
@@ -787,11 +790,10 @@ const char* launch_stem_pool(fav_handle* h, const void* images, int layout, int 
     return nullptr;
 }
 
-void launch_avgpool(fav_handle* h, const void* x, void* y, int n, int HW, int C, const DropParams& dp, hipStream_t s) {
+void launch_avgpool(fav_handle* h, const void* x, void* y, int n, int HW, int C, const DropParams& dp, const Group& G, hipStream_t s) {
     const long long total = (long long)n * (C / 16);
     Prof pr(h, s, FAV_K_AVGPOOL, 0.0, 2.0 * ((double)n * HW * C + (double)n * C));
     const float inv = 1.0f / (float)HW;
-    const fav_handle::Group G = h ? h->grp : fav_handle::Group{};
     hipLaunchKernelGGL(avgpool_kernel, dim3(grid_for(total), G.n), dim3(256), 0, s, (const uint4*)x, (uint4*)y, n, HW, C, inv,
                        dp, G.x, G.y);
 }
@@ -875,11 +877,26 @@ const char* check_sweep(const HeadSweep& sw, int C, int T, int kind) {
     return nullptr;
 }
 
+// What the head writes: labels and conf out_stride elements apart (2: interleaved records), the optional failure flags and
+// scores, and at most one of rec (one fav_uncertainty per frame), sets and sweep.  The public entry points build it;
+// classify_gate and classify_on_stream pass it through.
+struct HeadOut {
+    int32_t* labels = nullptr;
+    float* conf = nullptr;
+    uint8_t* fail = nullptr;
+    float* score = nullptr;
+    int out_stride = 1;
+    fav_uncertainty* rec = nullptr;
+    const HeadSets* sets = nullptr;
+    const HeadSweep* sweep = nullptr;
+};
+
 // rec (one fav_uncertainty per frame) or conf_kind FAV_CONF_MUTUAL_INFO: head_unc_kernel; sets: head_sets_kernel;
 // sweep: head_sweep_kernel (temperature, tau, labels .. score are then not used); otherwise head_kernel
 const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C, int ld, float temperature, int kind,
-                        float tau, int* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride = 1,
-                        fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr, const HeadSweep* sweep = nullptr) {
+                        float tau, const HeadOut& out, hipStream_t s) {
+    const HeadSets* const sets = out.sets;
+    const HeadSweep* const sweep = out.sweep;
     if (sweep)
         if (const char* e = check_sweep(*sweep, C, T, kind)) return e;
     if (C > 1024 || C < 1) return "head: num_classes must be in [1, 1024]";
@@ -937,17 +954,17 @@ const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C,
         p.first_index = sets->first_index;
         // bytes: the logits, the labels and scores of a calibration call, the outputs
         Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + (sets->true_labels ? 8.0 : 0.0) * n +
-                                       (sets->rec ? 160.0 : 0.0) * n + (fail ? 1.0 : 0.0) * n + (score ? 4.0 : 0.0) * n);
-        FAV_LAUNCH_HEAD(head_sets_kernel, 0, inv_lnK, p, sets->true_labels, sets->true_scores, (int*)sets->rec, fail, score);
-    } else if (rec || kind == FAV_CONF_MUTUAL_INFO) {
+                                       (sets->rec ? 160.0 : 0.0) * n + (out.fail ? 1.0 : 0.0) * n + (out.score ? 4.0 : 0.0) * n);
+        FAV_LAUNCH_HEAD(head_sets_kernel, 0, inv_lnK, p, sets->true_labels, sets->true_scores, (int*)sets->rec, out.fail, out.score);
+    } else if (out.rec || kind == FAV_CONF_MUTUAL_INFO) {
         if (T < 1 || T > 4096) return "head: the uncertainty head takes 1 <= T <= 4096 samples";
         // bytes: the logits, the second pass's p_t[label] reloads, the outputs
-        Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 4.0 * (double)T * n + (rec ? 72.0 : 8.0) * n);
+        Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 4.0 * (double)T * n + (out.rec ? 72.0 : 8.0) * n);
         // dynamic LDS: per-sample max and 1/sum
-        FAV_LAUNCH_HEAD(head_unc_kernel, (size_t)T * 8, inv_lnK, labels, conf, fail, score, out_stride, (int*)rec);
+        FAV_LAUNCH_HEAD(head_unc_kernel, (size_t)T * 8, inv_lnK, out.labels, out.conf, out.fail, out.score, out.out_stride, (int*)out.rec);
     } else {
         Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 8.0 * n);
-        FAV_LAUNCH_HEAD(head_kernel, 0, labels, conf, fail, score, out_stride);
+        FAV_LAUNCH_HEAD(head_kernel, 0, out.labels, out.conf, out.fail, out.score, out.out_stride);
     }
 #undef FAV_LAUNCH_HEAD
     return nullptr;
@@ -1094,15 +1111,14 @@ void launch_vit_assemble(fav_handle* h, const void* emb, const float* pos, void*
     hipLaunchKernelGGL(vit_assemble_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t*)emb, pos, (uint16_t*)x, n, ntok, D);
 }
 
-// A deep ensemble runs every op as ONE launch over its members (classify_on_stream) when: there is no MC-Dropout suffix, the
-// production math mode, the one-launch stem, the members' workspaces side by side, fav_config.ens_grouped_max >= 0 - and the call
-// has at most ens_grouped_max frames.  build_graph plans the size-dependent tail kernels of layers 3-4 for max_batch frames, so it
-// asks with the same predicate whether a call of max_batch frames will be grouped.
-bool will_group(const fav_handle* h, bool has_mc, bool stem_fused) {
+// A deep ensemble runs every op as ONE launch over its members (run_grouped) when: there is no MC-Dropout suffix, the production
+// math mode, the one-launch stem (every op is then one the grouped kernels cover), fav_config.ens_grouped_max >= 0 - and the call
+// has at most ens_grouped_max frames.  The one predicate: classify_on_stream asks it with the call's frames; build_graph, which
+// plans the size-dependent tail kernels of layers 3-4 for max_batch frames, asks whether a call of max_batch frames will be grouped.
+bool will_group(const fav_handle* h, int frames) {
     const fav_config& c = h->cfg;
-    if (h->n_members <= 1 || has_mc || c.math_mode != FAV_MATH_BF16 || !stem_fused || c.ens_grouped_max < 0) return false;
-    if (FAV_KNOB("FAV_ENS_STREAMS", 1) == 0) return false;
-    return c.ens_grouped_max == 0 || c.max_batch <= c.ens_grouped_max;
+    if (h->n_members <= 1 || h->plan_has_mc || c.math_mode != FAV_MATH_BF16 || !h->plan_stem_fused || c.ens_grouped_max < 0) return false;
+    return c.ens_grouped_max == 0 || frames <= c.ens_grouped_max;
 }
 
 fav_status build_graph(fav_handle* h) {
@@ -1140,6 +1156,7 @@ fav_status build_graph(fav_handle* h) {
     // production math mode: the whole ImageNet stem (normalise, 7x7/2, ReLU, max pool) is one launch
     const bool stem_fused = A.imagenet_stem && c.math_mode == FAV_MATH_BF16 && c.stem_fused >= 0 && !h->plan_no_fuse &&
                             conv_out(Ho, 3, 2, 1) >= 1 && conv_out(Wo, 3, 2, 1) >= 1;
+    h->plan_stem_fused = stem_fused;
     int stem_ops = 0;
     if (stem_fused) {
         Op o; o.kind = OP_STEM_POOL; o.layer = li; o.in = B_INPUT; o.out = cur; o.relu = 1;
@@ -1184,6 +1201,7 @@ fav_status build_graph(fav_handle* h) {
     int regroup_blk = c.regroup_block;
     if (regroup_blk < 0) regroup_blk = A.depths[0] + A.depths[1];
     regroup_blk = std::min(regroup_blk, nblocks_total);
+    h->plan_has_mc = mc_first_site >= 0;
     int pre_t1 = -1;   // rotating buffer already holding the coming block's conv1 output
     for (int st = 0; st < 4; ++st) {
         for (int bi = 0; bi < A.depths[st]; ++bi, ++bidx) {
@@ -1218,8 +1236,8 @@ fav_status build_graph(fav_handle* h) {
                 TailGeom tg;
                 // the 256-pixel / 8-wave kernels of layers 3-4 run one block per CU: they pay only when the planned launch
                 // (max_batch frames, x T samples behind the first dropout site) brings two blocks per CU
-                // (an ensemble without MC-Dropout runs every op as one launch over its members, see classify_on_stream)
-                const int plan_groups = will_group(h, mc_first_site >= 0, stem_fused) ? h->n_members : 1;
+                // (an ensemble without MC-Dropout runs every op as one launch over its members, see run_grouped)
+                const int plan_groups = will_group(h, c.max_batch) ? h->n_members : 1;
                 const long long plan_rows = (long long)c.max_batch * ((mc_first_site >= 0 && bidx > mc_first_site) ? c.n_samples : 1) * Hn * Wn * plan_groups;
                 const bool big_launch = c.tail_min_rows < 0 || plan_rows >= (c.tail_min_rows > 0 ? (long long)c.tail_min_rows : 512ll * 256);
                 const bool tail_3x3 = (s == 1) && (pl <= 128 || (pl == 256 && tail_wide3x3() && big_launch));
@@ -1404,12 +1422,9 @@ fav_status build_graph(fav_handle* h) {
 fav_status plan_memory(fav_handle* h) {
     const fav_config& c = h->cfg;
     const long long nv_max = (long long)c.max_batch * h->T_eff;
+    const size_t nph = h->phases.size();
+    if (nph > (size_t)kMaxPhases) { h->err = "schedule has more phases than a lane holds"; return FAV_ERR_UNSUPPORTED; }
     // chunk sizes
-    long long max_elems = 1, max_a1 = 1;
-    for (const Op& o : h->ops) {
-        if (o.out == B_A1) max_a1 = std::max(max_a1, o.out_elems);
-        else if (o.out >= 0) max_elems = std::max(max_elems, o.out_elems);
-    }
     for (size_t i = 0; i < h->phases.size(); ++i) {
         Phase& p = h->phases[i];
         long long pe = 1;
@@ -1429,171 +1444,125 @@ fav_status plan_memory(fav_handle* h) {
         const long long dom = p.suffix ? nv_max : c.max_batch;
         p.chunk = (int)std::max<long long>(1, std::min(chunk, dom));
     }
-    // pipeline the last two phases when they cover the same frames (both suffix, or both
-    // prefix when there is no MC-Dropout): FAV_PIPE = number of chunks.  Default 1 = off:
-    // measured on MI355X the two kernels only time-share the CUs (each already fills every
-    // CU's LDS), 118.5 ms/step off vs 119.0-121.2 with 2..16 chunks.
-    {
-        const int npipe = (int)std::max<long long>(1, FAV_KNOB("FAV_PIPE", 1));
-        const size_t np = h->phases.size();
-        h->pipe_first = -1;
-        if (npipe > 1 && np >= 2 && h->phases[np - 1].suffix == h->phases[np - 2].suffix) {
-            const long long dom = h->phases[np - 1].suffix ? nv_max : c.max_batch;
-            if (dom >= 2 * npipe) {
-                long long step = (dom + npipe - 1) / npipe;
-                if (c.chunk_a > 0) step = std::min<long long>(step, c.chunk_a);
-                step = std::min<long long>(step, std::min(h->phases[np - 2].chunk, h->phases[np - 1].chunk));
-                h->phases[np - 2].chunk = h->phases[np - 1].chunk = (int)step;
-                h->pipe_first = (int)np - 2;
-            }
-        }
-    }
-    int max_chunk = 1;
-    for (const Phase& p : h->phases) max_chunk = std::max(max_chunk, p.chunk);
+    // (Running the last two phases as a two-stream pipeline - the low-resolution phase of chunk c beside the high-resolution
+    // phase of chunk c+1 - measured 119.0-121.2 ms per step against 118.5 ms without; the code is gone, its
+    // record is tools/experiments/phase_pipeline_two_streams.diff.)
     // rotating buffers sized for the largest (chunk x tensor) in any phase
-    size_t act_bytes = 0, act2_bytes = 0, a1_bytes = 0;
-    for (size_t pi = 0; pi < h->phases.size(); ++pi) {
-        const Phase& p = h->phases[pi];
-        const bool second = h->pipe_first >= 0 && (int)pi == h->pipe_first + 1;
+    size_t act_bytes = 0, a1_bytes = 0;
+    for (const Phase& p : h->phases) {
         for (int k = p.op_begin; k < p.op_end; ++k) {
             const Op& o = h->ops[k];
             const size_t b = (size_t)o.out_elems * (o.out_f32 ? 4 : 2) * p.chunk;
             if (o.out == B_A1) a1_bytes = std::max(a1_bytes, b);
-            else if (o.out >= 0) (second ? act2_bytes : act_bytes) = std::max(second ? act2_bytes : act_bytes, b);
+            else if (o.out >= 0) act_bytes = std::max(act_bytes, b);
         }
     }
     act_bytes = (act_bytes + 255) / 256 * 256 + 256;
     a1_bytes = (a1_bytes + 255) / 256 * 256 + 256;
-    // deep ensemble with its members side by side: every workspace tensor is a slab of n_members equal parts (member 0's part
-    // is the handle's own buffer), so that a grouped launch finds member g's tensors at a constant stride
-    const int ens_streams = (int)FAV_KNOB("FAV_ENS_STREAMS", 1);
-    const bool side_by_side = h->n_members > 1 && ens_streams && h->pipe_first < 0;
-    const size_t parts = side_by_side ? (size_t)h->n_members : 1;
+    // every workspace tensor is a slab of n_members equal parts, so that a grouped launch finds member g's tensors at a constant stride
+    const size_t parts = (size_t)h->n_members;
     for (int i = 0; i < 5; ++i) HIP_TRY(h, hipMalloc(&h->act[i], act_bytes * parts));
     h->act_bytes = act_bytes;
-    if (h->pipe_first >= 0) {
-        act2_bytes = (act2_bytes + 255) / 256 * 256 + 256;
-        for (int i = 0; i < 5; ++i) HIP_TRY(h, hipMalloc(&h->act2[i], act2_bytes));
-        h->act2_bytes = act2_bytes;
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->stream_a, hipStreamNonBlocking));
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->stream_b, hipStreamNonBlocking));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_join_a, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_join_b, hipEventDisableTiming));
-    }
     HIP_TRY(h, hipMalloc(&h->a1, a1_bytes * parts));
     h->a1_bytes = a1_bytes;
-    h->phase_out.assign(h->phases.size(), nullptr);
-    std::vector<size_t> phase_bytes(h->phases.size(), 0);
-    for (size_t i = 0; i + 1 < h->phases.size(); ++i) {
+    h->phase_out.assign(nph, nullptr);
+    std::vector<size_t> phase_bytes(nph, 0);
+    for (size_t i = 0; i + 1 < nph; ++i) {
         const Phase& p = h->phases[i];
         const long long dom = p.suffix ? nv_max : c.max_batch;
         phase_bytes[i] = ((size_t)dom * p.out_elems * p.out_bytes_per_elem + 255) / 256 * 256 + 256;
         HIP_TRY(h, hipMalloc(&h->phase_out[i], phase_bytes[i] * parts));
     }
     HIP_TRY(h, hipMalloc((void**)&h->logits, (size_t)nv_max * h->n_members * h->cpad * 4 + 256));
-    h->phase_out.back() = h->logits;
-    if (side_by_side) {
-        h->mws.resize(h->n_members);
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_members, hipEventDisableTiming));
-        for (int m = 0; m < h->n_members; ++m) {
-            fav_handle::MemberWs& w = h->mws[m];
+    h->lanes.resize(h->n_members);
+    if (h->n_members > 1) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_members, hipEventDisableTiming));
+    for (int m = 0; m < h->n_members; ++m) {
+        Lane& w = h->lanes[m];
+        w.member = m;
+        if (h->n_members > 1) {     // a single model runs on the caller's stream
             HIP_TRY(h, hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
             HIP_TRY(h, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
-            w.phase_out.assign(h->phases.size(), nullptr);
-            for (int i = 0; i < 5; ++i) w.act[i] = (char*)h->act[i] + (size_t)m * act_bytes;
-            w.a1 = (char*)h->a1 + (size_t)m * a1_bytes;
-            for (size_t i = 0; i + 1 < h->phases.size(); ++i) w.phase_out[i] = (char*)h->phase_out[i] + (size_t)m * phase_bytes[i];
         }
-        // grouped launches: every op must be one the grouped kernels cover (no MC-Dropout suffix, fused stem)
-        h->can_group = h->T_eff == 1 && c.math_mode == FAV_MATH_BF16;
-        for (const Op& o : h->ops)
-            if (o.kind != OP_STEM_POOL && o.kind != OP_CONV && o.kind != OP_TAIL && o.kind != OP_AVGPOOL) h->can_group = false;
-        for (const Op& o : h->ops) if (o.site >= 0) h->can_group = false;
-        if (c.ens_grouped_max < 0) h->can_group = false;      // (build_graph planned with will_group(): the same conditions, asked for max_batch frames)
-        h->group_max_frames = c.ens_grouped_max > 0 ? c.ens_grouped_max : 0x7fffffff;
+        for (int i = 0; i < 5; ++i) w.act[i] = (char*)h->act[i] + (size_t)m * act_bytes;
+        w.a1 = (char*)h->a1 + (size_t)m * a1_bytes;
+        for (size_t i = 0; i + 1 < nph; ++i) w.phase_out[i] = (char*)h->phase_out[i] + (size_t)m * phase_bytes[i];
     }
     return FAV_OK;
 }
 
 // ------------------------------------------------------------------ execution
-// member >= 0: that ensemble member's weights (instead of the handle's current L.w / L.b); [k_lo, k_hi): restrict the
-// launches to these ops of the phase (-1: all) - the ensemble enqueues op by op across its members' streams
-fav_status run_chunks(fav_handle* h, size_t pi, const void* images, int layout, int n, long long first_index,
-                      hipStream_t s, long long v_begin, long long v_end, void** act_set, const fav_handle::MemberWs* ws = nullptr,
-                      int member = -1, int k_lo = -1, int k_hi = -1, int group_n = 1) {
+// Virtual frames [v_begin, v_end) of phase pi on the lane's stream, in the lane's workspace, with the lane's member's weights;
+// lane.groups > 1: every op one launch over that many members.  Member m writes logits[m][n][cpad]: the head then averages
+// members exactly as it averages samples.
+fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lane, long long v_begin, long long v_end) {
     const fav_config& c = h->cfg;
     const Phase& p = h->phases[pi];
-    auto LW = [&](int li) -> void* { return member >= 0 ? h->layers[li].w_m[member] : h->layers[li].w; };
-    auto LB = [&](int li) -> float* { return member >= 0 ? h->layers[li].b_m[member] : h->layers[li].b; };
-    const int op_lo = k_lo >= 0 ? std::max(k_lo, p.op_begin) : p.op_begin, op_hi = k_hi >= 0 ? std::min(k_hi, p.op_end) : p.op_end;
-    const long long dom = p.suffix ? (long long)n * h->T_eff : n;
-    const std::vector<void*>& phase_out = ws ? ws->phase_out : h->phase_out;
-    void* const a1 = ws ? ws->a1 : h->a1;
-    const char* pin_base = pi == 0 ? (const char*)images : (const char*)phase_out[pi - 1];
+    const hipStream_t s = lane.stream;
+    const int n = f.n, layout = f.layout;
+    auto LW = [&](int li) -> void* { return h->layers[li].w_m[lane.member]; };
+    auto LB = [&](int li) -> float* { return h->layers[li].b_m[lane.member]; };
+    const size_t logits_slot = (size_t)n * h->cpad * 4;     // one member's part of the logits in a call of n frames
+    const bool last = pi + 1 == h->phases.size();
+    const char* pin_base = pi == 0 ? (const char*)f.images : (const char*)lane.phase_out[pi - 1];
     const int in_bpe = pi == 0 ? (layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4) : h->phases[pi - 1].out_bytes_per_elem;
     // a suffix phase that follows the prefix reads frame (v % n); later phases read virtual frame v
     const bool in_is_virtual = pi > 0 && h->phases[pi - 1].suffix;
-    char* pout_base = (char*)phase_out[pi];
+    char* pout_base = last ? (char*)h->logits + (size_t)lane.member * logits_slot : (char*)lane.phase_out[pi];
     const uint32_t thr = (uint32_t)std::lround((double)c.dropout_p * 256.0);
     const float scale = thr > 0 ? (float)(1.0 / (1.0 - thr / 256.0)) : 1.0f;
     float istd[3] = {1.0f / c.stdev[0], 1.0f / c.stdev[1], 1.0f / c.stdev[2]};
 
-    (void)dom;
     for (long long v0 = v_begin; v0 < v_end; v0 += p.chunk) {
         const int cn = (int)std::min<long long>(p.chunk, v_end - v0);
-        auto buf = [&](int id, bool is_out, const Op& o) -> void* {
+        auto buf = [&](int id, const Op& o) -> void* {
             switch (id) {
                 case B_INPUT: return (void*)(pin_base + (size_t)v0 * o.in_elems * in_bpe);
                 case B_PHASE_IN:
                     if (!in_is_virtual && p.suffix) return (void*)pin_base;  // entry dropout indexes v % n itself
                     return (void*)(pin_base + (size_t)v0 * p.in_elems * in_bpe);
                 case B_PHASE_OUT: return (void*)(pout_base + (size_t)v0 * p.out_elems * p.out_bytes_per_elem);
-                case B_A1: return a1;
+                case B_A1: return lane.a1;
                 case B_NONE: return nullptr;
-                default: return act_set[id];
+                default: return lane.act[id];
             }
         };
-        // grouped launch (ws = member 0's workspace): byte stride from member 0's tensor to member 1's, per buffer and per layer
+        // grouped launch: byte stride from this lane's tensor to the next member's, per buffer and per layer
         auto gbuf = [&](int id) -> long long {
-            if (group_n <= 1) return 0;
-            const fav_handle::MemberWs &w0 = h->mws[0], &w1 = h->mws[1];
+            const Lane& next = h->lanes[lane.member + 1];
             switch (id) {
                 case B_INPUT: case B_NONE: return 0;
-                case B_PHASE_IN: return pi == 0 ? 0 : (char*)w1.phase_out[pi - 1] - (char*)w0.phase_out[pi - 1];
-                case B_PHASE_OUT: return (char*)w1.phase_out[pi] - (char*)w0.phase_out[pi];
-                case B_A1: return (char*)w1.a1 - (char*)w0.a1;
-                default: return (char*)w1.act[id] - (char*)w0.act[id];
+                case B_PHASE_IN: return pi == 0 ? 0 : (char*)next.phase_out[pi - 1] - (char*)lane.phase_out[pi - 1];
+                case B_PHASE_OUT: return last ? (long long)logits_slot : (char*)next.phase_out[pi] - (char*)lane.phase_out[pi];
+                case B_A1: return (char*)next.a1 - (char*)lane.a1;
+                default: return (char*)next.act[id] - (char*)lane.act[id];
             }
         };
-        auto gw = [&](int li) -> long long { return group_n > 1 && li >= 0 ? (long long)h->layers[li].w_stride : 0; };
-        auto gb = [&](int li) -> long long { return group_n > 1 && li >= 0 ? (long long)h->layers[li].b_stride : 0; };
-        struct GroupReset { fav_handle* h; ~GroupReset() { h->grp = fav_handle::Group{}; } } group_reset{h};
-        for (int k = op_lo; k < op_hi; ++k) {
+        auto gw = [&](int li) -> long long { return li >= 0 ? (long long)h->layers[li].w_stride : 0; };
+        auto gb = [&](int li) -> long long { return li >= 0 ? (long long)h->layers[li].b_stride : 0; };
+        for (int k = p.op_begin; k < p.op_end; ++k) {
             const Op& o = h->ops[k];
             h->cur_op = k;
-            if (group_n > 1) {
-                fav_handle::Group G;
-                G.n = group_n;
+            Group G;
+            if (lane.groups > 1) {
+                G.n = lane.groups;
                 G.x = gbuf(o.in); G.res = gbuf(o.res); G.y = gbuf(o.out); G.y2 = gbuf(o.out2);
                 if (o.kind == OP_TAIL) { G.w = gw(o.layer_c); G.b = gb(o.layer_c); G.wb = gw(o.layer); G.bb = gb(o.layer); G.wa = gw(o.layer_a); G.ba = gb(o.layer_a); }
                 else { G.w = gw(o.layer); G.b = gb(o.layer); }
-                h->grp = G;
             }
             fav_dropout_desc dd;
             dd.site = o.site; dd.threshold = thr; dd.scale = scale; dd.seed = c.seed;
-            dd.v0 = p.suffix ? v0 : 0; dd.n_img = n; dd.first_image_index = first_index;
+            dd.v0 = p.suffix ? v0 : 0; dd.n_img = n; dd.first_image_index = f.first_index;
             switch (o.kind) {
                 case OP_STEM_IM2COL: {
                     const Layer& L = h->layers[o.layer];
-                    launch_stem(h, buf(o.in, false, o), layout, cn, o.H, o.W, L.kh, L.kw, L.stride, L.pad, L.k, c.mean,
-                                istd, buf(o.out, true, o), s);
+                    launch_stem(h, buf(o.in, o), layout, cn, o.H, o.W, L.kh, L.kw, L.stride, L.pad, L.k, c.mean,
+                                istd, buf(o.out, o), s);
                     break;
                 }
                 case OP_CONV: {
                     const Layer& L = h->layers[o.layer];
                     fav_conv_desc d;
-                    d.x = buf(o.in, false, o); d.w = LW(o.layer); d.bias = LB(o.layer); d.res = buf(o.res, false, o); d.y = buf(o.out, true, o);
+                    d.x = buf(o.in, o); d.w = LW(o.layer); d.bias = LB(o.layer); d.res = buf(o.res, o); d.y = buf(o.out, o);
                     d.n_frames = cn; d.H = o.H; d.W = o.W; d.Cin = o.C; d.Cout = L.cout;
                     // the stem GEMM runs as a 1x1 conv over the im2col matrix
                     const bool stem = (o.in == B_A1);
@@ -1601,44 +1570,42 @@ fav_status run_chunks(fav_handle* h, size_t pi, const void* images, int layout, 
                     d.relu = o.relu; d.out_f32 = o.out_f32; d.math_mode = c.math_mode;
                     d.drop = dd;
                     const int ldy = o.out_f32 ? L.cout_pad : L.cout;
-                    if (const char* e = launch_conv(h, d, L.cout_pad, ldy, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
+                    if (const char* e = launch_conv(h, d, L.cout_pad, ldy, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 }
                 case OP_TAIL: {
-                    const Layer& Lc = h->layers[o.layer_c];
                     fav_tail_desc d;
                     memset(&d, 0, sizeof d);
-                    d.x = buf(o.in, false, o);
-                    (void)Lc;
+                    d.x = buf(o.in, o);
                     if (o.layer >= 0) { d.wb = LW(o.layer); d.bias_b = LB(o.layer); }
-                    d.wc = LW(o.layer_c); d.bias_c = LB(o.layer_c); d.res = buf(o.res, false, o); d.y = buf(o.out, true, o);
-                    if (o.layer_a >= 0) { d.wa = LW(o.layer_a); d.bias_a = LB(o.layer_a); d.t1n = buf(o.out2, true, o); }
+                    d.wc = LW(o.layer_c); d.bias_c = LB(o.layer_c); d.res = buf(o.res, o); d.y = buf(o.out, o);
+                    if (o.layer_a >= 0) { d.wa = LW(o.layer_a); d.bias_a = LB(o.layer_a); d.t1n = buf(o.out2, o); }
                     d.n_frames = cn; d.H = o.H; d.W = o.W; d.Cmid = o.C; d.Nred = o.Co2;
                     d.drop = dd;
                     if (o.res_entry) { d.res = pin_base; d.res_entry = 1; d.entry_site = h->first_site; }   // the cached prefix output
-                    if (const char* e = launch_tail(h, d, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
+                    if (const char* e = launch_tail(h, d, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 }
                 case OP_STEM_POOL:
-                    if (const char* e = launch_stem_pool(h, buf(o.in, false, o), layout, cn, o.H, o.W, LW(o.layer), LB(o.layer), c.mean, istd,
-                                                         buf(o.out, true, o), s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
+                    if (const char* e = launch_stem_pool(h, buf(o.in, o), layout, cn, o.H, o.W, LW(o.layer), LB(o.layer), c.mean, istd,
+                                                         buf(o.out, o), G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 case OP_MAXPOOL:
-                    launch_maxpool(h, buf(o.in, false, o), buf(o.out, true, o), cn, o.H, o.W, o.C, s);
+                    launch_maxpool(h, buf(o.in, o), buf(o.out, o), cn, o.H, o.W, o.C, s);
                     break;
                 case OP_AVGPOOL: {
                     DropParams dp = make_drop(&dd);
-                    launch_avgpool(h, buf(o.in, false, o), buf(o.out, true, o), cn, o.H * o.W, o.C, dp, s);
+                    launch_avgpool(h, buf(o.in, o), buf(o.out, o), cn, o.H * o.W, o.C, dp, G, s);
                     break;
                 }
                 case OP_ENTRY_DROPOUT: {
                     DropParams dp = make_drop(&dd);
-                    launch_entry_dropout(h, pin_base, buf(o.out, true, o), o.in_elems, cn, dp, s);
+                    launch_entry_dropout(h, pin_base, buf(o.out, o), o.in_elems, cn, dp, s);
                     break;
                 }
                 case OP_ENTRY_REDUCE: {
                     DropParams dp = make_drop(&dd);
-                    if (const char* e = launch_entry_reduce(h, pin_base, o.skip_y ? nullptr : buf(o.out, true, o), LW(o.layer_a), LB(o.layer_a), buf(o.out2, true, o), o.C, o.Co2,
+                    if (const char* e = launch_entry_reduce(h, pin_base, o.skip_y ? nullptr : buf(o.out, o), LW(o.layer_a), LB(o.layer_a), buf(o.out2, o), o.C, o.Co2,
                                                             o.H * o.W, cn, dp, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 }
@@ -1654,19 +1621,12 @@ void free_all(fav_handle* h) {
         if (L.w_slab) (void)hipFree(L.w_slab);
         if (L.b_slab) (void)hipFree(L.b_slab);
         L.w_slab = L.b_slab = nullptr;
-        L.w_m.clear(); L.b_m.clear(); L.w = nullptr; L.b = nullptr;
+        L.w_m.clear(); L.b_m.clear();
     }
     for (int i = 0; i < 5; ++i) if (h->act[i]) (void)hipFree(h->act[i]);
-    for (int i = 0; i < 5; ++i) if (h->act2[i]) (void)hipFree(h->act2[i]);
-    if (h->stream_a) (void)hipStreamDestroy(h->stream_a);
-    if (h->stream_b) (void)hipStreamDestroy(h->stream_b);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join_a) (void)hipEventDestroy(h->ev_join_a);
-    if (h->ev_join_b) (void)hipEventDestroy(h->ev_join_b);
-    for (auto e : h->ev_chunk) (void)hipEventDestroy(e);
     if (h->a1) (void)hipFree(h->a1);
-    for (size_t m = 0; m < h->mws.size(); ++m) {
-        fav_handle::MemberWs& w = h->mws[m];
+    for (Lane& w : h->lanes) {
         if (w.stream) (void)hipStreamDestroy(w.stream);
         if (w.done) (void)hipEventDestroy(w.done);
     }
@@ -1751,13 +1711,13 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
         const Layer& L = h->layers[layer];
         fav_conv_desc d;
         memset(&d, 0, sizeof d);
-        d.x = x; d.w = L.w; d.bias = L.b; d.res = res; d.y = y;
+        d.x = x; d.w = L.w_m[0]; d.bias = L.b_m[0]; d.res = res; d.y = y;
         d.n_frames = n; d.H = rows_per_frame; d.W = 1; d.Cin = L.k; d.Cout = L.cout;
         d.kh = 1; d.kw = 1; d.stride = 1; d.pad = 0; d.relu = act; d.out_f32 = out_f32; d.math_mode = c.math_mode;
         d.drop.site = -1;
         if (!out_f32 && c.math_mode == FAV_MATH_BF16 && L.cout == L.cout_pad &&
-            launch_gemm_streamk(h, x, L.w, L.b, res, y, (long long)n * rows_per_frame, L.k, L.cout, act, s)) return nullptr;
-        return launch_conv(h, d, L.cout_pad, out_f32 ? L.cout_pad : L.cout, s);
+            launch_gemm_streamk(h, x, L.w_m[0], L.b_m[0], res, y, (long long)n * rows_per_frame, L.k, L.cout, act, s)) return nullptr;
+        return launch_conv(h, d, L.cout_pad, out_f32 ? L.cout_pad : L.cout, Group{}, s);
     };
 #define FAV_VIT_TRY(expr)                                            \
     do {                                                             \
@@ -1767,20 +1727,20 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
     // patch embedding: normalise + im2col (k = (r*P + s)*3 + c), GEMM, add positions / class token
     launch_stem(h, images, layout, n, c.in_h, c.in_w, V.patch, V.patch, V.patch, 0, V.patch * V.patch * 3, c.mean, inv_std, B.v_patches, s);
     FAV_VIT_TRY(gemm(0, B.v_patches, gh * gw, nullptr, 0, B.v_emb, 0));
-    launch_vit_assemble(h, B.v_emb, (const float*)h->layers[1].w, B.v_x, n, ntok, D, s);
+    launch_vit_assemble(h, B.v_emb, (const float*)h->layers[1].w_m[0], B.v_x, n, ntok, D, s);
     int li = 2;
     for (int blk = 0; blk < V.depth; ++blk, li += 6) {
         const Layer &ln1 = h->layers[li], &ln2 = h->layers[li + 3];
-        FAV_VIT_TRY(launch_layernorm(h, B.v_x, D, (const float*)ln1.w, ln1.b, B.v_y, (long long)n * ntok, D, 1e-6f, s));
+        FAV_VIT_TRY(launch_layernorm(h, B.v_x, D, (const float*)ln1.w_m[0], ln1.b_m[0], B.v_y, (long long)n * ntok, D, 1e-6f, s));
         FAV_VIT_TRY(gemm(li + 1, B.v_y, ntok, nullptr, 0, B.v_qkv, 0));
         FAV_VIT_TRY(launch_attention(h, B.v_qkv, B.v_y, n, ntok, D, V.heads, c.math_mode, s));
         FAV_VIT_TRY(gemm(li + 2, B.v_y, ntok, B.v_x, 0, B.v_x, 0));                 // x = x + proj(attn), in place tile by tile
-        FAV_VIT_TRY(launch_layernorm(h, B.v_x, D, (const float*)ln2.w, ln2.b, B.v_y, (long long)n * ntok, D, 1e-6f, s));
+        FAV_VIT_TRY(launch_layernorm(h, B.v_x, D, (const float*)ln2.w_m[0], ln2.b_m[0], B.v_y, (long long)n * ntok, D, 1e-6f, s));
         FAV_VIT_TRY(gemm(li + 4, B.v_y, ntok, nullptr, 2, B.v_hid, 0));              // GELU fused
         FAV_VIT_TRY(gemm(li + 5, B.v_hid, ntok, B.v_x, 0, B.v_x, 0));
     }
     const Layer& lnf = h->layers[li];
-    FAV_VIT_TRY(launch_layernorm(h, B.v_x, (long long)ntok * D, (const float*)lnf.w, lnf.b, B.v_cls, n, D, 1e-6f, s));   // class tokens only
+    FAV_VIT_TRY(launch_layernorm(h, B.v_x, (long long)ntok * D, (const float*)lnf.w_m[0], lnf.b_m[0], B.v_cls, n, D, 1e-6f, s));   // class tokens only
     FAV_VIT_TRY(gemm(li + 1, B.v_cls, 1, nullptr, 0, B.logits, 1));
 #undef FAV_VIT_TRY
     return FAV_OK;
@@ -2034,17 +1994,104 @@ fav_status wait_last_use(fav_handle* h, hipStream_t s) {
 void mark_last_use(fav_handle* h, hipStream_t s) {
     if (h->ev_last && hipEventRecord(h->ev_last, s) == hipSuccess) h->ev_last_set = true;
 }
-fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
-                              int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride,
-                              fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr, const HeadSweep* sweep = nullptr);
+// ---- the three ways a call's frames become logits; classify_on_stream picks one.  Inside a fork / join region nothing returns
+//      (HIP_KEEP): a forked stream is always joined into the caller's.
+
+// ViT: the batch in fav_config.vit_streams (default 2) parts on as many streams: at 197 rows per frame every GEMM of the encoder is a
+// few hundred tiles, and the partial last round of one part's launch is filled by another part's (1: one stream)
+fav_status run_vit_call(fav_handle* h, const Frames& f, hipStream_t s) {
+    const int n = f.n;
+    const int vit_streams = h->cfg.vit_streams <= 0 ? 2 : std::min(4, (int)h->cfg.vit_streams);
+    if (!(vit_streams > 1 && n >= 8 * vit_streams)) {
+        h->sk_slot = 0;
+        return run_vit(h, f.images, f.layout, 0, n, s);
+    }
+    if (!h->ev_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    while ((int)h->vit_streams.size() < vit_streams) {
+        hipStream_t st_; hipEvent_t ev_;
+        HIP_TRY(h, hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+        HIP_TRY(h, hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
+        h->vit_streams.push_back(st_); h->vit_done.push_back(ev_);
+    }
+    HIP_TRY(h, hipEventRecord(h->ev_fork, s));
+    fav_status st = FAV_OK;     // from here to the join nothing returns: a forked stream is always joined into s
+    for (int part = 0; part < vit_streams; ++part) {
+        const int f0 = (int)((long long)n * part / vit_streams), f1 = (int)((long long)n * (part + 1) / vit_streams);
+        HIP_KEEP(h, st, hipStreamWaitEvent(h->vit_streams[part], h->ev_fork, 0));
+        h->sk_slot = 1 + part;
+        if (st == FAV_OK) st = run_vit(h, f.images, f.layout, f0, f1 - f0, h->vit_streams[part]);
+        HIP_KEEP(h, st, hipEventRecord(h->vit_done[part], h->vit_streams[part]));
+        HIP_KEEP(h, st, hipStreamWaitEvent(s, h->vit_done[part], 0));
+    }
+    return st;
+}
+
+// Every phase of `lane`, all (virtual) frames of the call
+fav_status run_phases(fav_handle* h, const Frames& f, const Lane& lane) {
+    for (size_t pi = 0; pi < h->phases.size(); ++pi) {
+        const long long dom = h->phases[pi].suffix ? (long long)f.n * h->T_eff : f.n;
+        if (fav_status st = run_chunks(h, pi, f, lane, 0, dom)) return st;
+    }
+    return FAV_OK;
+}
+
+// An ensemble's small calls (will_group): every op ONE launch over all members (block row = member), on the caller's stream.
+// At the 8-GPU share of configs[3] (32 frames) a member's launches are a few dozen tiles each; five of them in one grid fill
+// the chip where five streams only interleave (profiles/r3aa_ens_grouped_ab.txt)
+fav_status run_grouped(fav_handle* h, const Frames& f, hipStream_t s) {
+    Lane lane = h->lanes[0];
+    lane.stream = s;
+    lane.groups = h->n_members;
+    return run_phases(h, f, lane);
+}
+
+// Lanes side by side.  A single model is its one lane on the caller's stream: nothing to fork, nothing to join.  An ensemble
+// forks from the caller's stream, one stream per member, and joins before the head.
+fav_status run_lanes(fav_handle* h, const Frames& f, hipStream_t s) {
+    if (h->lanes.size() == 1) {
+        Lane lane = h->lanes[0];
+        lane.stream = s;
+        return run_phases(h, f, lane);
+    }
+    HIP_TRY(h, hipEventRecord(h->ev_members, s));
+    fav_status st = FAV_OK;         // nothing returns between the fork and the join
+    for (const Lane& w : h->lanes) HIP_KEEP(h, st, hipStreamWaitEvent(w.stream, h->ev_members, 0));
+    // member by member.  (Enqueuing op by op ACROSS the members - so that all five streams start together and the launches
+    // sharing the chip are the same op of different members - measured 5 % slower at 32 frames per call, 7 205 vs 7 585
+    // frames/s, and 1 % slower at 256: profiles/r3j_ens_interleave_ab.txt.)
+    for (const Lane& w : h->lanes)
+        if (st == FAV_OK) st = run_phases(h, f, w);
+    for (const Lane& w : h->lanes) {
+        HIP_KEEP(h, st, hipEventRecord(w.done, w.stream));
+        HIP_KEEP(h, st, hipStreamWaitEvent(s, w.done, 0));
+    }
+    return st;
+}
+
+fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out, hipStream_t s) {
+    h->ev_used = h->profiling ? h->ev_used : 0;
+    fav_status st;
+    if (h->vit) st = run_vit_call(h, f, s);
+    else if (will_group(h, f.n)) st = run_grouped(h, f, s);
+    else st = run_lanes(h, f, s);
+    if (st != FAV_OK) return st;
+    const int T_head = h->n_members > 1 ? h->n_members : h->T_eff;
+    if (const char* e = launch_head(h, h->logits, T_head, f.n, h->cfg.num_classes, h->cpad, h->cfg.temperature,
+                                    h->cfg.conf_kind, h->cfg.tau, out, s)) {
+        h->err = e;
+        return FAV_ERR_INVALID_ARG;
+    }
+    HIP_TRY(h, hipGetLastError());
+    h->last_T = T_head;
+    h->last_n = f.n;
+    return FAV_OK;
+}
 
 // The gate of every classify entry point: the argument checks, then classify_on_stream behind the previous user of the
 // handle's buffers.  who: the public name the messages carry; bad: the entry point's own complaint about its buffers and
 // parameters (NULL: none), reported after the handle and weights checks and before those on n, layout and first_index.
 fav_status classify_gate(const char* who, fav_handle* h, const char* bad, const void* images, int32_t n, int32_t layout,
-                         int64_t first_index, int32_t* labels, float* conf, uint8_t* fail, float* score, void* stream,
-                         int out_stride, fav_uncertainty* rec = nullptr, const HeadSets* sets = nullptr,
-                         const HeadSweep* sweep = nullptr) {
+                         int64_t first_index, const HeadOut& out, void* stream) {
     if (!h) return FAV_ERR_INVALID_ARG;
     if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", who); return FAV_ERR_NO_WEIGHTS; }
     if (bad) { h->err = fmt("%s: %s", who, bad); return FAV_ERR_INVALID_ARG; }
@@ -2054,7 +2101,7 @@ fav_status classify_gate(const char* who, fav_handle* h, const char* bad, const 
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (fav_status st = wait_last_use(h, s)) return st;
-    const fav_status st = classify_on_stream(h, images, n, layout, first_index, labels, conf, fail, score, s, out_stride, rec, sets, sweep);
+    const fav_status st = classify_on_stream(h, Frames{images, layout, n, first_index}, out, s);
     mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
     return st;
 }
@@ -2067,21 +2114,27 @@ const char* bad_sets_args(const void* images, const HeadSets& hs) {
 
 fav_status fav_classify_ex(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                            int32_t* labels, float* conf, uint8_t* fail, float* score, void* stream) {
-    return classify_gate("fav_classify", h, !images || !labels || !conf ? "null buffer" : nullptr, images, n, layout, first_index,
-                         labels, conf, fail, score, stream, 1);
+    HeadOut out;
+    out.labels = labels; out.conf = conf; out.fail = fail; out.score = score;
+    return classify_gate("fav_classify", h, !images || !labels || !conf ? "null buffer" : nullptr, images, n, layout, first_index, out,
+                         stream);
 }
 
 fav_status fav_classify_records(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                                 void* records, uint8_t* fail, float* score, void* stream) {
+    HeadOut out;
+    out.labels = (int32_t*)records; out.conf = (float*)records + 1; out.out_stride = 2; out.fail = fail; out.score = score;
     return classify_gate("fav_classify_records", h, !images || !records || ((uintptr_t)records & 7) ? kBadRecords : nullptr, images, n,
-                         layout, first_index, (int32_t*)records, (float*)records + 1, fail, score, stream, 2);
+                         layout, first_index, out, stream);
 }
 
 fav_status fav_classify_uncertainty(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                                     fav_uncertainty* records, uint8_t* fail, float* score, void* stream) {
     static_assert(sizeof(fav_uncertainty) == 72, "fav_uncertainty is 18 dwords");
+    HeadOut out;
+    out.rec = records; out.fail = fail; out.score = score;
     return classify_gate("fav_classify_uncertainty", h, !images || !records || ((uintptr_t)records & 7) ? kBadRecords : nullptr, images,
-                         n, layout, first_index, nullptr, nullptr, fail, score, stream, 1, records);
+                         n, layout, first_index, out, stream);
 }
 
 fav_status fav_classify_sets(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
@@ -2089,15 +2142,17 @@ fav_status fav_classify_sets(fav_handle* h, const void* images, int32_t n, int32
     static_assert(sizeof(fav_pred_set) == 160, "fav_pred_set is 40 dwords");
     static_assert(sizeof(fav_conformal) == 32, "fav_conformal is 32 bytes");
     const HeadSets hs{cp, first_index, nullptr, nullptr, records};
-    return classify_gate("fav_classify_sets", h, bad_sets_args(images, hs), images, n, layout, first_index, nullptr, nullptr, fail,
-                         score, stream, 1, nullptr, &hs);
+    HeadOut out;
+    out.sets = &hs; out.fail = fail; out.score = score;
+    return classify_gate("fav_classify_sets", h, bad_sets_args(images, hs), images, n, layout, first_index, out, stream);
 }
 
 fav_status fav_conformal_scores(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
                                 const fav_conformal* cp, const int32_t* labels, float* scores, void* stream) {
     const HeadSets hs{cp, first_index, labels, scores, nullptr};
-    return classify_gate("fav_conformal_scores", h, bad_sets_args(images, hs), images, n, layout, first_index, nullptr, nullptr,
-                         nullptr, nullptr, stream, 1, nullptr, &hs);
+    HeadOut out;
+    out.sets = &hs;
+    return classify_gate("fav_conformal_scores", h, bad_sets_args(images, hs), images, n, layout, first_index, out, stream);
 }
 
 fav_status fav_classify_sweep(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
@@ -2107,8 +2162,10 @@ fav_status fav_classify_sweep(fav_handle* h, const void* images, int32_t n, int3
     const HeadSweep sw{temps, K, true_labels, cells};
     // the handle's conf_kind was checked against its sample count by fav_create
     const char* bad = check_sweep(sw, h->cfg.num_classes, -1, h->cfg.conf_kind);
-    return classify_gate("fav_classify_sweep", h, bad ? bad : (!images ? "null buffer" : nullptr), images, n, layout, first_index,
-                         nullptr, nullptr, nullptr, nullptr, stream, 1, nullptr, nullptr, &sw);
+    HeadOut out;
+    out.sweep = &sw;
+    return classify_gate("fav_classify_sweep", h, bad ? bad : (!images ? "null buffer" : nullptr), images, n, layout, first_index, out,
+                         stream);
 }
 
 fav_status fav_set_temperature(fav_handle* h, float temperature) {
@@ -2127,131 +2184,6 @@ fav_status fav_set_tau(fav_handle* h, float tau) {
     h->cfg.tau = tau;
     return FAV_OK;
 }
-
-namespace {
-fav_status classify_on_stream(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index,
-                              int32_t* labels, float* conf, uint8_t* fail, float* score, hipStream_t s, int out_stride,
-                              fav_uncertainty* rec, const HeadSets* sets, const HeadSweep* sweep) {
-    h->ev_used = h->profiling ? h->ev_used : 0;
-    if (h->vit) {
-        for (auto& L : h->layers) { L.w = L.w_m[0]; L.b = L.b_m[0]; }
-        // the batch in fav_config.vit_streams (default 2) parts on as many streams: at 197 rows per frame every GEMM of the encoder is a
-        // few hundred tiles, and the partial last round of one part's launch is filled by another part's (1: one stream)
-        const int vit_streams = h->cfg.vit_streams <= 0 ? 2 : std::min(4, (int)h->cfg.vit_streams);
-        if (vit_streams > 1 && n >= 8 * vit_streams) {
-            if (!h->ev_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            while ((int)h->vit_streams.size() < vit_streams) {
-                hipStream_t st_; hipEvent_t ev_;
-                HIP_TRY(h, hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-                HIP_TRY(h, hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
-                h->vit_streams.push_back(st_); h->vit_done.push_back(ev_);
-            }
-            HIP_TRY(h, hipEventRecord(h->ev_fork, s));
-            fav_status st = FAV_OK;     // from here to the join nothing returns: a forked stream is always joined into s
-            for (int part = 0; part < vit_streams; ++part) {
-                const int f0 = (int)((long long)n * part / vit_streams), f1 = (int)((long long)n * (part + 1) / vit_streams);
-                HIP_KEEP(h, st, hipStreamWaitEvent(h->vit_streams[part], h->ev_fork, 0));
-                h->sk_slot = 1 + part;
-                if (st == FAV_OK) st = run_vit(h, images, layout, f0, f1 - f0, h->vit_streams[part]);
-                HIP_KEEP(h, st, hipEventRecord(h->vit_done[part], h->vit_streams[part]));
-                HIP_KEEP(h, st, hipStreamWaitEvent(s, h->vit_done[part], 0));
-            }
-            if (st != FAV_OK) return st;
-        } else {
-            h->sk_slot = 0;
-            fav_status st = run_vit(h, images, layout, 0, n, s);
-            if (st != FAV_OK) return st;
-        }
-    } else if (!h->mws.empty() && h->can_group && n <= h->group_max_frames) {
-        // small calls: every op ONE launch over all members (block row = member), on the caller's stream.  At the 8-GPU share
-        // of configs[3] (32 frames) a member's launches are a few dozen tiles each; five of them in one grid fill the chip
-        // where five streams only interleave (profiles/r3aa_ens_grouped_ab.txt)
-        for (int member = 0; member < h->n_members; ++member)
-            h->mws[member].phase_out.back() = (char*)h->logits + (size_t)member * n * h->cpad * 4;
-        for (size_t pi = 0; pi < h->phases.size(); ++pi) {
-            fav_status st = run_chunks(h, pi, images, layout, n, first_index, s, 0, n, h->mws[0].act, &h->mws[0], 0, -1, -1, h->n_members);
-            if (st != FAV_OK) return st;
-        }
-    } else if (!h->mws.empty()) {
-        // members side by side: fork from the caller's stream, one stream per member, join before the head
-        HIP_TRY(h, hipEventRecord(h->ev_members, s));
-        fav_status st = FAV_OK;         // nothing returns between the fork and the join
-        for (int member = 0; member < h->n_members; ++member) {
-            fav_handle::MemberWs& w = h->mws[member];
-            w.phase_out.back() = (char*)h->logits + (size_t)member * n * h->cpad * 4;
-            HIP_KEEP(h, st, hipStreamWaitEvent(w.stream, h->ev_members, 0));
-        }
-        // member by member.  (Enqueuing op by op ACROSS the members - so that all five streams start together and the launches
-        // sharing the chip are the same op of different members - measured 5 % slower at 32 frames per call, 7 205 vs 7 585
-        // frames/s, and 1 % slower at 256: profiles/r3j_ens_interleave_ab.txt.)
-        for (int member = 0; member < h->n_members && st == FAV_OK; ++member) {
-            fav_handle::MemberWs& w = h->mws[member];
-            for (size_t pi = 0; pi < h->phases.size() && st == FAV_OK; ++pi) {
-                const long long dom = h->phases[pi].suffix ? (long long)n * h->T_eff : n;
-                st = run_chunks(h, pi, images, layout, n, first_index, w.stream, 0, dom, w.act, &w, member);
-            }
-        }
-        for (int member = 0; member < h->n_members; ++member) {
-            fav_handle::MemberWs& w = h->mws[member];
-            HIP_KEEP(h, st, hipEventRecord(w.done, w.stream));
-            HIP_KEEP(h, st, hipStreamWaitEvent(s, w.done, 0));
-        }
-        if (st != FAV_OK) return st;
-    } else
-    for (int member = 0; member < h->n_members; ++member) {
-    for (auto& L : h->layers) { L.w = L.w_m[member]; L.b = L.b_m[member]; }
-    // member m writes logits[m][n][cpad]: the head then averages members exactly as it averages samples
-    h->phase_out.back() = (char*)h->logits + (size_t)member * n * h->cpad * 4;
-    const size_t nph = h->phases.size();
-    const size_t serial_end = h->pipe_first >= 0 ? (size_t)h->pipe_first : nph;
-    for (size_t pi = 0; pi < serial_end; ++pi) {
-        const long long dom = h->phases[pi].suffix ? (long long)n * h->T_eff : n;
-        fav_status st = run_chunks(h, pi, images, layout, n, first_index, s, 0, dom, h->act);
-        if (st != FAV_OK) return st;
-    }
-    if (h->pipe_first >= 0) {
-        const size_t pa = (size_t)h->pipe_first, pb = pa + 1;
-        const long long dom = h->phases[pa].suffix ? (long long)n * h->T_eff : n;
-        const long long step = h->phases[pa].chunk;  // == phases[pb].chunk
-        HIP_TRY(h, hipEventRecord(h->ev_fork, s));
-        HIP_TRY(h, hipStreamWaitEvent(h->stream_a, h->ev_fork, 0));
-        HIP_TRY(h, hipStreamWaitEvent(h->stream_b, h->ev_fork, 0));
-        size_t ci = 0;
-        fav_status st = FAV_OK;         // nothing returns between the fork and the join
-        for (long long v0 = 0; v0 < dom && st == FAV_OK; v0 += step, ++ci) {
-            const long long v1 = std::min(dom, v0 + step);
-            st = run_chunks(h, pa, images, layout, n, first_index, h->stream_a, v0, v1, h->act);
-            if (st != FAV_OK) break;
-            if (ci >= h->ev_chunk.size()) {
-                hipEvent_t e = nullptr;
-                HIP_KEEP(h, st, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                if (st != FAV_OK) break;
-                h->ev_chunk.push_back(e);
-            }
-            HIP_KEEP(h, st, hipEventRecord(h->ev_chunk[ci], h->stream_a));
-            HIP_KEEP(h, st, hipStreamWaitEvent(h->stream_b, h->ev_chunk[ci], 0));
-            if (st == FAV_OK) st = run_chunks(h, pb, images, layout, n, first_index, h->stream_b, v0, v1, h->act2);
-        }
-        HIP_KEEP(h, st, hipEventRecord(h->ev_join_a, h->stream_a));
-        HIP_KEEP(h, st, hipEventRecord(h->ev_join_b, h->stream_b));
-        HIP_KEEP(h, st, hipStreamWaitEvent(s, h->ev_join_a, 0));
-        HIP_KEEP(h, st, hipStreamWaitEvent(s, h->ev_join_b, 0));
-        if (st != FAV_OK) return st;
-    }
-    }
-    if (!h->vit) h->phase_out.back() = h->logits;
-    const int T_head = h->n_members > 1 ? h->n_members : h->T_eff;
-    if (const char* e = launch_head(h, h->logits, T_head, n, h->cfg.num_classes, h->cpad, h->cfg.temperature,
-                                    h->cfg.conf_kind, h->cfg.tau, labels, conf, fail, score, s, out_stride, rec, sets, sweep)) {
-        h->err = e;
-        return FAV_ERR_INVALID_ARG;
-    }
-    HIP_TRY(h, hipGetLastError());
-    h->last_T = T_head;
-    h->last_n = n;
-    return FAV_OK;
-}
-}  // namespace
 
 fav_status fav_classify(fav_handle* h, const void* images, int32_t n, int32_t layout, int32_t* labels, float* conf,
                         void* stream) {
@@ -2357,13 +2289,13 @@ static fav_status op_done(const char* e) {
 fav_status fav_op_conv2d(const fav_conv_desc* d, void* stream) {
     if (!d || !d->x || !d->w || !d->bias || !d->y) return op_done("fav_op_conv2d: null pointer");
     if (d->Cout % 64 != 0) return op_done("fav_op_conv2d: Cout must be a multiple of 64");
-    return op_done(launch_conv(nullptr, *d, d->Cout, d->Cout, (hipStream_t)stream));
+    return op_done(launch_conv(nullptr, *d, d->Cout, d->Cout, Group{}, (hipStream_t)stream));
 }
 
 fav_status fav_op_bottleneck_tail(const fav_tail_desc* d, void* stream) {
     if (!d || !d->x || !d->wc || !d->bias_c || !d->res || !d->y) return op_done("fav_op_bottleneck_tail: null pointer");
     if ((d->wb && !d->bias_b) || (d->wa && (!d->bias_a || !d->t1n))) return op_done("fav_op_bottleneck_tail: null pointer");
-    return op_done(launch_tail(nullptr, *d, (hipStream_t)stream));
+    return op_done(launch_tail(nullptr, *d, Group{}, (hipStream_t)stream));
 }
 
 fav_status fav_op_stem_im2col(const void* images, int32_t layout, int32_t n, int32_t H, int32_t W, int32_t kh, int32_t kw,
@@ -2377,7 +2309,7 @@ fav_status fav_op_stem_im2col(const void* images, int32_t layout, int32_t n, int
 fav_status fav_op_stem_pool(const void* images, int32_t layout, int32_t n, int32_t H, int32_t W, const void* w, const float* bias,
                             const float* mean3, const float* inv_std3, void* out, void* stream) {
     if (!images || !w || !bias || !mean3 || !inv_std3 || !out) return op_done("fav_op_stem_pool: null argument");
-    return op_done(launch_stem_pool(nullptr, images, layout, n, H, W, w, bias, mean3, inv_std3, out, (hipStream_t)stream));
+    return op_done(launch_stem_pool(nullptr, images, layout, n, H, W, w, bias, mean3, inv_std3, out, Group{}, (hipStream_t)stream));
 }
 
 fav_status fav_op_maxpool3x3s2(const void* x, void* y, int32_t n, int32_t H, int32_t W, int32_t C, void* stream) {
@@ -2388,7 +2320,7 @@ fav_status fav_op_maxpool3x3s2(const void* x, void* y, int32_t n, int32_t H, int
 
 fav_status fav_op_avgpool(const void* x, void* y, int32_t n, int32_t HW, int32_t C, const fav_dropout_desc* drop, void* stream) {
     if (!x || !y || C % 16 != 0 || HW < 1) return op_done("fav_op_avgpool: bad argument");
-    launch_avgpool(nullptr, x, y, n, HW, C, make_drop(drop), (hipStream_t)stream);
+    launch_avgpool(nullptr, x, y, n, HW, C, make_drop(drop), Group{}, (hipStream_t)stream);
     return op_done(nullptr);
 }
 
@@ -2409,7 +2341,9 @@ fav_status fav_op_head(const float* logits, int32_t T, int32_t n, int32_t C, int
     if (!logits || !labels || !conf || T < 1 || n < 1 || !(temperature > 0.f)) return op_done("fav_op_head: bad argument");
     if (kind == FAV_CONF_MUTUAL_INFO && (T < 2 || C < 2))
         return op_done("fav_op_head: conf_kind 2 (mutual information) needs T >= 2 samples and num_classes >= 2");
-    return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, labels, conf, fail, score, (hipStream_t)stream));
+    HeadOut out;
+    out.labels = labels; out.conf = conf; out.fail = fail; out.score = score;
+    return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, out, (hipStream_t)stream));
 }
 
 fav_status fav_op_head_uncertainty(const float* logits, int32_t T, int32_t n, int32_t C, int32_t ld, float temperature,
@@ -2417,8 +2351,9 @@ fav_status fav_op_head_uncertainty(const float* logits, int32_t T, int32_t n, in
     if (!logits || !records || ((uintptr_t)records & 7) || T < 1 || T > 4096 || n < 1 || kind < 0 || kind > 2 ||
         !(temperature > 0.f))
         return op_done("fav_op_head_uncertainty: bad argument (records non-NULL and 8-byte aligned, 1 <= T <= 4096, kind 0..2)");
-    return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, nullptr, nullptr, fail, score,
-                               (hipStream_t)stream, 1, records));
+    HeadOut out;
+    out.rec = records; out.fail = fail; out.score = score;
+    return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, out, (hipStream_t)stream));
 }
 
 fav_status fav_op_head_sets(const float* logits, int32_t T, int32_t n, int32_t C, int32_t ld, float temperature, int32_t kind,
@@ -2427,8 +2362,9 @@ fav_status fav_op_head_sets(const float* logits, int32_t T, int32_t n, int32_t C
     if (!logits || T < 1 || n < 1 || kind < 0 || kind > 2 || !(temperature > 0.f))
         return op_done("fav_op_head_sets: bad argument (logits non-NULL, T >= 1, n >= 1, kind 0..2, temperature > 0)");
     const HeadSets hs{cp, first_index, true_labels, true_scores, records};
-    return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, nullptr, nullptr, fail, score,
-                               (hipStream_t)stream, 1, nullptr, &hs));
+    HeadOut out;
+    out.sets = &hs; out.fail = fail; out.score = score;
+    return op_done(launch_head(nullptr, logits, T, n, C, ld, temperature, kind, tau, out, (hipStream_t)stream));
 }
 
 fav_status fav_op_head_sweep(const float* logits, int32_t T, int32_t n, int32_t C, int32_t ld, const float* temps, int32_t K,
@@ -2436,8 +2372,9 @@ fav_status fav_op_head_sweep(const float* logits, int32_t T, int32_t n, int32_t 
     const HeadSweep sw{temps, K, true_labels, cells};
     if (const char* e = check_sweep(sw, C, T, kind)) return op_done(fmt("fav_op_head_sweep: %s", e).c_str());
     if (!logits || T < 1 || n < 1) return op_done("fav_op_head_sweep: bad argument (logits non-NULL, T >= 1, n >= 1)");
-    return op_done(launch_head(nullptr, logits, T, n, C, ld, 1.0f, kind, 0.f, nullptr, nullptr, nullptr, nullptr,
-                               (hipStream_t)stream, 1, nullptr, nullptr, &sw));
+    HeadOut out;
+    out.sweep = &sw;
+    return op_done(launch_head(nullptr, logits, T, n, C, ld, 1.0f, kind, 0.f, out, (hipStream_t)stream));
 }
 
 fav_status fav_op_layernorm(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t rows, int32_t D,

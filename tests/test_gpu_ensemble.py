@@ -110,3 +110,30 @@ def test_ens5_grouped_launches_equal_member_streams(r50_members, n, monkeypatch)
     for a, b in zip(out["0"], out["4096"]):
         assert torch.equal(a, b)
     assert not torch.equal(out["0"][2][0], out["0"][2][1])
+
+
+def test_ens5_one_handle_alternates_member_streams_and_grouped_launches(r50_members):
+    """ONE handle whose calls take both forms in turn (max_batch 12, ens_grouped_max 8): 12 frames run member by member on
+    the members' streams, 4 frames as one grouped launch per op, then 12 and the same 4 again.  Every call's labels,
+    confidences and logits are bit-equal to the same frames on a handle that never groups (ens_grouped_max = -1): neither
+    form leaves anything behind that the other one picks up.  64x64 frames: the network still runs every op kind."""
+    first = 500
+    u8 = synth.synthetic_frames_u8(12, 64, 64, seed=FRAME_SEED, start_id=first)
+    x = torch.from_numpy(synth.gaussian_noise_f32(u8, SEVERITY, seed=NOISE_SEED, start_id=first)).cuda()
+    blobs = [b for b, _ in r50_members]
+
+    def run(be, frames):
+        labels, conf = be.classify(frames, first_index=first)
+        return labels.clone(), conf.clone(), be.logits().clone()
+
+    ref = Backend("resnet50", blobs, in_hw=(64, 64), max_batch=12, ens_grouped_max=-1)
+    want = {n: run(ref, x[:n]) for n in (12, 4)}
+    ref.close()
+    be = Backend("resnet50", blobs, in_hw=(64, 64), max_batch=12, ens_grouped_max=8)
+    for call, n in enumerate((12, 4, 12, 4)):
+        got = run(be, x[:n])
+        assert got[2].shape == (5, n, 1000)
+        for name, a, b in zip(("labels", "conf", "logits"), got, want[n]):
+            assert torch.equal(a, b), f"call {call} ({n} frames): {name} differ"
+    be.close()
+    assert not torch.equal(want[12][2][0], want[12][2][1])          # the members really are different networks
