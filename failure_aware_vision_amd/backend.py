@@ -200,7 +200,9 @@ class Backend:
         int32[n, 18] record buffer (``unpack_uncertainty``) - plus ``fail`` (uint8[n]) and ``score`` (fp32[n]).
         torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out (the frames
         are uploaded, the call is synchronous).  ``out``: a contiguous int32[n, 18] tensor on the frames' device to write
-        the records into (e.g. this rank's slot of an all-gather send buffer)."""
+        the records into (e.g. this rank's slot of an all-gather send buffer).
+        A non-finite frame (include/fav.h: a NaN or +inf among a sample's scaled logits, or a sample -inf throughout):
+        label 0, confidence 0, fail 1 whatever tau is, score 1; the other statistics NaN, top_label -1, top_prob 0."""
         torch = self._torch
         img, host, n, layout, stream = self._classify_args(images)
         dev = img.device
@@ -254,7 +256,9 @@ class Backend:
         plus ``fail`` (uint8[n], conf < tau), ``score`` (fp32[n]) and ``ambiguous`` (set_size != 1: the set-valued
         failure flag).  torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy
         out, synchronous.  ``out``: a contiguous int32[n, 40] tensor on the frames' device to write the records into
-        (e.g. this rank's slot of an all-gather send buffer)."""
+        (e.g. this rank's slot of an all-gather send buffer).
+        A non-finite frame (include/fav.h): label 0, confidence 0, fail 1 whatever tau is, score 1, an empty set
+        (set_size 0, set_mass 0, hence ambiguous); its calibration score is NaN, which calibrate_conformal refuses."""
         from .conformal import PRED_SET_DWORDS, unpack_sets
         torch = self._torch
         img, host, n, layout, stream = self._classify_args(images)
@@ -300,7 +304,8 @@ class Backend:
         (fav_classify_sweep): int32[n, K, 4] cells, ``calibration.unpack_cells`` -> label, confidence, nll, brier per
         (frame, temperature), ``labels`` (int[n]) being the frames' true classes.  The handle's own temperature is not
         used.  Batches of max_batch frames; torch CUDA frames in -> CUDA tensor out, asynchronous on the current stream;
-        numpy in -> numpy out, synchronous."""
+        numpy in -> numpy out, synchronous.  A frame that is non-finite at a temperature (include/fav.h) has label 0,
+        confidence 0 and NaN nll / brier in that cell; the temperature fit refuses a set that holds one."""
         torch = self._torch
         img, host, n, layout, stream = self._classify_args(images)
         dev = img.device

@@ -81,7 +81,7 @@ def fit_temperature(nll_of, lo: float = 0.25, hi: float = 8.0, K: int = MAX_TEMP
         v = np.asarray(nll_of(t), np.float64)
         rounds += 1
         if v.shape != (K,) or np.isnan(v).any():
-            raise ValueError("nll_of must return K values, none NaN (a label outside [0, num_classes)?)")
+            raise ValueError("nll_of must return K values, none NaN (a label outside [0, num_classes), or a non-finite frame?)")
         k = int(np.argmin(v))                       # the first of equal minima
         a, b = float(t[max(k - 1, 0)]), float(t[min(k + 1, K - 1)])
         if b / a <= 1.0 + rtol or rounds >= max_rounds:

@@ -60,7 +60,7 @@ def calibrate_qhat(scores, alpha: float) -> float:
     if s.size == 0:
         raise ValueError("no calibration scores")
     if np.isnan(s).any():
-        raise ValueError(f"{int(np.isnan(s).sum())} calibration scores are NaN (labels outside [0, num_classes)?)")
+        raise ValueError(f"{int(np.isnan(s).sum())} calibration scores are NaN (labels outside [0, num_classes), or non-finite frames?)")
     n = s.size
     k = math.ceil((n + 1) * (1.0 - alpha))
     if k > n:

@@ -3123,6 +3123,13 @@ __global__ __launch_bounds__(512, 4) void attention_kernel(const uint16_t* __res
 // head_kernel, head_unc_kernel and head_sets_kernel all compute pbar, label and
 // confidence with the head core below (head_load_row .. head_finish): one
 // sequence of fp32 operations, so the three give the same bits.
+// Non-finite frames.  A frame is non-finite when, in any of its T samples, the scaled row z holds a NaN or +inf among
+// its first C values or is -inf throughout: then z - mx is NaN somewhere, the row's sum of exponentials s is NaN (s
+// is never +inf: at most 1024 terms <= 1) and so is 1 / s, which turns EVERY p of the wave that took the sample into NaN
+// for good, hence every pbar of the frame.  No arg-max takes a NaN, so the frame's best value stays the -1 it starts
+// from (a sort puts a NaN first instead), where a finite frame's is >= 1 / C: head_nonfinite() of the best value is the
+// flag every writer uses - label 0, confidence 0, fail 1 whatever tau is, score 1; the other fields as documented in
+// include/fav.h.  The finite path computes what it always did.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -3225,6 +3232,8 @@ __device__ __forceinline__ void head_combine(float (&part)[4][NV * 256], const f
     h = wave_sum(h);
     if (lane == 0) red_h[wave] = h;
 }
+// bv = the frame's largest pbar as the arg-max (-1: nothing taken) or the sort (NaN) delivers it: the frame is non-finite
+__device__ __forceinline__ bool head_nonfinite(float bv) { return !(bv >= 0.f); }
 // pb past class C -> -1, below every probability: never selected by an arg-max
 __device__ __forceinline__ void head_mask_classes(float (&pb)[4], int tid, int C) {
 #pragma unroll
@@ -3248,12 +3257,14 @@ __device__ __forceinline__ HeadEntropies head_entropies(const float* red_h, cons
     return {hh, eh, fmaxf(hh - eh, 0.f)};
 }
 // The finish (one thread): confidence by conf_kind, fail and score (either may be NULL); returns the confidence.
+// A non-finite frame (head_nonfinite(bv)): confidence 0, fail 1 whatever tau is, score 1.
 // MI = false (head_kernel, which is never launched with conf_kind 2) leaves mi and inv_lnK unused.
 template <bool MI>
 __device__ __forceinline__ float head_finish(int conf_kind, float bv, float hh, float inv_lnC, float mi, float inv_lnK, float tau,
                                              int img, uint8_t* __restrict__ fail, float* __restrict__ score) {
-    const float cf = conf_kind == 0 ? bv : (!MI || conf_kind == 1 ? 1.0f - hh * inv_lnC : 1.0f - mi * inv_lnK);
-    if (fail) fail[img] = cf < tau ? 1 : 0;
+    const bool bad = head_nonfinite(bv);
+    const float cf = bad ? 0.f : conf_kind == 0 ? bv : (!MI || conf_kind == 1 ? 1.0f - hh * inv_lnC : 1.0f - mi * inv_lnK);
+    if (fail) fail[img] = bad || cf < tau ? 1 : 0;
     if (score) score[img] = fminf(fmaxf(1.0f - cf, 0.f), 1.f);
     return cf;
 }
@@ -3289,7 +3300,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ log
         float bv;
         int bi;
         argmax_of_waves(red_v, red_i, bv, bi);
-        labels[(long long)img * out_stride] = bi;
+        labels[(long long)img * out_stride] = head_nonfinite(bv) ? 0 : bi;
         conf[(long long)img * out_stride] = head_finish<false>(conf_kind, bv, sum_of_waves(red_h), inv_lnC, 0.f, 0.f, tau, img, fail, score);
     }
 }
@@ -3384,7 +3395,8 @@ __global__ __launch_bounds__(256) void head_unc_kernel(const float* __restrict__
         const HeadEntropies en = head_entropies(red_h, red_e, T, inv_T);
         const float sd = sqrtf(sum_of_waves(red_s) * inv_T);
         const float cf = head_finish<true>(conf_kind, bv, en.hh, inv_lnC, en.mi, inv_lnK, tau, img, fail, score);
-        if (labels) labels[(long long)img * out_stride] = bi;
+        const bool bad = head_nonfinite(bv);
+        if (labels) labels[(long long)img * out_stride] = bad ? 0 : bi;
         if (conf) conf[(long long)img * out_stride] = cf;
         out_rec[0] = bi;
         out_rec[1] = __float_as_int(cf);
@@ -3394,9 +3406,15 @@ __global__ __launch_bounds__(256) void head_unc_kernel(const float* __restrict__
         out_rec[5] = __float_as_int(en.eh);
         out_rec[6] = __float_as_int(en.mi);
         out_rec[7] = __float_as_int(bi < C ? (float)votes[bi] / (float)T : 0.f);
+        if (bad) {                              // label 0, confidence 0 (head_finish), every statistic NaN
+            out_rec[0] = 0;
+#pragma unroll
+            for (int k = 2; k < 8; ++k) out_rec[k] = 0x7fc00000;
+        }
     }
     if (tid < 5) {
-        // rank tid of top-5 (selected with compile-time indices: no scratch); fewer than 5 classes leave label -1, prob 0
+        // rank tid of top-5 (selected with compile-time indices: no scratch); fewer than 5 classes leave label -1, prob 0,
+        // and so does every rank of a non-finite frame: no arg-max takes a NaN, so every top_i stayed 0x7fffffff
         int ti = top_i[0];
         float tv = top_v[0];
 #pragma unroll
@@ -3576,8 +3594,10 @@ __global__ __launch_bounds__(256) void head_sets_kernel(const float* __restrict_
         const float bv = v[0];
         const HeadEntropies en = head_entropies(red_h, red_e, T, inv_T);
         const float cf = head_finish<true>(conf_kind, bv, en.hh, inv_lnC, en.mi, inv_lnK, tau, img, fail, score);
+        // a non-finite frame: every score above is NaN, so no class is a member (size 0, mass 0) and a true label in
+        // range got a NaN score; label 0 and confidence 0 (head_finish) as in the other heads
         if (true_labels && (y < 0 || y >= C)) true_scores[img] = __int_as_float(0x7fc00000);
-        out_rec[0] = bi;
+        out_rec[0] = head_nonfinite(bv) ? 0 : bi;
         out_rec[1] = __float_as_int(cf);
         out_rec[2] = set_n;
         out_rec[3] = __float_as_int(sum_of_waves(red_m));
@@ -3599,6 +3619,7 @@ __global__ __launch_bounds__(256) void head_sets_kernel(const float* __restrict_
 //   brier               sum_{c < C} (pbar[c] - [c == y])^2: a thread's 4 classes in order, wave butterfly, waves 0-3 in
 //                       order
 //   y outside [0, C): nll = brier = NaN, label / confidence still written.
+//   a non-finite frame: label 0, confidence 0, nll = brier = NaN.
 // Schedule.  The block first copies its frame's rows into LDS (rows[t][Cp], Cp = C rounded up to 4; a lane stores exactly
 // the classes head_load_row later makes it read, so no barrier separates the copy from the reads).  The temperatures then
 // go in groups of G = kSweepGroup: one pass over the T rows feeds G sets of accumulators (G independent exp chains per
@@ -3712,10 +3733,11 @@ __global__ __launch_bounds__(256) void head_sweep_kernel(const float* __restrict
                     const HeadEntropies en = head_entropies(red_h[g], red_e[g], T, inv_T);
                     const float cf = head_finish<true>(conf_kind, bv, en.hh, inv_lnC, en.mi, inv_lnK, 0.f, img, nullptr, nullptr);
                     const float nan = __int_as_float(0x7fc00000);
-                    const float nll = y_ok ? -logf(fmaxf(p_true[g], FLT_MIN)) : nan;
-                    const float brier = y_ok ? sum_of_waves(red_b[g]) : nan;
+                    const bool bad = head_nonfinite(bv);        // label 0, confidence 0 (head_finish), nll = brier = NaN
+                    const float nll = y_ok && !bad ? -logf(fmaxf(p_true[g], FLT_MIN)) : nan;
+                    const float brier = y_ok && !bad ? sum_of_waves(red_b[g]) : nan;
                     int* cell = cells + ((long long)img * sp.K + k0 + g) * 4;
-                    *(int2*)cell = make_int2(bi, __float_as_int(cf));
+                    *(int2*)cell = make_int2(bad ? 0 : bi, __float_as_int(cf));
                     *(int2*)(cell + 2) = make_int2(__float_as_int(nll), __float_as_int(brier));
                 }
             }

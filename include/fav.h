@@ -114,6 +114,15 @@ fav_status fav_plan_schedule(const fav_config* cfg, int32_t flags, char* out, si
 const char* fav_last_error(const fav_handle* h); /* h may be NULL: error of the last failed fav_create */
 int32_t fav_abi_version(void);
 
+/* Non-finite frames - the one rule of every fav_classify* and fav_op_head* entry point.  With z_t = fp32(logit_t *
+ * fp32(1 / temperature)) the T scaled rows of a frame, the frame is NON-FINITE when any of its rows holds a NaN or
+ * +inf among its num_classes values, or is -inf throughout (finite logits can get there: a huge logit times
+ * 1 / temperature > 1 overflows).  -inf in some classes of a row is finite input: that class has probability 0 in that
+ * sample.  For a non-finite frame every head writes
+ *   label = 0, confidence = 0.0f, fail = 1 whatever tau is (tau = -inf included), score = 1.0f
+ * and the remaining fields as stated beside fav_uncertainty, fav_pred_set and fav_calib_cell.  The other frames of the
+ * call are not affected, and the call itself still returns FAV_OK. */
+
 /* The hot path: n frames -> labels[n] (int32), conf[n] (fp32), both device
  * pointers.  Asynchronous on `hip_stream` (NULL = the default stream); results
  * are complete once the stream is synchronised.  Replaces the scorer call at
@@ -151,7 +160,9 @@ fav_status fav_classify_records(fav_handle* h, const void* images_dev, int32_t n
  *   mutual_info      max(pred_entropy - expected_entropy, 0)
  *   agreement        #{t : argmax z_t == label} / T (per-sample argmax on z_t, lowest index on ties)
  *   top_label/prob   classes by pbar, descending, lowest index first on ties; slots past num_classes: -1 / 0
- * T = 1: expected_entropy = pred_entropy, mutual_info = 0, agreement = 1, prob_std = 0. */
+ * T = 1: expected_entropy = pred_entropy, mutual_info = 0, agreement = 1, prob_std = 0.
+ * A non-finite frame (see above fav_classify): label 0, confidence 0; mean_prob, prob_std, the three entropies and
+ * agreement are NaN; top_label / top_prob are -1 / 0 in all five slots. */
 typedef struct fav_uncertainty {
     int32_t label; float confidence; float mean_prob; float prob_std;
     float pred_entropy; float expected_entropy; float mutual_info; float agreement;
@@ -188,7 +199,9 @@ typedef struct fav_conformal {
  *   set_size            number of classes in the set
  *   set_mass            fp32 sum of pbar over the set (each thread's 4 ranks in order, wave butterfly, waves in order)
  *   u                   the draw used: 1 when not randomized, 0 under FAV_CP_LAC
- *   member              bit c % 32 of word c / 32 set: class c is in the set (bits of classes >= num_classes are 0) */
+ *   member              bit c % 32 of word c / 32 set: class c is in the set (bits of classes >= num_classes are 0)
+ * A non-finite frame (see above fav_classify): label 0, confidence 0, set_size 0, set_mass 0, no member bit, u as usual;
+ * its calibration score (fav_conformal_scores) is NaN. */
 typedef struct fav_pred_set {
     int32_t label; float confidence; int32_t set_size; float set_mass;
     float u; int32_t reserved[3];
@@ -213,7 +226,8 @@ fav_status fav_conformal_scores(fav_handle* h, const void* images_dev, int32_t n
  *   label, confidence   bit-identical to fav_classify_ex's at that temperature (the handle's conf_kind)
  *   nll                 -logf(fmaxf(pbar[y], FLT_MIN)): at most 87.34, never +inf
  *   brier               sum over c < num_classes of (pbar[c] - [c == y])^2, fp32, in a fixed order
- * y outside [0, num_classes): nll and brier are NaN, label and confidence are still written.  The mean of nll over the
+ * y outside [0, num_classes): nll and brier are NaN, label and confidence are still written.  A non-finite frame (see
+ * above fav_classify): label 0, confidence 0, nll and brier NaN at the temperatures where it is non-finite.  The mean of nll over the
  * frames is what a temperature is fitted on; label / confidence feed the reliability and risk-coverage metrics. */
 #define FAV_SWEEP_MAX_TEMPS 32
 typedef struct fav_calib_cell { int32_t label; float confidence; float nll; float brier; } fav_calib_cell;   /* 16 bytes */
@@ -329,13 +343,16 @@ fav_status fav_op_entry_dropout(const void* x, void* out, int64_t elems_per_fram
  * y may be NULL: the dropped copies are then not stored (a tail with res_entry recomputes them). */
 fav_status fav_op_entry_reduce(const void* x, void* y, const void* wa, const float* bias_a, void* t1, int32_t C, int32_t Nred,
                                int32_t HW, int32_t n_out, const fav_dropout_desc* drop, void* hip_stream);
-/* logits fp32 [T][n][ld] -> labels, conf (and fail/score if non-NULL) */
+/* logits fp32 [T][n][ld] -> labels, conf (and fail/score if non-NULL).  The four fav_op_head* entry points read only
+ * the first num_classes values of a row (ld - num_classes padding values may hold anything) and apply the non-finite
+ * frame rule stated above fav_classify to the caller's logits. */
 fav_status fav_op_head(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld,
                        float temperature, int32_t conf_kind, float tau,
                        int32_t* labels, float* conf, uint8_t* fail, float* score, void* hip_stream);
 /* logits fp32 [T][n][ld] -> records[n] (fav_uncertainty, 8-byte aligned), fail / score if non-NULL.  T <= 4096,
  * num_classes <= 1024; conf_kind 0, 1 or 2 (kind 2 at T = 1 or num_classes = 1: conf = 1).  fav_op_head with conf_kind 2
- * runs the same kernel (and needs T >= 2, num_classes >= 2). */
+ * runs the same kernel (and needs T >= 2, num_classes >= 2).  Non-finite frames: the rule above fav_classify and the record's
+ * fields beside fav_uncertainty. */
 fav_status fav_op_head_uncertainty(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld,
                                    float temperature, int32_t conf_kind, float tau, fav_uncertainty* records,
                                    uint8_t* fail, float* score, void* hip_stream);
@@ -343,7 +360,8 @@ fav_status fav_op_head_uncertainty(const float* logits, int32_t T, int32_t n, in
 /* logits fp32 [T][n][ld] -> the prediction sets of fav_classify_sets under cp.  records (8-byte aligned) may be NULL
  * when true_labels is given; true_labels / true_scores (both or neither): the calibration scores of
  * fav_conformal_scores.  fail / score may be NULL.  num_classes <= 1024; conf_kind 0, 1 or 2; first_image_index is
- * the global index of frame 0 (the Philox counter of a randomized cp). */
+ * the global index of frame 0 (the Philox counter of a randomized cp).  Non-finite frames: the rule above fav_classify; the set
+ * is empty and the calibration score NaN (beside fav_pred_set). */
 fav_status fav_op_head_sets(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld,
                             float temperature, int32_t conf_kind, float tau, int64_t first_image_index,
                             const fav_conformal* cp, const int32_t* true_labels, float* true_scores,
@@ -351,7 +369,8 @@ fav_status fav_op_head_sets(const float* logits, int32_t T, int32_t n, int32_t n
 
 /* logits fp32 [T][n][ld] (device) -> cells[n][K] (fav_calib_cell, 8-byte aligned) at the K temperatures temps_host
  * (host floats, 1 <= K <= FAV_SWEEP_MAX_TEMPS, all finite and > 0), one launch that reads the logits once.  T <= 4096,
- * num_classes <= 1024; conf_kind 0, 1 or 2 (kind 2 needs T >= 2 and num_classes >= 2, as for fav_op_head). */
+ * num_classes <= 1024; conf_kind 0, 1 or 2 (kind 2 needs T >= 2 and num_classes >= 2, as for fav_op_head).  Non-finite
+ * frames: the rule above fav_classify, per temperature; nll and brier NaN (beside fav_calib_cell). */
 fav_status fav_op_head_sweep(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld,
                              const float* temps_host, int32_t K, int32_t conf_kind, const int32_t* true_labels_dev,
                              fav_calib_cell* cells_dev, void* hip_stream);
