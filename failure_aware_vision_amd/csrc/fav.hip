@@ -23,6 +23,9 @@
 
 #include "../../include/fav.h"
 #include "fav_kernels.hpp"
+#include "fav_plan.hpp"
+
+using namespace fav_plan;   // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 
 namespace {
 
@@ -56,59 +59,14 @@ std::string fmt(const char* f, ...) {
         }                                                                                        \
     } while (0)
 
-struct ArchDef {
-    bool bottleneck;
-    int depths[4];
-    int planes[4];
-    bool imagenet_stem;
-};
-const ArchDef kArch[2] = {
-    {false, {2, 2, 2, 2}, {64, 128, 256, 512}, false},
-    {true, {3, 4, 6, 3}, {64, 128, 256, 512}, true},
-};
-
-struct VitDef { int dim, depth, heads, mlp, patch; };
-// arch 2 = ViT-B/16 (BASELINE configs[4]); arch 3 = a two-layer miniature of it for the parity tests
-const VitDef kVit[2] = {{768, 12, 12, 3072, 16}, {128, 2, 2, 256, 16}};
 inline bool is_vit_arch(int arch) { return arch == 2 || arch == 3; }
 
-struct Layer {  // one convolution / fc
-    int cout, cin, kh, kw, stride, pad;
-    int cout_pad, k;         // device layout: w[cout_pad][k], bias[cout_pad]
+struct LayerWeights {  // the device side of one plan layer
     std::vector<uint16_t*> w_m;     // per ensemble member: w_slab + member * w_stride (one allocation, so that a grouped
     std::vector<float*> b_m;        // launch reaches member g's weights at a constant stride); a single model is member 0
     void *w_slab = nullptr, *b_slab = nullptr;
     size_t w_stride = 0, b_stride = 0;
 };
-
-enum OpKind { OP_STEM_IM2COL, OP_CONV, OP_MAXPOOL, OP_AVGPOOL, OP_ENTRY_DROPOUT, OP_TAIL, OP_ENTRY_REDUCE, OP_STEM_POOL };
-enum BufId { B_INPUT = -1, B_PHASE_IN = -2, B_PHASE_OUT = -3, B_NONE = -4, B_A1 = 5 };  // 0..4 rotating
-
-struct Op {
-    OpKind kind;
-    int layer = -1;          // conv layer index (OP_TAIL: the 3x3, or -1 when the tail starts at the expanding 1x1)
-    int layer_c = -1, layer_a = -1;   // OP_TAIL: the expanding 1x1 and the NEXT block's reducing 1x1 (-1: none)
-    int in = B_NONE, out = B_NONE, res = B_NONE;
-    int out2 = B_NONE;       // OP_TAIL: the next block's conv1 output
-    int Co2 = 0;
-    int H = 0, W = 0, C = 0;           // input dims per frame
-    int Ho = 0, Wo = 0, Co = 0;        // output dims per frame
-    int relu = 0, out_f32 = 0;
-    int site = -1;                     // dropout site fused into this op
-    int res_entry = 0;                 // OP_TAIL: the residual is the cached prefix output under the entry dropout (RESE)
-    int skip_y = 0;                    // OP_ENTRY_REDUCE: the dropped copies are not stored (the next tail recomputes them)
-    long long in_elems = 0, out_elems = 0;  // per frame
-};
-
-struct Phase {
-    int op_begin, op_end;
-    bool suffix;             // operates on virtual frames (t, i)
-    long long in_elems, out_elems;   // per (virtual) frame
-    int out_bytes_per_elem;
-    bool low_res;            // belongs to the low-resolution group (chunk_b)
-    int chunk;
-};
-const int kMaxPhases = 4;    // build_graph: prefix and suffix, each split at most once (at the low-resolution group)
 
 // What a grouped launch adds to a launch: every op of the schedule is ONE launch over all members - block row blockIdx.y is
 // member y, whose tensors lie at a constant byte stride behind member 0's (the workspaces and the weights are slabs).
@@ -136,10 +94,8 @@ struct Frames { const void* images; int layout; int n; long long first_index; };
 struct fav_handle {
     fav_config cfg;
     std::string err;
-    int nblocks = 0;
-    std::vector<Layer> layers;
-    std::vector<Op> ops;
-    std::vector<Phase> phases;
+    Plan plan;                         // what runs: layer shapes, ops, phases (fav_plan.hpp)
+    std::vector<LayerWeights> weights; // one entry per plan layer
     bool weights_loaded = false;
     std::vector<char> member_loaded;   // deep ensemble (BASELINE configs[3]): one checkpoint per member
     int n_members = 1;
@@ -157,20 +113,15 @@ struct fav_handle {
     // at 32 frames per call; the code is gone, its record is tools/experiments/ensemble_serial_members.diff.)
     std::vector<Lane> lanes;
     hipEvent_t ev_members = nullptr;
-    bool plan_has_mc = false, plan_stem_fused = false;   // build_graph: what will_group asks about the schedule
     std::vector<hipStream_t> vit_streams;   // ViT: parts of the batch side by side
     std::vector<hipEvent_t> vit_done;
     // chained stream-K GEMM (gemm_streamk_kernel): one workspace per stream the encoder may run on (slot 0: the caller's)
     struct SkWs { float* ws = nullptr; uint32_t* flags = nullptr; uint32_t* err = nullptr; uint32_t epoch = 0; int grid_cap = 0; };
     SkWs sk[5];
     int sk_slot = 0;                        // the slot run_vit's launches use
-    bool plan_no_fuse = false;      // fav_plan_schedule: build the layer-by-layer schedule (the fused one's reference)
     std::vector<void*> phase_out;   // output slab of each phase but the last (whose output is the logits)
     float* logits = nullptr;        // [T][max_batch][cpad]
-    int cpad = 0;
     int last_T = 0, last_n = 0;
-    int T_eff = 1;                  // samples actually run
-    int first_site = -1;
     void* host_stage = nullptr;     // for fav_classify_host
     hipStream_t host_stream = nullptr;
     // Every call that touches the handle's buffers (act[], a1, phase outputs, logits) records ev_last on its stream when it has
@@ -180,7 +131,6 @@ struct fav_handle {
     bool ev_last_set = false;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
-    int vit_ntok = 0;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
     // profiling
     bool profiling = false;
@@ -196,20 +146,12 @@ namespace {
 
 using namespace fav;
 
-// Experiment knobs.  A normal build has NONE: every FAV_KNOB below is its measured default, a compile-time constant, and the
-// library reads no environment variable.  `make EXPERIMENTS=1` (-DFAV_EXPERIMENTS) turns them back into environment variables -
-// that build is what tools/*_bench.py, the phase-clock dumps and the A/B records under profiles/ use.  Decided schedule choices
-// a caller may want to override are fav_config fields (tail_min_rows, ens_grouped_max, vit_streams, stem_fused), not knobs.
+// the experiment knobs (FAV_KNOB, fav_plan.hpp) that are text
 #ifdef FAV_EXPERIMENTS
-long long fav_knob_read(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
-#define FAV_KNOB(NAME, DFLT) ([] { static const long long v_ = fav_knob_read(NAME, (DFLT)); return v_; }())
 const char* fav_knob_str(const char* name) { return getenv(name); }
 #else
-#define FAV_KNOB(NAME, DFLT) ((long long)(DFLT))
 const char* fav_knob_str(const char*) { return nullptr; }
 #endif
-
-int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
 
 // ------------------------------------------------------------------ launchers
 struct Prof {
@@ -508,83 +450,8 @@ const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int
 }
 
 
-// ---- bottleneck tail (conv_b 3x3 -> conv_c 1x1 + residual + dropout -> next block's conv_a 1x1), one launch ----
-struct TailGeom { int patch_bytes, rega_bytes, lds_bytes, nw, wc2, rp, bias_b_off, bias_ca_off, wa_off0, wa_off1, zero_off; };
-// 512 mid channels (layer 4): the expanding 1x1 + residual + dropout on the row-owning structure.  FAV_TAIL_L4=0 disables.
-bool tail_l4() {
-    return FAV_KNOB("FAV_TAIL_L4", 1) != 0;
-}
-// LDS plan of bottleneck_tail_kernel<CMID, NRED, HAS3X3, NS, NW, WC2> (must match the kernel's own layout)
-bool tail_geometry(int cmid, int nred, bool has3x3, int W, TailGeom* g) {
-    const int cout = 4 * cmid;
-    // default plan behind the weight buffers: bias_b | bias_c | bias_a | 256 zero bytes on a 256-byte boundary
-    auto finish = [&](int bias_b_off, int wa_off0, int wa_bytes) {
-        g->bias_b_off = bias_b_off; g->bias_ca_off = bias_b_off + cmid * 5;
-        g->wa_off0 = wa_off0; g->wa_off1 = wa_off0 + wa_bytes;
-        g->zero_off = (bias_b_off + (cmid + cout + nred) * 5 + 255) & ~255;
-        g->lds_bytes = g->zero_off + 256;
-    };
-    // 256 mid channels (layer 3): the expanding 1x1 alone, or with the next block's reduce (then 8 waves x 16 rows)
-    if (cmid == 512) {      // layer 4: the expanding 1x1 alone
-        if (has3x3 || nred != 0) return false;
-        // 8 waves x 32 pixels, Wc double-buffered (2 x 64 KB), one block per CU: 1.14 ms against 1.24 ms for 4 waves with a
-        // single Wc buffer at two blocks per CU and 1.27 ms for the generic kernel (profiles/r2j_tail_l4.txt)
-        g->patch_bytes = 0; g->rega_bytes = 0; g->nw = 8; g->rp = 32; g->wc2 = 1;
-        finish(2 * 65536, 2 * 65536, 0);
-        return true;
-    }
-    else if (cmid == 256) { if ((has3x3 && nred != 0) || !(nred == 0 || nred == 256)) return false; }
-    else if ((cmid != 64 && cmid != 128) || !(nred == 0 || nred == cmid || nred == 128)) return false;
-    if (cmid == 256 && has3x3) {
-        // conv_b as the generic 256 x 256 x 64 loop (two 64 KB stages); T2, then the Wc buffers, reuse those 128 KB
-        g->patch_bytes = 0; g->rega_bytes = 128 * 1024; g->nw = 8; g->rp = 32; g->wc2 = 1;
-        finish(g->rega_bytes, g->rega_bytes, 0);
-        return true;
-    }
-    const int rp = (cmid == 256 && nred == 256) ? 16 : 32;
-    const int rowb = cmid * 2, ns = cmid == 64 ? 3 : 2;
-    const int wc_bytes = 64 * rowb, wa_bytes = nred * 128;
-    auto plan = [&](int nw) {
-        const int bm = rp * nw;
-        const int patch = has3x3 ? (int)((((long long)(bm + 2 * W + 2) * rowb) + 1023) / 1024 * 1024) : 0;
-        // region A: patch | T2 tile | Y chunk; without conv_b the T2 fragments come straight from global memory
-        int rega = has3x3 ? std::max(std::max(patch, bm * 128), bm * rowb) : (nred > 0 ? bm * 128 : 0);
-        rega = (rega + 1023) / 1024 * 1024;
-        const int ring = has3x3 ? ns * cmid * 128 : 0;
-        const int budget = nw == 4 ? 80 * 1024 : 160 * 1024;
-        g->patch_bytes = patch; g->rega_bytes = rega; g->nw = nw; g->rp = rp;
-        // Wc double-buffered when two blocks still fit a CU (4-wave blocks) / the block fits at all (8-wave blocks)
-        g->wc2 = 1;
-        int regb = std::max(ring, 2 * wc_bytes + 2 * wa_bytes);
-        finish(rega + regb, rega + 2 * wc_bytes, wa_bytes);
-        if (g->lds_bytes > budget) {
-            g->wc2 = 0;
-            regb = std::max(ring, wc_bytes + 2 * wa_bytes);
-            finish(rega + regb, rega + wc_bytes, wa_bytes);
-        }
-        return g->lds_bytes <= budget;
-    };
-    // Waves per block (pixels per block = 32 * waves).  64 mid channels: 4 waves (128 pixels, two blocks per CU; an 8-wave / 256-pixel
-    // variant measured the same, profiles/r2a_tail_bench.txt); 128 mid channels: 8 waves (256 pixels, one block per CU; 4-wave blocks
-    // at two per CU - 81 920 B each with a compact LDS plan - are bit-identical and within 1 %: profiles/r4d_l2_tail_two_blocks_per_cu.txt);
-    // 256 (conv_c alone): 4 waves, two blocks per CU.
-    return plan((cmid == 128 || (cmid == 256 && nred == 256)) ? 8 : 4);
-}
-
-bool tail_wide() {
-    return FAV_KNOB("FAV_TAIL_WIDE", 1) != 0;
-}
-
-// 256 mid channels: conv_b (generic loop) + conv_c in one launch.  FAV_TAIL_WIDE3X3=0 keeps the 3x3 as its own launch.
-bool tail_wide3x3() {
-    return FAV_KNOB("FAV_TAIL_WIDE3X3", 1) != 0;
-}
-
-// 512 mid channels (layer 4): the expanding 1x1 + residual + dropout on the row-owning structure.  FAV_TAIL_L4=0 disables.
-bool tail_enabled() {
-    return FAV_KNOB("FAV_FUSE", 1) != 0;
-}
-
+// ---- bottleneck tail (conv_b 3x3 -> conv_c 1x1 + residual + dropout -> next block's conv_a 1x1), one launch; its LDS plan
+//      is tail_geometry (fav_plan.hpp) ----
 const char* launch_tail(fav_handle* h, const fav_tail_desc& d, const Group& G, hipStream_t s) {
     const bool has3x3 = d.wb != nullptr;
     const int nred = d.wa ? d.Nred : 0;
@@ -806,14 +673,7 @@ void launch_entry_dropout(fav_handle* h, const void* x, void* out, long long ele
                        elems / 16, n_out, dp);
 }
 
-// Entry dropout + the 1x1 reduce behind it (entry_reduce_kernel): 256 -> 64 channels, the first dropout site of the
-// all_blocks policy.  FAV_ENTRY_FUSE=0 keeps the two launches.
-bool entry_reduce_enabled() {
-    return FAV_KNOB("FAV_ENTRY_FUSE", 1) != 0;
-}
-bool entry_reduce_supported(int C, int nred, long long n_img, long long HW) {
-    return C == 256 && nred == 64 && n_img * HW * C * 2 < 0x70000000LL;     // 32-bit byte offsets into the cached tensor
-}
+// Entry dropout + the 1x1 reduce behind it (entry_reduce_kernel); entry_reduce_supported: fav_plan.hpp
 const char* launch_entry_reduce(fav_handle* h, const void* x, void* y, const void* wa, const float* bias_a, void* t1, int C, int nred,
                                 int HW, int n_out, const DropParams& dp, hipStream_t s) {
     if (!entry_reduce_supported(C, nred, dp.n_img, HW)) return "entry reduce: unsupported shape";
@@ -970,7 +830,6 @@ const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C,
     return nullptr;
 }
 
-// ------------------------------------------------------------------ graph build
 // ------------------------------------------------------------------ ViT launchers
 const char* launch_layernorm(fav_handle* h, const void* x, long long ldx, const float* gamma, const float* beta, void* y, long long rows,
                              int D, float eps, hipStream_t s) {
@@ -1111,347 +970,32 @@ void launch_vit_assemble(fav_handle* h, const void* emb, const float* pos, void*
     hipLaunchKernelGGL(vit_assemble_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t*)emb, pos, (uint16_t*)x, n, ntok, D);
 }
 
-// A deep ensemble runs every op as ONE launch over its members (run_grouped) when: there is no MC-Dropout suffix, the production
-// math mode, the one-launch stem (every op is then one the grouped kernels cover), fav_config.ens_grouped_max >= 0 - and the call
-// has at most ens_grouped_max frames.  The one predicate: classify_on_stream asks it with the call's frames; build_graph, which
-// plans the size-dependent tail kernels of layers 3-4 for max_batch frames, asks whether a call of max_batch frames will be grouped.
-bool will_group(const fav_handle* h, int frames) {
+// ------------------------------------------------------------------ workspace
+// Everything the plan needs on the device, allocated once.  ResNet archs: five rotating buffers and the im2col matrix sized
+// for the largest (chunk x tensor) in any phase, the output of each phase but the last, the logits, one lane per member.
+fav_status alloc_workspace(fav_handle* h) {
     const fav_config& c = h->cfg;
-    if (h->n_members <= 1 || h->plan_has_mc || c.math_mode != FAV_MATH_BF16 || !h->plan_stem_fused || c.ens_grouped_max < 0) return false;
-    return c.ens_grouped_max == 0 || frames <= c.ens_grouped_max;
-}
-
-fav_status build_graph(fav_handle* h) {
-    const fav_config& c = h->cfg;
-    const ArchDef& A = kArch[c.arch];
-    h->layers.clear();
-    h->ops.clear();
-    auto add_layer = [&](int cout, int cin, int kh, int kw, int stride, int pad) {
-        Layer L;
-        L.cout = cout; L.cin = cin; L.kh = kh; L.kw = kw; L.stride = stride; L.pad = pad;
-        L.cout_pad = (cout + 63) / 64 * 64;
-        L.k = kh * kw * cin;
-        h->layers.push_back(L);
-        return (int)h->layers.size() - 1;
-    };
-    int H = c.in_h, W = c.in_w;
-    // stem: im2col (normalise fused) + dense GEMM over the padded patch matrix
-    int sk = A.imagenet_stem ? 7 : 3, ss = A.imagenet_stem ? 2 : 1, sp = A.imagenet_stem ? 3 : 1;
-    int li = add_layer(64, 3, sk, sk, ss, sp);
-    {
-        Layer& L = h->layers[li];
-        L.k = (sk * sk * 3 + 63) / 64 * 64;  // device K is the padded patch length
+    const Plan& P = h->plan;
+    h->weights.resize(P.layers.size());
+    if (h->vit) {
+        const VitDef& V = kVit[c.arch - 2];
+        const size_t B = (size_t)c.max_batch, D = (size_t)V.dim, ntok = (size_t)P.ntok, np = ntok - 1;
+        HIP_TRY(h, hipMalloc(&h->v_patches, B * np * (size_t)(V.patch * V.patch * 3) * 2 + 256));
+        HIP_TRY(h, hipMalloc(&h->v_emb, B * np * D * 2 + 256));
+        HIP_TRY(h, hipMalloc(&h->v_x, B * ntok * D * 2 + 256));
+        HIP_TRY(h, hipMalloc(&h->v_y, B * ntok * D * 2 + 256));
+        HIP_TRY(h, hipMalloc(&h->v_qkv, B * ntok * 3 * D * 2 + 256));
+        HIP_TRY(h, hipMalloc(&h->v_hid, B * ntok * (size_t)V.mlp * 2 + 256));
+        HIP_TRY(h, hipMalloc(&h->v_cls, B * D * 2 + 256));
+        HIP_TRY(h, hipMalloc((void**)&h->logits, B * P.cpad * 4 + 256));
+        return FAV_OK;
     }
-    int Ho = conv_out(H, sk, ss, sp), Wo = conv_out(W, sk, ss, sp);
-    if (Ho < 1 || Wo < 1) { h->err = "input too small"; return FAV_ERR_INVALID_ARG; }
-    int cur = 0;  // rotating buffer holding the current activation
-    auto other = [&](std::initializer_list<int> used) {
-        for (int i = 0; i < 5; ++i) {
-            bool u = false;
-            for (int x : used) u |= (x == i);
-            if (!u) return i;
-        }
-        return -1;
-    };
-    // production math mode: the whole ImageNet stem (normalise, 7x7/2, ReLU, max pool) is one launch
-    const bool stem_fused = A.imagenet_stem && c.math_mode == FAV_MATH_BF16 && c.stem_fused >= 0 && !h->plan_no_fuse &&
-                            conv_out(Ho, 3, 2, 1) >= 1 && conv_out(Wo, 3, 2, 1) >= 1;
-    h->plan_stem_fused = stem_fused;
-    int stem_ops = 0;
-    if (stem_fused) {
-        Op o; o.kind = OP_STEM_POOL; o.layer = li; o.in = B_INPUT; o.out = cur; o.relu = 1;
-        o.H = H; o.W = W; o.C = 3; o.Ho = conv_out(Ho, 3, 2, 1); o.Wo = conv_out(Wo, 3, 2, 1); o.Co = 64;
-        o.in_elems = (long long)H * W * 3; o.out_elems = (long long)o.Ho * o.Wo * 64;
-        h->ops.push_back(o);
-        H = o.Ho; W = o.Wo;
-        stem_ops = 1;
-    } else {
-        Op o; o.kind = OP_STEM_IM2COL; o.layer = li; o.in = B_INPUT; o.out = B_A1;
-        o.H = H; o.W = W; o.C = 3; o.Ho = Ho; o.Wo = Wo; o.Co = h->layers[li].k;
-        o.in_elems = (long long)H * W * 3; o.out_elems = (long long)Ho * Wo * o.Co;
-        h->ops.push_back(o);
-        Op g; g.kind = OP_CONV; g.layer = li; g.in = B_A1; g.out = cur; g.relu = 1;
-        g.H = Ho; g.W = Wo; g.C = h->layers[li].k; g.Ho = Ho; g.Wo = Wo; g.Co = 64;
-        g.in_elems = o.out_elems; g.out_elems = (long long)Ho * Wo * 64;
-        h->ops.push_back(g);
-        H = Ho; W = Wo;
-        stem_ops = 2;
-    }
-    int C = 64;
-    if (A.imagenet_stem && !stem_fused) {
-        ++stem_ops;
-        Op o; o.kind = OP_MAXPOOL; o.in = cur; o.out = other({cur});
-        o.H = H; o.W = W; o.C = C; o.Ho = conv_out(H, 3, 2, 1); o.Wo = conv_out(W, 3, 2, 1); o.Co = C;
-        o.in_elems = (long long)H * W * C; o.out_elems = (long long)o.Ho * o.Wo * C;
-        h->ops.push_back(o);
-        cur = o.out; H = o.Ho; W = o.Wo;
-    }
-    std::vector<int> block_last_op;
-    const int exp = A.bottleneck ? 4 : 1;
-    int inpl = 64, bidx = 0;
-    // phase boundaries in block units (known before the ops exist; the fused tails must not straddle them)
-    const int nblocks_total = A.depths[0] + A.depths[1] + A.depths[2] + A.depths[3];
-    int mc_first_site = -1;
-    {
-        const uint32_t thr0 = (uint32_t)std::lround((double)c.dropout_p * 256.0);
-        if (c.site_mask != 0 && thr0 > 0)
-            for (int sb = 0; sb <= nblocks_total; ++sb)
-                if (c.site_mask >> sb & 1) { mc_first_site = sb; break; }
-    }
-    int regroup_blk = c.regroup_block;
-    if (regroup_blk < 0) regroup_blk = A.depths[0] + A.depths[1];
-    regroup_blk = std::min(regroup_blk, nblocks_total);
-    h->plan_has_mc = mc_first_site >= 0;
-    int pre_t1 = -1;   // rotating buffer already holding the coming block's conv1 output
-    for (int st = 0; st < 4; ++st) {
-        for (int bi = 0; bi < A.depths[st]; ++bi, ++bidx) {
-            const int pl = A.planes[st];
-            const int s = (bi == 0 && st > 0) ? 2 : 1;
-            const bool ds = (bi == 0) && (s != 1 || inpl != pl * exp);
-            const int xin = cur;
-            int t1 = pre_t1 >= 0 ? pre_t1 : other({xin}), t2 = other({xin, t1});
-            auto conv_op = [&](int layer, int in, int out, int res, int relu, int Hi, int Wi) {
-                const Layer& L = h->layers[layer];
-                Op o; o.kind = OP_CONV; o.layer = layer; o.in = in; o.out = out; o.res = res; o.relu = relu;
-                o.H = Hi; o.W = Wi; o.C = L.cin;
-                o.Ho = conv_out(Hi, L.kh, L.stride, L.pad); o.Wo = conv_out(Wi, L.kw, L.stride, L.pad); o.Co = L.cout;
-                o.in_elems = (long long)Hi * Wi * L.cin; o.out_elems = (long long)o.Ho * o.Wo * L.cout;
-                h->ops.push_back(o);
-                return o;
-            };
-            int Hn, Wn;
-            if (A.bottleneck) {
-                int l1 = add_layer(pl, inpl, 1, 1, 1, 0), l2 = add_layer(pl, pl, 3, 3, s, 1), l3 = add_layer(pl * 4, pl, 1, 1, 1, 0);
-                if (pre_t1 < 0) conv_op(l1, xin, t1, B_NONE, 1, H, W);   // else: written by the previous block's fused tail
-                pre_t1 = -1;
-                Hn = conv_out(H, 3, s, 1); Wn = conv_out(W, 3, s, 1);
-                int ld = -1;
-                if (ds) ld = add_layer(pl * exp, inpl, 1, 1, s, 0);
-                // Fused tail (bottleneck_tail_kernel): conv2 (when 3x3/1) + conv3 (+ the NEXT block's conv1 unless a
-                // phase boundary or the end of the network lies between the two blocks).  Production math mode only.
-                const bool last_block = (st == 3 && bi + 1 == A.depths[3]);
-                const bool boundary_after = last_block || (mc_first_site == bidx) || (bidx + 1 == regroup_blk);
-                const int next_pl = (bi + 1 < A.depths[st]) ? pl : (st < 3 ? A.planes[st + 1] : 0);
-                int nred = boundary_after ? 0 : next_pl;
-                TailGeom tg;
-                // the 256-pixel / 8-wave kernels of layers 3-4 run one block per CU: they pay only when the planned launch
-                // (max_batch frames, x T samples behind the first dropout site) brings two blocks per CU
-                // (an ensemble without MC-Dropout runs every op as one launch over its members, see run_grouped)
-                const int plan_groups = will_group(h, c.max_batch) ? h->n_members : 1;
-                const long long plan_rows = (long long)c.max_batch * ((mc_first_site >= 0 && bidx > mc_first_site) ? c.n_samples : 1) * Hn * Wn * plan_groups;
-                const bool big_launch = c.tail_min_rows < 0 || plan_rows >= (c.tail_min_rows > 0 ? (long long)c.tail_min_rows : 512ll * 256);
-                const bool tail_3x3 = (s == 1) && (pl <= 128 || (pl == 256 && tail_wide3x3() && big_launch));
-                if (pl > 128) nred = 0;   // wide blocks: the expanding 1x1 alone (with the next block's reduce in the launch it measured 3.01 ms against 1.77 + 0.95: only fav_op_bottleneck_tail still reaches that kernel)
-                bool fuse = tail_enabled() && !h->plan_no_fuse && c.math_mode == FAV_MATH_BF16 && (pl == 64 || pl == 128 || (pl == 256 && tail_wide()) || (pl == 512 && tail_l4() && big_launch));
-                if (fuse && !tail_geometry(pl, nred, tail_3x3, Wn, &tg)) {
-                    nred = 0;
-                    fuse = tail_geometry(pl, 0, tail_3x3, Wn, &tg);
-                }
-                int t2v = t1;
-                if (!(fuse && tail_3x3)) {                          // the 3x3 as its own launch
-                    conv_op(l2, t1, t2, B_NONE, 1, H, W);
-                    t2v = t2;
-                }
-                int idn = xin;
-                // blob order is conv1, conv2, conv3, downsample; launch order: downsample before conv3
-                if (ds) { idn = other({xin, t1, t2}); conv_op(ld, xin, idn, B_NONE, 0, H, W); }
-                if (fuse) {
-                    const int yout = other({xin, t1, t2v, idn});    // t2 is free when the 3x3 is fused, xin when it is not the residual
-                    Op o; o.kind = OP_TAIL; o.layer = tail_3x3 ? l2 : -1; o.layer_c = l3;
-                    o.layer_a = nred > 0 ? (int)h->layers.size() : -1;      // the next add_layer() is the next block's conv1
-                    o.in = t2v; o.res = idn; o.out = yout; o.relu = 1;
-                    o.H = Hn; o.W = Wn; o.C = pl; o.Ho = Hn; o.Wo = Wn; o.Co = pl * 4; o.Co2 = nred;
-                    o.in_elems = (long long)Hn * Wn * pl; o.out_elems = (long long)Hn * Wn * pl * 4;
-                    if (nred > 0) { o.out2 = other({t2v, idn, yout}); pre_t1 = o.out2; }
-                    h->ops.push_back(o);
-                    cur = yout;
-                } else {
-                    int yout = ds ? other({xin, t1, t2, idn}) : t1;  // t1 is dead after conv2
-                    conv_op(l3, t2, yout, idn, 1, Hn, Wn);
-                    cur = yout;
-                }
-            } else {
-                int l1 = add_layer(pl, inpl, 3, 3, s, 1), l2 = add_layer(pl, pl, 3, 3, 1, 1);
-                Op o1 = conv_op(l1, xin, t1, B_NONE, 1, H, W);
-                Hn = o1.Ho; Wn = o1.Wo;
-                int idn = xin, ld = -1;
-                if (ds) ld = add_layer(pl * exp, inpl, 1, 1, s, 0);
-                if (ds) { idn = t2; conv_op(ld, xin, idn, B_NONE, 0, H, W); }
-                int yout = other({xin, t1, idn});
-                conv_op(l2, t1, yout, idn, 1, Hn, Wn);
-                cur = yout;
-            }
-            block_last_op.push_back((int)h->ops.size() - 1);
-            H = Hn; W = Wn; inpl = pl * exp; C = inpl;
-        }
-    }
-    h->nblocks = bidx;
-    {
-        Op o; o.kind = OP_AVGPOOL; o.in = cur; o.out = other({cur});
-        o.H = H; o.W = W; o.C = C; o.Ho = 1; o.Wo = 1; o.Co = C;
-        o.in_elems = (long long)H * W * C; o.out_elems = C;
-        h->ops.push_back(o);
-        cur = o.out;
-    }
-    const int pool_op = (int)h->ops.size() - 1;
-    int lfc = add_layer(c.num_classes, C, 1, 1, 1, 0);
-    h->cpad = h->layers[lfc].cout_pad;
-    {
-        Op o; o.kind = OP_CONV; o.layer = lfc; o.in = cur; o.out = other({cur}); o.out_f32 = 1;
-        o.H = 1; o.W = 1; o.C = C; o.Ho = 1; o.Wo = 1; o.Co = c.num_classes;
-        o.in_elems = C; o.out_elems = h->cpad;
-        h->ops.push_back(o);
-    }
-
-    // ---- dropout sites and prefix / suffix split -----------------------------
-    const uint32_t valid_mask = (h->nblocks + 1 >= 32) ? 0xFFFFFFFFu : ((1u << (h->nblocks + 1)) - 1);
-    if (c.site_mask & ~valid_mask) { h->err = "site_mask has bits beyond the pooled-feature site"; return FAV_ERR_INVALID_ARG; }
-    const uint32_t thr = (uint32_t)std::lround((double)c.dropout_p * 256.0);
-    const bool mc = c.site_mask != 0 && thr > 0;
-    h->T_eff = mc ? c.n_samples : 1;
-    h->first_site = -1;
-    int split = (int)h->ops.size();  // ops [0, split) are the prefix
-    if (mc) {
-        for (int s = 0; s <= h->nblocks; ++s)
-            if (c.site_mask >> s & 1) { h->first_site = s; break; }
-        const int first_op = h->first_site < h->nblocks ? block_last_op[h->first_site] : pool_op;
-        split = first_op + 1;
-        for (int s = h->first_site + 1; s <= h->nblocks; ++s)
-            if (c.site_mask >> s & 1) h->ops[s < h->nblocks ? block_last_op[s] : pool_op].site = s;
-    }
-    // op index where the low-resolution group starts
-    int regroup = c.regroup_block;
-    if (regroup < 0) regroup = A.bottleneck ? A.depths[0] + A.depths[1] : A.depths[0] + A.depths[1];
-    regroup = std::min(regroup, h->nblocks);
-    const int regroup_op = regroup == 0 ? stem_ops
-                                        : (regroup >= h->nblocks ? pool_op : block_last_op[regroup - 1] + 1);
-
-    // ---- phases ---------------------------------------------------------------
-    h->phases.clear();
-    int regroup_now = regroup_op;  // op index of the low-resolution group in the CURRENT op list
-    auto add_phase = [&](int b, int e, bool suffix) {
-        if (b >= e) return;
-        Phase p; p.op_begin = b; p.op_end = e; p.suffix = suffix;
-        p.low_res = b >= regroup_now;
-        p.in_elems = h->ops[b].in_elems;
-        p.out_elems = h->ops[e - 1].out_elems;
-        p.out_bytes_per_elem = h->ops[e - 1].out_f32 ? 4 : 2;
-        p.chunk = 0;
-        h->phases.push_back(p);
-    };
-    auto add_range = [&](int b, int e, bool suffix) {
-        if (b < regroup_op && regroup_op < e) { add_phase(b, regroup_op, suffix); add_phase(regroup_op, e, suffix); }
-        else add_phase(b, e, suffix);
-    };
-    add_range(0, split, false);
-    if (mc) {
-        // the suffix starts with the entry dropout of the cached prefix output
-        Op ed; ed.kind = OP_ENTRY_DROPOUT; ed.in = B_PHASE_IN; ed.site = h->first_site;
-        ed.in_elems = ed.out_elems = h->ops[split - 1].out_elems;
-        ed.out = 0;  // patched below
-        // insert before ops[split]; the op list after `split` reads its input from
-        // whatever buffer the prefix's last op wrote, so write the dropout there.
-        ed.out = h->ops[split - 1].out;
-        h->ops.insert(h->ops.begin() + split, ed);
-        regroup_now = regroup_op >= split ? regroup_op + 1 : regroup_op;
-        // the 1x1 reduce that follows (the next block's conv1) joins the dropout launch when both lie in one phase
-        if (split + 2 < (int)h->ops.size() && split + 1 != regroup_now && tail_enabled() && entry_reduce_enabled() && !h->plan_no_fuse &&
-            c.math_mode == FAV_MATH_BF16) {
-            const Op& cv = h->ops[split + 1];
-            const Op& e0 = h->ops[split];
-            if (cv.kind == OP_CONV && cv.in == e0.out && cv.res == B_NONE && cv.relu == 1 && !cv.out_f32 && cv.out != e0.out && cv.site < 0) {
-                const Layer& L = h->layers[cv.layer];
-                if (L.kh == 1 && L.kw == 1 && L.stride == 1 && L.pad == 0 && L.cout == L.cout_pad &&
-                    entry_reduce_supported(L.cin, L.cout, c.max_batch, (long long)cv.H * cv.W)) {
-                    Op f = e0;
-                    f.kind = OP_ENTRY_REDUCE; f.layer_a = cv.layer; f.out2 = cv.out; f.Co2 = L.cout;
-                    f.H = cv.H; f.W = cv.W; f.C = L.cin; f.relu = 1;
-                    h->ops[split] = f;
-                    h->ops.erase(h->ops.begin() + split + 1);
-                    if (regroup_now > split + 1) --regroup_now;
-                    // The block behind the entry: its tail can take its residual - the dropped copy of the cached prefix output -
-                    // from the cached tensor itself and apply the entry mask in its epilogue; the T copies are then neither
-                    // written (12 GB per step at the headline shape) nor read back.  FAV_ENTRY_RES=0 keeps them.
-                    const bool entry_res = FAV_KNOB("FAV_ENTRY_RES", 1) != 0;
-                    const int y0 = f.out;
-                    if (entry_res && split + 1 < (int)h->ops.size() && regroup_now != split + 1) {
-                        Op& tl = h->ops[split + 1];
-                        bool ok = tl.kind == OP_TAIL && tl.res == y0 && tl.in == f.out2 && tl.layer >= 0 && tl.C == 64 && tl.Co2 == 64 &&
-                                  tl.layer_a >= 0 && tl.site >= 0 && tl.out != y0 && tl.out2 != y0 &&
-                                  (double)c.max_batch * f.H * f.W * f.C * 2.0 < 2147483647.0;
-                        const int phase_end = regroup_now > split + 1 ? regroup_now : (int)h->ops.size();
-                        for (int k = split + 2; ok && k < phase_end; ++k) {     // nobody else reads the copies before their buffer is reused
-                            const Op& o = h->ops[k];
-                            if (o.in == y0 || o.res == y0) ok = false;
-                            if (o.out == y0 || o.out2 == y0) break;
-                        }
-                        if (ok) { tl.res_entry = 1; h->ops[split].skip_y = 1; }
-                    }
-                }
-            }
-        }
-        const int nops = (int)h->ops.size();
-        // split the suffix only if at least one real op lies on each side
-        if (split + 1 < regroup_now && regroup_now < nops) { add_phase(split, regroup_now, true); add_phase(regroup_now, nops, true); }
-        else add_phase(split, nops, true);
-    }
-    // mark phase boundaries in the ops' buffers
-    for (size_t i = 0; i < h->phases.size(); ++i) {
-        Phase& p = h->phases[i];
-        Op& first = h->ops[p.op_begin];
-        if (first.kind != OP_STEM_IM2COL && first.kind != OP_STEM_POOL) {
-            // consumers of the phase input: every op in the phase reading the buffer the
-            // previous phase's last op wrote, until that rotating buffer is overwritten
-            const bool entry = first.kind == OP_ENTRY_DROPOUT || first.kind == OP_ENTRY_REDUCE;
-            const int src = entry ? B_PHASE_IN : first.in;
-            if (!entry) {
-                for (int k = p.op_begin; k < p.op_end; ++k) {
-                    Op& o = h->ops[k];
-                    if (o.in == src) o.in = B_PHASE_IN;
-                    if (o.res == src) o.res = B_PHASE_IN;
-                    if (o.out == src || o.out2 == src) break;
-                }
-            }
-        }
-        h->ops[p.op_end - 1].out = B_PHASE_OUT;
-    }
-    return FAV_OK;
-}
-
-// ------------------------------------------------------------------ memory plan
-fav_status plan_memory(fav_handle* h) {
-    const fav_config& c = h->cfg;
-    const long long nv_max = (long long)c.max_batch * h->T_eff;
-    const size_t nph = h->phases.size();
-    if (nph > (size_t)kMaxPhases) { h->err = "schedule has more phases than a lane holds"; return FAV_ERR_UNSUPPORTED; }
-    // chunk sizes
-    for (size_t i = 0; i < h->phases.size(); ++i) {
-        Phase& p = h->phases[i];
-        long long pe = 1;
-        for (int k = p.op_begin; k < p.op_end; ++k) {
-            const Op& o = h->ops[k];
-            pe = std::max(pe, o.out == B_A1 ? o.out_elems / 2 : o.out_elems);
-        }
-        // Pass size: measured on MI355X, fewer and larger launches beat
-        // keeping producer->consumer tensors inside the 256 MiB Infinity Cache at every
-        // size tried (launch ramp/tail cost more than the HBM round trip), so by default a
-        // phase runs all its frames in one pass, bounded by a 16 GiB-per-tensor arena
-        // budget (5 rotating tensors; 288 GB of HBM makes that a non-issue).
-        const long long target = 16ll << 30;
-        long long auto_chunk = std::max<long long>(1, target / (pe * 2));
-        const int want = p.low_res ? c.chunk_b : c.chunk_a;
-        long long chunk = want > 0 ? want : auto_chunk;
-        const long long dom = p.suffix ? nv_max : c.max_batch;
-        p.chunk = (int)std::max<long long>(1, std::min(chunk, dom));
-    }
-    // (Running the last two phases as a two-stream pipeline - the low-resolution phase of chunk c beside the high-resolution
-    // phase of chunk c+1 - measured 119.0-121.2 ms per step against 118.5 ms without; the code is gone, its
-    // record is tools/experiments/phase_pipeline_two_streams.diff.)
-    // rotating buffers sized for the largest (chunk x tensor) in any phase
+    const long long nv_max = (long long)c.max_batch * P.T_eff;
+    const size_t nph = P.phases.size();
     size_t act_bytes = 0, a1_bytes = 0;
-    for (const Phase& p : h->phases) {
+    for (const Phase& p : P.phases) {
         for (int k = p.op_begin; k < p.op_end; ++k) {
-            const Op& o = h->ops[k];
+            const Op& o = P.ops[k];
             const size_t b = (size_t)o.out_elems * (o.out_f32 ? 4 : 2) * p.chunk;
             if (o.out == B_A1) a1_bytes = std::max(a1_bytes, b);
             else if (o.out >= 0) act_bytes = std::max(act_bytes, b);
@@ -1468,12 +1012,12 @@ fav_status plan_memory(fav_handle* h) {
     h->phase_out.assign(nph, nullptr);
     std::vector<size_t> phase_bytes(nph, 0);
     for (size_t i = 0; i + 1 < nph; ++i) {
-        const Phase& p = h->phases[i];
+        const Phase& p = P.phases[i];
         const long long dom = p.suffix ? nv_max : c.max_batch;
         phase_bytes[i] = ((size_t)dom * p.out_elems * p.out_bytes_per_elem + 255) / 256 * 256 + 256;
         HIP_TRY(h, hipMalloc(&h->phase_out[i], phase_bytes[i] * parts));
     }
-    HIP_TRY(h, hipMalloc((void**)&h->logits, (size_t)nv_max * h->n_members * h->cpad * 4 + 256));
+    HIP_TRY(h, hipMalloc((void**)&h->logits, (size_t)nv_max * h->n_members * P.cpad * 4 + 256));
     h->lanes.resize(h->n_members);
     if (h->n_members > 1) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_members, hipEventDisableTiming));
     for (int m = 0; m < h->n_members; ++m) {
@@ -1496,17 +1040,17 @@ fav_status plan_memory(fav_handle* h) {
 // members exactly as it averages samples.
 fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lane, long long v_begin, long long v_end) {
     const fav_config& c = h->cfg;
-    const Phase& p = h->phases[pi];
+    const Phase& p = h->plan.phases[pi];
     const hipStream_t s = lane.stream;
     const int n = f.n, layout = f.layout;
-    auto LW = [&](int li) -> void* { return h->layers[li].w_m[lane.member]; };
-    auto LB = [&](int li) -> float* { return h->layers[li].b_m[lane.member]; };
-    const size_t logits_slot = (size_t)n * h->cpad * 4;     // one member's part of the logits in a call of n frames
-    const bool last = pi + 1 == h->phases.size();
+    auto LW = [&](int li) -> void* { return h->weights[li].w_m[lane.member]; };
+    auto LB = [&](int li) -> float* { return h->weights[li].b_m[lane.member]; };
+    const size_t logits_slot = (size_t)n * h->plan.cpad * 4;     // one member's part of the logits in a call of n frames
+    const bool last = pi + 1 == h->plan.phases.size();
     const char* pin_base = pi == 0 ? (const char*)f.images : (const char*)lane.phase_out[pi - 1];
-    const int in_bpe = pi == 0 ? (layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4) : h->phases[pi - 1].out_bytes_per_elem;
+    const int in_bpe = pi == 0 ? (layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4) : h->plan.phases[pi - 1].out_bytes_per_elem;
     // a suffix phase that follows the prefix reads frame (v % n); later phases read virtual frame v
-    const bool in_is_virtual = pi > 0 && h->phases[pi - 1].suffix;
+    const bool in_is_virtual = pi > 0 && h->plan.phases[pi - 1].suffix;
     char* pout_base = last ? (char*)h->logits + (size_t)lane.member * logits_slot : (char*)lane.phase_out[pi];
     const uint32_t thr = (uint32_t)std::lround((double)c.dropout_p * 256.0);
     const float scale = thr > 0 ? (float)(1.0 / (1.0 - thr / 256.0)) : 1.0f;
@@ -1537,10 +1081,10 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
                 default: return (char*)next.act[id] - (char*)lane.act[id];
             }
         };
-        auto gw = [&](int li) -> long long { return li >= 0 ? (long long)h->layers[li].w_stride : 0; };
-        auto gb = [&](int li) -> long long { return li >= 0 ? (long long)h->layers[li].b_stride : 0; };
+        auto gw = [&](int li) -> long long { return li >= 0 ? (long long)h->weights[li].w_stride : 0; };
+        auto gb = [&](int li) -> long long { return li >= 0 ? (long long)h->weights[li].b_stride : 0; };
         for (int k = p.op_begin; k < p.op_end; ++k) {
-            const Op& o = h->ops[k];
+            const Op& o = h->plan.ops[k];
             h->cur_op = k;
             Group G;
             if (lane.groups > 1) {
@@ -1554,13 +1098,13 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
             dd.v0 = p.suffix ? v0 : 0; dd.n_img = n; dd.first_image_index = f.first_index;
             switch (o.kind) {
                 case OP_STEM_IM2COL: {
-                    const Layer& L = h->layers[o.layer];
+                    const LayerShape& L = h->plan.layers[o.layer];
                     launch_stem(h, buf(o.in, o), layout, cn, o.H, o.W, L.kh, L.kw, L.stride, L.pad, L.k, c.mean,
                                 istd, buf(o.out, o), s);
                     break;
                 }
                 case OP_CONV: {
-                    const Layer& L = h->layers[o.layer];
+                    const LayerShape& L = h->plan.layers[o.layer];
                     fav_conv_desc d;
                     d.x = buf(o.in, o); d.w = LW(o.layer); d.bias = LB(o.layer); d.res = buf(o.res, o); d.y = buf(o.out, o);
                     d.n_frames = cn; d.H = o.H; d.W = o.W; d.Cin = o.C; d.Cout = L.cout;
@@ -1582,7 +1126,7 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
                     if (o.layer_a >= 0) { d.wa = LW(o.layer_a); d.bias_a = LB(o.layer_a); d.t1n = buf(o.out2, o); }
                     d.n_frames = cn; d.H = o.H; d.W = o.W; d.Cmid = o.C; d.Nred = o.Co2;
                     d.drop = dd;
-                    if (o.res_entry) { d.res = pin_base; d.res_entry = 1; d.entry_site = h->first_site; }   // the cached prefix output
+                    if (o.res_entry) { d.res = pin_base; d.res_entry = 1; d.entry_site = h->plan.first_site; }   // the cached prefix output
                     if (const char* e = launch_tail(h, d, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 }
@@ -1617,7 +1161,7 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
 }
 
 void free_all(fav_handle* h) {
-    for (auto& L : h->layers) {
+    for (auto& L : h->weights) {
         if (L.w_slab) (void)hipFree(L.w_slab);
         if (L.b_slab) (void)hipFree(L.b_slab);
         L.w_slab = L.b_slab = nullptr;
@@ -1643,58 +1187,13 @@ void free_all(fav_handle* h) {
     for (auto& e : h->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
 }
 
-
-// ViT: layers in blob order, fixed buffers, no phases (single deterministic pass).
-fav_status build_vit(fav_handle* h) {
-    const fav_config& c = h->cfg;
-    const VitDef& V = kVit[c.arch - 2];
-    if (c.in_h % V.patch || c.in_w % V.patch) { h->err = "ViT input must be a multiple of the patch size"; return FAV_ERR_INVALID_ARG; }
-    const int np = (c.in_h / V.patch) * (c.in_w / V.patch), ntok = np + 1;
-    if (ntok > 256) { h->err = "ViT path supports at most 256 tokens"; return FAV_ERR_UNSUPPORTED; }
-    if (c.site_mask != 0 && c.dropout_p > 0.f) { h->err = "the ViT path has no dropout sites"; return FAV_ERR_UNSUPPORTED; }
-    if (c.n_members > 1) { h->err = "the ViT path has no ensemble mode"; return FAV_ERR_UNSUPPORTED; }
-    h->vit = true;
-    h->vit_ntok = ntok;
-    h->T_eff = 1;
-    h->layers.clear();
-    auto lin = [&](int cout, int cin, int kh, int kw, int stride) {
-        Layer L; L.cout = cout; L.cin = cin; L.kh = kh; L.kw = kw; L.stride = stride; L.pad = 0;
-        L.cout_pad = (cout + 63) / 64 * 64; L.k = kh * kw * cin;
-        h->layers.push_back(L);
-    };
-    auto vec = [&](int len) {
-        Layer L; L.cout = len; L.cin = 0; L.kh = 0; L.kw = 0; L.stride = 0; L.pad = 0; L.cout_pad = len; L.k = 0;
-        h->layers.push_back(L);
-    };
-    lin(V.dim, 3, V.patch, V.patch, V.patch);
-    vec(ntok * V.dim);
-    for (int i = 0; i < V.depth; ++i) {
-        vec(V.dim); lin(3 * V.dim, V.dim, 1, 1, 1); lin(V.dim, V.dim, 1, 1, 1);
-        vec(V.dim); lin(V.mlp, V.dim, 1, 1, 1); lin(V.dim, V.mlp, 1, 1, 1);
-    }
-    vec(V.dim);
-    lin(c.num_classes, V.dim, 1, 1, 1);
-    h->cpad = h->layers.back().cout_pad;
-    HIP_TRY(h, hipSetDevice(c.device));
-    const size_t B = (size_t)c.max_batch, D = (size_t)V.dim;
-    HIP_TRY(h, hipMalloc(&h->v_patches, B * np * (size_t)(V.patch * V.patch * 3) * 2 + 256));
-    HIP_TRY(h, hipMalloc(&h->v_emb, B * np * D * 2 + 256));
-    HIP_TRY(h, hipMalloc(&h->v_x, B * ntok * D * 2 + 256));
-    HIP_TRY(h, hipMalloc(&h->v_y, B * ntok * D * 2 + 256));
-    HIP_TRY(h, hipMalloc(&h->v_qkv, B * ntok * 3 * D * 2 + 256));
-    HIP_TRY(h, hipMalloc(&h->v_hid, B * ntok * (size_t)V.mlp * 2 + 256));
-    HIP_TRY(h, hipMalloc(&h->v_cls, B * D * 2 + 256));
-    HIP_TRY(h, hipMalloc((void**)&h->logits, B * h->cpad * 4 + 256));
-    return FAV_OK;
-}
-
 // One forward pass of the ViT encoder over n frames -> fp32 logits [n][cpad].
 // Frames [f0, f0 + n) of the call: every buffer is indexed by frame, so two halves of a batch can run side by side
 // on two streams (fav_classify_ex).
 fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, int n, hipStream_t s) {
     const fav_config& c = h->cfg;
     const VitDef& V = kVit[c.arch - 2];
-    const int ntok = h->vit_ntok, D = V.dim, gh = c.in_h / V.patch, gw = c.in_w / V.patch;
+    const int ntok = h->plan.ntok, D = V.dim, gh = c.in_h / V.patch, gw = c.in_w / V.patch;
     const float inv_std[3] = {1.0f / c.stdev[0], 1.0f / c.stdev[1], 1.0f / c.stdev[2]};
     const size_t F = (size_t)f0, np = (size_t)gh * gw;
     const void* images = (const char*)images_all + F * c.in_h * c.in_w * 3 * (layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4);
@@ -1706,17 +1205,19 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
     B.v_qkv = (char*)h->v_qkv + F * ntok * 3 * D * 2;
     B.v_hid = (char*)h->v_hid + F * ntok * (size_t)V.mlp * 2;
     B.v_cls = (char*)h->v_cls + F * D * 2;
-    B.logits = h->logits + F * h->cpad;
+    B.logits = h->logits + F * h->plan.cpad;
     auto gemm = [&](int layer, const void* x, int rows_per_frame, const void* res, int act, void* y, int out_f32) -> const char* {
-        const Layer& L = h->layers[layer];
+        const LayerShape& L = h->plan.layers[layer];
+        const void* w = h->weights[layer].w_m[0];
+        const float* bias = h->weights[layer].b_m[0];
         fav_conv_desc d;
         memset(&d, 0, sizeof d);
-        d.x = x; d.w = L.w_m[0]; d.bias = L.b_m[0]; d.res = res; d.y = y;
+        d.x = x; d.w = w; d.bias = bias; d.res = res; d.y = y;
         d.n_frames = n; d.H = rows_per_frame; d.W = 1; d.Cin = L.k; d.Cout = L.cout;
         d.kh = 1; d.kw = 1; d.stride = 1; d.pad = 0; d.relu = act; d.out_f32 = out_f32; d.math_mode = c.math_mode;
         d.drop.site = -1;
         if (!out_f32 && c.math_mode == FAV_MATH_BF16 && L.cout == L.cout_pad &&
-            launch_gemm_streamk(h, x, L.w_m[0], L.b_m[0], res, y, (long long)n * rows_per_frame, L.k, L.cout, act, s)) return nullptr;
+            launch_gemm_streamk(h, x, w, bias, res, y, (long long)n * rows_per_frame, L.k, L.cout, act, s)) return nullptr;
         return launch_conv(h, d, L.cout_pad, out_f32 ? L.cout_pad : L.cout, Group{}, s);
     };
 #define FAV_VIT_TRY(expr)                                            \
@@ -1727,10 +1228,10 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
     // patch embedding: normalise + im2col (k = (r*P + s)*3 + c), GEMM, add positions / class token
     launch_stem(h, images, layout, n, c.in_h, c.in_w, V.patch, V.patch, V.patch, 0, V.patch * V.patch * 3, c.mean, inv_std, B.v_patches, s);
     FAV_VIT_TRY(gemm(0, B.v_patches, gh * gw, nullptr, 0, B.v_emb, 0));
-    launch_vit_assemble(h, B.v_emb, (const float*)h->layers[1].w_m[0], B.v_x, n, ntok, D, s);
+    launch_vit_assemble(h, B.v_emb, (const float*)h->weights[1].w_m[0], B.v_x, n, ntok, D, s);
     int li = 2;
     for (int blk = 0; blk < V.depth; ++blk, li += 6) {
-        const Layer &ln1 = h->layers[li], &ln2 = h->layers[li + 3];
+        const LayerWeights &ln1 = h->weights[li], &ln2 = h->weights[li + 3];
         FAV_VIT_TRY(launch_layernorm(h, B.v_x, D, (const float*)ln1.w_m[0], ln1.b_m[0], B.v_y, (long long)n * ntok, D, 1e-6f, s));
         FAV_VIT_TRY(gemm(li + 1, B.v_y, ntok, nullptr, 0, B.v_qkv, 0));
         FAV_VIT_TRY(launch_attention(h, B.v_qkv, B.v_y, n, ntok, D, V.heads, c.math_mode, s));
@@ -1739,7 +1240,7 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
         FAV_VIT_TRY(gemm(li + 4, B.v_y, ntok, nullptr, 2, B.v_hid, 0));              // GELU fused
         FAV_VIT_TRY(gemm(li + 5, B.v_hid, ntok, B.v_x, 0, B.v_x, 0));
     }
-    const Layer& lnf = h->layers[li];
+    const LayerWeights& lnf = h->weights[li];
     FAV_VIT_TRY(launch_layernorm(h, B.v_x, (long long)ntok * D, (const float*)lnf.w_m[0], lnf.b_m[0], B.v_cls, n, D, 1e-6f, s));   // class tokens only
     FAV_VIT_TRY(gemm(li + 1, B.v_cls, 1, nullptr, 0, B.logits, 1));
 #undef FAV_VIT_TRY
@@ -1795,7 +1296,7 @@ fav_status fav_create(const fav_config* cfg, fav_handle** out) {
         return FAV_ERR_INVALID_ARG;
     }
     if (cfg->conf_kind == FAV_CONF_MUTUAL_INFO) {
-        // the samples the head averages (the T_eff / n_members rule of build_graph; the ViT path is a single pass)
+        // the samples the head averages (the T_eff / n_members rule of plan_resnet; the ViT path is a single pass)
         const bool mc = !is_vit_arch(cfg->arch) && cfg->site_mask != 0 && std::lround((double)cfg->dropout_p * 256.0) > 0;
         const int T = cfg->n_members > 1 ? cfg->n_members : (mc ? cfg->n_samples : 1);
         if (T < 2 || cfg->num_classes < 2) {
@@ -1821,8 +1322,9 @@ fav_status fav_create(const fav_config* cfg, fav_handle** out) {
     h->n_members = cfg->n_members > 1 ? cfg->n_members : 1;
     h->member_loaded.assign(h->n_members, 0);
     if (hipSetDevice(cfg->device) != hipSuccess) { g_create_error = "hipSetDevice failed"; delete h; return FAV_ERR_HIP; }
-    fav_status st = is_vit_arch(cfg->arch) ? build_vit(h) : build_graph(h);
-    if (st == FAV_OK && !h->vit) st = plan_memory(h);
+    h->vit = is_vit_arch(cfg->arch);
+    fav_status st = h->vit ? plan_vit(h->cfg, &h->plan, &h->err) : plan_resnet(h->cfg, h->n_members, false, &h->plan, &h->err);
+    if (st == FAV_OK) st = alloc_workspace(h);
     if (st != FAV_OK) { g_create_error = h->err; free_all(h); delete h; return st; }
     *out = h;
     return FAV_OK;
@@ -1830,26 +1332,23 @@ fav_status fav_create(const fav_config* cfg, fav_handle** out) {
 
 // The static schedule of a configuration as text, one line per op - no device needed (tests/test_host.py replays it
 // symbolically and checks that the fused schedule computes the same dataflow as the layer-by-layer one).
-//   "op <i> kind=<k> phase=<p> layer=<l> lc=<l> la=<l> in=<b> res=<b> out=<b> out2=<b> site=<s> relu=<r>"
-// buffers: 0..4 rotating, 5 im2col matrix, -1 frames, -2 phase input, -3 phase output, -4 none.
+//   "op <i> kind=<k> phase=<p> layer=<l> lc=<l> la=<l> in=<b> res=<b> out=<b> out2=<b> site=<s> relu=<r> suffix=<0|1>
+//    rese=<0|1> skipy=<0|1> esite=<s>"
+// buffers: 0..4 rotating, 5 im2col matrix, -1 frames, -2 phase input, -3 phase output, -4 none; suffix: the op's phase runs
+// once per sample; rese / skipy: Op::res_entry / Op::skip_y; esite: the schedule's first dropout site (the entry op's).
 fav_status fav_plan_schedule(const fav_config* cfg, int32_t flags, char* out, size_t cap) {
     if (!cfg || !out || cap < 2 || cfg->struct_size != sizeof(fav_config) || cfg->arch < 0 || cfg->arch > 1) return FAV_ERR_INVALID_ARG;
-    fav_handle h;
-    h.cfg = *cfg;
-    h.n_members = cfg->n_members > 1 ? cfg->n_members : 1;
-    h.plan_no_fuse = (flags & 1) != 0;
-    fav_status st = build_graph(&h);
-    if (st != FAV_OK) { snprintf(out, cap, "%s", h.err.c_str()); return st; }
+    Plan P;
+    std::string err;
+    fav_status st = plan_resnet(*cfg, cfg->n_members > 1 ? cfg->n_members : 1, (flags & 1) != 0, &P, &err);
+    if (st != FAV_OK) { snprintf(out, cap, "%s", err.c_str()); return st; }
     std::string txt;
-    for (size_t i = 0; i < h.ops.size(); ++i) {
-        const Op& o = h.ops[i];
-        int phase = -1;
-        for (size_t pi = 0; pi < h.phases.size(); ++pi)
-            if ((int)i >= h.phases[pi].op_begin && (int)i < h.phases[pi].op_end) phase = (int)pi;
-        txt += fmt("op %zu kind=%d phase=%d layer=%d lc=%d la=%d in=%d res=%d out=%d out2=%d site=%d relu=%d suffix=%d rese=%d skipy=%d esite=%d\n", i, (int)o.kind, phase, o.layer,
-                   o.layer_c, o.layer_a, o.in, o.res, o.out, o.out2, o.site, o.relu, phase >= 0 ? (int)h.phases[phase].suffix : 0, o.res_entry, o.skip_y,
-                   h.first_site);
-    }
+    for (size_t pi = 0; pi < P.phases.size(); ++pi)
+        for (int i = P.phases[pi].op_begin; i < P.phases[pi].op_end; ++i) {
+            const Op& o = P.ops[i];
+            txt += fmt("op %d kind=%d phase=%zu layer=%d lc=%d la=%d in=%d res=%d out=%d out2=%d site=%d relu=%d suffix=%d rese=%d skipy=%d esite=%d\n", i, (int)o.kind, pi,
+                       o.layer, o.layer_c, o.layer_a, o.in, o.res, o.out, o.out2, o.site, o.relu, (int)P.phases[pi].suffix, o.res_entry, o.skip_y, P.first_site);
+        }
     if (txt.size() + 1 > cap) return FAV_ERR_INVALID_ARG;
     memcpy(out, txt.c_str(), txt.size() + 1);
     return FAV_OK;
@@ -1912,7 +1411,7 @@ fav_status fav_check_blob(const void* blob, size_t size, char* err, size_t err_c
 
 namespace {
 // one allocation per layer for the weights of all members (and one for the biases): member m at slab + m * stride
-fav_status alloc_layer_slabs(fav_handle* h, Layer& L, size_t wbytes, size_t bbytes) {
+fav_status alloc_layer_slabs(fav_handle* h, LayerWeights& L, size_t wbytes, size_t bbytes) {
     if (L.w_slab) return FAV_OK;
     L.w_stride = (wbytes + 255) / 256 * 256;
     L.b_stride = (bbytes + 255) / 256 * 256;
@@ -1938,16 +1437,17 @@ fav_status fav_load_member_weights(fav_handle* h, int32_t member, const void* bl
     const uint8_t* p = (const uint8_t*)blob;
     uint32_t hdr[8];
     memcpy(hdr, p, 32);
-    if ((int)hdr[2] != h->cfg.arch || (int)hdr[3] != h->cfg.num_classes || hdr[4] != h->layers.size()) {
+    if ((int)hdr[2] != h->cfg.arch || (int)hdr[3] != h->cfg.num_classes || hdr[4] != h->plan.layers.size()) {
         h->err = fmt("fav_load_weights: blob is arch %u / %u classes / %u layers, handle expects %d / %d / %zu", hdr[2], hdr[3],
-                     hdr[4], h->cfg.arch, h->cfg.num_classes, h->layers.size());
+                     hdr[4], h->cfg.arch, h->cfg.num_classes, h->plan.layers.size());
         return FAV_ERR_BAD_BLOB;
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     std::vector<uint16_t> wtmp;
     std::vector<float> btmp;
-    for (size_t i = 0; i < h->layers.size(); ++i) {
-        Layer& L = h->layers[i];
+    for (size_t i = 0; i < h->plan.layers.size(); ++i) {
+        const LayerShape& L = h->plan.layers[i];
+        LayerWeights& Wt = h->weights[i];
         uint32_t t[8];
         uint64_t off[2];
         memcpy(t, p + 32 + 48 * i, 32);
@@ -1960,9 +1460,9 @@ fav_status fav_load_member_weights(fav_handle* h, int32_t member, const void* bl
         if (L.kh == 0) {   // a pair of fp32 vectors (LayerNorm gamma / beta, ViT position table)
             const size_t vb = (size_t)L.cout * 4;
             // (ranges and alignment already validated by fav_check_blob against these very table entries)
-            if (fav_status st = alloc_layer_slabs(h, L, vb, vb)) return st;
-            HIP_TRY(h, hipMemcpy(L.w_m[member], p + off[0], vb, hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMemcpy(L.b_m[member], p + off[1], vb, hipMemcpyHostToDevice));
+            if (fav_status st = alloc_layer_slabs(h, Wt, vb, vb)) return st;
+            HIP_TRY(h, hipMemcpy(Wt.w_m[member], p + off[0], vb, hipMemcpyHostToDevice));
+            HIP_TRY(h, hipMemcpy(Wt.b_m[member], p + off[1], vb, hipMemcpyHostToDevice));
             continue;
         }
         const size_t kreal = (size_t)L.kh * L.kw * L.cin;
@@ -1974,9 +1474,9 @@ fav_status fav_load_member_weights(fav_handle* h, int32_t member, const void* bl
         for (int n = 0; n < L.cout; ++n) memcpy(&wtmp[(size_t)n * L.k], src + (size_t)n * kreal, kreal * 2);
         btmp.assign(L.cout_pad, 0.f);
         memcpy(btmp.data(), p + off[1], bbytes);
-        if (fav_status st = alloc_layer_slabs(h, L, wtmp.size() * 2, btmp.size() * 4)) return st;
-        HIP_TRY(h, hipMemcpy(L.w_m[member], wtmp.data(), wtmp.size() * 2, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(L.b_m[member], btmp.data(), btmp.size() * 4, hipMemcpyHostToDevice));
+        if (fav_status st = alloc_layer_slabs(h, Wt, wtmp.size() * 2, btmp.size() * 4)) return st;
+        HIP_TRY(h, hipMemcpy(Wt.w_m[member], wtmp.data(), wtmp.size() * 2, hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(Wt.b_m[member], btmp.data(), btmp.size() * 4, hipMemcpyHostToDevice));
     }
     h->member_loaded[member] = 1;
     h->weights_loaded = true;
@@ -2028,8 +1528,8 @@ fav_status run_vit_call(fav_handle* h, const Frames& f, hipStream_t s) {
 
 // Every phase of `lane`, all (virtual) frames of the call
 fav_status run_phases(fav_handle* h, const Frames& f, const Lane& lane) {
-    for (size_t pi = 0; pi < h->phases.size(); ++pi) {
-        const long long dom = h->phases[pi].suffix ? (long long)f.n * h->T_eff : f.n;
+    for (size_t pi = 0; pi < h->plan.phases.size(); ++pi) {
+        const long long dom = h->plan.phases[pi].suffix ? (long long)f.n * h->plan.T_eff : f.n;
         if (fav_status st = run_chunks(h, pi, f, lane, 0, dom)) return st;
     }
     return FAV_OK;
@@ -2072,11 +1572,11 @@ fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out
     h->ev_used = h->profiling ? h->ev_used : 0;
     fav_status st;
     if (h->vit) st = run_vit_call(h, f, s);
-    else if (will_group(h, f.n)) st = run_grouped(h, f, s);
+    else if (will_group(h->cfg, h->n_members, h->plan, f.n)) st = run_grouped(h, f, s);
     else st = run_lanes(h, f, s);
     if (st != FAV_OK) return st;
-    const int T_head = h->n_members > 1 ? h->n_members : h->T_eff;
-    if (const char* e = launch_head(h, h->logits, T_head, f.n, h->cfg.num_classes, h->cpad, h->cfg.temperature,
+    const int T_head = h->n_members > 1 ? h->n_members : h->plan.T_eff;
+    if (const char* e = launch_head(h, h->logits, T_head, f.n, h->cfg.num_classes, h->plan.cpad, h->cfg.temperature,
                                     h->cfg.conf_kind, h->cfg.tau, out, s)) {
         h->err = e;
         return FAV_ERR_INVALID_ARG;
@@ -2228,7 +1728,7 @@ fav_status fav_get_logits(fav_handle* h, float* out, int32_t* t_out, int32_t* n_
     if (n_out) *n_out = h->last_n;
     if (out) {
         if (fav_status st = wait_last_use(h, (hipStream_t)stream)) return st;
-        HIP_TRY(h, hipMemcpy2DAsync(out, (size_t)h->cfg.num_classes * 4, h->logits, (size_t)h->cpad * 4,
+        HIP_TRY(h, hipMemcpy2DAsync(out, (size_t)h->cfg.num_classes * 4, h->logits, (size_t)h->plan.cpad * 4,
                                     (size_t)h->cfg.num_classes * 4, (size_t)h->last_T * h->last_n,
                                     hipMemcpyDeviceToDevice, (hipStream_t)stream));
         mark_last_use(h, (hipStream_t)stream);
@@ -2241,14 +1741,14 @@ fav_status fav_set_profiling(fav_handle* h, int32_t enable) {
     h->profiling = enable != 0;
     h->ev_used = 0;
     memset(&h->prof, 0, sizeof h->prof);
-    h->op_prof.assign(h->ops.size(), fav_op_profile{});
-    for (size_t i = 0; i < h->ops.size(); ++i) {
-        const Op& o = h->ops[i];
+    h->op_prof.assign(h->plan.ops.size(), fav_op_profile{});
+    for (size_t i = 0; i < h->plan.ops.size(); ++i) {
+        const Op& o = h->plan.ops[i];
         fav_op_profile& r = h->op_prof[i];
         r.op_index = (int)i; r.kind = (int)o.kind;
         r.H = o.H; r.W = o.W; r.Cin = o.C; r.Ho = o.Ho; r.Wo = o.Wo; r.Cout = o.Co;
         r.kh = r.kw = r.stride = 0;
-        if (o.layer >= 0) { const Layer& L = h->layers[o.layer]; r.kh = L.kh; r.kw = L.kw; r.stride = L.stride; }
+        if (o.layer >= 0) { const LayerShape& L = h->plan.layers[o.layer]; r.kh = L.kh; r.kw = L.kw; r.stride = L.stride; }
         if (o.kind == OP_ENTRY_REDUCE) { r.reserved = o.Co2; r.kh = r.kw = r.stride = 1; r.Ho = o.H; r.Wo = o.W; r.Cout = o.C; }
         if (o.kind == OP_TAIL) { r.reserved = o.Co2; if (o.layer < 0) { r.kh = r.kw = r.stride = 1; } }   // reserved: channels of the fused next-block conv1
     }

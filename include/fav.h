@@ -109,6 +109,11 @@ void fav_destroy(fav_handle* h);
  * receives a message.  The blob is file-supplied, hence untrusted. */
 fav_status fav_check_blob(const void* blob_host, size_t size, char* err, size_t err_cap);
 /* The static launch schedule of a configuration (ResNet archs) as text, one line per op; needs no device.
+ *   "op <i> kind=<k> phase=<p> layer=<l> lc=<l> la=<l> in=<b> res=<b> out=<b> out2=<b> site=<s> relu=<r> suffix=<0|1>
+ *    rese=<0|1> skipy=<0|1> esite=<s>"
+ * buffers <b>: 0..4 rotating, 5 im2col matrix, -1 frames, -2 phase input, -3 phase output, -4 none.  suffix: the op's phase
+ * runs once per MC-Dropout sample; rese: a fused tail takes its residual from the cached phase input and drops it itself;
+ * skipy: the entry op does not store the dropped copies; esite: the first dropout site (the entry op's), -1 without MC-Dropout.
  * flags bit 0: the layer-by-layer schedule (no fused bottleneck tails).  A test / inspection hook. */
 fav_status fav_plan_schedule(const fav_config* cfg, int32_t flags, char* out, size_t cap);
 const char* fav_last_error(const fav_handle* h); /* h may be NULL: error of the last failed fav_create */

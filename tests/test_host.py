@@ -461,6 +461,56 @@ def test_fused_schedule_computes_the_layer_by_layer_dataflow(lib):
     assert not any(o["kind"] == 5 for o in _plan(lib, 1, 0, math_mode=1))
 
 
+def _plan_text(lib, arch, **kw):
+    """(status, text) of fav_plan_schedule: the schedule, or the planner's refusal."""
+    from failure_aware_vision_amd import _lib
+    cfg = _lib.FavConfig()
+    lib.fav_default_config(C.byref(cfg), arch)
+    for k, v in kw.items():
+        setattr(cfg, k, v)
+    buf = C.create_string_buffer(1 << 17)
+    st = lib.fav_plan_schedule(C.byref(cfg), 0, buf, len(buf))
+    return st, buf.value.decode()
+
+
+def _pinned_schedules():
+    from failure_aware_vision_amd import weights
+    return {
+        # the headline: ResNet-50, all_blocks, T = 30, 224x224, batch 256
+        "r50_mc30_all_blocks_224_b256": (1, dict(site_mask=weights.site_mask_for(1, "all_blocks"), n_samples=30, dropout_p=0.1,
+                                                 in_h=224, in_w=224, max_batch=256)),
+        "r50_ens5_b32": (1, dict(n_members=5, max_batch=32)),               # grouped: every op one launch over the members
+        "r50_single_f32_exact": (1, dict(math_mode=1)),                     # the validation math mode: layer by layer
+        "r18_cifar_last_layer_32": (0, dict(site_mask=weights.site_mask_for(0, "last_layer"), n_samples=30, dropout_p=0.1,
+                                            in_h=32, in_w=32)),
+    }
+
+
+@pytest.mark.parametrize("name", ["r50_mc30_all_blocks_224_b256", "r50_ens5_b32", "r50_single_f32_exact", "r18_cifar_last_layer_32"])
+def test_schedule_text_is_pinned(lib, name):
+    """The schedule text of four configurations, byte for byte.  The fixtures (tests/golden/schedules/) were written by the
+    library of the commit before the planner moved into csrc/fav_plan.hpp: a planner change that moves an op, a buffer,
+    a phase boundary or a dropout site shows up here as a diff of a few lines."""
+    arch, kw = _pinned_schedules()[name]
+    st, text = _plan_text(lib, arch, **kw)
+    assert st == 0, text
+    with open(os.path.join(ROOT, "tests", "golden", "schedules", name + ".txt")) as f:
+        assert text == f.read()
+
+
+def test_planner_refusals_keep_status_and_text(lib):
+    """What the planner refuses, with the status and the text a caller sees.  Only the ResNet refusals can be reached without
+    a device (fav_plan_schedule takes no ViT arch, and fav_create asks for the device first): the ViT ones - an input that
+    is no multiple of the patch size, dropout sites - are tests/test_gpu_vit.py's."""
+    for arch, nb in ((0, 8), (1, 16)):
+        assert _plan_text(lib, arch, site_mask=1 << (nb + 1), n_samples=3, dropout_p=0.1) == \
+            (1, "site_mask has bits beyond the pooled-feature site")
+        assert _plan_text(lib, arch, site_mask=(1 << (nb + 1)) | 1) == (1, "site_mask has bits beyond the pooled-feature site")
+        assert _plan_text(lib, arch, site_mask=1 << nb, n_samples=3, dropout_p=0.1)[0] == 0      # the pooled-feature site itself
+    assert _plan_text(lib, 1, in_h=-1) == (1, "input too small")
+    assert _plan_text(lib, 2)[0] == 1 and _plan_text(lib, 3)[0] == 1                             # no ViT schedule to print
+
+
 def test_bench_config_table_and_roofline_objects():
     """bench.py without a GPU: every --config entry names its BASELINE config, scaling mode and roofline bound, and the
     roofline builder turns a per-class profile into the objects the driver's line carries."""
