@@ -9,5 +9,7 @@ from .backend import Backend, anomaly_score_from_confidence, unpack_uncertainty 
 from .conformal import Conformal, calibrate_qhat, unpack_sets  # noqa: F401
 from .calibration import (Calibration, fit_temperature, reliability, risk_coverage, tau_for_risk, temperature_grid,  # noqa: F401
                           unpack_cells)
+from .corrupt import CORRUPTIONS, SEVERITY, Corruptor  # noqa: F401
 from .distributed import classify_sharded, shard_range  # noqa: F401
-from . import synth, weights  # noqa: F401
+from . import robustness, synth, weights  # noqa: F401
+from .robustness import summarize  # noqa: F401

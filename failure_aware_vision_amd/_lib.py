@@ -91,6 +91,17 @@ class FavCalibCell(C.Structure):
     _fields_ = [("label", C.c_int32), ("confidence", C.c_float), ("nll", C.c_float), ("brier", C.c_float)]
 
 
+#: fav_corruption, in enum order
+CORRUPTION_KINDS = ("impulse_noise", "speckle_noise", "gaussian_blur", "defocus_blur", "contrast", "pixelate", "brightness",
+                    "saturate")
+
+
+class FavCorruptionDesc(C.Structure):
+    """fav_corruption_desc: one corruption of fav_op_corrupt_c (32 bytes)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("seed", C.c_uint64),
+                ("first_frame_index", C.c_int64)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -161,6 +172,10 @@ _SIGNATURES = {
                                    C.c_void_p, C.c_void_p]),
     "fav_op_head_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_corruption_params": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "fav_corruption_taps": (C.c_int, [C.c_int32, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)]),
+    "fav_op_corrupt_c": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(FavCorruptionDesc),
+                                   C.c_void_p]),
 }
 
 _lib = None

@@ -24,6 +24,7 @@ import dataclasses
 import numpy as np
 
 from . import _lib, weights as _weights
+from .corrupt import CORRUPTIONS
 
 _ARCH = {"resnet18_cifar": _lib.ARCH_RESNET18_CIFAR, "resnet50": _lib.ARCH_RESNET50, "vit_b16": _lib.ARCH_VIT_B16,
          "vit_tiny": _lib.ARCH_VIT_TINY}
@@ -377,6 +378,42 @@ class Backend:
         cells = self.calibration_sweep(images, labels, [self.cfg.temperature], first_index)
         lab = labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()
         return report_from_cells(cells if isinstance(cells, np.ndarray) else cells.cpu().numpy(), lab)
+
+    def robustness_report(self, frames_u8, labels, corruptions=CORRUPTIONS, severities=(1, 2, 3, 4, 5), seed: int = 0,
+                          first_index: int = 0) -> dict:
+        """How accuracy, confidence and the failure flag hold up as corruptions get worse: a ``"clean"`` row and one row
+        per (kind, severity) of ``corruptions`` (default ``corrupt.CORRUPTIONS``) -> ``{("clean", 0): row, (kind, s): row}``,
+        each row ``robustness.summarize`` at the handle's current temperature and tau (``robustness.table`` prints them).
+        ``frames_u8``: labelled uint8 frames (numpy or CUDA); they are corrupted on the device in batches of max_batch
+        (``Corruptor(seed).imagenet_c``, frame i at global index first_index + i) and each batch runs through
+        ``calibration_sweep`` as fp32 frames.  The handle is not changed."""
+        from .calibration import unpack_cells
+        from .corrupt import Corruptor
+        from .robustness import summarize
+        torch = self._torch
+        self._check_shape(frames_u8)
+        if self._layout_of(frames_u8) != _lib.LAYOUT_NHWC_U8:
+            raise TypeError("robustness_report takes uint8 frames")
+        img, _ = self._frames_on_device(frames_u8)
+        n, mb = int(img.shape[0]), int(self.cfg.max_batch)
+        lab = self._labels_on(labels, n, img.device)
+        lab_host = lab.cpu().numpy()
+        cor = Corruptor(seed=seed)
+        temps = [self.cfg.temperature]
+
+        def row(make):
+            cells = []
+            for b in range(0, n, mb):
+                e = min(n, b + mb)
+                cells.append(self.calibration_sweep(make(img[b:e], int(first_index) + b), lab[b:e], temps, int(first_index) + b))
+            c = unpack_cells(torch.cat(cells).cpu().numpy())
+            return summarize(c["label"][:, 0], c["confidence"][:, 0], c["nll"][:, 0], lab_host, self.cfg.tau)
+
+        rows = {("clean", 0): row(lambda fr, first: fr)}
+        for kind in corruptions:
+            for s in severities:
+                rows[(kind, int(s))] = row(lambda fr, first: cor.imagenet_c(fr, kind, int(s), first_index=first))
+        return rows
 
     def set_temperature(self, temperature: float):
         """Softmax temperature of the calls made from now on (finite, > 0); calls already enqueued keep the old one."""

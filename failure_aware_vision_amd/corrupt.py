@@ -5,15 +5,57 @@ plus ``apply(frames)`` which actually produces the corrupted frames on the GPU
 (``fav_op_corrupt``) — what the browser canvas does in the reference (app.js:782-857) — and
 ``gaussian(frames, severity)`` for ImageNet-C style noise.  Deterministic in (seed, frame index);
 the generator keeps the low 32 bits of the frame index, so frame 2**32 + k repeats frame k.
+
+``imagenet_c(frames, kind, severity)`` is the ImageNet-C style family (``fav_op_corrupt_c``):
+the eight ``CORRUPTIONS`` kinds plus ``"gaussian_noise"`` (the Gaussian mode above), severities 1..5 from ``SEVERITY``.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections.abc import Mapping
 
 from . import _lib
 from .synth import GAUSSIAN_NOISE_SIGMA
 
 VALID_MODES = ("normal", "frozen", "blank", "corrupted")
+#: the kinds ``Corruptor.imagenet_c`` takes: fav_corruption in enum order, then the Gaussian mode of fav_op_corrupt
+CORRUPTIONS = _lib.CORRUPTION_KINDS + ("gaussian_noise",)
+
+
+class _SeverityTable(Mapping):
+    """``SEVERITY[kind][severity - 1] -> (a, b)``: the library's own table (fav_corruption_params), read on first use so
+    that importing the package does not load the library; ``"gaussian_noise"``: (sigma, 0) of synth.GAUSSIAN_NOISE_SIGMA."""
+
+    def __init__(self):
+        self._table = None
+
+    def _load(self):
+        if self._table is None:
+            lib = _lib.load()
+            table = {}
+            for k, name in enumerate(_lib.CORRUPTION_KINDS):
+                rows = []
+                for sev in range(1, 6):
+                    a, b = C.c_float(), C.c_float()
+                    _lib.check(lib.fav_corruption_params(k, sev, C.byref(a), C.byref(b)))
+                    rows.append((a.value, b.value))
+                table[name] = tuple(rows)
+            table["gaussian_noise"] = tuple((float(s), 0.0) for s in GAUSSIAN_NOISE_SIGMA)
+            self._table = table
+        return self._table
+
+    def __getitem__(self, kind):
+        return self._load()[kind]
+
+    def __iter__(self):
+        return iter(CORRUPTIONS)
+
+    def __len__(self):
+        return len(CORRUPTIONS)
+
+
+SEVERITY = _SeverityTable()
+
 _STATUS = {"normal": "VISION_OK", "frozen": "VISION_FROZEN", "blank": "VISION_BLANK", "corrupted": "VISION_CORRUPTED"}
 
 
@@ -75,3 +117,32 @@ class Corruptor:
     def gaussian(self, frames, severity: int, first_index: int = 0):
         """uint8 frames -> fp32 [0,1] frames with Gaussian noise of ImageNet-C severity 1..5."""
         return self._run(frames, 3, self._torch.float32, GAUSSIAN_NOISE_SIGMA[severity - 1], first_index)
+
+    def imagenet_c(self, frames, kind: str, severity: int | None = None, *, a: float | None = None, b: float | None = None,
+                   first_index: int = 0):
+        """uint8 CUDA frames [n, H, W, 3] -> fp32 [0,1] CUDA frames under corruption ``kind`` (one of ``CORRUPTIONS``), at
+        ``severity`` 1..5 (``SEVERITY[kind]``) or at explicit parameters ``a`` (and ``b``; a parameter left None comes from
+        ``severity`` when that is given, else it is 0).  Frame i has global index first_index + i; the result is a pure
+        function of (seed, global index), so shards of a set agree with the whole.  One launch on the current stream."""
+        if kind not in CORRUPTIONS:
+            raise ValueError(f"kind must be one of {CORRUPTIONS}, got {kind!r}")
+        if severity is None and a is None:
+            raise ValueError("give a severity (1..5) or the parameter a")
+        if severity is not None and not 1 <= int(severity) <= 5:
+            raise ValueError(f"severity must be in 1..5, got {severity}")
+        ta, tb = SEVERITY[kind][int(severity) - 1] if severity is not None else (0.0, 0.0)
+        a = ta if a is None else float(a)
+        b = tb if b is None else float(b)
+        torch = self._torch
+        if kind == "gaussian_noise":
+            return self._run(frames, 3, torch.float32, a, first_index)
+        if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[3] != 3 or not frames.is_cuda:
+            raise ValueError("imagenet_c takes uint8 CUDA frames [n, H, W, 3]")
+        frames = frames.contiguous()
+        n, H, W, _ = frames.shape
+        out = torch.empty(frames.shape, dtype=torch.float32, device=frames.device)
+        d = _lib.FavCorruptionDesc(C.sizeof(_lib.FavCorruptionDesc), _lib.CORRUPTION_KINDS.index(kind), a, b, self.seed,
+                                   int(first_index))
+        stream = torch.cuda.current_stream(frames.device).cuda_stream
+        _lib.check(self.lib.fav_op_corrupt_c(frames.data_ptr(), out.data_ptr(), n, H, W, C.byref(d), stream))
+        return out

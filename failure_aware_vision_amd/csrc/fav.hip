@@ -23,6 +23,7 @@
 
 #include "../../include/fav.h"
 #include "fav_kernels.hpp"
+#include "fav_corrupt_c.hpp"
 #include "fav_plan.hpp"
 
 using namespace fav_plan;   // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
@@ -1926,6 +1927,146 @@ fav_status fav_op_corrupt(const uint8_t* frames, void* out, int32_t n, int32_t H
     cp.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); cp.seed_hi = (uint32_t)(seed >> 32); cp.first_index = first_index;
     hipLaunchKernelGGL(corrupt_kernel, dim3(grid_for((long long)n * H * W)), dim3(256), 0, (hipStream_t)stream, frames, out,
                        n, H, W, cp);
+    return op_done(nullptr);
+}
+
+// ---- the ImageNet-C style corruption family (fav_corrupt_c.hpp)
+static const float kCorruptionSeverity[FAV_C_COUNT][5][2] = {
+    {{.03f, 0.f}, {.06f, 0.f}, {.09f, 0.f}, {.17f, 0.f}, {.27f, 0.f}},      // impulse: amount
+    {{.15f, 0.f}, {.2f, 0.f}, {.35f, 0.f}, {.45f, 0.f}, {.6f, 0.f}},        // speckle: sigma
+    {{1.f, 0.f}, {2.f, 0.f}, {3.f, 0.f}, {4.f, 0.f}, {6.f, 0.f}},           // gaussian blur: sigma
+    {{3.f, .1f}, {4.f, .5f}, {6.f, .5f}, {8.f, .5f}, {10.f, .5f}},          // defocus: radius, alias sigma
+    {{.4f, 0.f}, {.3f, 0.f}, {.2f, 0.f}, {.1f, 0.f}, {.05f, 0.f}},          // contrast: c
+    {{.6f, 0.f}, {.5f, 0.f}, {.4f, 0.f}, {.3f, 0.f}, {.25f, 0.f}},          // pixelate: c
+    {{.1f, 0.f}, {.2f, 0.f}, {.3f, 0.f}, {.4f, 0.f}, {.5f, 0.f}},           // brightness: c
+    {{.3f, 0.f}, {.1f, 0.f}, {2.f, 0.f}, {5.f, .1f}, {20.f, .2f}},          // saturate: a, b
+};
+
+// what is wrong with (kind, a, b), or nullptr
+static const char* corruption_params_error(int32_t kind, float a, float b) {
+    if (kind < 0 || kind >= FAV_C_COUNT) return "kind outside [0, FAV_C_COUNT)";
+    if (!std::isfinite(a) || !std::isfinite(b)) return "a and b must be finite";
+    switch (kind) {
+    case FAV_C_IMPULSE_NOISE: return a >= 0.f && a <= 1.f ? nullptr : "impulse amount a outside [0, 1]";
+    case FAV_C_SPECKLE_NOISE: return a >= 0.f ? nullptr : "speckle sigma a below 0";
+    case FAV_C_GAUSSIAN_BLUR:
+        if (!(a > 0.f)) return "gaussian blur sigma a must be above 0";
+        return 4.0 * (double)a + 0.5 < (double)(CC_GAUSS_MAX_R + 1) ? nullptr : "gaussian blur radius (int)(4 a + 0.5) above 32";
+    case FAV_C_DEFOCUS_BLUR:
+        if (!(a >= 1.f && a < 13.f)) return "defocus radius (int)a outside 1..12";
+        return b > 0.f ? nullptr : "defocus alias sigma b must be above 0";
+    case FAV_C_CONTRAST: return a >= 0.f && a <= 1.f ? nullptr : "contrast a outside [0, 1]";
+    case FAV_C_PIXELATE: return a > 0.f && a <= 1.f ? nullptr : "pixelate a outside (0, 1]";
+    case FAV_C_BRIGHTNESS: return a >= 0.f && a <= 1.f ? nullptr : "brightness a outside [0, 1]";
+    default:
+        if (!(a >= 0.f)) return "saturate a below 0";
+        return b >= -1.f && b <= 1.f ? nullptr : "saturate b outside [-1, 1]";
+    }
+}
+
+// EXPERIMENTS build only: FAV_CORRUPT_C_STORE = 1 / 2 stores a group's values straight from registers (float4 / scalar), read at
+// every call so that one process can alternate; the normal build always stages a wave's stores through LDS
+static int corrupt_c_store_mode() {
+    const char* v = fav_knob_str("FAV_CORRUPT_C_STORE");
+    return v ? std::max(0, std::min(2, atoi(v))) : CC_STORE_STAGED;
+}
+
+static fav_status corruption_rejected(const char* fn, const char* why) {
+    g_create_error = fmt("%s: %s", fn, why);
+    return FAV_ERR_INVALID_ARG;
+}
+
+fav_status fav_corruption_params(int32_t kind, int32_t severity, float* a, float* b) {
+    if (!a || !b) return corruption_rejected("fav_corruption_params", "null pointer");
+    if (kind < 0 || kind >= FAV_C_COUNT) return corruption_rejected("fav_corruption_params", "kind outside [0, FAV_C_COUNT)");
+    if (severity < 1 || severity > 5) return corruption_rejected("fav_corruption_params", "severity outside 1..5");
+    *a = kCorruptionSeverity[kind][severity - 1][0];
+    *b = kCorruptionSeverity[kind][severity - 1][1];
+    return FAV_OK;
+}
+
+fav_status fav_corruption_taps(int32_t kind, float a, float b, float* taps, int32_t cap, int32_t* radius) {
+    if (!taps || !radius) return corruption_rejected("fav_corruption_taps", "null pointer");
+    if (kind != FAV_C_GAUSSIAN_BLUR && kind != FAV_C_DEFOCUS_BLUR)
+        return corruption_rejected("fav_corruption_taps", "only the two blur kinds have taps");
+    if (const char* why = corruption_params_error(kind, a, b)) return corruption_rejected("fav_corruption_taps", why);
+    const int R = kind == FAV_C_GAUSSIAN_BLUR ? gauss_radius(a) : disk_radius(a);
+    const int count = kind == FAV_C_GAUSSIAN_BLUR ? 2 * R + 1 : (2 * R + 1) * (2 * R + 1);
+    if (cap < count) return corruption_rejected("fav_corruption_taps", "cap is smaller than the number of taps");
+    if (kind == FAV_C_GAUSSIAN_BLUR) gauss_taps(a, R, taps);
+    else disk_taps(a, b, taps);
+    *radius = R;
+    return FAV_OK;
+}
+
+fav_status fav_op_corrupt_c(const uint8_t* frames, float* out, int32_t n, int32_t H, int32_t W, const fav_corruption_desc* d,
+                            void* stream) {
+    static_assert(sizeof(fav_corruption_desc) == 32, "fav_corruption_desc layout");
+    const char* fn = "fav_op_corrupt_c";
+    if (!frames || !out || !d) return corruption_rejected(fn, "null pointer");
+    if (n < 1 || H < 1 || W < 1) return corruption_rejected(fn, "n, H and W must be at least 1");
+    if (d->struct_size != sizeof(fav_corruption_desc)) return corruption_rejected(fn, "struct_size is not sizeof(fav_corruption_desc)");
+    if (const char* why = corruption_params_error(d->kind, d->a, d->b)) return corruption_rejected(fn, why);
+    if ((uintptr_t)out % 4 != 0) return corruption_rejected(fn, "out must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const long long npx = (long long)H * W, total = npx * n;
+    const long long max_grid = (1ll << 24) - 1;
+    CorruptCParams cp;
+    cp.a = d->a; cp.b = d->b;
+    cp.seed_lo = (uint32_t)(d->seed & 0xFFFFFFFFull); cp.seed_hi = (uint32_t)(d->seed >> 32); cp.first_index = d->first_frame_index;
+    const int tiles_x = (W + CC_TILE - 1) / CC_TILE, tiles_y = (H + CC_TILE - 1) / CC_TILE;
+    const long long tiles = (long long)tiles_x * tiles_y * n;
+    const unsigned tile_grid = (unsigned)std::min(tiles, max_grid);
+    switch (d->kind) {
+    case FAV_C_IMPULSE_NOISE: case FAV_C_SPECKLE_NOISE: case FAV_C_BRIGHTNESS: case FAV_C_SATURATE: {
+        const dim3 grid(grid_for(px_group_count(total)));
+        const int store_mode = corrupt_c_store_mode();
+        if (d->kind == FAV_C_IMPULSE_NOISE)
+            hipLaunchKernelGGL((corrupt_c_point_kernel<CC_IMPULSE>), grid, dim3(256), 0, s, frames, out, npx, total, cp, store_mode);
+        else if (d->kind == FAV_C_SPECKLE_NOISE)
+            hipLaunchKernelGGL((corrupt_c_point_kernel<CC_SPECKLE>), grid, dim3(256), 0, s, frames, out, npx, total, cp, store_mode);
+        else if (d->kind == FAV_C_BRIGHTNESS)
+            hipLaunchKernelGGL((corrupt_c_point_kernel<CC_BRIGHTNESS>), grid, dim3(256), 0, s, frames, out, npx, total, cp, store_mode);
+        else
+            hipLaunchKernelGGL((corrupt_c_point_kernel<CC_SATURATE>), grid, dim3(256), 0, s, frames, out, npx, total, cp, store_mode);
+        break;
+    }
+    case FAV_C_CONTRAST: {
+        // blocks per frame: one per 4096 pixels, at most 16 (each of them reads the whole frame once for the sums)
+        const int per_frame = (int)std::max<long long>(1, std::min<long long>((npx + 4095) / 4096, 16));
+        if ((long long)n * per_frame > 0x7FFFFFFFll) return corruption_rejected(fn, "too many frames for one contrast launch");
+        hipLaunchKernelGGL(contrast_kernel, dim3((unsigned)(n * per_frame)), dim3(256), 0, s, frames, out, npx, per_frame,
+                           (double)H * W * 255.0, d->a, corrupt_c_store_mode());
+        break;
+    }
+    case FAV_C_PIXELATE: {
+        if (W > CC_PIXELATE_MAX_W) return corruption_rejected(fn, "pixelate takes frames up to 2048 pixels wide");
+        const int hd = std::max(1, (int)((double)H * (double)d->a)), wd = std::max(1, (int)((double)W * (double)d->a));
+        const long long items = (long long)n * hd;
+        const size_t lds = (size_t)4 * W * 4 + (size_t)3 * wd * 4;
+        hipLaunchKernelGGL(pixelate_kernel, dim3((unsigned)std::min(items, max_grid)), dim3(256), lds, s, frames, out, H, W, hd,
+                           wd, items);
+        break;
+    }
+    case FAV_C_GAUSSIAN_BLUR: {
+        const int R = gauss_radius(d->a);
+        GaussTaps tp;
+        memset(&tp, 0, sizeof tp);
+        gauss_taps(d->a, R, tp.v);
+        hipLaunchKernelGGL(gauss_blur_kernel, dim3(tile_grid), dim3(256), gauss_blur_lds(R), s, frames, out, H, W, R, tp, tiles_x,
+                           tiles_y, tiles);
+        break;
+    }
+    default: {
+        const int R = disk_radius(d->a);
+        DiskTaps tp;
+        memset(&tp, 0, sizeof tp);
+        disk_taps(d->a, d->b, tp.v);
+        hipLaunchKernelGGL(defocus_kernel, dim3(tile_grid), dim3(256), defocus_lds(R), s, frames, out, H, W, R, tp, tiles_x, tiles_y,
+                           tiles);
+        break;
+    }
+    }
     return op_done(nullptr);
 }
 

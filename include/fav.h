@@ -434,6 +434,37 @@ fav_status fav_op_corrupt(const uint8_t* frames, void* out, int32_t n, int32_t H
                           float noise_level, float brightness_gain, float gaussian_sigma, uint64_t seed,
                           int64_t first_frame_index, void* hip_stream);
 
+/* ---- ImageNet-C style corruption family on the device: eight corruptions at severities 1..5, every one a pure function
+ * of (seed, global frame index) like fav_op_corrupt.  frames: uint8 [n][H][W][3] on the device; out: fp32 [n][H][W][3] in
+ * [0,1] (FAV_LAYOUT_NHWC_F32, which fav_classify* accepts), 4-byte aligned.  x_c = u8 / 255 in fp32; the definitions
+ *  are this build's contract, not bit-parity with scikit-image, PIL or OpenCV:
+ *   impulse    a = amount in [0,1]: channel c of a pixel is hit iff its uniform draw is below a; a hit is 0 or 1
+ *   speckle    a = sigma >= 0: clamp(x + (x a) z), z standard normal (Box-Muller, as FAV_CORRUPT_GAUSSIAN)
+ *   gaussian blur  a = sigma > 0: separable, R = (int)(4 a + 0.5) <= 32, replicate borders
+ *   defocus    a = disk radius, (int)a in 1..12; b = alias sigma > 0; reflect-101 borders
+ *   contrast   a in [0,1]: clamp((x - m_c) a + m_c), m_c the frame's channel mean
+ *   pixelate   a in (0,1]: box means over max(1, (int)(H a)) x max(1, (int)(W a)) cells; W <= 2048
+ *   brightness a in [0,1]: HSV value V -> min(V + a, 1)
+ *   saturate   a >= 0, b in [-1,1]: HSV saturation S -> clamp(S a + b)
+ * The noise kinds draw Philox4x32-10 with key = seed and counter = (pixel index in the frame, low 32 bits of
+ * first_frame_index + f, stream, 0), stream 16 for impulse and 17 for speckle. */
+typedef enum fav_corruption { FAV_C_IMPULSE_NOISE = 0, FAV_C_SPECKLE_NOISE = 1, FAV_C_GAUSSIAN_BLUR = 2,
+    FAV_C_DEFOCUS_BLUR = 3, FAV_C_CONTRAST = 4, FAV_C_PIXELATE = 5, FAV_C_BRIGHTNESS = 6, FAV_C_SATURATE = 7,
+    FAV_C_COUNT = 8 } fav_corruption;
+typedef struct fav_corruption_desc { uint32_t struct_size; int32_t kind; float a, b; uint64_t seed;
+    int64_t first_frame_index; } fav_corruption_desc;            /* 32 bytes */
+/* host only, no device: the severity table; severity 1..5 */
+fav_status fav_corruption_params(int32_t kind, int32_t severity, float* a, float* b);
+/* host only: the fp32 taps the blur kernels use for (kind, a, b).
+ * GAUSSIAN_BLUR: 2R+1 taps.  DEFOCUS_BLUR: (2R+1)^2 taps, row-major.
+ * *radius = R; FAV_ERR_INVALID_ARG if cap is too small or the kind has no taps */
+fav_status fav_corruption_taps(int32_t kind, float a, float b, float* taps, int32_t cap, int32_t* radius);
+/* One launch, no allocation, no workspace, no synchronisation.  A rejected call (FAV_ERR_INVALID_ARG: a NULL pointer, n, H or
+ * W below 1, a wrong struct_size, a kind outside [0, FAV_C_COUNT), a non-finite a or b, a parameter outside the range stated
+ * above) launches nothing and leaves a message that names the function in fav_last_error(NULL). */
+fav_status fav_op_corrupt_c(const uint8_t* frames_dev, float* out_dev, int32_t n, int32_t H, int32_t W,
+                            const fav_corruption_desc* d, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
