@@ -212,6 +212,23 @@ DropParams make_drop(const fav_dropout_desc* d) {
     return p;
 }
 
+// The one validation of a dropout descriptor (the ranges beside fav_dropout_desc in fav.h), for a launch whose rows are the
+// virtual frames [v0, v0 + rows): what is wrong with it, prefixed with the op's name, or nullptr.  A descriptor without a
+// site (NULL, site < 0) is not read any further.  The kernels hold v, the sample v / n_img and the fastdiv operand in 32 bits
+// (fastdiv is exact below 2^31 only), the draw is 8 bits wide, and scale multiplies every kept value.
+const char* check_drop(const char* who, const fav_dropout_desc* d, long long rows) {
+    if (!d || d->site < 0) return nullptr;
+    const char* why = nullptr;
+    if (d->threshold > 255u) why = "dropout threshold above 255 (the draw is 8 bits wide: everything would be dropped)";
+    else if (!std::isfinite(d->scale) || !(d->scale > 0.f)) why = "dropout scale must be finite and > 0";
+    else if (d->n_img < 1) why = "dropout n_img must be >= 1";
+    else if (d->v0 < 0 || d->v0 + rows > 0x7fffffffLL) why = "virtual frame index out of range";
+    if (!why) return nullptr;
+    thread_local std::string msg;
+    msg = std::string(who) + ": " + why;
+    return msg.c_str();
+}
+
 // K-tile depth and ring stages of the 128-row tiles.  Measured on MI355X (profiles/r1d_conv_sweep.txt):
 //  * 3x3: MFMA-bound, 64-deep tiles (half the barriers per FLOP), double buffer;
 //  * 1x1 with a residual (the expanding convolution of a bottleneck): bound by HBM and by the
@@ -314,7 +331,7 @@ const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int
     p.drop = make_drop(&d.drop);
     p.div_hwo = fastdiv_make((uint32_t)p.HWo);
     p.div_w = fastdiv_make((uint32_t)p.Wo);
-    if (p.drop.site >= 0 && (p.drop.v0 < 0 || p.drop.v0 + d.n_frames > 0x7fffffffLL)) return "conv: virtual frame index out of range";
+    if (const char* e = check_drop("conv", &d.drop, d.n_frames)) return e;
     p.dbg = nullptr;
     p.g_x = G.x; p.g_w = G.w; p.g_bias = G.b; p.g_res = G.res; p.g_y = G.y;
     if (d.out_f32 && p.drop.site >= 0) return "conv: dropout on fp32 output unsupported";
@@ -471,7 +488,7 @@ const char* launch_tail(fav_handle* h, const fav_tail_desc& d, const Group& G, h
     p.drop = make_drop(&d.drop);
     p.div_hw = fastdiv_make((uint32_t)p.HW);
     p.div_w = fastdiv_make((uint32_t)d.W);
-    if (p.drop.site >= 0 && (p.drop.v0 < 0 || p.drop.v0 + d.n_frames > 0x7fffffffLL)) return "bottleneck tail: virtual frame index out of range";
+    if (const char* e = check_drop("bottleneck tail", &d.drop, d.n_frames)) return e;
     p.g_t1 = G.x; p.g_res = G.res; p.g_y = G.y; p.g_t1n = G.y2;
     p.g_wb = G.wb; p.g_bb = G.bb; p.g_wc = G.w; p.g_bc = G.b; p.g_wa = G.wa; p.g_ba = G.ba;
     p.site_e = d.entry_site;
@@ -598,8 +615,12 @@ unsigned grid_for(long long work_items) {
     return (unsigned)std::max<long long>(1, std::min<long long>(g, (1ll << 24) - 1));
 }
 
-void launch_stem(fav_handle* h, const void* images, int layout, int n, int H, int W, int kh, int kw, int stride, int pad,
-                 int kpad, const float* mean, const float* istd, void* out, hipStream_t s) {
+const char* launch_stem(fav_handle* h, const void* images, int layout, int n, int H, int W, int kh, int kw, int stride, int pad,
+                        int kpad, const float* mean, const float* istd, void* out, hipStream_t s) {
+    // conv_out truncates towards zero: an empty frame would come out as one output pixel
+    if (n < 1 || H < 1 || W < 1) return "stem im2col: n, H and W must be >= 1";
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return "stem im2col: unknown layout";
+    if (kh < 1 || kw < 1 || stride < 1 || pad < 0 || H + 2 * pad < kh || W + 2 * pad < kw) return "stem im2col: the window does not fit the padded frame";
     const int Ho = conv_out(H, kh, stride, pad), Wo = conv_out(W, kw, stride, pad);
     const long long total = (long long)n * Ho * Wo * (kpad / 8);
     Prof pr(h, s, FAV_K_STEM, 0.0, (double)n * H * W * 3 * (layout == 0 ? 1 : 4) + (double)total * 16);
@@ -614,7 +635,7 @@ void launch_stem(fav_handle* h, const void* images, int layout, int n, int H, in
         else
             hipLaunchKernelGGL((stem_im2col_rows_kernel<1>), dim3(blocks), dim3(256), lds, s, images, (uint4*)out, total_pix, H, W, Ho, Wo,
                                kh, kw, stride, pad, kpad, ppb, mean[0], mean[1], mean[2], istd[0], istd[1], istd[2]);
-        return;
+        return nullptr;
     }
     if (layout == FAV_LAYOUT_NHWC_U8)
         hipLaunchKernelGGL((stem_im2col_kernel<0>), dim3(grid_for(total)), dim3(256), 0, s, images, (uint4*)out, n, H, W,
@@ -622,14 +643,18 @@ void launch_stem(fav_handle* h, const void* images, int layout, int n, int H, in
     else
         hipLaunchKernelGGL((stem_im2col_kernel<1>), dim3(grid_for(total)), dim3(256), 0, s, images, (uint4*)out, n, H, W,
                            Ho, Wo, kh, kw, stride, pad, kpad, mean[0], mean[1], mean[2], istd[0], istd[1], istd[2]);
+    return nullptr;
 }
 
-void launch_maxpool(fav_handle* h, const void* x, void* y, int n, int H, int W, int C, hipStream_t s) {
+const char* launch_maxpool(fav_handle* h, const void* x, void* y, int n, int H, int W, int C, hipStream_t s) {
+    // (H + 2 - 3) / 2 + 1 is 1 at H = 0: an empty frame would store a row of -inf
+    if (n < 1 || H < 1 || W < 1 || C < 8) return "max pool: n, H and W must be >= 1 and C >= 8";
     const int Ho = conv_out(H, 3, 2, 1), Wo = conv_out(W, 3, 2, 1);
     const long long total = (long long)n * Ho * Wo * (C / 8);
     Prof pr(h, s, FAV_K_MAXPOOL, 0.0, 2.0 * ((double)n * H * W * C + (double)n * Ho * Wo * C));
     hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const uint4*)x, (uint4*)y, n, H, W,
                        C, Ho, Wo);
+    return nullptr;
 }
 
 // normalise + 7x7/2 conv (64 channels, weights [64][192]) + bias + ReLU + 3x3/2 max pool, frames -> [n][Hp][Wp][64] bf16
@@ -658,27 +683,39 @@ const char* launch_stem_pool(fav_handle* h, const void* images, int layout, int 
     return nullptr;
 }
 
-void launch_avgpool(fav_handle* h, const void* x, void* y, int n, int HW, int C, const DropParams& dp, const Group& G, hipStream_t s) {
+const char* launch_avgpool(fav_handle* h, const void* x, void* y, int n, int HW, int C, const fav_dropout_desc* drop, const Group& G,
+                           hipStream_t s) {
+    if (n < 1 || HW < 1 || C < 16) return "average pool: n and HW must be >= 1 and C >= 16";
+    if (const char* e = check_drop("average pool", drop, n)) return e;
+    const DropParams dp = make_drop(drop);
     const long long total = (long long)n * (C / 16);
     Prof pr(h, s, FAV_K_AVGPOOL, 0.0, 2.0 * ((double)n * HW * C + (double)n * C));
     const float inv = 1.0f / (float)HW;
     hipLaunchKernelGGL(avgpool_kernel, dim3(grid_for(total), G.n), dim3(256), 0, s, (const uint4*)x, (uint4*)y, n, HW, C, inv,
                        dp, G.x, G.y);
+    return nullptr;
 }
 
-void launch_entry_dropout(fav_handle* h, const void* x, void* out, long long elems, int n_out, const DropParams& dp,
-                          hipStream_t s) {
+const char* launch_entry_dropout(fav_handle* h, const void* x, void* out, long long elems, int n_out, const fav_dropout_desc* drop,
+                                 hipStream_t s) {
+    if (!drop || drop->site < 0) return "entry dropout: needs a dropout site";
+    if (elems < 16 || n_out < 1) return "entry dropout: elems_per_frame must be >= 16 and n_out >= 1";
+    if (const char* e = check_drop("entry dropout", drop, n_out)) return e;
+    const DropParams dp = make_drop(drop);
     const long long total = (elems / 16) * std::min<long long>(dp.n_img, n_out);   // threads: one per cached chunk
     Prof pr(h, s, FAV_K_DROPOUT, 0.0, 2.0 * (double)elems * (n_out + std::min<long long>(dp.n_img, n_out)));
     hipLaunchKernelGGL(entry_dropout_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const uint4*)x, (uint4*)out,
                        elems / 16, n_out, dp);
+    return nullptr;
 }
 
 // Entry dropout + the 1x1 reduce behind it (entry_reduce_kernel); entry_reduce_supported: fav_plan.hpp
 const char* launch_entry_reduce(fav_handle* h, const void* x, void* y, const void* wa, const float* bias_a, void* t1, int C, int nred,
-                                int HW, int n_out, const DropParams& dp, hipStream_t s) {
+                                int HW, int n_out, const fav_dropout_desc* drop, hipStream_t s) {
+    if (!drop || drop->site < 0 || n_out < 1 || HW < 1) return "entry reduce: needs a dropout site, n_out >= 1 and HW >= 1";
+    if (const char* e = check_drop("entry reduce", drop, n_out)) return e;
+    const DropParams dp = make_drop(drop);
     if (!entry_reduce_supported(C, nred, dp.n_img, HW)) return "entry reduce: unsupported shape";
-    if (dp.site < 0 || n_out < 1 || dp.v0 < 0 || dp.v0 + n_out > 0x7fffffffLL) return "entry reduce: bad dropout descriptor";
     EntryReduceParams p;
     p.x = (const uint16_t*)x; p.y = (uint16_t*)y; p.wa = (const uint16_t*)wa; p.bias_a = bias_a; p.t1 = (uint16_t*)t1;
     p.HW = HW; p.M = (int)((long long)dp.n_img * HW); p.n_out = n_out;
@@ -1100,8 +1137,8 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
             switch (o.kind) {
                 case OP_STEM_IM2COL: {
                     const LayerShape& L = h->plan.layers[o.layer];
-                    launch_stem(h, buf(o.in, o), layout, cn, o.H, o.W, L.kh, L.kw, L.stride, L.pad, L.k, c.mean,
-                                istd, buf(o.out, o), s);
+                    if (const char* e = launch_stem(h, buf(o.in, o), layout, cn, o.H, o.W, L.kh, L.kw, L.stride, L.pad, L.k, c.mean,
+                                                    istd, buf(o.out, o), s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 }
                 case OP_CONV: {
@@ -1136,24 +1173,18 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
                                                          buf(o.out, o), G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 case OP_MAXPOOL:
-                    launch_maxpool(h, buf(o.in, o), buf(o.out, o), cn, o.H, o.W, o.C, s);
+                    if (const char* e = launch_maxpool(h, buf(o.in, o), buf(o.out, o), cn, o.H, o.W, o.C, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
-                case OP_AVGPOOL: {
-                    DropParams dp = make_drop(&dd);
-                    launch_avgpool(h, buf(o.in, o), buf(o.out, o), cn, o.H * o.W, o.C, dp, G, s);
+                case OP_AVGPOOL:
+                    if (const char* e = launch_avgpool(h, buf(o.in, o), buf(o.out, o), cn, o.H * o.W, o.C, &dd, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
-                }
-                case OP_ENTRY_DROPOUT: {
-                    DropParams dp = make_drop(&dd);
-                    launch_entry_dropout(h, pin_base, buf(o.out, o), o.in_elems, cn, dp, s);
+                case OP_ENTRY_DROPOUT:
+                    if (const char* e = launch_entry_dropout(h, pin_base, buf(o.out, o), o.in_elems, cn, &dd, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
-                }
-                case OP_ENTRY_REDUCE: {
-                    DropParams dp = make_drop(&dd);
+                case OP_ENTRY_REDUCE:
                     if (const char* e = launch_entry_reduce(h, pin_base, o.skip_y ? nullptr : buf(o.out, o), LW(o.layer_a), LB(o.layer_a), buf(o.out2, o), o.C, o.Co2,
-                                                            o.H * o.W, cn, dp, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
+                                                            o.H * o.W, cn, &dd, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
-                }
             }
         }
     }
@@ -1227,7 +1258,7 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
     } while (0)
     h->cur_op = -1;
     // patch embedding: normalise + im2col (k = (r*P + s)*3 + c), GEMM, add positions / class token
-    launch_stem(h, images, layout, n, c.in_h, c.in_w, V.patch, V.patch, V.patch, 0, V.patch * V.patch * 3, c.mean, inv_std, B.v_patches, s);
+    FAV_VIT_TRY(launch_stem(h, images, layout, n, c.in_h, c.in_w, V.patch, V.patch, V.patch, 0, V.patch * V.patch * 3, c.mean, inv_std, B.v_patches, s));
     FAV_VIT_TRY(gemm(0, B.v_patches, gh * gw, nullptr, 0, B.v_emb, 0));
     launch_vit_assemble(h, B.v_emb, (const float*)h->weights[1].w_m[0], B.v_x, n, ntok, D, s);
     int li = 2;
@@ -1294,6 +1325,12 @@ fav_status fav_create(const fav_config* cfg, fav_handle** out) {
         cfg->tail_min_rows < -1 || cfg->ens_grouped_max < -1 || cfg->vit_streams < 0 || cfg->vit_streams > 4 || cfg->stem_fused < -1 || cfg->stem_fused > 0 ||
         (cfg->n_members > 1 && cfg->site_mask != 0 && cfg->dropout_p > 0.f)) {   // ensemble members are deterministic
         g_create_error = "fav_create: config value out of range";
+        return FAV_ERR_INVALID_ARG;
+    }
+    if (std::lround((double)cfg->dropout_p * 256.0) > 255) {
+        // the masks draw 8 bits and drop below round(256 p): 256 would drop every element and scale = 1 / (1 - 256/256) is infinite
+        g_create_error = fmt("fav_create: dropout_p = %.9g rounds to the 8-bit threshold 256 (every element dropped, infinite scale); "
+                             "the largest usable value is below 255.5 / 256", (double)cfg->dropout_p);
         return FAV_ERR_INVALID_ARG;
     }
     if (cfg->conf_kind == FAV_CONF_MUTUAL_INFO) {
@@ -1786,25 +1823,30 @@ static fav_status op_done(const char* e) {
     if (hipGetLastError() != hipSuccess) { g_create_error = "kernel launch failed"; return FAV_ERR_HIP; }
     return FAV_OK;
 }
+// the same for a launcher's message ("conv: ..."), which does not name the entry point: "<fn>: conv: ..."
+static fav_status op_done(const char* fn, const char* e) {
+    if (e) { g_create_error = fmt("%s: %s", fn, e); return FAV_ERR_INVALID_ARG; }
+    if (hipGetLastError() != hipSuccess) { g_create_error = "kernel launch failed"; return FAV_ERR_HIP; }
+    return FAV_OK;
+}
 
 fav_status fav_op_conv2d(const fav_conv_desc* d, void* stream) {
     if (!d || !d->x || !d->w || !d->bias || !d->y) return op_done("fav_op_conv2d: null pointer");
     if (d->Cout % 64 != 0) return op_done("fav_op_conv2d: Cout must be a multiple of 64");
-    return op_done(launch_conv(nullptr, *d, d->Cout, d->Cout, Group{}, (hipStream_t)stream));
+    return op_done("fav_op_conv2d", launch_conv(nullptr, *d, d->Cout, d->Cout, Group{}, (hipStream_t)stream));
 }
 
 fav_status fav_op_bottleneck_tail(const fav_tail_desc* d, void* stream) {
     if (!d || !d->x || !d->wc || !d->bias_c || !d->res || !d->y) return op_done("fav_op_bottleneck_tail: null pointer");
     if ((d->wb && !d->bias_b) || (d->wa && (!d->bias_a || !d->t1n))) return op_done("fav_op_bottleneck_tail: null pointer");
-    return op_done(launch_tail(nullptr, *d, Group{}, (hipStream_t)stream));
+    return op_done("fav_op_bottleneck_tail", launch_tail(nullptr, *d, Group{}, (hipStream_t)stream));
 }
 
 fav_status fav_op_stem_im2col(const void* images, int32_t layout, int32_t n, int32_t H, int32_t W, int32_t kh, int32_t kw,
                               int32_t stride, int32_t pad, int32_t kpad, const float* mean3, const float* inv_std3,
                               void* out, void* stream) {
     if (!images || !out || !mean3 || !inv_std3 || kpad % 64 != 0 || kpad < kh * kw * 3) return op_done("fav_op_stem_im2col: bad argument");
-    launch_stem(nullptr, images, layout, n, H, W, kh, kw, stride, pad, kpad, mean3, inv_std3, out, (hipStream_t)stream);
-    return op_done(nullptr);
+    return op_done("fav_op_stem_im2col", launch_stem(nullptr, images, layout, n, H, W, kh, kw, stride, pad, kpad, mean3, inv_std3, out, (hipStream_t)stream));
 }
 
 fav_status fav_op_stem_pool(const void* images, int32_t layout, int32_t n, int32_t H, int32_t W, const void* w, const float* bias,
@@ -1815,26 +1857,23 @@ fav_status fav_op_stem_pool(const void* images, int32_t layout, int32_t n, int32
 
 fav_status fav_op_maxpool3x3s2(const void* x, void* y, int32_t n, int32_t H, int32_t W, int32_t C, void* stream) {
     if (!x || !y || C % 8 != 0) return op_done("fav_op_maxpool3x3s2: bad argument");
-    launch_maxpool(nullptr, x, y, n, H, W, C, (hipStream_t)stream);
-    return op_done(nullptr);
+    return op_done("fav_op_maxpool3x3s2", launch_maxpool(nullptr, x, y, n, H, W, C, (hipStream_t)stream));
 }
 
 fav_status fav_op_avgpool(const void* x, void* y, int32_t n, int32_t HW, int32_t C, const fav_dropout_desc* drop, void* stream) {
-    if (!x || !y || C % 16 != 0 || HW < 1) return op_done("fav_op_avgpool: bad argument");
-    launch_avgpool(nullptr, x, y, n, HW, C, make_drop(drop), Group{}, (hipStream_t)stream);
-    return op_done(nullptr);
+    if (!x || !y || C % 16 != 0) return op_done("fav_op_avgpool: bad argument");
+    return op_done("fav_op_avgpool", launch_avgpool(nullptr, x, y, n, HW, C, drop, Group{}, (hipStream_t)stream));
 }
 
 fav_status fav_op_entry_reduce(const void* x, void* y, const void* wa, const float* bias_a, void* t1, int32_t C, int32_t Nred,
                                int32_t HW, int32_t n_out, const fav_dropout_desc* drop, void* stream) {
-    if (!x || !wa || !bias_a || !t1 || !drop || drop->site < 0 || HW < 1) return op_done("fav_op_entry_reduce: bad argument");
-    return op_done(launch_entry_reduce(nullptr, x, y, wa, bias_a, t1, C, Nred, HW, n_out, make_drop(drop), (hipStream_t)stream));
+    if (!x || !wa || !bias_a || !t1) return op_done("fav_op_entry_reduce: bad argument");
+    return op_done("fav_op_entry_reduce", launch_entry_reduce(nullptr, x, y, wa, bias_a, t1, C, Nred, HW, n_out, drop, (hipStream_t)stream));
 }
 
 fav_status fav_op_entry_dropout(const void* x, void* out, int64_t elems, int32_t n_out, const fav_dropout_desc* drop, void* stream) {
-    if (!x || !out || !drop || drop->site < 0 || elems % 16 != 0) return op_done("fav_op_entry_dropout: bad argument");
-    launch_entry_dropout(nullptr, x, out, elems, n_out, make_drop(drop), (hipStream_t)stream);
-    return op_done(nullptr);
+    if (!x || !out || elems % 16 != 0) return op_done("fav_op_entry_dropout: bad argument");
+    return op_done("fav_op_entry_dropout", launch_entry_dropout(nullptr, x, out, elems, n_out, drop, (hipStream_t)stream));
 }
 
 fav_status fav_op_head(const float* logits, int32_t T, int32_t n, int32_t C, int32_t ld, float temperature, int32_t kind,

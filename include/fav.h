@@ -284,6 +284,21 @@ fav_status fav_get_profile(fav_handle* h, fav_profile* out, int32_t reset); /* s
 
 /* ---- Operator level (one launch each; used by the executor and by the
  * per-kernel parity tests).  All tensors NHWC, bf16 unless noted. ---- */
+/* The MC-Dropout mask of one launch.  Row r of the launch is virtual frame v = v0 + r: sample t = v / n_img of frame
+ * i = v % n_img.  Element e of that row draws byte e % 16 (little endian over the four words) of
+ *   Philox4x32-10(counter = (e / 16, low 32 bits of (first_image_index + i), t, site), key = (low, high half of seed))
+ * and is KEPT iff the byte is >= threshold; a kept value is bf16(fp32 value * scale), a dropped one +0.
+ * Ranges, checked by every fav_op_* that takes a descriptor (conv2d, bottleneck_tail, avgpool, entry_dropout,
+ * entry_reduce) before anything is launched - FAV_ERR_INVALID_ARG otherwise; with site < 0 no other field is read:
+ *   site               0 .. 2^31 - 1, the fourth counter word
+ *   threshold          0 .. 255 (0: site enabled, nothing dropped; the draw is 8 bits wide, so 256 would drop everything)
+ *   scale              finite and > 0 (1 / (1 - threshold/256) keeps the expectation; the kernels multiply by what is given)
+ *   n_img              >= 1
+ *   v0, v0 + rows      0 <= v0 and v0 + rows <= 2^31 - 1: the kernels hold v and t in 32 bits
+ *   first_image_index  any value; ONLY ITS LOW 32 BITS enter the counter, so frames 2^32 apart share their masks
+ *                      (and the frame word wraps inside a launch that crosses a multiple of 2^32)
+ *   seed               any value
+ * fav_create refuses a dropout_p whose round(256 p) is 256. */
 typedef struct fav_dropout_desc {
     int32_t site;            /* -1 = no dropout */
     uint32_t threshold;      /* drop iff 8-bit draw < threshold (= round(p * 256)) */
@@ -327,7 +342,8 @@ typedef struct fav_tail_desc {
     int32_t res_entry, entry_site;
 } fav_tail_desc;
 fav_status fav_op_bottleneck_tail(const fav_tail_desc* d, void* hip_stream);
-/* frames (u8 or fp32 NHWC3) -> normalised bf16 im2col matrix [n*Ho*Wo][kpad] */
+/* frames (u8 or fp32 NHWC3) -> normalised bf16 im2col matrix [n*Ho*Wo][kpad].  n, H, W >= 1, a known layout and a window that
+ * fits the padded frame, else FAV_ERR_INVALID_ARG and nothing is launched (the same holds for the pools and the entry ops below). */
 fav_status fav_op_stem_im2col(const void* images, int32_t layout, int32_t n, int32_t H, int32_t W,
                               int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t kpad,
                               const float* mean3, const float* inv_std3, void* out, void* hip_stream);
@@ -336,10 +352,15 @@ fav_status fav_op_stem_im2col(const void* images, int32_t layout, int32_t n, int
  * bit-identical to fav_op_stem_im2col + fav_op_conv2d + fav_op_maxpool3x3s2 */
 fav_status fav_op_stem_pool(const void* images, int32_t layout, int32_t n, int32_t H, int32_t W, const void* w, const float* bias,
                             const float* mean3, const float* inv_std3, void* out, void* hip_stream);
+/* 3x3 / stride 2 / pad 1 max pool, [n][H][W][C] -> [n][(H-1)/2+1][(W-1)/2+1][C]; n, H, W >= 1, C % 8 == 0.  Rounds nothing:
+ * subnormals and infinities pass as they are; -0 and +0 are not ordered. */
 fav_status fav_op_maxpool3x3s2(const void* x, void* y, int32_t n, int32_t H, int32_t W, int32_t C, void* hip_stream);
+/* global average pool [n][HW][C] -> [n][C]: sequential fp32 sum in row order, times fp32(1 / HW), the optional dropout site, one
+ * bf16 rounding; n, HW >= 1, C % 16 == 0; drop may be NULL */
 fav_status fav_op_avgpool(const void* x, void* y, int32_t n, int32_t HW, int32_t C,
                           const fav_dropout_desc* drop, void* hip_stream);
-/* out[v - v0][e] = dropout(x[v % n_img][e]) for v in [v0, v0 + n_out) */
+/* out[v - v0][e] = dropout(x[v % n_img][e]) for v in [v0, v0 + n_out); elems_per_frame >= 16 and a multiple of 16, n_out >= 1,
+ * drop->site >= 0 */
 fav_status fav_op_entry_dropout(const void* x, void* out, int64_t elems_per_frame, int32_t n_out,
                                 const fav_dropout_desc* drop, void* hip_stream);
 /* entry dropout and the 1x1 reduce behind it in one launch (C = 256, Nred = 64):
