@@ -147,6 +147,7 @@ _SIGNATURES = {
     "fav_get_op_profile": (C.c_int, [C.c_void_p, C.POINTER(FavOpProfile), C.c_int32, C.POINTER(C.c_int32)]),
     "fav_op_conv2d": (C.c_int, [C.POINTER(FavConvDesc), C.c_void_p]),
     "fav_op_bottleneck_tail": (C.c_int, [C.POINTER(FavTailDesc), C.c_void_p]),
+    "fav_op_last_route": (C.c_int, [C.c_char_p, C.c_size_t]),
     "fav_op_linear_streamk": (C.c_int, [C.POINTER(FavLinearDesc), C.c_void_p]),
     "fav_op_stem_im2col": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -200,6 +201,13 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def last_route() -> str:
+    """fav_op_last_route: the kernel the calling thread's most recent fav_op_* launch took ('' after a refusal)."""
+    buf = C.create_string_buffer(96)
+    check(load().fav_op_last_route(buf, len(buf)))
+    return buf.value.decode("ascii")
 
 
 class FavError(RuntimeError):

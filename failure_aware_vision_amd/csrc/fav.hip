@@ -41,6 +41,46 @@ std::string fmt(const char* f, ...) {
     return buf;
 }
 
+// ---- route report (fav_op_last_route, fav.h): which kernel instantiation the calling thread's last launch took.  The launch
+//      site stores an enum and a few ints; text is formatted only when somebody asks.
+enum RouteKind { ROUTE_NONE = 0, ROUTE_CONV_IGEMM, ROUTE_CONV_HALO, ROUTE_PROJ, ROUTE_TAIL, ROUTE_ATTENTION, ROUTE_ENTRY_REDUCE, ROUTE_STEM_POOL };
+struct Route { int kind; int a[8]; bool fresh; };   // fresh: recorded since the last fav_op_* returned
+thread_local Route g_route = {ROUTE_NONE, {0, 0, 0, 0, 0, 0, 0, 0}, false};
+
+inline void route_set(int kind, int a0 = 0, int a1 = 0, int a2 = 0, int a3 = 0, int a4 = 0, int a5 = 0, int a6 = 0, int a7 = 0) {
+    g_route = Route{kind, {a0, a1, a2, a3, a4, a5, a6, a7}, true};
+}
+inline void route_clear() { g_route.kind = ROUTE_NONE; g_route.fresh = false; }
+// at the end of a fav_op_*: a refusal, or a launch through a launcher that records nothing, leaves no route behind
+inline void route_close(bool ok) {
+    if (!ok || !g_route.fresh) g_route.kind = ROUTE_NONE;
+    g_route.fresh = false;
+}
+
+std::string route_text(const Route& r) {
+    const int* a = r.a;
+    const char* mode = a[4] ? "f32" : "bf16";
+    switch (r.kind) {
+    case ROUTE_CONV_IGEMM:    // BM, BN, BK, NS, MODE, EPI, PP, GELU
+        return fmt("conv_igemm<%d,%d,%d,%d,%s,epi%d%s%s>", a[0], a[1], a[2], a[3], mode, a[5], a[6] ? ",pp" : "", a[7] ? ",gelu" : "");
+    case ROUTE_CONV_HALO:     // CIN, BN, BM, NS, MODE (a[4])
+        return fmt("conv3x3_halo<%d,%d,%d,%d,%s>", a[0], a[1], a[2], a[3], mode);
+    case ROUTE_PROJ:          // CIN, COUT, NW
+        return fmt("proj<%d,%d,nw%d>", a[0], a[1], a[2]);
+    case ROUTE_TAIL:          // CMID, NRED, HAS3X3, NW, WC2, RP, RESE
+        return fmt("tail<%d,%d,%s,nw%d,wc%d%s%s>", a[0], a[1], a[2] ? "3x3" : "1x1", a[3], a[4] ? 2 : 1, a[5] == 16 ? ",rp16" : "",
+                   a[6] ? ",res_entry" : "");
+    case ROUTE_ATTENTION:     // MODE, NKT, FULL
+        return fmt("attention<%s,%d%s>", a[0] ? "f32" : "bf16", a[1], a[2] ? ",full" : "");
+    case ROUTE_ENTRY_REDUCE:  // C, NRED
+        return fmt("entry_reduce<%d,%d>", a[0], a[1]);
+    case ROUTE_STEM_POOL:     // LAYOUT
+        return fmt("stem7_pool<%s>", a[0] ? "f32" : "u8");
+    default:
+        return std::string();
+    }
+}
+
 // inside a fork/join region: remember the first failure but keep going, so that every forked stream is joined
 #define HIP_KEEP(h, st, expr)                                                                    \
     do {                                                                                         \
@@ -301,14 +341,23 @@ bool launch_proj(fav_handle* h, const fav_conv_desc& d, const Group& G, hipStrea
     const double flops = 2.0 * (double)M * d.Cin * d.Cout * G.n;
     const double bytes = 2.0 * ((double)M * (d.Cin + d.Cout) + (double)d.Cin * d.Cout) * G.n;
     Prof pr(h, s, FAV_K_CONV, flops, bytes);
-    if (wide) hipLaunchKernelGGL(kern_w, dim3((unsigned)((M + 255) / 256), G.n), dim3(512), lds, s, p, 0);
-    else hipLaunchKernelGGL(kern, dim3((unsigned)((M + 127) / 128), G.n), dim3(256), lds, s, p, 0);
+    if (wide) { route_set(ROUTE_PROJ, 512, 1024, 8); hipLaunchKernelGGL(kern_w, dim3((unsigned)((M + 255) / 256), G.n), dim3(512), lds, s, p, 0); }
+    else { route_set(ROUTE_PROJ, 256, 512, 4); hipLaunchKernelGGL(kern, dim3((unsigned)((M + 127) / 128), G.n), dim3(256), lds, s, p, 0); }
     return true;
 }
 
 
 const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int ldy, const Group& G, hipStream_t s) {
-    if (d.Cin % 64 != 0) return "conv: Cin must be a multiple of 64";
+    // conv_out divides by the stride and truncates towards zero: a window larger than the padded frame would come out as
+    // Ho = Wo = -1, that is M = n_frames > 0 rows
+    if (d.n_frames < 1 || d.H < 1 || d.W < 1) return "conv: n_frames, H and W must be >= 1";
+    if (d.kh < 1 || d.kw < 1 || d.stride < 1 || d.pad < 0) return "conv: kh, kw and stride must be >= 1 and pad >= 0";
+    if ((long long)d.H + 2ll * d.pad < d.kh || (long long)d.W + 2ll * d.pad < d.kw) return "conv: the window does not fit the padded frame";
+    if (d.relu < 0 || d.relu > 2) return "conv: relu must be 0 (none), 1 (ReLU) or 2 (GELU)";
+    if (d.out_f32 != 0 && d.out_f32 != 1) return "conv: out_f32 must be 0 or 1";
+    if (d.math_mode != FAV_MATH_BF16 && d.math_mode != FAV_MATH_F32_EXACT) return "conv: unknown math_mode";
+    if (d.Cin < 64 || d.Cin % 64 != 0) return "conv: Cin must be a multiple of 64 and >= 64";
+    if (d.Cout < 1 || cout_pad < d.Cout) return "conv: Cout must be >= 1 and the padded Cout must cover it";   // else tiles_n <= 0: an empty or a wrapped grid
     if (cout_pad % 64 != 0) return "conv: padded Cout must be a multiple of 64";
     // the bf16 epilogues store whole 16-byte groups of channels and range-check rows only: padded columns would land in
     // the next pixel's first channels.  Only the fp32 (logit) output, whose row pitch is the padded width, may be padded.
@@ -400,25 +449,27 @@ const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int
         if (lds <= 160 * 1024) {
             p.nk = 9 * d.Cin / 64;
             dim3 hgrid((unsigned)((p.M + HBM - 1) / HBM), G.n);
-#define FAV_HALO(KERNEL_)                                                                                            \
+#define FAV_HALO(CIN_, BN_, BM_, NS_, SUB_, OCC_, MODE_)                                                             \
     do {                                                                                                             \
         static DeviceFlags attr_set;   /* hipFuncSetAttribute applies to the CURRENT device only */                  \
         if (!attr_set.test_current()) {                                                                              \
-            if (hipFuncSetAttribute((const void*)KERNEL_, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
+            if (hipFuncSetAttribute((const void*)conv3x3_halo_kernel<CIN_, BN_, BM_, NS_, SUB_, OCC_, MODE_>,                \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                   \
                 return "conv: cannot reserve LDS for the staged 3x3 kernel";                                         \
             attr_set.set_current();                                                                                  \
         }                                                                                                            \
-        hipLaunchKernelGGL(KERNEL_, hgrid, dim3(HBM * 2), lds, s, p, patch_bytes);                                   \
+        route_set(ROUTE_CONV_HALO, CIN_, BN_, BM_, NS_, MODE_);                                                      \
+        hipLaunchKernelGGL((conv3x3_halo_kernel<CIN_, BN_, BM_, NS_, SUB_, OCC_, MODE_>), hgrid, dim3(HBM * 2), lds, s, p, patch_bytes); \
     } while (0)
             const bool bf = d.math_mode == FAV_MATH_BF16;
             if (d.Cin == 64 && halo_cfg == 0) {
-                if (bf) FAV_HALO((conv3x3_halo_kernel<64, 64, 128, 2, 1, 3, 0>)); else FAV_HALO((conv3x3_halo_kernel<64, 64, 128, 2, 1, 3, 1>));
+                if (bf) FAV_HALO(64, 64, 128, 2, 1, 3, 0); else FAV_HALO(64, 64, 128, 2, 1, 3, 1);
             } else if (d.Cin == 64) {
-                if (bf) FAV_HALO((conv3x3_halo_kernel<64, 64, 256, 3, 1, 4, 0>)); else FAV_HALO((conv3x3_halo_kernel<64, 64, 256, 3, 1, 4, 1>));
+                if (bf) FAV_HALO(64, 64, 256, 3, 1, 4, 0); else FAV_HALO(64, 64, 256, 3, 1, 4, 1);
             } else if (halo_cfg == 0) {
-                if (bf) FAV_HALO((conv3x3_halo_kernel<128, 128, 128, 2, 1, 2, 0>)); else FAV_HALO((conv3x3_halo_kernel<128, 128, 128, 2, 1, 2, 1>));
+                if (bf) FAV_HALO(128, 128, 128, 2, 1, 2, 0); else FAV_HALO(128, 128, 128, 2, 1, 2, 1);
             } else {
-                if (bf) FAV_HALO((conv3x3_halo_kernel<128, 128, 256, 2, 2, 2, 0>)); else FAV_HALO((conv3x3_halo_kernel<128, 128, 256, 2, 2, 2, 1>));
+                if (bf) FAV_HALO(128, 128, 256, 2, 2, 2, 0); else FAV_HALO(128, 128, 256, 2, 2, 2, 1);
             }
 #undef FAV_HALO
             dbg_report((p.M + HBM - 1) / HBM, HBM, d.Cout, 64);
@@ -435,6 +486,7 @@ const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int
     const int epi = epi_forced >= 0 ? epi_forced : ((d.res && !big) ? 0 : 1);
 #define FAV_LAUNCH(BN_, BK_, NS_, MODE_)                                                                          \
     do {                                                                                                          \
+        route_set(ROUTE_CONV_IGEMM, 128, BN_, BK_, NS_, MODE_, epi ? 1 : 0, 0, d.relu == 2);                     \
         if (d.relu == 2) {      /* GELU (ViT MLP): the instantiations that carry it */                            \
             if (epi) hipLaunchKernelGGL((conv_igemm_kernel<128, BN_, BK_, NS_, MODE_, 2, 0, 1, 0, true>), grid, dim3(256), 0, s, p); \
             else hipLaunchKernelGGL((conv_igemm_kernel<128, BN_, BK_, NS_, MODE_, 2, 0, 0, 0, true>), grid, dim3(256), 0, s, p);     \
@@ -449,6 +501,7 @@ const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int
 #define FAV_LAUNCH_BIG(MODE_)                                                                                     \
     do {                                                                                                          \
         const int pp = (int)FAV_KNOB("FAV_CONV_PP", 1);                                                           \
+        route_set(ROUTE_CONV_IGEMM, 256, 256, 64, 2, MODE_, epi ? 1 : 0, (epi && pp && MODE_ == 0) ? 1 : 0, d.relu == 2);       \
         if (d.relu == 2) {                                                                                        \
             if (epi && pp && MODE_ == 0) hipLaunchKernelGGL((conv_igemm_kernel<256, 256, 64, 2, 0, 2, 0, 1, 1, true>), grid, dim3(512), 0, s, p); \
             else if (epi) hipLaunchKernelGGL((conv_igemm_kernel<256, 256, 64, 2, MODE_, 2, 0, 1, 0, true>), grid, dim3(512), 0, s, p);    \
@@ -471,6 +524,7 @@ const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int
 // ---- bottleneck tail (conv_b 3x3 -> conv_c 1x1 + residual + dropout -> next block's conv_a 1x1), one launch; its LDS plan
 //      is tail_geometry (fav_plan.hpp) ----
 const char* launch_tail(fav_handle* h, const fav_tail_desc& d, const Group& G, hipStream_t s) {
+    if (d.n_frames < 1 || d.H < 1 || d.W < 1) return "bottleneck tail: n_frames, H and W must be >= 1";
     const bool has3x3 = d.wb != nullptr;
     const int nred = d.wa ? d.Nred : 0;
     TailGeom g;
@@ -549,6 +603,7 @@ const char* launch_tail(fav_handle* h, const fav_tail_desc& d, const Group& G, h
                 return "bottleneck tail: cannot reserve LDS";                                                         \
             attr_set.set_current();                                                                                   \
         }                                                                                                             \
+        route_set(ROUTE_TAIL, CMID_, NRED_, H3_, NW_, WC2_, 32, 0);                                                   \
         hipLaunchKernelGGL((bottleneck_tail_kernel<CMID_, NRED_, H3_, NS_, NW_, WC2_>), grid, dim3(NW_ * 64), g.lds_bytes, s, p, g.patch_bytes); \
         dbg_report();                                                                                                 \
         return nullptr;                                                                                               \
@@ -572,6 +627,7 @@ const char* launch_tail(fav_handle* h, const fav_tail_desc& d, const Group& G, h
                 return "bottleneck tail: cannot reserve LDS";
             attr_set.set_current();
         }
+        route_set(ROUTE_TAIL, 64, 64, 1, 4, g.wc2 ? 1 : 0, 32, 1);
         if (g.wc2) hipLaunchKernelGGL(k1, grid, dim3(256), g.lds_bytes, s, p, g.patch_bytes);
         else hipLaunchKernelGGL(k0, grid, dim3(256), g.lds_bytes, s, p, g.patch_bytes);
         dbg_report();
@@ -597,6 +653,7 @@ const char* launch_tail(fav_handle* h, const fav_tail_desc& d, const Group& G, h
                 return "bottleneck tail: cannot reserve LDS";
             attr_set.set_current();
         }
+        route_set(ROUTE_TAIL, 256, 256, 0, 8, g.wc2 ? 1 : 0, 16, 0);
         if (g.wc2) hipLaunchKernelGGL((bottleneck_tail_kernel<256, 256, false, 2, 8, true, 16>), grid, dim3(512), g.lds_bytes, s, p, g.patch_bytes);
         else hipLaunchKernelGGL((bottleneck_tail_kernel<256, 256, false, 2, 8, false, 16>), grid, dim3(512), g.lds_bytes, s, p, g.patch_bytes);
         dbg_report();
@@ -678,6 +735,7 @@ const char* launch_stem_pool(fav_handle* h, const void* images, int layout, int 
             ((double)n * H * W * 3 * (layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4) + 2.0 * n * p.Hp * p.Wp * 64 + 2.0 * 64 * 192) * G.n);
     // two blocks per CU (232 VGPRs, 66 KB of LDS); blocks loop over the tiles with the weights in registers
     const unsigned blocks = (unsigned)std::min<long long>(p.tiles, std::max(1, 256 * 2 / G.n));
+    route_set(ROUTE_STEM_POOL, layout == FAV_LAYOUT_NHWC_U8 ? 0 : 1);
     if (layout == FAV_LAYOUT_NHWC_U8) hipLaunchKernelGGL(stem7_pool_kernel<0>, dim3(blocks, G.n), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(stem7_pool_kernel<1>, dim3(blocks, G.n), dim3(256), 0, s, p);
     return nullptr;
@@ -724,6 +782,7 @@ const char* launch_entry_reduce(fav_handle* h, const void* x, void* y, const voi
     const long long cached = std::min<long long>(dp.n_img, n_out);
     const double rows = (double)n_out * HW;
     Prof pr(h, s, FAV_K_CONV, 2.0 * rows * C * nred, 2.0 * ((double)cached * HW * C + rows * ((y ? C : 0) + nred) + (double)C * nred));
+    route_set(ROUTE_ENTRY_REDUCE, 256, 64);
     hipLaunchKernelGGL((entry_reduce_kernel<256, 64>), dim3((unsigned)((p.M + 127) / 128)), dim3(256), 0, s, p);
     return nullptr;
 }
@@ -995,9 +1054,9 @@ const char* launch_attention(fav_handle* h, const void* qkv, void* out, int n, i
     const double flops = 4.0 * n * heads * (double)T * T * 64;
     Prof pr(h, s, FAV_K_CONV, flops, (double)n * T * D * 2 * 4);
     const dim3 grid((unsigned)(n * heads)), block(nw * 64);
-#define FAV_ATTN(MODE_, ...) hipLaunchKernelGGL((attention_kernel<MODE_, __VA_ARGS__>), grid, block, lds, s, (const uint16_t*)qkv, (uint16_t*)out, T, D, heads)
-    if (math_mode == FAV_MATH_BF16) { if (nkt == 13) FAV_ATTN(0, 13, true); else if (nkt < 13) FAV_ATTN(0, 13); else FAV_ATTN(0, 16); }
-    else { if (nkt <= 13) FAV_ATTN(1, 13); else FAV_ATTN(1, 16); }
+#define FAV_ATTN(MODE_, ...) route_set(ROUTE_ATTENTION, MODE_, __VA_ARGS__); hipLaunchKernelGGL((attention_kernel<MODE_, __VA_ARGS__>), grid, block, lds, s, (const uint16_t*)qkv, (uint16_t*)out, T, D, heads)
+    if (math_mode == FAV_MATH_BF16) { if (nkt == 13) { FAV_ATTN(0, 13, true); } else if (nkt < 13) { FAV_ATTN(0, 13); } else { FAV_ATTN(0, 16); } }
+    else { if (nkt <= 13) { FAV_ATTN(1, 13); } else { FAV_ATTN(1, 16); } }
 #undef FAV_ATTN
     return nullptr;
 }
@@ -1630,6 +1689,7 @@ fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out
 // parameters (NULL: none), reported after the handle and weights checks and before those on n, layout and first_index.
 fav_status classify_gate(const char* who, fav_handle* h, const char* bad, const void* images, int32_t n, int32_t layout,
                          int64_t first_index, const HeadOut& out, void* stream) {
+    route_clear();            // the report speaks of fav_op_* launches only: empty after a classify call, refused or not
     if (!h) return FAV_ERR_INVALID_ARG;
     if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", who); return FAV_ERR_NO_WEIGHTS; }
     if (bad) { h->err = fmt("%s: %s", who, bad); return FAV_ERR_INVALID_ARG; }
@@ -1640,6 +1700,7 @@ fav_status classify_gate(const char* who, fav_handle* h, const char* bad, const 
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (fav_status st = wait_last_use(h, s)) return st;
     const fav_status st = classify_on_stream(h, Frames{images, layout, n, first_index}, out, s);
+    route_clear();            // the report speaks of fav_op_* launches only
     mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
     return st;
 }
@@ -1819,14 +1880,28 @@ fav_status fav_get_op_profile(fav_handle* h, fav_op_profile* out, int32_t cap, i
 
 // ---- operator level --------------------------------------------------------
 static fav_status op_done(const char* e) {
+    route_close(!e);
     if (e) { g_create_error = e; return FAV_ERR_INVALID_ARG; }
-    if (hipGetLastError() != hipSuccess) { g_create_error = "kernel launch failed"; return FAV_ERR_HIP; }
+    if (hipGetLastError() != hipSuccess) { route_clear(); g_create_error = "kernel launch failed"; return FAV_ERR_HIP; }
     return FAV_OK;
 }
 // the same for a launcher's message ("conv: ..."), which does not name the entry point: "<fn>: conv: ..."
 static fav_status op_done(const char* fn, const char* e) {
+    route_close(!e);
     if (e) { g_create_error = fmt("%s: %s", fn, e); return FAV_ERR_INVALID_ARG; }
-    if (hipGetLastError() != hipSuccess) { g_create_error = "kernel launch failed"; return FAV_ERR_HIP; }
+    if (hipGetLastError() != hipSuccess) { route_clear(); g_create_error = "kernel launch failed"; return FAV_ERR_HIP; }
+    return FAV_OK;
+}
+
+fav_status fav_op_last_route(char* out, size_t cap) {
+    if (!out || cap == 0) { g_create_error = "fav_op_last_route: null or empty buffer"; return FAV_ERR_INVALID_ARG; }
+    const std::string t = route_text(g_route);
+    if (t.size() + 1 > cap) {
+        out[0] = 0;
+        g_create_error = fmt("fav_op_last_route: the name needs %zu bytes, the buffer has %zu", t.size() + 1, cap);
+        return FAV_ERR_INVALID_ARG;
+    }
+    memcpy(out, t.c_str(), t.size() + 1);
     return FAV_OK;
 }
 
@@ -2042,6 +2117,7 @@ fav_status fav_op_corrupt_c(const uint8_t* frames, float* out, int32_t n, int32_
                             void* stream) {
     static_assert(sizeof(fav_corruption_desc) == 32, "fav_corruption_desc layout");
     const char* fn = "fav_op_corrupt_c";
+    route_clear();
     if (!frames || !out || !d) return corruption_rejected(fn, "null pointer");
     if (n < 1 || H < 1 || W < 1) return corruption_rejected(fn, "n, H and W must be at least 1");
     if (d->struct_size != sizeof(fav_corruption_desc)) return corruption_rejected(fn, "struct_size is not sizeof(fav_corruption_desc)");

@@ -309,6 +309,13 @@ typedef struct fav_dropout_desc {
     int64_t first_image_index;
 } fav_dropout_desc;
 
+/* Ranges of a convolution, checked before anything touches the device (FAV_ERR_INVALID_ARG, message "conv: ..."):
+ *   n_frames, H, W, kh, kw, stride   >= 1
+ *   pad                              >= 0, with H + 2*pad >= kh and W + 2*pad >= kw (the window fits the padded frame)
+ *   Cin, Cout                        multiples of 64, >= 64 (Cout 0 or negative would be an empty or a wrapped grid)
+ *   relu 0, 1 or 2; out_f32 0 or 1; math_mode a fav_math_mode
+ *   n_frames * Ho * Wo               <= 2^31 - 1
+ * kh != kw is supported (w is [Cout][kh][kw][Cin] as for a square window). */
 typedef struct fav_conv_desc {
     const void* x;           /* [n_frames][H][W][Cin] bf16, Cin % 64 == 0 */
     const void* w;           /* [Cout][kh][kw][Cin] bf16, Cout % 64 == 0 */
@@ -325,7 +332,8 @@ fav_status fav_op_conv2d(const fav_conv_desc* d, void* hip_stream);
  * input), conv_c 1x1 Cmid->4*Cmid + bias + residual + ReLU + dropout site -> y, and the NEXT block's conv_a
  * 1x1 4*Cmid->Nred + ReLU -> t1n (skipped when wa == NULL).  Same arithmetic, k order and rounding points as the
  * three fav_op_conv2d launches it replaces (bit-identical results); production math mode only.
- * Cmid in {64, 128}; Nred in {0, Cmid, 128}. */
+ * Cmid in {64, 128}; Nred in {0, Cmid, 128}.  n_frames, H and W >= 1, else FAV_ERR_INVALID_ARG ("bottleneck tail: ...")
+ * before anything touches the device. */
 typedef struct fav_tail_desc {
     const void* x;                          /* [n][H][W][Cmid] bf16 */
     const void* wb; const float* bias_b;    /* [Cmid][3][3][Cmid] bf16, [Cmid] */
@@ -342,6 +350,22 @@ typedef struct fav_tail_desc {
     int32_t res_entry, entry_site;
 } fav_tail_desc;
 fav_status fav_op_bottleneck_tail(const fav_tail_desc* d, void* hip_stream);
+/* Route report: the kernel instantiation that the calling thread's most recent fav_op_* launch took, as text in out
+ * (NUL-terminated; FAV_ERR_INVALID_ARG, a message of its own in fav_last_error(NULL) and an empty string if cap is too
+ * small - 64 bytes hold every name; the recorded route stays).  Empty after a refused call, after a fav_op_* whose launcher
+ * has one kernel only (pools, heads, LayerNorm, stream-K, corruptions, ...) and after any fav_classify*, served or refused.
+ * The launch site records an enum and a few ints; the text is made here.  Names, with the template arguments that tell
+ * instantiations apart:
+ *   conv_igemm<BM,BN,BK,NS,bf16|f32,epi0|epi1[,pp][,gelu]>   implicit-GEMM tile: rows x columns x K depth, ring stages, math
+ *                                                            mode, epilogue (0 staged through LDS, 1 in registers), ping-pong
+ *                                                            K loop, GELU compiled in
+ *   conv3x3_halo<CIN,BN,BM,NS,bf16|f32>                      staged-patch 3x3: channels in / out, pixels per tile, weight stages
+ *   proj<CIN,COUT,nwN>                                       row-owning projection shortcut, N waves
+ *   tail<CMID,NRED,3x3|1x1,nwN,wc1|wc2[,rp16][,res_entry]>   bottleneck tail: with / without conv_b, waves, Wc buffers, 16 rows
+ *                                                            per wave pass, residual recomputed from the cached entry tensor
+ *   attention<bf16|f32,NKT[,full]>                           key tiles compiled for (13 or 16); full: exactly 13, no masking
+ *   entry_reduce<C,NRED>     stem7_pool<u8|f32> */
+fav_status fav_op_last_route(char* out, size_t cap);
 /* frames (u8 or fp32 NHWC3) -> normalised bf16 im2col matrix [n*Ho*Wo][kpad].  n, H, W >= 1, a known layout and a window that
  * fits the padded frame, else FAV_ERR_INVALID_ARG and nothing is launched (the same holds for the pools and the entry ops below). */
 fav_status fav_op_stem_im2col(const void* images, int32_t layout, int32_t n, int32_t H, int32_t W,

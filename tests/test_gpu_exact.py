@@ -27,7 +27,7 @@ def lib():
     (64, 64, 1, 1, 0, 14, 14, 3), (64, 128, 3, 2, 1, 15, 15, 2), (128, 256, 3, 1, 1, 9, 9, 2),
     (512, 128, 1, 1, 0, 7, 7, 3), (192, 64, 1, 1, 0, 16, 16, 2), (256, 512, 1, 2, 0, 14, 14, 1),
     (64, 128, 3, 1, 1, 40, 44, 10),   # M=17600
-    (64, 256, 3, 1, 1, 40, 44, 10),   # M=17600, Cout 256 -> the 256x256 tile (8 waves)
+    (64, 256, 3, 1, 1, 40, 44, 10),   # M=17600, Cout 256: 68 big tiles, fewer than the 512 the 256x256 tile asks for -> 128-row tiles, BN 128
 ])
 def test_conv_exact_bitwise(lib, cin, cout, k, stride, pad, H, W, n):
     rng = np.random.default_rng(cin + cout + k)
@@ -68,8 +68,8 @@ def test_conv3x3_staged_patch_bitwise(lib, c, H, W, n, mode):
 @pytest.mark.parametrize("cin,cout,k,stride,pad,H,W,n,use_res", [
     (64, 64, 1, 1, 0, 14, 14, 3, False), (64, 128, 3, 2, 1, 15, 15, 2, True), (128, 256, 3, 1, 1, 9, 9, 2, False),
     (512, 128, 1, 1, 0, 7, 7, 3, True), (192, 64, 1, 1, 0, 16, 16, 2, False),
-    (128, 256, 3, 1, 1, 30, 30, 19, False),   # 256x256 tile, 64-deep steps
-    (512, 256, 1, 1, 0, 30, 30, 19, False),   # 256x256 tile on a 1x1
+    (128, 256, 3, 1, 1, 30, 30, 19, False),   # M=17100: 66 big tiles, below the 256x256 tile's 512 -> 128-row tiles, BN 128, 64-deep steps
+    (512, 256, 1, 1, 0, 30, 30, 19, False),   # likewise on a 1x1 with K=512 (the 256x256 tile against the oracle: test_gpu_conv_routes.py)
     (64, 64, 3, 1, 1, 56, 56, 2, True),       # 128x64 tile
 ])
 def test_conv_production_mode_bitwise(lib, cin, cout, k, stride, pad, H, W, n, use_res):
@@ -199,6 +199,9 @@ def test_resnet50_wide_frames_mix_fused_tails_and_fallbacks(r50_blob):
     assert np.array_equal(got, ref)
 
 
+STEM_POOL_ROUTES = ("stem7_pool<u8>", "stem7_pool<f32>")    # by frame layout (fav_op_last_route)
+
+
 @pytest.mark.parametrize("layout", [0, 1])
 @pytest.mark.parametrize("n,H,W", [(2, 224, 224), (3, 64, 80), (1, 33, 47), (1, 240, 320), (5, 9, 7)])
 def test_stem_pool_fused_bitwise(lib, layout, n, H, W):
@@ -225,6 +228,7 @@ def test_stem_pool_fused_bitwise(lib, layout, n, H, W):
     bd = torch.from_numpy(b).cuda()
     _lib.check(lib.fav_op_stem_pool(torch.from_numpy(img).cuda().data_ptr(), layout, n, H, W, wd.data_ptr(), bd.data_ptr(), m3, i3,
                                     out.data_ptr(), None))
+    assert _lib.last_route() == STEM_POOL_ROUTES[layout]
     torch.cuda.synchronize()
     got = out.to(torch.float32).cpu().numpy()
     assert np.array_equal(got, ref), f"{np.mean(got != ref):.5f} of elements differ"

@@ -66,10 +66,10 @@ CONV_CASES = [
     (512, 128, 1, 1, 0, 5, 5, 1, False),      # M=25: a single partial tile
     (192, 64, 1, 1, 0, 16, 16, 2, False),     # the stem GEMM shape (K=192)
     (64, 64, 3, 1, 1, 56, 56, 1, True),       # 25 tiles, tail tile of 64 rows
-    (64, 64, 3, 1, 1, 56, 56, 6, True),       # M=18816 -> 256-row tiles (8 waves), BN=64, ragged last tile
+    (64, 64, 3, 1, 1, 56, 56, 6, True),       # M=18816 = 147 whole 128-row tiles, BN=64 (Cout 64 never takes the 256-row tile; the residual keeps it off the staged-patch 3x3)
     (128, 128, 3, 2, 1, 57, 57, 21, True),    # M=17661, stride 2, odd size
-    (128, 256, 3, 1, 1, 30, 30, 19, False),   # M=17100, Cout 256, no residual -> the 256x256 tile (8 waves)
-    (512, 256, 1, 1, 0, 30, 30, 19, False),   # 1x1 with K=512 on the 256x256 tile
+    (128, 256, 3, 1, 1, 30, 30, 19, False),   # M=17100, Cout 256, no residual: 66 big tiles, below the 512 the 256x256 tile asks for -> 128-row tiles, BN 128, 64-deep
+    (512, 256, 1, 1, 0, 30, 30, 19, False),   # 1x1 with K=512: likewise 128-row tiles (the 256x256 tile: test_gpu_conv_routes.py)
 ]
 
 
@@ -207,6 +207,9 @@ def test_entry_dropout_exact(lib):
     assert np.array_equal(host_f32(out), ref)
 
 
+ENTRY_REDUCE_ROUTE = "entry_reduce<256,64>"     # the one instantiation (fav_op_last_route)
+
+
 @pytest.mark.parametrize("n_img,H,W,v0,n_out", [(3, 7, 9, 2, 7),        # partial first and last sample, tiles span frames
                                                  (5, 14, 14, 0, 15),     # three whole samples, ragged last tile (M = 980)
                                                  (2, 56, 56, 1, 2),      # layer-1 frames, window inside the samples
@@ -230,6 +233,7 @@ def test_entry_reduce_bitwise_vs_separate_launches_and_oracle(lib, n_img, H, W, 
     tbig = torch.full((n_out * HW * nred + 2 * guard,), 3.0, dtype=torch.bfloat16, device="cuda")
     _lib.check(lib.fav_op_entry_reduce(xd.data_ptr(), ybig.data_ptr() + 2 * guard, wd.data_ptr(), bd.data_ptr(), tbig.data_ptr() + 2 * guard,
                                        Cc, nred, HW, n_out, C.byref(d), None))
+    assert _lib.last_route() == ENTRY_REDUCE_ROUTE
     torch.cuda.synchronize()
     for big in (ybig, tbig):
         assert bool((big[:guard] == 3.0).all()) and bool((big[-guard:] == 3.0).all())
@@ -257,6 +261,7 @@ def test_entry_reduce_rejects_unsupported_shapes(lib):
     x = torch.zeros(4096, dtype=torch.bfloat16, device="cuda")
     d = drop_desc(1, 26, 1.1, 7, 0, 1, 0)
     assert lib.fav_op_entry_reduce(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), 128, 64, 4, 1, C.byref(d), None) == 1
+    assert _lib.last_route() == ""
 
 
 @pytest.mark.parametrize("T,n,Cc,ld", [(1, 5, 1000, 1024), (30, 9, 1000, 1024), (3, 4, 10, 64), (7, 3, 257, 320)])
@@ -295,9 +300,10 @@ def test_head_tie_breaks_to_lowest_index(lib):
     assert labels.cpu().tolist() == [7, 0]
 
 
-# Launches large enough for the 256 x 256 ping-pong tile against the SAME operation on 32-frame slices, which take the 128-row tiles:
-# every tile kernel implements one k order, so the bits must agree whatever the tile and the grid - a size-independent property at a
-# size no CPU oracle reaches (and the check any other schedule of that tile has to pass: tools/experiments/r4_persistent_big_tile.diff).
+# Launches large enough for the 256 x 256 tile against the SAME operation on 32-frame slices, which take the 128-row tiles (both
+# asserted by name, fav_op_last_route): every tile kernel implements one k order, so the bits must agree whatever the tile and the
+# grid - a size-independent property at a size no CPU oracle reaches (and the check any other schedule of that tile has to pass:
+# tools/experiments/r4_persistent_big_tile.diff).  The first and the last frame are also compared with the oracle.
 BIG_TILE_CASES = [
     # cin, cout, k, H, W, frames, residual, relu, dropout
     (512, 512, 1, 14, 14, 1024, True, 1, True),
@@ -308,8 +314,7 @@ BIG_TILE_CASES = [
 ]
 
 
-@pytest.mark.parametrize("cin,cout,k,H,W,n,use_res,relu,use_drop", BIG_TILE_CASES)
-def test_big_tile_matches_sliced_launches(lib, cin, cout, k, H, W, n, use_res, relu, use_drop):
+def big_tile_against_slices_and_oracle(lib, cin, cout, k, H, W, n, use_res, relu, use_drop, mode):
     g = torch.Generator(device="cuda").manual_seed(cin + cout + k + n)
     pad = k // 2
     x = (torch.randn((n, H, W, cin), device="cuda", generator=g) * 0.7).to(torch.bfloat16)
@@ -318,17 +323,44 @@ def test_big_tile_matches_sliced_launches(lib, cin, cout, k, H, W, n, use_res, r
     res = torch.randn((n, H, W, cout), device="cuda", generator=g).to(torch.bfloat16) if use_res else None
     y = torch.zeros((n, H, W, cout), dtype=torch.bfloat16, device="cuda")
     y2 = torch.zeros_like(y)
+    thr, site, seed, first = 26, 3, 77, 5
+    scale = 1.0 / (1 - thr / 256)
 
     def launch(lo, hi, out):
-        dd = drop_desc(3, 26, 1.0 / (1 - 26 / 256), 77, lo, n, 5) if use_drop else drop_desc()
+        dd = drop_desc(site, thr, scale, seed, lo, n, first) if use_drop else drop_desc()
         d = _lib.FavConvDesc(x[lo:hi].data_ptr(), w.data_ptr(), b.data_ptr(), res[lo:hi].data_ptr() if use_res else None,
-                             out[lo:hi].data_ptr(), hi - lo, H, W, cin, cout, k, k, 1, pad, relu, 0, 0, dd)
+                             out[lo:hi].data_ptr(), hi - lo, H, W, cin, cout, k, k, 1, pad, relu, 0, mode, dd)
         _lib.check(lib.fav_op_conv2d(C.byref(d), None))
+        return _lib.last_route()
 
-    launch(0, n, y)
+    big = "conv_igemm<256,256,64,2," + ("bf16,epi1,pp" if mode == 0 else "f32,epi1") + (",gelu" if relu == 2 else "") + ">"
+    assert launch(0, n, y) == big
     for lo in range(0, n, 32):
-        launch(lo, min(n, lo + 32), y2)
+        assert launch(lo, min(n, lo + 32), y2).startswith("conv_igemm<128,128,")
     torch.cuda.synchronize()
     assert torch.equal(y.view(torch.int16), y2.view(torch.int16)), \
         f"{(y.view(torch.int16) != y2.view(torch.int16)).float().mean().item():.6f} of elements differ"
     assert y.float().abs().sum().item() > 0
+    # the first and the last frame against the oracle (row v of the launch is virtual frame v: sample 0 of frame first + v)
+    ends = [0, n - 1]
+    xs, ws, bs = x[ends].float().cpu().numpy(), w.float().cpu().numpy(), b.cpu().numpy()
+    rs = res[ends].float().cpu().numpy() if use_res else None
+    acc = O.conv_acc_exact(xs, ws, k, k, 1, pad, mode="mfma" if mode == 0 else True)
+    if relu == 2:
+        exp = O.bf16_round(O.gelu_exact(acc + bs))
+    else:
+        keep = np.stack([O.dropout_keep(seed, 0, site, np.array([first + v]), H * W * cout, thr)[0] for v in ends]) if use_drop else None
+        exp = O.epilogue(acc, bs, res=rs, relu=bool(relu), keep=keep, scale=np.float32(scale))
+    got = y[ends].float().cpu().numpy()
+    assert np.array_equal(got, exp), f"{np.mean(got != exp):.6f} of the first and last frames differ from the oracle"
+
+
+@pytest.mark.parametrize("cin,cout,k,H,W,n,use_res,relu,use_drop", BIG_TILE_CASES)
+def test_big_tile_matches_sliced_launches(lib, cin, cout, k, H, W, n, use_res, relu, use_drop):
+    big_tile_against_slices_and_oracle(lib, cin, cout, k, H, W, n, use_res, relu, use_drop, mode=0)
+
+
+@pytest.mark.parametrize("cin,cout,k,H,W,n,use_res,relu,use_drop", BIG_TILE_CASES)
+def test_big_tile_matches_sliced_launches_f32_exact(lib, cin, cout, k, H, W, n, use_res, relu, use_drop):
+    """The FAV_MATH_F32_EXACT instantiation of the 256 x 256 tile - what validation mode runs at large batches."""
+    big_tile_against_slices_and_oracle(lib, cin, cout, k, H, W, n, use_res, relu, use_drop, mode=1)

@@ -359,7 +359,7 @@ def test_entry_reduce_edge_descriptors(lib, desc):
     assert np.array_equal(got.view(np.uint32), run_entry_dropout(lib, x, desc).view(np.uint32))
 
 
-TAIL_CASE = min(TAIL_CASES, key=lambda c: c[3] * c[4] * c[5])            # (cmid, nred, has3x3, H, W, n): the fewest rows
+TAIL_CASE = min(TAIL_CASES, key=lambda c: c[3] * c[4] * c[5])[:6]        # (cmid, nred, has3x3, H, W, n): the fewest rows
 
 
 @pytest.mark.parametrize("desc", R.EDGE_DESCRIPTORS, ids=R.EDGE_IDS)

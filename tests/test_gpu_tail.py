@@ -43,30 +43,39 @@ def run_tail(lib, x, wb, bb, wc, bc, res, wa, ba, drop=None):
 
 
 CASES = [
-    # cmid, nred, has3x3, H, W, n
-    (64, 64, True, 56, 56, 2),      # layer 1 inner boundary; M = 6272 = 49 tiles
-    (64, 128, True, 56, 56, 1),     # layer 1 -> layer 2 (the next block reduces to 128)
-    (64, 0, True, 20, 12, 3),       # no next block; ragged last tile (M = 720)
-    (64, 64, True, 7, 9, 37),       # frames much smaller than a tile; M = 2331 (ragged)
-    (64, 64, True, 60, 80, 1),      # the 240x320 seam at layer 1 (H != W)
-    (128, 128, True, 28, 28, 3),    # layer 2 inner boundary
-    (128, 0, True, 28, 28, 2),      # last block of the high-resolution group
-    (128, 128, False, 28, 28, 3),   # the stride-2 block: its 3x3 stays a separate launch
-    (64, 64, False, 14, 10, 5),
-    (128, 128, True, 9, 11, 7),
-    (256, 0, False, 14, 14, 11),    # layer 3's expanding 1x1 alone (wide tail: weight buffers reuse the T2 region); M = 2156
-    (256, 0, False, 7, 9, 3),
-    (256, 256, False, 14, 14, 11),  # layer 3 inner boundary: expand + the next block's reduce, 8 waves x 16 rows
-    (256, 256, False, 5, 7, 9),
-    (512, 0, False, 7, 7, 45),      # layer 4's expanding 1x1 alone (single Wc buffer of 64 KB); M = 2205 (ragged)
-    (512, 0, False, 8, 10, 3),
-    (256, 0, True, 14, 14, 11),     # layer 3: conv_b as the generic 256x256x64 loop + conv_c in one launch; M = 2156 (ragged)
-    (256, 0, True, 7, 9, 5),        # frames much smaller than a tile
-    (256, 0, True, 15, 20, 2),      # the 240x320 seam at layer 3 (H != W)
+    # cmid, nred, has3x3, H, W, n, the kernel it must take (fav_op_last_route: wc2 / wc1 = Wc double- / single-buffered,
+    # as the LDS budget of tail_geometry allows at this W)
+    (64, 64, True, 56, 56, 2, "tail<64,64,3x3,nw4,wc2>"),      # layer 1 inner boundary; M = 6272 = 49 tiles
+    (64, 128, True, 56, 56, 1, "tail<64,128,3x3,nw4,wc1>"),    # layer 1 -> layer 2 (the next block reduces to 128)
+    (64, 0, True, 20, 12, 3, "tail<64,0,3x3,nw4,wc2>"),        # no next block; ragged last tile (M = 720)
+    (64, 64, True, 7, 9, 37, "tail<64,64,3x3,nw4,wc2>"),       # frames much smaller than a tile; M = 2331 (ragged)
+    (64, 64, True, 60, 80, 1, "tail<64,64,3x3,nw4,wc2>"),      # the 240x320 seam at layer 1 (H != W)
+    (128, 128, True, 28, 28, 3, "tail<128,128,3x3,nw8,wc2>"),  # layer 2 inner boundary
+    (128, 0, True, 28, 28, 2, "tail<128,0,3x3,nw8,wc2>"),      # last block of the high-resolution group
+    (128, 128, False, 28, 28, 3, "tail<128,128,1x1,nw8,wc2>"),  # the stride-2 block: its 3x3 stays a separate launch
+    (64, 64, False, 14, 10, 5, "tail<64,64,1x1,nw4,wc2>"),
+    (128, 128, True, 9, 11, 7, "tail<128,128,3x3,nw8,wc2>"),
+    (256, 0, False, 14, 14, 11, "tail<256,0,1x1,nw4,wc2>"),    # layer 3's expanding 1x1 alone (wide tail: weight buffers reuse the T2 region); M = 2156
+    (256, 0, False, 7, 9, 3, "tail<256,0,1x1,nw4,wc2>"),
+    (256, 256, False, 14, 14, 11, "tail<256,256,1x1,nw8,wc2,rp16>"),  # layer 3 inner boundary: expand + the next block's reduce, 8 waves x 16 rows
+    (256, 256, False, 5, 7, 9, "tail<256,256,1x1,nw8,wc2,rp16>"),
+    (512, 0, False, 7, 7, 45, "tail<512,0,1x1,nw8,wc2>"),      # layer 4's expanding 1x1 alone (Wc double-buffered, 2 x 64 KB); M = 2205 (ragged)
+    (512, 0, False, 8, 10, 3, "tail<512,0,1x1,nw8,wc2>"),
+    (256, 0, True, 14, 14, 11, "tail<256,0,3x3,nw8,wc2>"),     # layer 3: conv_b as the generic 256x256x64 loop + conv_c in one launch; M = 2156 (ragged)
+    (256, 0, True, 7, 9, 5, "tail<256,0,3x3,nw8,wc2>"),        # frames much smaller than a tile
+    (256, 0, True, 15, 20, 2, "tail<256,0,3x3,nw8,wc2>"),      # the 240x320 seam at layer 3 (H != W)
+    # the arms and Wc plans no case above takes
+    (64, 0, False, 14, 10, 3, "tail<64,0,1x1,nw4,wc2>"),
+    (64, 128, False, 14, 10, 3, "tail<64,128,1x1,nw4,wc2>"),
+    (128, 0, False, 9, 11, 3, "tail<128,0,1x1,nw8,wc2>"),
+    (64, 128, True, 12, 20, 3, "tail<64,128,3x3,nw4,wc2>"),    # a patch narrow enough for two Wc buffers beside the 128-wide reduce
+    (64, 64, True, 3, 120, 2, "tail<64,64,3x3,nw4,wc1>"),      # W 116..147: the patch leaves room for one Wc buffer
+    (128, 128, True, 5, 60, 2, "tail<128,128,3x3,nw8,wc1>"),   # W 56..87: likewise at 128 mid channels
 ]
+ROUTE_OF = {c[:6]: c[6] for c in CASES}
 
 
-@pytest.mark.parametrize("cmid,nred,has3x3,H,W,n", CASES)
+@pytest.mark.parametrize("cmid,nred,has3x3,H,W,n", [c[:6] for c in CASES])
 @pytest.mark.parametrize("with_drop", [False, True])
 def test_tail_bitwise_vs_separate_launches_and_oracle(lib, cmid, nred, has3x3, H, W, n, with_drop):
     rng = np.random.default_rng(cmid * 31 + nred * 7 + H * W + n + int(has3x3))
@@ -86,6 +95,7 @@ def test_tail_bitwise_vs_separate_launches_and_oracle(lib, cmid, nred, has3x3, H
     y_ref = run_conv(lib, t2, wc, bc, res, 1, 0, relu=1, drop=dd)
     t1n_ref = run_conv(lib, y_ref, wa, ba, None, 1, 0, relu=1) if nred else None
     y, t1n = run_tail(lib, x, wb, bb, wc, bc, res, wa, ba, drop=dd)
+    assert _lib.last_route() == ROUTE_OF[(cmid, nred, has3x3, H, W, n)]
     assert np.array_equal(y, y_ref), f"Y: {np.mean(y != y_ref):.5f} of elements differ from the separate launches"
     if nred:
         assert np.array_equal(t1n, t1n_ref), f"t1': {np.mean(t1n != t1n_ref):.5f} of elements differ"
@@ -125,6 +135,9 @@ def test_projection_shortcut_on_the_row_owning_kernel(lib, stride, H, W, n):
     assert np.array_equal(got, ref), f"{np.mean(got != ref):.5f} of elements differ"
 
 
+WIDE_PROJ_ROUTE = "proj<512,1024,nw8>"
+
+
 @pytest.mark.parametrize("stride,H,W,n", [(2, 28, 28, 672), (1, 14, 14, 700)])
 def test_wide_projection_shortcut_on_the_row_owning_kernel(lib, stride, H, W, n):
     """1x1 / stride s, 512 -> 1024 (layer 3's projection shortcut) takes the 8-wave row-owning kernel once the launch
@@ -142,6 +155,7 @@ def test_wide_projection_shortcut_on_the_row_owning_kernel(lib, stride, H, W, n)
     for out, f32 in ((y, 0), (yf, 1)):
         d = _lib.FavConvDesc(x.data_ptr(), w.data_ptr(), b.data_ptr(), None, out.data_ptr(), n, H, W, 512, 1024, 1, 1, stride, 0, 0, f32, 0, drop_desc())
         _lib.check(lib.fav_op_conv2d(C.byref(d), None))
+        assert _lib.last_route() == (WIDE_PROJ_ROUTE if not f32 else "conv_igemm<256,256,64,2,bf16,epi1,pp>")
     torch.cuda.synchronize()
     assert torch.equal(y, yf.to(torch.bfloat16)), "row-owning kernel differs from the generic kernel"
     for sl in (slice(0, 3), slice(n - 3, n)):
@@ -150,8 +164,17 @@ def test_wide_projection_shortcut_on_the_row_owning_kernel(lib, stride, H, W, n)
         assert np.array_equal(y[sl].float().cpu().numpy(), ref)
 
 
-@pytest.mark.parametrize("H,W,n_img,v0,n_out", [(56, 56, 3, 0, 9), (20, 12, 4, 2, 9), (7, 9, 5, 13, 37), (60, 80, 2, 1, 3),
-                                                (16, 16, 2, 4, 6), (8, 16, 3, 0, 6), (56, 56, 4, 0, 12)])   # whole samples of whole tiles: sample-minor tile order
+RES_ENTRY_CASES = [   # H, W, n_img, v0, n_out, the kernel it must take
+    (56, 56, 3, 0, 9, "tail<64,64,3x3,nw4,wc2,res_entry>"), (20, 12, 4, 2, 9, "tail<64,64,3x3,nw4,wc2,res_entry>"),
+    (7, 9, 5, 13, 37, "tail<64,64,3x3,nw4,wc2,res_entry>"), (60, 80, 2, 1, 3, "tail<64,64,3x3,nw4,wc2,res_entry>"),
+    (16, 16, 2, 4, 6, "tail<64,64,3x3,nw4,wc2,res_entry>"), (8, 16, 3, 0, 6, "tail<64,64,3x3,nw4,wc2,res_entry>"),
+    (56, 56, 4, 0, 12, "tail<64,64,3x3,nw4,wc2,res_entry>"),   # whole samples of whole tiles: sample-minor tile order
+    (3, 120, 2, 1, 5, "tail<64,64,3x3,nw4,wc1,res_entry>"),    # W 116..147: a single Wc buffer
+]
+RES_ENTRY_ROUTE_OF = {c[:5]: c[5] for c in RES_ENTRY_CASES}
+
+
+@pytest.mark.parametrize("H,W,n_img,v0,n_out", [c[:5] for c in RES_ENTRY_CASES])
 def test_tail_entry_residual_recomputes_the_dropped_copies(lib, H, W, n_img, v0, n_out):
     """res_entry: the tail behind the entry dropout of an MC-Dropout suffix takes its residual from the CACHED prefix
     output x0 [n_img] - virtual frame v reads frame v % n_img and applies the entry site's mask in the epilogue - and gives
@@ -193,6 +216,7 @@ def test_tail_entry_residual_recomputes_the_dropped_copies(lib, H, W, n_img, v0,
                          x0d.data_ptr(), y.data_ptr(), keep[5].data_ptr(), keep[6].data_ptr(), t1n.data_ptr(),
                          n_out, H, W, cmid, nred, do, 1, site_e)
     _lib.check(lib.fav_op_bottleneck_tail(C.byref(d), None))
+    assert _lib.last_route() == RES_ENTRY_ROUTE_OF[(H, W, n_img, v0, n_out)]
     torch.cuda.synchronize()
     assert np.array_equal(host_f32(y), y_ref), f"Y: {np.mean(host_f32(y) != y_ref):.5f} of elements differ"
     assert np.array_equal(host_f32(t1n), t1n_ref)
@@ -207,3 +231,4 @@ def test_tail_entry_residual_recomputes_the_dropped_copies(lib, H, W, n_img, v0,
                            x0d.data_ptr(), y.data_ptr(), keep[5].data_ptr(), keep[6].data_ptr(), t1n.data_ptr(),
                            n_out, H, W, cmid, nred, drop_desc(), 1, site_e)
     assert lib.fav_op_bottleneck_tail(C.byref(bad), None) != 0
+    assert _lib.last_route() == ""

@@ -156,7 +156,23 @@ def attention_violation(out, qkv, heads, scale=0.125):
     return float(((out.double() - ref).abs() / (ATTN_C * mass + ATTN_TINY)).max())
 
 
-@pytest.mark.parametrize("T,heads", [(1, 1), (16, 2), (17, 3), (32, 1), (33, 2), (196, 4), (197, 12), (208, 2), (224, 3), (256, 12)])
+ATTENTION_CASES = [(1, 1), (16, 2), (17, 3), (32, 1), (33, 2), (196, 4), (197, 12), (208, 2), (224, 3), (256, 12)]   # T, heads
+# the instantiation each T must take (fav_op_last_route), production mode and validation mode: the kernel compiled for 13 key
+# tiles of 16 up to 208 tokens - without masking when there are exactly 13 (T 193..208) - and the one for 16 above
+ATTENTION_ROUTES = {
+    1: ("attention<bf16,13>", "attention<f32,13>"), 16: ("attention<bf16,13>", "attention<f32,13>"),
+    17: ("attention<bf16,13>", "attention<f32,13>"), 32: ("attention<bf16,13>", "attention<f32,13>"),
+    33: ("attention<bf16,13>", "attention<f32,13>"), 196: ("attention<bf16,13,full>", "attention<f32,13>"),
+    197: ("attention<bf16,13,full>", "attention<f32,13>"), 208: ("attention<bf16,13,full>", "attention<f32,13>"),
+    224: ("attention<bf16,16>", "attention<f32,16>"), 256: ("attention<bf16,16>", "attention<f32,16>"),
+}
+
+
+def attention_route(T, mode):
+    return ATTENTION_ROUTES[T][mode]
+
+
+@pytest.mark.parametrize("T,heads", ATTENTION_CASES)
 @pytest.mark.parametrize("mode", [0, 1])
 def test_attention_vs_float64(lib, T, heads, mode):
     n = 7
@@ -171,6 +187,7 @@ def test_attention_vs_float64(lib, T, heads, mode):
     obig = torch.full((rows * D + 2 * OUT_GUARD,), OUT_GUARD_VALUE, dtype=torch.bfloat16, device="cuda")
     _lib.check(lib.fav_op_attention(big.data_ptr() + ATTN_GUARD * 3 * D * 2, obig.data_ptr() + OUT_GUARD * 2, n, T, D, heads,
                                     mode, None))
+    assert _lib.last_route() == attention_route(T, mode)
     tight_in = qkv.to(torch.bfloat16).contiguous()
     tight = torch.empty((n, T, D), dtype=torch.bfloat16, device="cuda")
     _lib.check(lib.fav_op_attention(tight_in.data_ptr(), tight.data_ptr(), n, T, D, heads, mode, None))
