@@ -148,6 +148,9 @@ _SIGNATURES = {
     "fav_op_conv2d": (C.c_int, [C.POINTER(FavConvDesc), C.c_void_p]),
     "fav_op_bottleneck_tail": (C.c_int, [C.POINTER(FavTailDesc), C.c_void_p]),
     "fav_op_last_route": (C.c_int, [C.c_char_p, C.c_size_t]),
+    "fav_route_conv2d": (C.c_int, [C.POINTER(FavConvDesc), C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    "fav_route_bottleneck_tail": (C.c_int, [C.POINTER(FavTailDesc), C.c_int32, C.c_char_p, C.c_size_t]),
+    "fav_route_attention": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
     "fav_op_linear_streamk": (C.c_int, [C.POINTER(FavLinearDesc), C.c_void_p]),
     "fav_op_stem_im2col": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -208,6 +211,28 @@ def last_route() -> str:
     buf = C.create_string_buffer(96)
     check(load().fav_op_last_route(buf, len(buf)))
     return buf.value.decode("ascii")
+
+
+def _route_query(fn, *args):
+    """(status, text) of a fav_route_*: the route name with FAV_OK, the refusal text with FAV_ERR_INVALID_ARG."""
+    buf = C.create_string_buffer(160)
+    status = fn(*args, buf, len(buf))
+    return status, buf.value.decode("ascii")
+
+
+def route_conv2d(desc: FavConvDesc, vit: int = 0, groups: int = 1):
+    """fav_route_conv2d: the kernel fav_op_conv2d would take for this descriptor; no device, nothing launched."""
+    return _route_query(load().fav_route_conv2d, C.byref(desc), vit, groups)
+
+
+def route_bottleneck_tail(desc: FavTailDesc, groups: int = 1):
+    """fav_route_bottleneck_tail: likewise for fav_op_bottleneck_tail."""
+    return _route_query(load().fav_route_bottleneck_tail, C.byref(desc), groups)
+
+
+def route_attention(n: int, T: int, D: int, heads: int, math_mode: int = 0):
+    """fav_route_attention: likewise for fav_op_attention."""
+    return _route_query(load().fav_route_attention, n, T, D, heads, math_mode)
 
 
 class FavError(RuntimeError):

@@ -14,7 +14,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,60 +24,30 @@
 #include "fav_kernels.hpp"
 #include "fav_corrupt_c.hpp"
 #include "fav_plan.hpp"
+#include "fav_route.hpp"
 
-using namespace fav_plan;   // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
+using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
+using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
 
 namespace {
 
 thread_local std::string g_create_error;
 
-std::string fmt(const char* f, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(buf, sizeof buf, f, ap);
-    va_end(ap);
-    return buf;
-}
+// ---- route report (fav_op_last_route, fav.h): which kernel instantiation the calling thread's last launch took.  A launcher
+//      stores the Route it launches from (fav_route.hpp); text is formatted only when somebody asks.
+thread_local Route g_route;
 
-// ---- route report (fav_op_last_route, fav.h): which kernel instantiation the calling thread's last launch took.  The launch
-//      site stores an enum and a few ints; text is formatted only when somebody asks.
-enum RouteKind { ROUTE_NONE = 0, ROUTE_CONV_IGEMM, ROUTE_CONV_HALO, ROUTE_PROJ, ROUTE_TAIL, ROUTE_ATTENTION, ROUTE_ENTRY_REDUCE, ROUTE_STEM_POOL };
-struct Route { int kind; int a[8]; bool fresh; };   // fresh: recorded since the last fav_op_* returned
-thread_local Route g_route = {ROUTE_NONE, {0, 0, 0, 0, 0, 0, 0, 0}, false};
-
-inline void route_set(int kind, int a0 = 0, int a1 = 0, int a2 = 0, int a3 = 0, int a4 = 0, int a5 = 0, int a6 = 0, int a7 = 0) {
-    g_route = Route{kind, {a0, a1, a2, a3, a4, a5, a6, a7}, true};
+// the launchers with one kernel and no selector (entry reduce, fused stem)
+inline void route_set(int kind, int a0 = 0, int a1 = 0) {
+    Route r;
+    r.kind = kind; r.a[0] = a0; r.a[1] = a1;
+    g_route = r;
 }
 inline void route_clear() { g_route.kind = ROUTE_NONE; g_route.fresh = false; }
 // at the end of a fav_op_*: a refusal, or a launch through a launcher that records nothing, leaves no route behind
 inline void route_close(bool ok) {
     if (!ok || !g_route.fresh) g_route.kind = ROUTE_NONE;
     g_route.fresh = false;
-}
-
-std::string route_text(const Route& r) {
-    const int* a = r.a;
-    const char* mode = a[4] ? "f32" : "bf16";
-    switch (r.kind) {
-    case ROUTE_CONV_IGEMM:    // BM, BN, BK, NS, MODE, EPI, PP, GELU
-        return fmt("conv_igemm<%d,%d,%d,%d,%s,epi%d%s%s>", a[0], a[1], a[2], a[3], mode, a[5], a[6] ? ",pp" : "", a[7] ? ",gelu" : "");
-    case ROUTE_CONV_HALO:     // CIN, BN, BM, NS, MODE (a[4])
-        return fmt("conv3x3_halo<%d,%d,%d,%d,%s>", a[0], a[1], a[2], a[3], mode);
-    case ROUTE_PROJ:          // CIN, COUT, NW
-        return fmt("proj<%d,%d,nw%d>", a[0], a[1], a[2]);
-    case ROUTE_TAIL:          // CMID, NRED, HAS3X3, NW, WC2, RP, RESE
-        return fmt("tail<%d,%d,%s,nw%d,wc%d%s%s>", a[0], a[1], a[2] ? "3x3" : "1x1", a[3], a[4] ? 2 : 1, a[5] == 16 ? ",rp16" : "",
-                   a[6] ? ",res_entry" : "");
-    case ROUTE_ATTENTION:     // MODE, NKT, FULL
-        return fmt("attention<%s,%d%s>", a[0] ? "f32" : "bf16", a[1], a[2] ? ",full" : "");
-    case ROUTE_ENTRY_REDUCE:  // C, NRED
-        return fmt("entry_reduce<%d,%d>", a[0], a[1]);
-    case ROUTE_STEM_POOL:     // LAYOUT
-        return fmt("stem7_pool<%s>", a[0] ? "f32" : "u8");
-    default:
-        return std::string();
-    }
 }
 
 // inside a fork/join region: remember the first failure but keep going, so that every forked stream is joined
@@ -252,167 +221,138 @@ DropParams make_drop(const fav_dropout_desc* d) {
     return p;
 }
 
-// The one validation of a dropout descriptor (the ranges beside fav_dropout_desc in fav.h), for a launch whose rows are the
-// virtual frames [v0, v0 + rows): what is wrong with it, prefixed with the op's name, or nullptr.  A descriptor without a
-// site (NULL, site < 0) is not read any further.  The kernels hold v, the sample v / n_img and the fastdiv operand in 32 bits
-// (fastdiv is exact below 2^31 only), the draw is 8 bits wide, and scale multiplies every kept value.
-const char* check_drop(const char* who, const fav_dropout_desc* d, long long rows) {
-    if (!d || d->site < 0) return nullptr;
-    const char* why = nullptr;
-    if (d->threshold > 255u) why = "dropout threshold above 255 (the draw is 8 bits wide: everything would be dropped)";
-    else if (!std::isfinite(d->scale) || !(d->scale > 0.f)) why = "dropout scale must be finite and > 0";
-    else if (d->n_img < 1) why = "dropout n_img must be >= 1";
-    else if (d->v0 < 0 || d->v0 + rows > 0x7fffffffLL) why = "virtual frame index out of range";
-    if (!why) return nullptr;
-    thread_local std::string msg;
-    msg = std::string(who) + ": " + why;
-    return msg.c_str();
+// ---- kernel tables: one per kernel family, from a Route's kind and template arguments to the instantiation (all of a family
+//      share one signature).  They name every instantiation the build contains, those only an experiment knob reaches too.
+template <class Fn> struct KernelEntry { int kind; int a[8]; Fn fn; mutable DeviceFlags lds_set; };   // lds_set: see find_kernel
+using ConvKernel = void (*)(const ConvParams);
+using HaloKernel = void (*)(const ConvParams, int);
+using TailKernel = void (*)(const TailParams, int);
+using AttnKernel = void (*)(const uint16_t*, uint16_t*, int, int, int);
+
+template <int BM, int BN, int BK, int NS, int MODE, int EPI, int PP = 0, bool GELU = false>
+KernelEntry<ConvKernel> igemm() { return {ROUTE_CONV_IGEMM, {BM, BN, BK, NS, MODE, EPI, PP, GELU}, conv_igemm_kernel<BM, BN, BK, NS, MODE, 2, 0, EPI, PP, GELU>}; }
+template <int CIN, int BN, int BM, int NS, int SUB, int OCC, int MODE>
+KernelEntry<HaloKernel> halo() { return {ROUTE_CONV_HALO, {CIN, BN, BM, NS, MODE}, conv3x3_halo_kernel<CIN, BN, BM, NS, SUB, OCC, MODE>}; }
+template <int CMID, int NRED, bool H3, int NS, int NW, bool WC2, int RP = 32, bool RESE = false>
+KernelEntry<TailKernel> tail() { return {ROUTE_TAIL, {CMID, NRED, H3, NW, WC2, RP, RESE}, bottleneck_tail_kernel<CMID, NRED, H3, NS, NW, WC2, RP, 0, true, true, RESE>}; }
+template <int MODE, int NKT, bool FULL = false>
+KernelEntry<AttnKernel> attn() { return {ROUTE_ATTENTION, {MODE, NKT, FULL}, attention_kernel<MODE, NKT, FULL>}; }
+
+// 128-row tiles: BN 64 | 128, 32-deep steps in a three-stage ring or 64-deep in two, both math modes, both epilogues, with and
+// without the GELU; 256 x 256 x 64: the ping-pong loop in the production mode, the plain one in both (FAV_CONV_PP, FAV_CONV_EPI)
+const KernelEntry<ConvKernel> kConvKernels[] = {
+    igemm<128, 64, 32, 3, 0, 0>(), igemm<128, 64, 32, 3, 0, 1>(), igemm<128, 64, 32, 3, 0, 0, 0, true>(), igemm<128, 64, 32, 3, 0, 1, 0, true>(),
+    igemm<128, 64, 32, 3, 1, 0>(), igemm<128, 64, 32, 3, 1, 1>(), igemm<128, 64, 32, 3, 1, 0, 0, true>(), igemm<128, 64, 32, 3, 1, 1, 0, true>(),
+    igemm<128, 64, 64, 2, 0, 0>(), igemm<128, 64, 64, 2, 0, 1>(), igemm<128, 64, 64, 2, 0, 0, 0, true>(), igemm<128, 64, 64, 2, 0, 1, 0, true>(),
+    igemm<128, 64, 64, 2, 1, 0>(), igemm<128, 64, 64, 2, 1, 1>(), igemm<128, 64, 64, 2, 1, 0, 0, true>(), igemm<128, 64, 64, 2, 1, 1, 0, true>(),
+    igemm<128, 128, 32, 3, 0, 0>(), igemm<128, 128, 32, 3, 0, 1>(), igemm<128, 128, 32, 3, 0, 0, 0, true>(), igemm<128, 128, 32, 3, 0, 1, 0, true>(),
+    igemm<128, 128, 32, 3, 1, 0>(), igemm<128, 128, 32, 3, 1, 1>(), igemm<128, 128, 32, 3, 1, 0, 0, true>(), igemm<128, 128, 32, 3, 1, 1, 0, true>(),
+    igemm<128, 128, 64, 2, 0, 0>(), igemm<128, 128, 64, 2, 0, 1>(), igemm<128, 128, 64, 2, 0, 0, 0, true>(), igemm<128, 128, 64, 2, 0, 1, 0, true>(),
+    igemm<128, 128, 64, 2, 1, 0>(), igemm<128, 128, 64, 2, 1, 1>(), igemm<128, 128, 64, 2, 1, 0, 0, true>(), igemm<128, 128, 64, 2, 1, 1, 0, true>(),
+    igemm<256, 256, 64, 2, 0, 1, 1>(), igemm<256, 256, 64, 2, 0, 1, 1, true>(),
+    igemm<256, 256, 64, 2, 0, 0>(), igemm<256, 256, 64, 2, 0, 1>(), igemm<256, 256, 64, 2, 0, 0, 0, true>(), igemm<256, 256, 64, 2, 0, 1, 0, true>(),
+    igemm<256, 256, 64, 2, 1, 0>(), igemm<256, 256, 64, 2, 1, 1>(), igemm<256, 256, 64, 2, 1, 0, 0, true>(), igemm<256, 256, 64, 2, 1, 1, 0, true>(),
+};
+// 256-pixel tiles; the 128-pixel ones are FAV_HALO_CFG=0's
+const KernelEntry<HaloKernel> kHaloKernels[] = {
+    halo<64, 64, 256, 3, 1, 4, 0>(), halo<64, 64, 256, 3, 1, 4, 1>(), halo<128, 128, 256, 2, 2, 2, 0>(), halo<128, 128, 256, 2, 2, 2, 1>(),
+    halo<64, 64, 128, 2, 1, 3, 0>(), halo<64, 64, 128, 2, 1, 3, 1>(), halo<128, 128, 128, 2, 1, 2, 0>(), halo<128, 128, 128, 2, 1, 2, 1>(),
+};
+// 64 mid channels: 4 waves, a three-stage ring; 128: 8 waves; each with two Wc buffers or one; layers 3 and 4; the res_entry
+// pair; and the projections, which are the tail kernel without conv_b, residual and ReLU at a fixed Cout
+const KernelEntry<TailKernel> kTailKernels[] = {
+    tail<64, 0, true, 3, 4, true>(), tail<64, 0, true, 3, 4, false>(), tail<64, 64, true, 3, 4, true>(), tail<64, 64, true, 3, 4, false>(),
+    tail<64, 128, true, 3, 4, true>(), tail<64, 128, true, 3, 4, false>(),
+    tail<64, 0, false, 3, 4, true>(), tail<64, 0, false, 3, 4, false>(), tail<64, 64, false, 3, 4, true>(), tail<64, 64, false, 3, 4, false>(),
+    tail<64, 128, false, 3, 4, true>(), tail<64, 128, false, 3, 4, false>(),
+    tail<128, 0, true, 2, 8, true>(), tail<128, 0, true, 2, 8, false>(), tail<128, 128, true, 2, 8, true>(), tail<128, 128, true, 2, 8, false>(),
+    tail<128, 0, false, 2, 8, true>(), tail<128, 0, false, 2, 8, false>(), tail<128, 128, false, 2, 8, true>(), tail<128, 128, false, 2, 8, false>(),
+    tail<512, 0, false, 2, 8, true>(), tail<256, 0, true, 2, 8, true>(), tail<256, 0, false, 2, 4, true>(), tail<256, 0, false, 2, 4, false>(),
+    tail<256, 256, false, 2, 8, true, 16>(), tail<256, 256, false, 2, 8, false, 16>(),
+    tail<64, 64, true, 3, 4, true, 32, true>(), tail<64, 64, true, 3, 4, false, 32, true>(),
+    {ROUTE_PROJ, {256, 512, 4}, bottleneck_tail_kernel<256, 0, false, 2, 4, true, 32, 512, false, false>},
+    {ROUTE_PROJ, {512, 1024, 8}, bottleneck_tail_kernel<512, 0, false, 2, 8, true, 32, 1024, false, false>},
+};
+const KernelEntry<AttnKernel> kAttnKernels[] = {attn<0, 13, true>(), attn<0, 13>(), attn<0, 16>(), attn<1, 13>(), attn<1, 16>()};
+
+// The table's kernel for a Route, nullptr if it has none.  A kernel with dynamic LDS has its limit raised first, once per
+// (entry, device): hipFuncSetAttribute applies to the CURRENT device only; *lds_ok says whether that worked.
+template <class Fn, size_t N>
+Fn find_kernel(const KernelEntry<Fn> (&table)[N], const Route& r, bool* lds_ok) {
+    *lds_ok = true;
+    for (const KernelEntry<Fn>& e : table) {
+        if (e.kind != r.kind || memcmp(e.a, r.a, sizeof r.a) != 0) continue;
+        if (r.lds > 0 && !e.lds_set.test_current()) {
+            *lds_ok = hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+            if (*lds_ok) e.lds_set.set_current();
+        }
+        return e.fn;
+    }
+    return nullptr;
 }
 
-// K-tile depth and ring stages of the 128-row tiles.  Measured on MI355X (profiles/r1d_conv_sweep.txt):
-//  * 3x3: MFMA-bound, 64-deep tiles (half the barriers per FLOP), double buffer;
-//  * 1x1 with a residual (the expanding convolution of a bottleneck): bound by HBM and by the
-//    epilogue; 32-deep tiles with a 3-stage ring (50 KB of LDS -> 3 blocks per CU, which is also
-//    what the 143 VGPRs allow);
-//  * 1x1 without residual: the same up to K = 256; 64-deep tiles and a double buffer from K = 512.
-// FAV_CONV_BK=32|64 forces a value (experiments build).
-int conv_bk(int kh, int kw, int K, bool has_res) {
-    const int forced = (int)FAV_KNOB("FAV_CONV_BK", 0);
-    if (forced == 32 || forced == 64) return forced;
-    return (kh * kw > 1 || (!has_res && K >= 512) || K >= 1024) ? 64 : 32;   // K >= 1024 with a residual: the ViT MLP's second GEMM
-}
-
-// ring depth: three 32-deep stages or two 64-deep ones (the other depths measured no better; their
-// instantiations were dropped in round 3) - fixed in the launch table of launch_conv
-
-// 256 x 256 x 64 tile (8 waves, 128 KB of LDS, one block per CU): twice the FLOPs per
-// byte staged from L2, which is what bounds the MFMA-heavy shapes.
-// Measured on MI355X it wins on the residual-free 3x3 convolutions and on the 1x1
-// convolutions with K >= 512 (+6..25 %), and loses on the shallow 1x1 (K <= 256), whose
-// time is the epilogue (nothing overlaps it at one block per CU).  FAV_CONV_BIG: 0 never, 1 always
-// when Cout % 256 == 0, unset = the measured rule.
-bool conv_big(int kh, int kw, long long M, int cout_pad, int K, bool has_res) {
-    const int mode = (int)FAV_KNOB("FAV_CONV_BIG", 2);
-    const long long min_m = FAV_KNOB("FAV_CONV_BIG_MINM", 8192);
-    if (mode == 0 || cout_pad % 256 != 0 || M < min_m) return false;
-    if (mode == 1) return true;
-    if ((M / 256) * (cout_pad / 256) < 512) return false;   // fewer than two 256x256 tiles per CU: 128-row tiles fill the chip better
-    return kh * kw > 1 ? !has_res : K >= 512;
-}
-
-// ---- projection shortcut (1x1 / stride s, 256 -> 512, no residual, no ReLU) on the row-owning structure of the tail
-//      kernel: every wave gathers the fragments of its 32 output pixels straight from global memory (a strided gather
-//      costs nothing there), the 512 output channels stream through as 8 weight chunks, register epilogue.  Measured
-//      against the generic kernel on layer 2's shortcut (56x56x256 -> 28x28x512): see profiles/r2e_*.  FAV_PROJ=0 disables.
-bool proj_enabled() {
-    return FAV_KNOB("FAV_PROJ", 1) != 0;
-}
-
-bool launch_proj(fav_handle* h, const fav_conv_desc& d, const Group& G, hipStream_t s) {
-    const bool wide = d.Cin == 512 && d.Cout == 1024;       // layer 3's shortcut: 8 waves x 32 pixels, one block per CU
-    if (!proj_enabled() || d.kh != 1 || d.kw != 1 || d.pad != 0 || !((d.Cin == 256 && d.Cout == 512) || wide) || d.res || d.drop.site >= 0 ||
-        d.out_f32 || d.relu != 0 || d.math_mode != FAV_MATH_BF16 || (d.stride != 1 && d.stride != 2)) return false;
-    const int Ho = conv_out(d.H, 1, d.stride, 0), Wo = conv_out(d.W, 1, d.stride, 0);
-    const long long M = (long long)d.n_frames * Ho * Wo;
-    if (M * G.n < (wide ? 512 * 256 : 4096) || M > 0x7fffffffLL || (long long)d.H * d.W * d.Cin * 2 * 4 >= 0x40000000LL) return false;
+// the tail kernel's parameters that do not depend on what feeds it: geometry, the LDS plan, fast divisions
+TailParams tail_params(const Route& r) {
     TailParams p;
     memset(&p, 0, sizeof p);
-    p.t1 = (const uint16_t*)d.x; p.wc = (const uint16_t*)d.w; p.bias_c = d.bias; p.y = (uint16_t*)d.y;
-    p.H = Ho; p.W = Wo; p.HW = Ho * Wo; p.M = (int)M;
-    p.in_W = d.W; p.in_HW = d.H * d.W; p.in_stride = d.stride;
-    p.rega_bytes = 0;
-    // [Wc x 2 | bias_b (unused) | bias_c | 256 zero bytes on a 256-byte boundary]
-    p.bias_b_off = 2 * 64 * d.Cin * 2; p.bias_ca_off = p.bias_b_off + d.Cin * 5; p.wa_off0 = p.wa_off1 = p.bias_b_off;
-    p.zero_off = (p.bias_b_off + (d.Cin + d.Cout) * 5 + 255) & ~255;
-    p.drop = make_drop(nullptr);
+    p.H = r.Ho; p.W = r.Wo; p.HW = r.Ho * r.Wo; p.M = r.M;
+    p.in_W = p.W; p.in_HW = p.HW; p.in_stride = 1;
+    const TailGeom& g = r.geom;
+    p.rega_bytes = g.rega_bytes;
+    p.bias_b_off = g.bias_b_off; p.bias_ca_off = g.bias_ca_off; p.wa_off0 = g.wa_off0; p.wa_off1 = g.wa_off1; p.zero_off = g.zero_off;
     p.div_hw = fastdiv_make((uint32_t)p.HW);
-    p.div_w = fastdiv_make((uint32_t)Wo);
-    p.dbg = nullptr;
-    p.g_t1 = G.x; p.g_wc = G.w; p.g_bc = G.b; p.g_y = G.y;
-    const int lds = p.zero_off + 256;
-    auto kern = bottleneck_tail_kernel<256, 0, false, 2, 4, true, 32, 512, false, false>;
-    auto kern_w = bottleneck_tail_kernel<512, 0, false, 2, 8, true, 32, 1024, false, false>;
-    static DeviceFlags attr_set;
-    if (!attr_set.test_current()) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)kern_w, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-        attr_set.set_current();
-    }
-    const double flops = 2.0 * (double)M * d.Cin * d.Cout * G.n;
-    const double bytes = 2.0 * ((double)M * (d.Cin + d.Cout) + (double)d.Cin * d.Cout) * G.n;
-    Prof pr(h, s, FAV_K_CONV, flops, bytes);
-    if (wide) { route_set(ROUTE_PROJ, 512, 1024, 8); hipLaunchKernelGGL(kern_w, dim3((unsigned)((M + 255) / 256), G.n), dim3(512), lds, s, p, 0); }
-    else { route_set(ROUTE_PROJ, 256, 512, 4); hipLaunchKernelGGL(kern, dim3((unsigned)((M + 127) / 128), G.n), dim3(256), lds, s, p, 0); }
-    return true;
+    p.div_w = fastdiv_make((uint32_t)p.W);
+    p.rs_T = r.rs_T; p.rs_tps = r.rs_tps;
+    return p;
 }
 
+// the projection shortcut (route_proj): the tail kernel as a strided 1x1
+const char* launch_proj(fav_handle* h, const fav_conv_desc& d, const Route& r, const Group& G, hipStream_t s) {
+    TailParams p = tail_params(r);
+    p.t1 = (const uint16_t*)d.x; p.wc = (const uint16_t*)d.w; p.bias_c = d.bias; p.y = (uint16_t*)d.y;
+    p.in_W = d.W; p.in_HW = d.H * d.W; p.in_stride = d.stride;
+    p.drop = make_drop(nullptr);
+    p.g_t1 = G.x; p.g_wc = G.w; p.g_bc = G.b; p.g_y = G.y;
+    bool lds_ok;
+    const TailKernel kern = find_kernel(kTailKernels, r, &lds_ok);
+    if (!kern || !lds_ok) return kern ? "conv: cannot reserve LDS for the projection kernel" : "conv: no kernel for this route";
+    const double flops = 2.0 * (double)r.M * d.Cin * d.Cout * G.n;
+    const double bytes = 2.0 * ((double)r.M * (d.Cin + d.Cout) + (double)d.Cin * d.Cout) * G.n;
+    Prof pr(h, s, FAV_K_CONV, flops, bytes);
+    g_route = r;
+    hipLaunchKernelGGL(kern, dim3(r.grid, r.groups), dim3(r.block), r.lds, s, p, 0);
+    return nullptr;
+}
 
-const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int ldy, const Group& G, hipStream_t s) {
-    // conv_out divides by the stride and truncates towards zero: a window larger than the padded frame would come out as
-    // Ho = Wo = -1, that is M = n_frames > 0 rows
-    if (d.n_frames < 1 || d.H < 1 || d.W < 1) return "conv: n_frames, H and W must be >= 1";
-    if (d.kh < 1 || d.kw < 1 || d.stride < 1 || d.pad < 0) return "conv: kh, kw and stride must be >= 1 and pad >= 0";
-    if ((long long)d.H + 2ll * d.pad < d.kh || (long long)d.W + 2ll * d.pad < d.kw) return "conv: the window does not fit the padded frame";
-    if (d.relu < 0 || d.relu > 2) return "conv: relu must be 0 (none), 1 (ReLU) or 2 (GELU)";
-    if (d.out_f32 != 0 && d.out_f32 != 1) return "conv: out_f32 must be 0 or 1";
-    if (d.math_mode != FAV_MATH_BF16 && d.math_mode != FAV_MATH_F32_EXACT) return "conv: unknown math_mode";
-    if (d.Cin < 64 || d.Cin % 64 != 0) return "conv: Cin must be a multiple of 64 and >= 64";
-    if (d.Cout < 1 || cout_pad < d.Cout) return "conv: Cout must be >= 1 and the padded Cout must cover it";   // else tiles_n <= 0: an empty or a wrapped grid
-    if (cout_pad % 64 != 0) return "conv: padded Cout must be a multiple of 64";
-    // the bf16 epilogues store whole 16-byte groups of channels and range-check rows only: padded columns would land in
-    // the next pixel's first channels.  Only the fp32 (logit) output, whose row pitch is the padded width, may be padded.
-    if (!d.out_f32 && cout_pad != d.Cout) return "conv: a bf16 output needs Cout to be a multiple of 64 (no column padding)";
-    if (d.out_f32 && ldy < cout_pad) return "conv: the fp32 output's row pitch must cover the padded Cout";
-    if (cout_pad == d.Cout && ldy == d.Cout && launch_proj(h, d, G, s)) return nullptr;
+// vit: a GEMM of the ViT encoder, which has a tile rule of its own (route_conv)
+const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int ldy, bool vit, const Group& G, hipStream_t s) {
+    const Route r = route_conv(d, cout_pad, ldy, vit, G.n);
+    if (r.refusal) return r.refusal;
+    if (r.kind == ROUTE_PROJ) return launch_proj(h, d, r, G, s);
     ConvParams p;
     p.x = (const uint16_t*)d.x; p.w = (const uint16_t*)d.w; p.bias = d.bias; p.res = (const uint16_t*)d.res; p.y = d.y;
     p.H = d.H; p.W = d.W; p.Cin = d.Cin;
-    p.Ho = conv_out(d.H, d.kh, d.stride, d.pad);
-    p.Wo = conv_out(d.W, d.kw, d.stride, d.pad);
-    p.HWo = p.Ho * p.Wo;
+    p.Ho = r.Ho; p.Wo = r.Wo; p.HWo = r.Ho * r.Wo;
     p.Cout = d.Cout; p.ldy = ldy;
     p.kw = d.kw; p.stride = d.stride; p.pad = d.pad;
-    const long long M = (long long)d.n_frames * p.HWo;
-    if (M <= 0 || M > 0x7fffffffLL) return "conv: row count out of range";
-    p.M = (int)M;
-    p.K = d.kh * d.kw * d.Cin; p.nk = p.K / 64;
+    p.M = r.M; p.K = r.K; p.nk = r.nk;
     p.relu = d.relu; p.out_f32 = d.out_f32;
+    p.tiles_m = r.tiles_m; p.tiles_n = r.tiles_n; p.stage_mid = r.stage_mid;
     p.drop = make_drop(&d.drop);
     p.div_hwo = fastdiv_make((uint32_t)p.HWo);
     p.div_w = fastdiv_make((uint32_t)p.Wo);
-    if (const char* e = check_drop("conv", &d.drop, d.n_frames)) return e;
     p.dbg = nullptr;
     p.g_x = G.x; p.g_w = G.w; p.g_bias = G.b; p.g_res = G.res; p.g_y = G.y;
-    if (d.out_f32 && p.drop.site >= 0) return "conv: dropout on fp32 output unsupported";
-    // the ViT encoder's GEMMs (M = 197 rows per frame, K = 768 / 3072): the 256 x 256 tile from 50 of them up (measured, round 4,
-    // tools/experiments/r4_vit_tiles.sh: +18 % at 128 frames on two streams, +1.5 % at the 64-frame share; since the GELU epilogue
-    // shrank to 14 instructions per element it no longer needs a second block per CU to hide behind); below that 128-row tiles with
-    // 32-deep steps at three blocks per CU
-    const bool vit = h && h->vit;
-    const long long vit_big_tiles = FAV_KNOB("FAV_VIT_BIG_TILES", 50);
-    const bool vit_big = vit && cout_pad % 256 == 0 && d.kh * d.kw * d.Cin >= 512 && (M / 256) * (cout_pad / 256) >= vit_big_tiles &&
-                         FAV_KNOB("FAV_CONV_BIG", 2) != 0;
-    const bool big = vit ? vit_big
-                         : conv_big(d.kh, d.kw, M * G.n, cout_pad, d.kh * d.kw * d.Cin, d.res != nullptr);   // 256 x 256 x 64 tile, 8 waves, 128 KB of LDS
-    const int BN = big ? 256 : ((cout_pad % 128 == 0) ? 128 : 64);
-    const int BK = big ? 64 : (vit ? 32 : conv_bk(d.kh, d.kw, d.kh * d.kw * d.Cin, d.res != nullptr));
-    const int BM = big ? 256 : 128;   // (256-row tiles with 128 columns lose to two blocks per CU of 128-row tiles on every 3x3 shape)
-    // measured: issuing the DMA after the first MFMA group gains ~7 % on the 256x256 3x3 launches and
-    // loses 3-5 % on the 128-row tiles and on every 1x1
-    p.stage_mid = (big && d.kh * d.kw > 1) ? 1 : 0;
-    {   // LDS-DMA offsets are 32-bit from the tile's first frame; out-of-range lanes use 0x80000000
-        const double frame_bytes = 2.0 * d.H * d.W * d.Cin;
-        const double span = (BM / (double)p.HWo + 2.0) * frame_bytes + 2.0 * ((double)d.pad * d.W + d.pad) * d.Cin +
-                            2.0 * (((double)d.kh * d.W + d.kw) * d.Cin);
-        if (span >= 2147483647.0 || 2.0 * BN * (double)p.K >= 2147483647.0) return "conv: frame too large for 32-bit tile offsets";
-    }
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.tiles_n = cout_pad / BN;
-    const long long tiles = (long long)p.tiles_m * p.tiles_n;
-    if (tiles > 0x7fffffffLL) return "conv: too many tiles";
-    const double flops = 2.0 * (double)M * d.Cout * p.K * G.n;
-    const double bytes = 2.0 * ((double)d.n_frames * d.H * d.W * d.Cin + (double)M * d.Cout * (d.res ? 2 : 1) * (d.out_f32 ? 2 : 1)
-                                + (double)d.Cout * p.K) * G.n;
+    const bool halo = r.kind == ROUTE_CONV_HALO;
+    bool lds_ok;
+    const HaloKernel kern_halo = halo ? find_kernel(kHaloKernels, r, &lds_ok) : nullptr;
+    const ConvKernel kern = halo ? nullptr : find_kernel(kConvKernels, r, &lds_ok);
+    if (!kern_halo && !kern) return "conv: no kernel for this route";
+    if (!lds_ok) return "conv: cannot reserve LDS for the staged 3x3 kernel";
+    const double flops = 2.0 * (double)r.M * d.Cout * r.K * G.n;
+    const double bytes = 2.0 * ((double)d.n_frames * d.H * d.W * d.Cin + (double)r.M * d.Cout * (d.res ? 2 : 1) * (d.out_f32 ? 2 : 1)
+                                + (double)d.Cout * r.K) * G.n;
+    const long long tiles = (long long)r.tiles_m * r.tiles_n;
     const bool dbg_on = FAV_KNOB("FAV_CONV_DBG", 0) != 0;   // experiments build only: per-block phase clocks
     if (dbg_on && !h) { (void)hipMalloc((void**)&p.dbg, (size_t)tiles * 32); (void)hipMemset(p.dbg, 0, (size_t)tiles * 32); }
     auto dbg_report = [&](long long nblocks, int bm, int bn, int bk) {
@@ -433,136 +373,36 @@ const char* launch_conv(fav_handle* h, const fav_conv_desc& d, int cout_pad, int
                 ph[2] / nblocks / 100.0, life / span / 256.0);
     };
     Prof pr(h, s, FAV_K_CONV, flops, bytes);
-    // 3x3 / stride 1 / pad 1 with Cin <= 128 and the whole Cout in one tile: the input patch is staged once
-    // per 256 output pixels instead of once per tap (conv3x3_halo_kernel).  FAV_CONV_HALO=0 disables.
-    const int halo_mode = (int)FAV_KNOB("FAV_CONV_HALO", 1);
-    if (halo_mode && d.kh == 3 && d.kw == 3 && d.stride == 1 && d.pad == 1 && !d.res && p.drop.site < 0 && !d.out_f32 &&
-        (d.Cin == 64 || d.Cin == 128) && d.Cout == cout_pad && d.Cout == d.Cin && M * G.n >= 2048) {
-        // Cin 64: 512-pixel tiles, all 9 K tiles of the weights resident; Cin 128: 256-pixel tiles, weights double-buffered per tap
-        // 256-pixel tiles, 8 waves (measured best on both shapes); FAV_HALO_CFG=0 selects 128-pixel tiles with 4 waves and
-        // several blocks per CU for experiments
-        const int halo_cfg = (int)FAV_KNOB("FAV_HALO_CFG", 1);
-        const int HBM = halo_cfg == 0 ? 128 : 256;
-        const int wstages = d.Cin == 64 ? (halo_cfg == 0 ? 2 : 3) : (halo_cfg == 0 ? 2 : 4);   // K tiles of weights held in LDS
-        const int patch_bytes = (int)((((long long)(HBM + 2 * d.W + 2) * d.Cin * 2) + 1023) / 1024 * 1024);
-        const int lds = patch_bytes + wstages * d.Cout * 128 + d.Cout * 5 + 512;   // + 256 zero bytes on a 256-byte boundary
-        if (lds <= 160 * 1024) {
-            p.nk = 9 * d.Cin / 64;
-            dim3 hgrid((unsigned)((p.M + HBM - 1) / HBM), G.n);
-#define FAV_HALO(CIN_, BN_, BM_, NS_, SUB_, OCC_, MODE_)                                                             \
-    do {                                                                                                             \
-        static DeviceFlags attr_set;   /* hipFuncSetAttribute applies to the CURRENT device only */                  \
-        if (!attr_set.test_current()) {                                                                              \
-            if (hipFuncSetAttribute((const void*)conv3x3_halo_kernel<CIN_, BN_, BM_, NS_, SUB_, OCC_, MODE_>,                \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                   \
-                return "conv: cannot reserve LDS for the staged 3x3 kernel";                                         \
-            attr_set.set_current();                                                                                  \
-        }                                                                                                            \
-        route_set(ROUTE_CONV_HALO, CIN_, BN_, BM_, NS_, MODE_);                                                      \
-        hipLaunchKernelGGL((conv3x3_halo_kernel<CIN_, BN_, BM_, NS_, SUB_, OCC_, MODE_>), hgrid, dim3(HBM * 2), lds, s, p, patch_bytes); \
-    } while (0)
-            const bool bf = d.math_mode == FAV_MATH_BF16;
-            if (d.Cin == 64 && halo_cfg == 0) {
-                if (bf) FAV_HALO(64, 64, 128, 2, 1, 3, 0); else FAV_HALO(64, 64, 128, 2, 1, 3, 1);
-            } else if (d.Cin == 64) {
-                if (bf) FAV_HALO(64, 64, 256, 3, 1, 4, 0); else FAV_HALO(64, 64, 256, 3, 1, 4, 1);
-            } else if (halo_cfg == 0) {
-                if (bf) FAV_HALO(128, 128, 128, 2, 1, 2, 0); else FAV_HALO(128, 128, 128, 2, 1, 2, 1);
-            } else {
-                if (bf) FAV_HALO(128, 128, 256, 2, 2, 2, 0); else FAV_HALO(128, 128, 256, 2, 2, 2, 1);
-            }
-#undef FAV_HALO
-            dbg_report((p.M + HBM - 1) / HBM, HBM, d.Cout, 64);
-            return nullptr;
-        }
-    }
-    dim3 grid((unsigned)tiles, G.n);
-    p.nk = p.K / BK;
-    // FAV_CONV_EPI=0 selects the round-1 epilogue (fp32 staging through LDS) for A/B measurements
-    // measured (profiles/r2b_conv_epilogue_ab.txt): the register epilogue wins 2-4 % on the 3x3 and K >= 512 launches
-    // (also with a residual on the 256 x 256 tile: layer 4's expand 1.24 vs 1.29 ms) and loses ~3 % on the 128-row
-    // tiles with a residual, so those keep the staged one.  FAV_CONV_EPI=0|1 forces.
-    const int epi_forced = (int)FAV_KNOB("FAV_CONV_EPI", -1);
-    const int epi = epi_forced >= 0 ? epi_forced : ((d.res && !big) ? 0 : 1);
-#define FAV_LAUNCH(BN_, BK_, NS_, MODE_)                                                                          \
-    do {                                                                                                          \
-        route_set(ROUTE_CONV_IGEMM, 128, BN_, BK_, NS_, MODE_, epi ? 1 : 0, 0, d.relu == 2);                     \
-        if (d.relu == 2) {      /* GELU (ViT MLP): the instantiations that carry it */                            \
-            if (epi) hipLaunchKernelGGL((conv_igemm_kernel<128, BN_, BK_, NS_, MODE_, 2, 0, 1, 0, true>), grid, dim3(256), 0, s, p); \
-            else hipLaunchKernelGGL((conv_igemm_kernel<128, BN_, BK_, NS_, MODE_, 2, 0, 0, 0, true>), grid, dim3(256), 0, s, p);     \
-        } else if (epi) hipLaunchKernelGGL((conv_igemm_kernel<128, BN_, BK_, NS_, MODE_, 2, 0, 1>), grid, dim3(256), 0, s, p); \
-        else hipLaunchKernelGGL((conv_igemm_kernel<128, BN_, BK_, NS_, MODE_, 2, 0, 0>), grid, dim3(256), 0, s, p);     \
-    } while (0)
-#define FAV_LAUNCH_MODE(MODE_)                                                                    \
-    do {                                                                                          \
-        if (BN == 128) { if (BK == 32) FAV_LAUNCH(128, 32, 3, MODE_); else FAV_LAUNCH(128, 64, 2, MODE_); } \
-        else { if (BK == 32) FAV_LAUNCH(64, 32, 3, MODE_); else FAV_LAUNCH(64, 64, 2, MODE_); }   \
-    } while (0)
-#define FAV_LAUNCH_BIG(MODE_)                                                                                     \
-    do {                                                                                                          \
-        const int pp = (int)FAV_KNOB("FAV_CONV_PP", 1);                                                           \
-        route_set(ROUTE_CONV_IGEMM, 256, 256, 64, 2, MODE_, epi ? 1 : 0, (epi && pp && MODE_ == 0) ? 1 : 0, d.relu == 2);       \
-        if (d.relu == 2) {                                                                                        \
-            if (epi && pp && MODE_ == 0) hipLaunchKernelGGL((conv_igemm_kernel<256, 256, 64, 2, 0, 2, 0, 1, 1, true>), grid, dim3(512), 0, s, p); \
-            else if (epi) hipLaunchKernelGGL((conv_igemm_kernel<256, 256, 64, 2, MODE_, 2, 0, 1, 0, true>), grid, dim3(512), 0, s, p);    \
-            else hipLaunchKernelGGL((conv_igemm_kernel<256, 256, 64, 2, MODE_, 2, 0, 0, 0, true>), grid, dim3(512), 0, s, p);        \
-        } else if (epi && pp && MODE_ == 0) hipLaunchKernelGGL((conv_igemm_kernel<256, 256, 64, 2, 0, 2, 0, 1, 1>), grid, dim3(512), 0, s, p); \
-        else if (epi) hipLaunchKernelGGL((conv_igemm_kernel<256, 256, 64, 2, MODE_, 2, 0, 1>), grid, dim3(512), 0, s, p);    \
-        else hipLaunchKernelGGL((conv_igemm_kernel<256, 256, 64, 2, MODE_, 2, 0, 0>), grid, dim3(512), 0, s, p);        \
-    } while (0)
-    if (big) {
-        if (d.math_mode == FAV_MATH_BF16) FAV_LAUNCH_BIG(0); else FAV_LAUNCH_BIG(1);
-    } else if (d.math_mode == FAV_MATH_BF16) FAV_LAUNCH_MODE(0); else FAV_LAUNCH_MODE(1);
-#undef FAV_LAUNCH_BIG
-#undef FAV_LAUNCH_MODE
-#undef FAV_LAUNCH
-    dbg_report(tiles, BM, BN, BK);
+    g_route = r;
+    if (halo) hipLaunchKernelGGL(kern_halo, dim3(r.grid, r.groups), dim3(r.block), r.lds, s, p, r.patch_bytes);
+    else hipLaunchKernelGGL(kern, dim3(r.grid, r.groups), dim3(r.block), 0, s, p);
+    dbg_report(r.grid, halo ? r.a[2] : r.a[0], r.a[1], halo ? 64 : r.a[2]);     // rows x columns x K depth of a tile
     return nullptr;
 }
 
-
-// ---- bottleneck tail (conv_b 3x3 -> conv_c 1x1 + residual + dropout -> next block's conv_a 1x1), one launch; its LDS plan
-//      is tail_geometry (fav_plan.hpp) ----
 const char* launch_tail(fav_handle* h, const fav_tail_desc& d, const Group& G, hipStream_t s) {
-    if (d.n_frames < 1 || d.H < 1 || d.W < 1) return "bottleneck tail: n_frames, H and W must be >= 1";
-    const bool has3x3 = d.wb != nullptr;
-    const int nred = d.wa ? d.Nred : 0;
-    TailGeom g;
-    if (!tail_geometry(d.Cmid, nred, has3x3, d.W, &g)) return "bottleneck tail: unsupported shape";
-    const long long M = (long long)d.n_frames * d.H * d.W;
-    if (M <= 0 || M > 0x7fffffffLL) return "bottleneck tail: row count out of range";
-    TailParams p;
+    const Route r = route_tail(d, G.n);
+    if (r.refusal) return r.refusal;
+    TailParams p = tail_params(r);
     p.t1 = (const uint16_t*)d.x; p.wb = (const uint16_t*)d.wb; p.bias_b = d.bias_b;
     p.wc = (const uint16_t*)d.wc; p.bias_c = d.bias_c; p.res = (const uint16_t*)d.res; p.y = (uint16_t*)d.y;
     p.wa = (const uint16_t*)d.wa; p.bias_a = d.bias_a; p.t1n = (uint16_t*)d.t1n;
-    p.H = d.H; p.W = d.W; p.HW = d.H * d.W; p.M = (int)M;
-    p.in_W = d.W; p.in_HW = p.HW; p.in_stride = 1;
-    p.rega_bytes = g.rega_bytes;
-    p.bias_b_off = g.bias_b_off; p.bias_ca_off = g.bias_ca_off; p.wa_off0 = g.wa_off0; p.wa_off1 = g.wa_off1; p.zero_off = g.zero_off;
     p.drop = make_drop(&d.drop);
-    p.div_hw = fastdiv_make((uint32_t)p.HW);
-    p.div_w = fastdiv_make((uint32_t)d.W);
-    if (const char* e = check_drop("bottleneck tail", &d.drop, d.n_frames)) return e;
     p.g_t1 = G.x; p.g_res = G.res; p.g_y = G.y; p.g_t1n = G.y2;
     p.g_wb = G.wb; p.g_bb = G.bb; p.g_wc = G.w; p.g_bc = G.b; p.g_wa = G.wa; p.g_ba = G.ba;
     p.site_e = d.entry_site;
-    p.rs_T = 0; p.rs_tps = 0;
-    if (d.res_entry) {
-        if (!(d.Cmid == 64 && nred == 64 && has3x3) || p.drop.site < 0 || d.entry_site < 0 || !d.res)
-            return "bottleneck tail: res_entry needs Cmid = Nred = 64 with the 3x3 and both dropout sites";
-        if ((double)p.drop.n_img * p.HW * 4.0 * d.Cmid * 2.0 >= 2147483647.0) return "bottleneck tail: cached tensor too large for 32-bit offsets";
-    }
-    const int cmid = d.Cmid, cout = 4 * cmid;
+    bool lds_ok;
+    const TailKernel kern = find_kernel(kTailKernels, r, &lds_ok);
+    if (!kern) return "bottleneck tail: unsupported shape";
+    if (!lds_ok) return "bottleneck tail: cannot reserve LDS";
+    const int cmid = d.Cmid, cout = 4 * cmid, nred = r.a[1], bm = r.geom.rp * r.geom.nw;
+    const bool has3x3 = r.a[2] != 0;
+    const long long M = r.M, nblocks = r.grid;
     const double flops = 2.0 * (double)M * ((has3x3 ? 9.0 * cmid * cmid : 0.0) + (double)cmid * cout + (double)cout * nred) * G.n;
     // res_entry: the residual is the cached tensor [n_img][HW][cout], counted ONCE (every sample's tile re-reads it, from L2), not once per row it serves
     const double res_rows = d.res_entry ? (double)std::min<long long>(d.n_frames, p.drop.n_img) * p.HW : (double)M;
     const double bytes = 2.0 * ((double)M * (cmid + 1.0 * cout + nred) + res_rows * cout + (has3x3 ? 9.0 * cmid * cmid : 0.0) + (double)cmid * cout + (double)cout * nred) * G.n;
     Prof pr(h, s, FAV_K_CONV, flops, bytes);
-    { const int lds_pad = (int)FAV_KNOB("FAV_TAIL_LDS_PAD", 0); if (g.lds_bytes + lds_pad <= 160 * 1024) g.lds_bytes += lds_pad; }   // experiments build: fewer blocks per CU
-    const int bm = g.rp * g.nw;
-    const long long nblocks = (M + bm - 1) / bm;
-    dim3 grid((unsigned)nblocks, G.n);
-    p.dbg = nullptr;
     const bool dbg_on = FAV_KNOB("FAV_CONV_DBG", 0) != 0;   // experiments build only: per-block phase clocks
     if (dbg_on && !h) { (void)hipMalloc((void**)&p.dbg, (size_t)nblocks * 128); (void)hipMemset(p.dbg, 0, (size_t)nblocks * 128); }
     auto dbg_report = [&]() {
@@ -594,75 +434,10 @@ const char* launch_tail(fav_handle* h, const fav_tail_desc& d, const Group& G, h
                 cy[0] / nblocks, cy[1] / nblocks, cy[2] / nblocks, cy[3] / nblocks, cy[4] / nblocks);
         fprintf(stderr, "[tail dbg]   ... residual wait %.0f, next chunk's requests %.0f, whole chunk 1 %.0f\n", cz[0] / nblocks, cz[1] / nblocks, cz[2] / nblocks);
     };
-#define FAV_TAIL(CMID_, NRED_, H3_, NS_, NW_, WC2_)                                                                   \
-    do {                                                                                                              \
-        static DeviceFlags attr_set;                                                                                  \
-        if (!attr_set.test_current()) {                                                                               \
-            if (hipFuncSetAttribute((const void*)bottleneck_tail_kernel<CMID_, NRED_, H3_, NS_, NW_, WC2_>,           \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)            \
-                return "bottleneck tail: cannot reserve LDS";                                                         \
-            attr_set.set_current();                                                                                   \
-        }                                                                                                             \
-        route_set(ROUTE_TAIL, CMID_, NRED_, H3_, NW_, WC2_, 32, 0);                                                   \
-        hipLaunchKernelGGL((bottleneck_tail_kernel<CMID_, NRED_, H3_, NS_, NW_, WC2_>), grid, dim3(NW_ * 64), g.lds_bytes, s, p, g.patch_bytes); \
-        dbg_report();                                                                                                 \
-        return nullptr;                                                                                               \
-    } while (0)
-#define FAV_TAIL_W(CMID_, NRED_, H3_, NS_, NW_) do { if (g.wc2) FAV_TAIL(CMID_, NRED_, H3_, NS_, NW_, true); else FAV_TAIL(CMID_, NRED_, H3_, NS_, NW_, false); } while (0)
-#define FAV_TAIL_N(CMID_, NRED_, H3_, NS_) FAV_TAIL_W(CMID_, NRED_, H3_, NS_, 4)
-    if (d.res_entry) {
-        // whole samples, tiles that do not straddle them: the T tiles over one pixel tile of the cached tensor run back to back
-        const bool sample_minor = FAV_KNOB("FAV_ENTRY_RES_ORDER", 1) != 0;
-        const long long sample_rows = (long long)p.drop.n_img * p.HW;
-        if (sample_minor && p.drop.v0 % p.drop.n_img == 0 && d.n_frames % p.drop.n_img == 0 && sample_rows % bm == 0) {
-            p.rs_T = d.n_frames / p.drop.n_img;
-            p.rs_tps = (int)(sample_rows / bm);
-        }
-        static DeviceFlags attr_set;
-        auto k0 = bottleneck_tail_kernel<64, 64, true, 3, 4, false, 32, 0, true, true, true>;
-        auto k1 = bottleneck_tail_kernel<64, 64, true, 3, 4, true, 32, 0, true, true, true>;
-        if (!attr_set.test_current()) {
-            if (hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return "bottleneck tail: cannot reserve LDS";
-            attr_set.set_current();
-        }
-        route_set(ROUTE_TAIL, 64, 64, 1, 4, g.wc2 ? 1 : 0, 32, 1);
-        if (g.wc2) hipLaunchKernelGGL(k1, grid, dim3(256), g.lds_bytes, s, p, g.patch_bytes);
-        else hipLaunchKernelGGL(k0, grid, dim3(256), g.lds_bytes, s, p, g.patch_bytes);
-        dbg_report();
-        return nullptr;
-    }
-    if (cmid == 64) {
-        if (has3x3) { if (nred == 0) FAV_TAIL_N(64, 0, true, 3); if (nred == 64) FAV_TAIL_N(64, 64, true, 3); if (nred == 128) FAV_TAIL_N(64, 128, true, 3); }
-        else { if (nred == 0) FAV_TAIL_N(64, 0, false, 3); if (nred == 64) FAV_TAIL_N(64, 64, false, 3); if (nred == 128) FAV_TAIL_N(64, 128, false, 3); }
-    } else if (cmid == 128) {
-        if (has3x3) { if (nred == 0) FAV_TAIL_W(128, 0, true, 2, 8); if (nred == 128) FAV_TAIL_W(128, 128, true, 2, 8); }
-        else { if (nred == 0) FAV_TAIL_W(128, 0, false, 2, 8); if (nred == 128) FAV_TAIL_W(128, 128, false, 2, 8); }
-    } else if (cmid == 512) {
-        FAV_TAIL(512, 0, false, 2, 8, true);
-    } else if (nred == 0 && has3x3) {
-        FAV_TAIL(256, 0, true, 2, 8, true);
-    } else if (nred == 0) {
-        FAV_TAIL_W(256, 0, false, 2, 4);
-    } else {
-        static DeviceFlags attr_set;
-        if (!attr_set.test_current()) {
-            if (hipFuncSetAttribute((const void*)bottleneck_tail_kernel<256, 256, false, 2, 8, true, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute((const void*)bottleneck_tail_kernel<256, 256, false, 2, 8, false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return "bottleneck tail: cannot reserve LDS";
-            attr_set.set_current();
-        }
-        route_set(ROUTE_TAIL, 256, 256, 0, 8, g.wc2 ? 1 : 0, 16, 0);
-        if (g.wc2) hipLaunchKernelGGL((bottleneck_tail_kernel<256, 256, false, 2, 8, true, 16>), grid, dim3(512), g.lds_bytes, s, p, g.patch_bytes);
-        else hipLaunchKernelGGL((bottleneck_tail_kernel<256, 256, false, 2, 8, false, 16>), grid, dim3(512), g.lds_bytes, s, p, g.patch_bytes);
-        dbg_report();
-        return nullptr;
-    }
-#undef FAV_TAIL_N
-#undef FAV_TAIL_W
-#undef FAV_TAIL
-    return "bottleneck tail: unsupported shape";
+    g_route = r;
+    hipLaunchKernelGGL(kern, dim3(r.grid, r.groups), dim3(r.block), r.lds, s, p, r.patch_bytes);
+    dbg_report();
+    return nullptr;
 }
 
 // One work item per thread whenever the grid allows (grid-stride loops only catch the rest): on gfx9
@@ -1032,32 +807,16 @@ bool launch_gemm_streamk(fav_handle* h, const void* a, const void* w, const floa
 }
 
 const char* launch_attention(fav_handle* h, const void* qkv, void* out, int n, int T, int D, int heads, int math_mode, hipStream_t s) {
-    if (T < 1 || T > 256 || heads * 64 != D || n < 1) return "attention: need 1 <= tokens <= 256 and 64-wide heads";
-    const int nkt = (T + 15) / 16, Tp2 = (T + 31) / 32 * 32;
-    // as few rounds of query tiles as 8 waves allow, then as few waves as those rounds need (197 tokens: 13 tiles = 2 rounds of 7
-    // waves); K and V are all the LDS a block holds (55 KB), so two blocks share a CU
-    const int rounds = (nkt + 7) / 8;
-    int nw = (nkt + rounds - 1) / rounds;
-    const int attn_nw = (int)FAV_KNOB("FAV_ATTN_WAVES", 0);   // experiments build: another block shape
-    if (attn_nw >= 1 && attn_nw <= 8) nw = attn_nw;
-    const int lds = nkt * 16 * 128 + Tp2 * 128;
-    static DeviceFlags attr_set;
-    if (!attr_set.test_current()) {
-        if (hipFuncSetAttribute((const void*)attention_kernel<0, 13, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)attention_kernel<0, 13>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)attention_kernel<0, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)attention_kernel<1, 13>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)attention_kernel<1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return "attention: cannot reserve LDS";
-        attr_set.set_current();
-    }
+    const Route r = route_attention(n, T, D, heads, math_mode);
+    if (r.refusal) return r.refusal;
+    bool lds_ok;
+    const AttnKernel kern = find_kernel(kAttnKernels, r, &lds_ok);
+    if (!kern) return "attention: no kernel for this route";
+    if (!lds_ok) return "attention: cannot reserve LDS";
     const double flops = 4.0 * n * heads * (double)T * T * 64;
     Prof pr(h, s, FAV_K_CONV, flops, (double)n * T * D * 2 * 4);
-    const dim3 grid((unsigned)(n * heads)), block(nw * 64);
-#define FAV_ATTN(MODE_, ...) route_set(ROUTE_ATTENTION, MODE_, __VA_ARGS__); hipLaunchKernelGGL((attention_kernel<MODE_, __VA_ARGS__>), grid, block, lds, s, (const uint16_t*)qkv, (uint16_t*)out, T, D, heads)
-    if (math_mode == FAV_MATH_BF16) { if (nkt == 13) { FAV_ATTN(0, 13, true); } else if (nkt < 13) { FAV_ATTN(0, 13); } else { FAV_ATTN(0, 16); } }
-    else { if (nkt <= 13) { FAV_ATTN(1, 13); } else { FAV_ATTN(1, 16); } }
-#undef FAV_ATTN
+    g_route = r;
+    hipLaunchKernelGGL(kern, dim3(r.grid), dim3(r.block), r.lds, s, (const uint16_t*)qkv, (uint16_t*)out, T, D, heads);
     return nullptr;
 }
 
@@ -1211,7 +970,7 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
                     d.relu = o.relu; d.out_f32 = o.out_f32; d.math_mode = c.math_mode;
                     d.drop = dd;
                     const int ldy = o.out_f32 ? L.cout_pad : L.cout;
-                    if (const char* e = launch_conv(h, d, L.cout_pad, ldy, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
+                    if (const char* e = launch_conv(h, d, L.cout_pad, ldy, false, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 }
                 case OP_TAIL: {
@@ -1309,7 +1068,7 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
         d.drop.site = -1;
         if (!out_f32 && c.math_mode == FAV_MATH_BF16 && L.cout == L.cout_pad &&
             launch_gemm_streamk(h, x, w, bias, res, y, (long long)n * rows_per_frame, L.k, L.cout, act, s)) return nullptr;
-        return launch_conv(h, d, L.cout_pad, out_f32 ? L.cout_pad : L.cout, Group{}, s);
+        return launch_conv(h, d, L.cout_pad, out_f32 ? L.cout_pad : L.cout, true, Group{}, s);
     };
 #define FAV_VIT_TRY(expr)                                            \
     do {                                                             \
@@ -1905,16 +1664,47 @@ fav_status fav_op_last_route(char* out, size_t cap) {
     return FAV_OK;
 }
 
+// the gates in front of a convolution's and a tail's selector: what fav_op_* and fav_route_* refuse alike
+static const char* conv_gate(const fav_conv_desc* d) {
+    if (!d || !d->x || !d->w || !d->bias || !d->y) return "null pointer";
+    return d->Cout % 64 != 0 ? "Cout must be a multiple of 64" : nullptr;
+}
+static const char* tail_gate(const fav_tail_desc* d) {
+    if (!d || !d->x || !d->wc || !d->bias_c || !d->res || !d->y) return "null pointer";
+    return ((d->wb && !d->bias_b) || (d->wa && (!d->bias_a || !d->t1n))) ? "null pointer" : nullptr;
+}
+
 fav_status fav_op_conv2d(const fav_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->w || !d->bias || !d->y) return op_done("fav_op_conv2d: null pointer");
-    if (d->Cout % 64 != 0) return op_done("fav_op_conv2d: Cout must be a multiple of 64");
-    return op_done("fav_op_conv2d", launch_conv(nullptr, *d, d->Cout, d->Cout, Group{}, (hipStream_t)stream));
+    if (const char* e = conv_gate(d)) return op_done("fav_op_conv2d", e);
+    return op_done("fav_op_conv2d", launch_conv(nullptr, *d, d->Cout, d->Cout, false, Group{}, (hipStream_t)stream));
 }
 
 fav_status fav_op_bottleneck_tail(const fav_tail_desc* d, void* stream) {
-    if (!d || !d->x || !d->wc || !d->bias_c || !d->res || !d->y) return op_done("fav_op_bottleneck_tail: null pointer");
-    if ((d->wb && !d->bias_b) || (d->wa && (!d->bias_a || !d->t1n))) return op_done("fav_op_bottleneck_tail: null pointer");
+    if (const char* e = tail_gate(d)) return op_done("fav_op_bottleneck_tail", e);
     return op_done("fav_op_bottleneck_tail", launch_tail(nullptr, *d, Group{}, (hipStream_t)stream));
+}
+
+// ---- route queries: the selector's answer as text.  No device, no launch, and fav_op_last_route keeps what it had.
+static fav_status route_reply(const char* gate, const Route& r, char* out, size_t cap) {
+    const char* refusal = gate ? gate : r.refusal;
+    const std::string t = refusal ? refusal : route_text(r);
+    if (!out || t.size() + 1 > cap) return FAV_ERR_INVALID_ARG;
+    memcpy(out, t.c_str(), t.size() + 1);
+    return refusal ? FAV_ERR_INVALID_ARG : FAV_OK;
+}
+
+fav_status fav_route_conv2d(const fav_conv_desc* d, int32_t vit, int32_t groups, char* out, size_t cap) {
+    const char* gate = groups < 1 ? "groups must be >= 1" : conv_gate(d);
+    return route_reply(gate, gate ? Route{} : route_conv(*d, d->Cout, d->Cout, vit != 0, groups), out, cap);
+}
+
+fav_status fav_route_bottleneck_tail(const fav_tail_desc* d, int32_t groups, char* out, size_t cap) {
+    const char* gate = groups < 1 ? "groups must be >= 1" : tail_gate(d);
+    return route_reply(gate, gate ? Route{} : route_tail(*d, groups), out, cap);
+}
+
+fav_status fav_route_attention(int32_t n, int32_t T, int32_t D, int32_t heads, int32_t math_mode, char* out, size_t cap) {
+    return route_reply(nullptr, route_attention(n, T, D, heads, math_mode), out, cap);
 }
 
 fav_status fav_op_stem_im2col(const void* images, int32_t layout, int32_t n, int32_t H, int32_t W, int32_t kh, int32_t kw,

@@ -366,6 +366,15 @@ fav_status fav_op_bottleneck_tail(const fav_tail_desc* d, void* hip_stream);
  *   attention<bf16|f32,NKT[,full]>                           key tiles compiled for (13 or 16); full: exactly 13, no masking
  *   entry_reduce<C,NRED>     stem7_pool<u8|f32> */
 fav_status fav_op_last_route(char* out, size_t cap);
+/* Which kernel instantiation fav_op_conv2d, fav_op_bottleneck_tail or fav_op_attention would launch for these arguments: the
+ * name fav_op_last_route reports after the launch, in out (NUL-terminated; 128 bytes hold every answer) - or, with
+ * FAV_ERR_INVALID_ARG, the text the op refuses them with, without its "fav_op_...: " prefix.  No device is needed and nothing
+ * is launched; a descriptor's pointers are tested for NULL as the op tests them and never read; fav_op_last_route keeps what
+ * it held.  vit != 0: as a GEMM of the ViT encoder (its own tile rule); groups >= 1: as one launch over that many ensemble
+ * members (the row thresholds count rows x members).  A test / inspection hook. */
+fav_status fav_route_conv2d(const fav_conv_desc* d, int32_t vit, int32_t groups, char* out, size_t cap);
+fav_status fav_route_bottleneck_tail(const fav_tail_desc* d, int32_t groups, char* out, size_t cap);
+fav_status fav_route_attention(int32_t n, int32_t T, int32_t D, int32_t heads, int32_t math_mode, char* out, size_t cap);
 /* frames (u8 or fp32 NHWC3) -> normalised bf16 im2col matrix [n*Ho*Wo][kpad].  n, H, W >= 1, a known layout and a window that
  * fits the padded frame, else FAV_ERR_INVALID_ARG and nothing is launched (the same holds for the pools and the entry ops below). */
 fav_status fav_op_stem_im2col(const void* images, int32_t layout, int32_t n, int32_t H, int32_t W,

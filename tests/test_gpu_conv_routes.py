@@ -175,6 +175,7 @@ def test_conv_route_bits_and_guards(lib, c):
                          _lib.FavDropoutDesc(-1, 0, 1.0, 0, 0, 1, 0))
     _lib.check(lib.fav_op_conv2d(C.byref(d), None))
     route = _lib.last_route()
+    assert _lib.route_conv2d(d) == (0, route) and _lib.last_route() == route     # the selector, asked without a launch, names what ran
     torch.cuda.synchronize()
     assert route == c.route
     assert bool((ybig[:GUARD] == GUARD_VALUE).all()) and bool((ybig[-GUARD:] == GUARD_VALUE).all()), "wrote outside the output"

@@ -38,6 +38,7 @@ def run_tail(lib, x, wb, bb, wc, bc, res, wa, ba, drop=None):
                          bad.data_ptr() if bad is not None else None, t1n.data_ptr() if wad is not None else None,
                          n, H, W, cmid, nred, drop or drop_desc())
     _lib.check(lib.fav_op_bottleneck_tail(C.byref(d), None))
+    assert _lib.route_bottleneck_tail(d) == (0, _lib.last_route()) and _lib.last_route() != ""     # the selector names what ran
     torch.cuda.synchronize()
     return host_f32(y), (host_f32(t1n) if wa is not None else None)
 
