@@ -11,5 +11,6 @@ from .calibration import (Calibration, fit_temperature, reliability, risk_covera
                           unpack_cells)
 from .corrupt import CORRUPTIONS, SEVERITY, Corruptor  # noqa: F401
 from .distributed import classify_sharded, shard_range  # noqa: F401
-from . import robustness, synth, weights  # noqa: F401
+from . import robustness, synth, views, weights  # noqa: F401
+from .views import View  # noqa: F401
 from .robustness import summarize  # noqa: F401

@@ -102,6 +102,16 @@ class FavCorruptionDesc(C.Structure):
                 ("first_frame_index", C.c_int64)]
 
 
+MAX_VIEWS = 64
+BORDER_REFLECT101, BORDER_REPLICATE, BORDER_ZERO = 0, 1, 2
+
+
+class FavView(C.Structure):
+    """fav_view: one test-time-augmentation view (24 bytes; views.View mirrors it)."""
+    _fields_ = [("flip_x", C.c_int32), ("flip_y", C.c_int32), ("transpose", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
+                ("border", C.c_int32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -139,6 +149,10 @@ _SIGNATURES = {
                                      C.c_int32, C.c_void_p, C.c_void_p]),
     "fav_set_temperature": (C.c_int, [C.c_void_p, C.c_float]),
     "fav_set_tau": (C.c_int, [C.c_void_p, C.c_float]),
+    "fav_set_conf_kind": (C.c_int, [C.c_void_p, C.c_int32]),
+    "fav_check_views": (C.c_int, [C.POINTER(FavView), C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    "fav_set_views": (C.c_int, [C.c_void_p, C.POINTER(FavView), C.c_int32]),
+    "fav_get_views": (C.c_int, [C.c_void_p, C.POINTER(FavView), C.c_int32, C.POINTER(C.c_int32)]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
@@ -180,6 +194,8 @@ _SIGNATURES = {
     "fav_corruption_taps": (C.c_int, [C.c_int32, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)]),
     "fav_op_corrupt_c": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(FavCorruptionDesc),
                                    C.c_void_p]),
+    "fav_op_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(FavView), C.c_int32,
+                               C.c_void_p]),
 }
 
 _lib = None

@@ -23,7 +23,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, weights as _weights
+from . import _lib, views as _views, weights as _weights
 from .corrupt import CORRUPTIONS
 
 _ARCH = {"resnet18_cifar": _lib.ARCH_RESNET18_CIFAR, "resnet50": _lib.ARCH_RESNET50, "vit_b16": _lib.ARCH_VIT_B16,
@@ -41,7 +41,7 @@ class Backend:
                  site_mask: int | None = None, temperature: float = 1.0, conf_kind: str = "max_softmax",
                  tau: float = 0.5, math_mode: str = "bf16", mean=None, std=None,
                  chunk_a: int = 0, chunk_b: int = 0, regroup_block: int = -1,
-                 tail_min_rows: int = 0, ens_grouped_max: int = 0, vit_streams: int = 0, stem_fused: int = 0):
+                 tail_min_rows: int = 0, ens_grouped_max: int = 0, vit_streams: int = 0, stem_fused: int = 0, views=None):
         import torch
         self._torch = torch
         self._h = None
@@ -78,6 +78,13 @@ class Backend:
         cfg.vit_streams, cfg.stem_fused = int(vit_streams), int(stem_fused)
         members = list(blob) if isinstance(blob, (list, tuple)) else None   # deep ensemble: one blob per member
         cfg.n_members = len(members) if members else 1
+        self.mc = cfg.site_mask != 0 and round(cfg.dropout_p * 256) > 0
+        views = list(views) if views else []
+        # mutual information over views alone: fav_create refuses the kind on a single-sample handle, so the handle is created
+        # with another kind and gets this one once the views are set
+        kind_after_views = None
+        if cfg.conf_kind == _lib.CONF_MUTUAL_INFO and len(views) >= 2 and cfg.n_members == 1 and not self.mc:
+            kind_after_views, cfg.conf_kind = conf_kind, _lib.CONF_MAX_SOFTMAX
         self.cfg = cfg
         h = C.c_void_p()
         _lib.check(self.lib.fav_create(C.byref(cfg), C.byref(h)))
@@ -92,9 +99,45 @@ class Backend:
             elif blob is None:
                 blob, self.weights_info = _weights.make_synthetic(arch, seed=seed_weights, num_classes=cfg.num_classes)
             self.load_weights(blob)
-        self.mc = cfg.site_mask != 0 and round(cfg.dropout_p * 256) > 0
-        self.T = cfg.n_samples if self.mc else max(1, cfg.n_members)
+        self._T_head = cfg.n_samples if self.mc else max(1, cfg.n_members)
+        self._views = ()
+        if views:
+            self.set_views(views)
+        if kind_after_views is not None:
+            self.set_conf_kind(kind_after_views)
         self._rules = None   # SignalAnalyzerHIP, created on the first analyze_frame
+
+    # -- test-time augmentation (views.py; include/fav.h fav_set_views) ----------------------------------------------------
+    @property
+    def views(self) -> tuple:
+        """The views in force (``views.View``), () when off."""
+        return self._views
+
+    @property
+    def T(self) -> int:
+        """The samples the head averages: MC-Dropout passes or ensemble members, times the views."""
+        return self._T_head * max(1, len(self._views))
+
+    @property
+    def frames_per_call(self) -> int:
+        """The most frames one call takes: max_batch // max(1, number of views)."""
+        return int(self.cfg.max_batch) // max(1, len(self._views))
+
+    def set_views(self, views):
+        """Classify every frame under each of ``views`` (a sequence of ``views.View``, e.g. ``views.hflip()``) and average
+        the softmax outputs as further samples, from the next call on; None or empty: off.  Every classify method then takes
+        at most ``frames_per_call`` frames a call and costs ``len(views)`` forward passes a frame.  Refused on a handle that
+        draws MC-Dropout masks."""
+        vs = list(views) if views else []
+        arr, n = _views.to_c_array(vs)
+        _lib.check(self.lib.fav_set_views(self._h, arr if n else None, n), self._h)
+        self._views = tuple(vs)
+
+    def set_conf_kind(self, kind: str):
+        """The confidence kind ("max_softmax", "entropy", "mutual_info") of the calls made from now on; "mutual_info" needs
+        at least two samples (``T``) and two classes."""
+        _lib.check(self.lib.fav_set_conf_kind(self._h, _CONF[kind]), self._h)
+        self.cfg.conf_kind = _CONF[kind]
 
     # -- lifecycle ------------------------------------------------------------
     def load_weights(self, blob: bytes, member: int = 0):
@@ -220,7 +263,7 @@ class Backend:
     def conformal_scores(self, images, labels, cp, first_index: int = 0):
         """Calibration scores s(y) of the true classes ``labels`` (int[n]) under ``cp`` (a ``conformal.Conformal``; its qhat
         is not used), fp32[n], NaN where a label lies outside [0, num_classes).  Frame i has global index first_index + i
-        (the key of a randomized score's draw); batches of max_batch frames.  torch CUDA frames in -> CUDA tensor out,
+        (the key of a randomized score's draw); batches of frames_per_call frames.  torch CUDA frames in -> CUDA tensor out,
         asynchronous on the current stream; numpy in -> numpy out, synchronous."""
         torch = self._torch
         img, host, n, layout, stream = self._classify_args(images)
@@ -230,7 +273,7 @@ class Backend:
         lab = (torch.from_numpy(np.asarray(labels)) if isinstance(labels, np.ndarray) else labels).to(dev, torch.int32).contiguous()
         out = torch.empty(n, dtype=torch.float32, device=dev)
         c = cp.to_c()
-        mb = int(self.cfg.max_batch)
+        mb = self.frames_per_call
         for b in range(0, n, mb):
             e = min(n, b + mb)
             _lib.check(self.lib.fav_conformal_scores(self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b,
@@ -304,7 +347,7 @@ class Backend:
         """The confidence head at every one of ``temperatures`` (1 to 32 of them) in one launch per batch
         (fav_classify_sweep): int32[n, K, 4] cells, ``calibration.unpack_cells`` -> label, confidence, nll, brier per
         (frame, temperature), ``labels`` (int[n]) being the frames' true classes.  The handle's own temperature is not
-        used.  Batches of max_batch frames; torch CUDA frames in -> CUDA tensor out, asynchronous on the current stream;
+        used.  Batches of frames_per_call frames; torch CUDA frames in -> CUDA tensor out, asynchronous on the current stream;
         numpy in -> numpy out, synchronous.  A frame that is non-finite at a temperature (include/fav.h) has label 0,
         confidence 0 and NaN nll / brier in that cell; the temperature fit refuses a set that holds one."""
         torch = self._torch
@@ -313,7 +356,7 @@ class Backend:
         lab = self._labels_on(labels, n, dev)
         t, tp = self._temps_c(temperatures)
         cells = torch.empty((n, t.size, 4), dtype=torch.int32, device=dev)
-        mb = int(self.cfg.max_batch)
+        mb = self.frames_per_call
         for b in range(0, n, mb):
             e = min(n, b + mb)
             _lib.check(self.lib.fav_classify_sweep(self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b,
@@ -337,7 +380,8 @@ class Backend:
         n = int(images.shape[0])
         need = 4 * self.T * n * ((int(self.cfg.num_classes) + 3) // 4 * 4)
         if need > int(logits_budget_bytes):
-            raise ValueError(f"calibrate_temperature keeps the calibration set's logits on the device: {self.T} samples x {n} "
+            raise ValueError(f"calibrate_temperature keeps the calibration set's logits on the device: {self.T} samples (views "
+                             f"included) x {n} "
                              f"frames x {self.cfg.num_classes} classes = {need} bytes ({need / 2**30:.2f} GiB) exceed "
                              f"logits_budget_bytes = {int(logits_budget_bytes)}; calibrate on fewer frames")
         kept = []
@@ -353,8 +397,8 @@ class Backend:
         return fit_temperature(nll_of, lo=lo, hi=hi, rtol=rtol)
 
     def _detect_batched(self, images, first_index: int = 0):
-        """classify_detect over batches of max_batch frames -> numpy (labels, conf)."""
-        n, mb = int(images.shape[0]), int(self.cfg.max_batch)
+        """classify_detect over batches of frames_per_call frames -> numpy (labels, conf)."""
+        n, mb = int(images.shape[0]), self.frames_per_call
         out_l, out_c = [], []
         for b in range(0, n, mb):
             l, c, _, _ = self.classify_detect(images[b:min(n, b + mb)], int(first_index) + b)
@@ -384,7 +428,7 @@ class Backend:
         """How accuracy, confidence and the failure flag hold up as corruptions get worse: a ``"clean"`` row and one row
         per (kind, severity) of ``corruptions`` (default ``corrupt.CORRUPTIONS``) -> ``{("clean", 0): row, (kind, s): row}``,
         each row ``robustness.summarize`` at the handle's current temperature and tau (``robustness.table`` prints them).
-        ``frames_u8``: labelled uint8 frames (numpy or CUDA); they are corrupted on the device in batches of max_batch
+        ``frames_u8``: labelled uint8 frames (numpy or CUDA); they are corrupted on the device in batches of frames_per_call
         (``Corruptor(seed).imagenet_c``, frame i at global index first_index + i) and each batch runs through
         ``calibration_sweep`` as fp32 frames.  The handle is not changed."""
         from .calibration import unpack_cells
@@ -395,7 +439,7 @@ class Backend:
         if self._layout_of(frames_u8) != _lib.LAYOUT_NHWC_U8:
             raise TypeError("robustness_report takes uint8 frames")
         img, _ = self._frames_on_device(frames_u8)
-        n, mb = int(img.shape[0]), int(self.cfg.max_batch)
+        n, mb = int(img.shape[0]), self.frames_per_call
         lab = self._labels_on(labels, n, img.device)
         lab_host = lab.cpu().numpy()
         cor = Corruptor(seed=seed)

@@ -25,6 +25,7 @@
 #include "fav_corrupt_c.hpp"
 #include "fav_plan.hpp"
 #include "fav_route.hpp"
+#include "fav_views.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -139,6 +140,12 @@ struct fav_handle {
     // stream and host_stream, or two torch streams) are then ordered on the device instead of racing on the activations.
     hipEvent_t ev_last = nullptr;
     bool ev_last_set = false;
+    // Test-time augmentation (fav_set_views): the views in force (n_views = 0: off) and the buffer a call's frames are expanded
+    // into, [n_views][n] frames of the call's layout; allocated by the first call that needs it, for max_batch frames
+    fav_view views[FAV_MAX_VIEWS];
+    int n_views = 0;
+    void* view_buf = nullptr;
+    size_t view_buf_bytes = 0;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -1031,6 +1038,7 @@ void free_all(fav_handle* h) {
     for (size_t i = 0; i + 1 < h->phase_out.size(); ++i) if (h->phase_out[i]) (void)hipFree(h->phase_out[i]);
     if (h->logits) (void)hipFree(h->logits);
     if (h->host_stage) (void)hipFree(h->host_stage);
+    if (h->view_buf) (void)hipFree(h->view_buf);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
@@ -1095,6 +1103,41 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
     FAV_VIT_TRY(gemm(li + 1, B.v_cls, 1, nullptr, 0, B.logits, 1));
 #undef FAV_VIT_TRY
     return FAV_OK;
+}
+
+// The two launches behind fav_op_views and a handle's views (fav_views.hpp): the views without transpose, those with.  The
+// arguments have been checked (fav_check_views, the sizes, the alignment).
+template <class U>
+void launch_views_of(const U* in, U* out, int n, int H, int W, const fav_view* views, int n_views, hipStream_t s) {
+    ViewsArg va;
+    memset(&va, 0, sizeof va);
+    memcpy(va.v, views, (size_t)n_views * sizeof(fav_view));
+    const long long max_grid = (1ll << 24) - 1;
+    for (int tr = 0; tr < 2; ++tr) {
+        va.count = 0;
+        for (int a = 0; a < n_views; ++a)
+            if (views[a].transpose == tr) va.idx[va.count++] = (uint8_t)a;
+        if (!va.count) continue;
+        if (!tr) {
+            const int G = 1 + (W + 3) / 4;
+            const int parts = (int)(((long long)H * G + 255) / 256);
+            const long long blocks = (long long)va.count * n * parts;
+            const size_t units = (size_t)n * H * W * 3;
+            const U* lo = (const U*)(((uintptr_t)in + 3) & ~(uintptr_t)3);
+            const U* hi = (const U*)((uintptr_t)(in + units) & ~(uintptr_t)3);
+            hipLaunchKernelGGL((views_straight_kernel<U>), dim3((unsigned)std::min(blocks, max_grid)), dim3(256), 0, s, in, out, n, H,
+                               W, va, parts, fastdiv_make((uint32_t)G), blocks, lo, hi);
+        } else {
+            const int t1 = (H + VW_TILE - 1) / VW_TILE;
+            const long long tiles = (long long)va.count * n * t1 * t1;
+            hipLaunchKernelGGL((views_transpose_kernel<U>), dim3((unsigned)std::min(tiles, max_grid)), dim3(256), 0, s, in, out, n, H,
+                               va, t1, tiles);
+        }
+    }
+}
+void launch_views(const void* in, void* out, int n, int H, int W, int layout, const fav_view* views, int n_views, hipStream_t s) {
+    if (layout == FAV_LAYOUT_NHWC_U8) launch_views_of((const uint8_t*)in, (uint8_t*)out, n, H, W, views, n_views, s);
+    else launch_views_of((const uint32_t*)in, (uint32_t*)out, n, H, W, views, n_views, s);
 }
 
 }  // namespace
@@ -1424,22 +1467,24 @@ fav_status run_lanes(fav_handle* h, const Frames& f, hipStream_t s) {
     return st;
 }
 
-fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out, hipStream_t s) {
+// views: the frames are `views` views of f.n / views frames each, ordered [view][frame]; the head then averages views times as many
+// samples on f.n / views frames (sample m * views + a: member or pass m under view a)
+fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out, hipStream_t s, int views = 1) {
     h->ev_used = h->profiling ? h->ev_used : 0;
     fav_status st;
     if (h->vit) st = run_vit_call(h, f, s);
     else if (will_group(h->cfg, h->n_members, h->plan, f.n)) st = run_grouped(h, f, s);
     else st = run_lanes(h, f, s);
     if (st != FAV_OK) return st;
-    const int T_head = h->n_members > 1 ? h->n_members : h->plan.T_eff;
-    if (const char* e = launch_head(h, h->logits, T_head, f.n, h->cfg.num_classes, h->plan.cpad, h->cfg.temperature,
+    const int T_head = (h->n_members > 1 ? h->n_members : h->plan.T_eff) * views, n_head = f.n / views;
+    if (const char* e = launch_head(h, h->logits, T_head, n_head, h->cfg.num_classes, h->plan.cpad, h->cfg.temperature,
                                     h->cfg.conf_kind, h->cfg.tau, out, s)) {
         h->err = e;
         return FAV_ERR_INVALID_ARG;
     }
     HIP_TRY(h, hipGetLastError());
     h->last_T = T_head;
-    h->last_n = f.n;
+    h->last_n = n_head;
     return FAV_OK;
 }
 
@@ -1452,13 +1497,35 @@ fav_status classify_gate(const char* who, fav_handle* h, const char* bad, const 
     if (!h) return FAV_ERR_INVALID_ARG;
     if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", who); return FAV_ERR_NO_WEIGHTS; }
     if (bad) { h->err = fmt("%s: %s", who, bad); return FAV_ERR_INVALID_ARG; }
+    const int A = h->n_views;       // read once: this call's views
+    if (A > 0 && (n < 1 || (long long)n * A > h->cfg.max_batch)) {
+        h->err = fmt("%s: n=%d frames x n_views=%d views outside [1, max_batch=%d]", who, n, A, h->cfg.max_batch);
+        return FAV_ERR_INVALID_ARG;
+    }
     if (n < 1 || n > h->cfg.max_batch) { h->err = fmt("%s: n=%d outside [1, max_batch=%d]", who, n, h->cfg.max_batch); return FAV_ERR_INVALID_ARG; }
     if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) { h->err = fmt("%s: unknown layout", who); return FAV_ERR_INVALID_ARG; }
     if (first_index < 0 || first_index + n > 0xFFFFFFFFll) { h->err = fmt("%s: first_image_index out of range", who); return FAV_ERR_INVALID_ARG; }
+    if (A > 0 && layout == FAV_LAYOUT_NHWC_F32 && ((uintptr_t)images & 3)) { h->err = fmt("%s: fp32 frames must be 4-byte aligned", who); return FAV_ERR_INVALID_ARG; }
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (A > 0) {
+        // the view buffer: max_batch frames of this call's layout.  Growing it (fp32 frames after uint8 ones) frees the old one,
+        // which waits for the device
+        const size_t need = (size_t)h->cfg.max_batch * h->cfg.in_h * h->cfg.in_w * 3 * (layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4);
+        if (h->view_buf_bytes < need) {
+            if (h->view_buf) { HIP_TRY(h, hipFree(h->view_buf)); h->view_buf = nullptr; h->view_buf_bytes = 0; }
+            HIP_TRY(h, hipMalloc(&h->view_buf, need));
+            h->view_buf_bytes = need;
+        }
+    }
     if (fav_status st = wait_last_use(h, s)) return st;
-    const fav_status st = classify_on_stream(h, Frames{images, layout, n, first_index}, out, s);
+    fav_status st;
+    if (A > 0) {
+        launch_views(images, h->view_buf, n, h->cfg.in_h, h->cfg.in_w, layout, h->views, A, s);
+        st = classify_on_stream(h, Frames{h->view_buf, layout, n * A, first_index}, out, s, A);
+    } else {
+        st = classify_on_stream(h, Frames{images, layout, n, first_index}, out, s);
+    }
     route_clear();            // the report speaks of fav_op_* launches only
     mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
     return st;
@@ -1540,6 +1607,78 @@ fav_status fav_set_tau(fav_handle* h, float tau) {
     if (!h) return FAV_ERR_INVALID_ARG;
     if (std::isnan(tau)) { h->err = "fav_set_tau: tau is NaN"; return FAV_ERR_INVALID_ARG; }
     h->cfg.tau = tau;
+    return FAV_OK;
+}
+
+namespace {
+// the samples the head averages on a handle with n_views views (0: off)
+int head_samples(const fav_handle* h, int n_views) {
+    return (h->n_members > 1 ? h->n_members : h->plan.T_eff) * std::max(1, n_views);
+}
+}  // namespace
+
+fav_status fav_check_views(const fav_view* views, int32_t n_views, int32_t H, int32_t W, char* err, size_t err_cap) {
+    static_assert(sizeof(fav_view) == 24, "fav_view is 6 dwords");
+    static_assert(FAV_MAX_VIEWS == VW_MAX_VIEWS && sizeof(ViewsArg) <= 2048, "the views travel in the kernel arguments");
+    if (err && err_cap) err[0] = 0;
+    const std::string why = views_error(views, n_views, H, W);
+    if (why.empty()) return FAV_OK;
+    if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
+    return FAV_ERR_INVALID_ARG;
+}
+
+fav_status fav_set_views(fav_handle* h, const fav_view* views, int32_t n_views) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (n_views != 0) {
+        char why[256];
+        if (fav_check_views(views, n_views, h->cfg.in_h, h->cfg.in_w, why, sizeof why) != FAV_OK) {
+            h->err = fmt("fav_set_views: %s", why);
+            return FAV_ERR_INVALID_ARG;
+        }
+        if (!h->vit && h->plan.has_mc) {
+            h->err = "fav_set_views: this handle draws MC-Dropout masks, which are keyed by batch row; views are not supported on it";
+            return FAV_ERR_UNSUPPORTED;
+        }
+        // the view kernels hold a frame's work items in 32 bits (the limit fav_op_views states)
+        if ((long long)h->cfg.in_h * h->cfg.in_w > 0x7FFFFFFFll / 12) {
+            h->err = fmt("fav_set_views: in_h * in_w = %lld above (2^31 - 1) / 12 pixels", (long long)h->cfg.in_h * h->cfg.in_w);
+            return FAV_ERR_INVALID_ARG;
+        }
+        if (n_views > h->cfg.max_batch) {
+            h->err = fmt("fav_set_views: n_views=%d above max_batch=%d: not even one frame fits a call", n_views, h->cfg.max_batch);
+            return FAV_ERR_INVALID_ARG;
+        }
+        if (head_samples(h, n_views) > 4096) {
+            h->err = fmt("fav_set_views: %d members x %d views is above the heads' limit of 4096 samples", head_samples(h, 0), n_views);
+            return FAV_ERR_INVALID_ARG;
+        }
+    }
+    if (h->cfg.conf_kind == FAV_CONF_MUTUAL_INFO && head_samples(h, n_views) < 2) {
+        h->err = fmt("fav_set_views: the confidence kind is FAV_CONF_MUTUAL_INFO and %d view(s) would leave it %d sample; change the "
+                     "kind first (fav_set_conf_kind)", n_views, head_samples(h, n_views));
+        return FAV_ERR_INVALID_ARG;
+    }
+    if (n_views) memcpy(h->views, views, (size_t)n_views * sizeof(fav_view));   // read on the host when a call is enqueued
+    h->n_views = n_views;
+    return FAV_OK;
+}
+
+fav_status fav_get_views(const fav_handle* h, fav_view* out, int32_t cap, int32_t* n_out) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (n_out) *n_out = h->n_views;
+    if (out) for (int a = 0; a < cap && a < h->n_views; ++a) out[a] = h->views[a];
+    return FAV_OK;
+}
+
+fav_status fav_set_conf_kind(fav_handle* h, int32_t conf_kind) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (conf_kind < 0 || conf_kind > 2) { h->err = fmt("fav_set_conf_kind: conf_kind=%d is not a fav_conf_kind", conf_kind); return FAV_ERR_INVALID_ARG; }
+    if (conf_kind == FAV_CONF_MUTUAL_INFO && (head_samples(h, h->n_views) < 2 || h->cfg.num_classes < 2)) {
+        h->err = fmt("fav_set_conf_kind: FAV_CONF_MUTUAL_INFO (mutual information) needs at least 2 samples and 2 classes; this handle "
+                     "has T=%d (views included), num_classes=%d", head_samples(h, h->n_views), h->cfg.num_classes);
+        return FAV_ERR_INVALID_ARG;
+    }
+    h->cfg.conf_kind = conf_kind;   // read on the host when a head is launched
     return FAV_OK;
 }
 
@@ -1972,6 +2111,28 @@ fav_status fav_op_corrupt_c(const uint8_t* frames, float* out, int32_t n, int32_
         break;
     }
     }
+    return op_done(nullptr);
+}
+
+fav_status fav_op_views(const void* frames, void* out, int32_t n, int32_t H, int32_t W, int32_t layout, const fav_view* views,
+                        int32_t n_views, void* stream) {
+    const char* fn = "fav_op_views";
+    route_clear();
+    if (!frames || !out) return corruption_rejected(fn, "null pointer");
+    if (n < 1 || H < 1 || W < 1) return corruption_rejected(fn, "n, H and W must be at least 1");
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return corruption_rejected(fn, "unknown layout");
+    const std::string why = views_error(views, n_views, H, W);
+    if (!why.empty()) return corruption_rejected(fn, why.c_str());
+    const size_t esz = layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4;
+    if (((uintptr_t)frames | (uintptr_t)out) % esz != 0) return corruption_rejected(fn, "fp32 frames and out must be 4-byte aligned");
+    // the kernels hold a frame's work items in 32 bits: H * (1 + ceil(W / 4)) <= H * W / 4 + 2 H stays below 2^31
+    if ((long long)H * W > 0x7FFFFFFFll / 12) return corruption_rejected(fn, "H * W above (2^31 - 1) / 12 pixels");
+    const long long frame_bytes = (long long)H * W * 3 * (long long)esz;
+    if ((long long)n * n_views > 0x7FFFFFFFll) return corruption_rejected(fn, "n * n_views above 2^31 - 1");
+    const uintptr_t in_lo = (uintptr_t)frames, in_hi = in_lo + (uintptr_t)frame_bytes * (uintptr_t)n;
+    const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + (uintptr_t)frame_bytes * (uintptr_t)n * (uintptr_t)n_views;
+    if (in_lo < out_hi && out_lo < in_hi) return corruption_rejected(fn, "out overlaps frames");
+    launch_views(frames, out, n, H, W, layout, views, n_views, (hipStream_t)stream);
     return op_done(nullptr);
 }
 

@@ -55,7 +55,7 @@ typedef enum fav_layout { FAV_LAYOUT_NHWC_U8 = 0, FAV_LAYOUT_NHWC_F32 = 1 } fav_
 typedef enum fav_arch { FAV_ARCH_RESNET18_CIFAR = 0, FAV_ARCH_RESNET50 = 1, FAV_ARCH_VIT_B16 = 2, FAV_ARCH_VIT_TINY = 3 } fav_arch;
 /* FAV_CONF_MUTUAL_INFO: conf = 1 - MI / ln(min(C, T)), the epistemic part of the samples' spread (fav_uncertainty below);
  * fav_create accepts it only when the head averages T >= 2 samples (MC-Dropout with an active site and round(256 p) > 0,
- * or n_members > 1) over num_classes >= 2. */
+ * or n_members > 1) over num_classes >= 2; a single-sample handle gets there with fav_set_views, then fav_set_conf_kind. */
 typedef enum fav_conf_kind { FAV_CONF_MAX_SOFTMAX = 0, FAV_CONF_ENTROPY = 1, FAV_CONF_MUTUAL_INFO = 2 } fav_conf_kind;
 /* FAV_MATH_BF16: bf16 MFMA, fp32 accumulate (production).
  * FAV_MATH_F32_EXACT: same bf16 operands fed to the fp32-input MFMA, whose
@@ -248,6 +248,47 @@ fav_status fav_classify_sweep(fav_handle* h, const void* images_dev, int32_t n, 
  * the setter returns; calls already enqueued keep the old value.  A rejected value leaves the handle as it was. */
 fav_status fav_set_temperature(fav_handle* h, float temperature);
 fav_status fav_set_tau(fav_handle* h, float tau);
+/* The third live setter: the handle's fav_conf_kind, for calls enqueued after it returns.  Kinds 0 and 1 are always accepted;
+ * FAV_CONF_MUTUAL_INFO needs num_classes >= 2 and a current sample count (the head's T times max(1, n_views), see
+ * fav_set_views below) of at least 2.  fav_create's own rule is unchanged.  A rejected value leaves the handle as it was. */
+fav_status fav_set_conf_kind(fav_handle* h, int32_t conf_kind);
+
+/* ---- Test-time augmentation: the third source of samples beside MC-Dropout and a deep ensemble.
+ * A view is pure data movement on [H][W][3] frames of either layout; every element is copied bit for bit (an fp32 NaN
+ * included: sanitising stays the stem's job).  For output pixel (y, x):
+ *   1. (u, v) = (y - dy, x - dx)
+ *   2. the border rule, u against H and v against W.  FAV_BORDER_REFLECT101: period 2(n-1), at any distance, a dimension of
+ *      1 maps to index 0 (the defocus kernel's rule); FAV_BORDER_REPLICATE: the index is clamped; FAV_BORDER_ZERO: a pixel
+ *      whose u or v falls outside the frame is 0 (0.0f) in all three channels
+ *   3. flip_y: u = H-1-u; flip_x: v = W-1-v
+ *   4. transpose: u and v are swapped (needs H == W)
+ *   5. out[y][x][c] = in[u][v][c]
+ * Ranges: the three flags 0 or 1; |dy|, |dx| <= 65535; border a fav_border value; 1 <= n_views <= FAV_MAX_VIEWS. */
+typedef enum fav_border { FAV_BORDER_REFLECT101 = 0, FAV_BORDER_REPLICATE = 1, FAV_BORDER_ZERO = 2 } fav_border;
+typedef struct fav_view { int32_t flip_x, flip_y, transpose, dy, dx, border; } fav_view;   /* 24 bytes */
+#define FAV_MAX_VIEWS 64
+/* Host only, no device: the ranges above for views of H x W frames (a transpose with H != W included), the one place these
+ * rules live; fav_op_views and fav_set_views call it first.  FAV_ERR_INVALID_ARG and a message in err (may be NULL) otherwise. */
+fav_status fav_check_views(const fav_view* views, int32_t n_views, int32_t H, int32_t W, char* err, size_t err_cap);
+/* The handle's views (copied; n_views = 0, the default: off).  Like temperature and tau they are read on the host when a call
+ * is enqueued: they take effect for calls enqueued after the setter returns, and calls already enqueued keep theirs.  While
+ * views are set, EVERY fav_classify* entry point (fav_classify_host, fav_conformal_scores and fav_classify_sweep included)
+ *   - accepts 1 <= n with n * n_views <= max_batch (FAV_ERR_INVALID_ARG with the three numbers otherwise),
+ *   - expands the n frames into n * n_views view frames, ordered [view][frame], in a buffer the handle owns (max_batch frames
+ *     of the call's layout, allocated on the first such call), on the call's stream, behind the previous use of the handle.
+ *     A handle that has served uint8 frames and then gets fp32 frames frees that buffer and allocates the larger one: this
+ *     one call waits for the whole device (hipFree) before it enqueues anything; later calls in either layout do not,
+ *   - runs the unchanged forward pass on them and the requested head on n frames with T = T_head * n_views samples: sample
+ *     s = m * n_views + a is member (or pass) m under view a.  first_image_index, the conformal draw's key, stays the caller's.
+ * fav_get_logits then reports T = T_head * n_views and n.  With no views set nothing changes.
+ * Refused: a handle that draws dropout masks (an MC-Dropout site active with round(256 p) > 0), FAV_ERR_UNSUPPORTED - the masks
+ * are keyed by batch row, and a shard-invariant key for view rows would change the mask kernels; single-pass ResNets,
+ * ensembles and both ViT archs are supported.  Also refused (FAV_ERR_INVALID_ARG): what fav_check_views refuses for
+ * in_h x in_w frames; in_h * in_w above (2^31 - 1) / 12; n_views > max_batch; members x n_views > 4096 (the heads' limit); and turning the views off, or down
+ * to one, while the confidence kind is FAV_CONF_MUTUAL_INFO and fewer than 2 samples would be left (change the kind first). */
+fav_status fav_set_views(fav_handle* h, const fav_view* views, int32_t n_views);
+/* The views in force: *n_out (may be NULL) = their number, the first min(cap, number) of them copied to out (may be NULL). */
+fav_status fav_get_views(const fav_handle* h, fav_view* out, int32_t cap, int32_t* n_out);
 
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
@@ -259,7 +300,8 @@ fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, 
 fav_status fav_get_logits(fav_handle* h, float* logits_dev, int32_t* t_out, int32_t* n_out, void* hip_stream);
 
 /* Per-kernel-class timing with HIP events on the launch stream (bench.py's
- * roofline leg).  Classes: see fav_kernel_class. */
+ * roofline leg).  Classes: see fav_kernel_class.  The launches that make a call's views (fav_set_views) are booked in no
+ * class: the profile speaks of the forward pass and the head only. */
 typedef enum fav_kernel_class {
     FAV_K_STEM = 0, FAV_K_CONV = 1, FAV_K_MAXPOOL = 2, FAV_K_AVGPOOL = 3,
     FAV_K_DROPOUT = 4, FAV_K_HEAD = 5, FAV_K_COUNT = 6
@@ -518,6 +560,16 @@ fav_status fav_corruption_taps(int32_t kind, float a, float b, float* taps, int3
  * above) launches nothing and leaves a message that names the function in fav_last_error(NULL). */
 fav_status fav_op_corrupt_c(const uint8_t* frames_dev, float* out_dev, int32_t n, int32_t H, int32_t W,
                             const fav_corruption_desc* d, void* hip_stream);
+
+/* ---- The views defined above fav_set_views, made on the device: frames [n][H][W][3] of `layout` -> out [n_views][n][H][W][3]
+ * of the same element type, view a of frame i at row a*n + i.  The views travel in the kernel arguments: views_host (at most
+ * 1536 bytes) is read before the call returns.  No allocation, no workspace, no synchronisation; at most two launches (the
+ * views without transpose, those with).  Pointers need the element type's alignment only (any byte for uint8, 4 for fp32).
+ * A refused call (FAV_ERR_INVALID_ARG: a NULL pointer, n, H or W below 1, an unknown layout, what fav_check_views refuses, a
+ * misaligned fp32 pointer, H * W above (2^31 - 1) / 12, n * n_views above 2^31 - 1, out overlapping frames) launches nothing and leaves a message
+ * that names the function in fav_last_error(NULL). */
+fav_status fav_op_views(const void* frames_dev, void* out_dev, int32_t n, int32_t H, int32_t W, int32_t layout,
+                        const fav_view* views_host, int32_t n_views, void* hip_stream);
 
 #ifdef __cplusplus
 }
