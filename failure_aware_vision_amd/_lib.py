@@ -112,6 +112,18 @@ class FavView(C.Structure):
                 ("border", C.c_int32)]
 
 
+class FavOodModel(C.Structure):
+    """fav_ood_model: the Mahalanobis model as a whitening projection, host pointers (ood.OODModel.to_c fills it)."""
+    _fields_ = [("struct_size", C.c_uint32), ("D", C.c_int32), ("k", C.c_int32), ("R", C.c_int32),
+                ("mu", C.POINTER(C.c_float)), ("P", C.POINTER(C.c_float)), ("M", C.POINTER(C.c_float)),
+                ("class_id", C.POINTER(C.c_int32)), ("threshold", C.c_float)]
+
+
+class FavOodRecord(C.Structure):
+    """fav_ood_record: one 16-byte score per frame (ood.unpack_records reads it as int32[n, 4])."""
+    _fields_ = [("min_dist", C.c_float), ("min_class", C.c_int32), ("label_dist", C.c_float), ("ood", C.c_int32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -153,6 +165,15 @@ _SIGNATURES = {
     "fav_check_views": (C.c_int, [C.POINTER(FavView), C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
     "fav_set_views": (C.c_int, [C.c_void_p, C.POINTER(FavView), C.c_int32]),
     "fav_get_views": (C.c_int, [C.c_void_p, C.POINTER(FavView), C.c_int32, C.POINTER(C.c_int32)]),
+    "fav_set_feature_tap": (C.c_int, [C.c_void_p, C.c_int32]),
+    "fav_get_features": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.c_void_p]),
+    "fav_check_ood_model": (C.c_int, [C.POINTER(FavOodModel), C.c_int32, C.c_char_p, C.c_size_t]),
+    "fav_set_ood": (C.c_int, [C.c_void_p, C.POINTER(FavOodModel)]),
+    "fav_classify_ood": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_ood_score": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),

@@ -100,6 +100,7 @@ class Backend:
                 blob, self.weights_info = _weights.make_synthetic(arch, seed=seed_weights, num_classes=cfg.num_classes)
             self.load_weights(blob)
         self._T_head = cfg.n_samples if self.mc else max(1, cfg.n_members)
+        self._tap, self._ood = False, None   # the caller's own feature tap; the ood.OODModel in force
         self._views = ()
         if views:
             self.set_views(views)
@@ -488,6 +489,111 @@ class Backend:
         stream = torch.cuda.current_stream(out.device).cuda_stream
         _lib.check(self.lib.fav_get_logits(self._h, out.data_ptr(), None, None, stream), self._h)
         return out
+
+    # -- feature tap and feature-space OOD scoring (ood.py; include/fav.h fav_set_ood) -----------------------------------
+    def set_feature_tap(self, enable: bool):
+        """Keep the rows the final fc layer reads (fav_set_feature_tap) from the next call on; ``features()`` reads them.
+        Turning it off is refused while an OOD model is set, which reads it."""
+        _lib.check(self.lib.fav_set_feature_tap(self._h, 1 if enable else 0), self._h)
+        self._tap = bool(enable)
+
+    def features(self):
+        """fp32 [S, n, D] features of the last classify call made with the tap on (torch CUDA tensor), indexed like
+        ``logits()``: the pooled features the fc layer read (post-dropout when the pooled-feature site is active), or the
+        ViT's final class tokens."""
+        torch = self._torch
+        s, n, d = C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(self.lib.fav_get_features(self._h, None, C.byref(s), C.byref(n), C.byref(d), None), self._h)
+        out = torch.empty((s.value, n.value, d.value), dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        _lib.check(self.lib.fav_get_features(self._h, out.data_ptr(), None, None, None, stream), self._h)
+        return out
+
+    @property
+    def ood_model(self):
+        """The ``ood.OODModel`` in force, None when off."""
+        return self._ood
+
+    def fit_ood(self, frames, labels, **kw):
+        """Fit an ``ood.OODModel`` on labelled in-distribution frames: batches of frames_per_call frames run through the
+        classifier with the tap on, the mean over the samples of each frame's features goes to ``ood.fit_mahalanobis``
+        (``k``, ``shrinkage``).  The handle is left as it was: see ``set_ood``."""
+        from .ood import fit_mahalanobis
+        n, mb = int(frames.shape[0]), self.frames_per_call
+        lab = np.asarray(labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()).ravel()
+        if lab.shape[0] != n:
+            raise ValueError("one label per frame")
+        own_tap = self._ood is None and not self._tap
+        if own_tap:
+            self.set_feature_tap(True)
+        try:
+            rows = []
+            for b in range(0, n, mb):
+                self.classify_detect(frames[b:min(n, b + mb)], b)
+                rows.append(self.features().to(self._torch.float64).mean(dim=0).cpu().numpy())
+        finally:
+            if own_tap:
+                self.set_feature_tap(False)
+        return fit_mahalanobis(np.concatenate(rows), lab, **kw)
+
+    def set_ood(self, model):
+        """Adopt an ``ood.OODModel`` (fav_set_ood: copied to the device, the tap goes on), or None: off.  Refused on a deep
+        ensemble, and for a model whose D is not this arch's feature width."""
+        if model is None:
+            _lib.check(self.lib.fav_set_ood(self._h, None), self._h)
+        else:
+            c = model.to_c()
+            _lib.check(self.lib.fav_set_ood(self._h, C.byref(c)), self._h)
+        self._ood = model
+
+    def classify_ood(self, images, first_index: int = 0) -> dict:
+        """frames -> ``label``, ``conf``, ``fail``, ``score`` as ``classify_detect`` gives them, plus the OOD record of each
+        frame (fav_classify_ood): ``min_dist`` (squared Mahalanobis distance to the nearest class mean), ``nearest_class``,
+        ``label_dist`` (the distance to the predicted class; NaN when the model has no row for it) and ``ood`` (not
+        min_dist <= threshold).  torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in ->
+        numpy out, synchronous."""
+        from .ood import OOD_RECORD_DWORDS, unpack_records
+        torch = self._torch
+        img, host, n, layout, stream = self._classify_args(images)
+        dev = img.device
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        conf = torch.empty(n, dtype=torch.float32, device=dev)
+        fail = torch.empty(n, dtype=torch.uint8, device=dev)
+        score = torch.empty(n, dtype=torch.float32, device=dev)
+        rec = torch.empty((n, OOD_RECORD_DWORDS), dtype=torch.int32, device=dev)
+        _lib.check(self.lib.fav_classify_ood(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
+                                             conf.data_ptr(), fail.data_ptr(), score.data_ptr(), rec.data_ptr(), stream), self._h)
+        if host:
+            labels, conf, fail, score, rec = (t.cpu().numpy() for t in (labels, conf, fail, score, rec))
+        return dict(unpack_records(rec), label=labels, conf=conf, fail=fail, score=score)
+
+    def _min_dists(self, frames) -> np.ndarray:
+        n, mb = int(frames.shape[0]), self.frames_per_call
+        out = []
+        for b in range(0, n, mb):
+            d = self.classify_ood(frames[b:min(n, b + mb)], b)["min_dist"]
+            out.append(d if isinstance(d, np.ndarray) else d.cpu().numpy())
+        return np.concatenate(out)
+
+    def calibrate_ood(self, frames, tpr: float = 0.95) -> float:
+        """Set the model's threshold so that at least ``tpr`` of these in-distribution frames pass, and return it."""
+        if self.ood_model is None:
+            raise ValueError("calibrate_ood needs a model: set_ood first")
+        thr = self.ood_model.threshold_for_tpr(self._min_dists(frames), tpr)
+        self.set_ood(self.ood_model.with_threshold(thr))
+        return thr
+
+    def ood_report(self, id_frames, ood_frames) -> dict:
+        """How well min_dist separates ``ood_frames`` from ``id_frames``: auroc, fpr_at_tpr95, the mean distances and, at the
+        model's current threshold, the share of each set that is flagged."""
+        if self.ood_model is None:
+            raise ValueError("ood_report needs a model: set_ood first")
+        from .ood import OODModel
+        a, b = self._min_dists(id_frames), self._min_dists(ood_frames)
+        thr = self.ood_model.threshold
+        return dict(auroc=OODModel.auroc(a, b), fpr_at_tpr95=OODModel.fpr_at_tpr(a, b, 0.95),
+                    id_mean_dist=float(a.mean()), ood_mean_dist=float(b.mean()), threshold=thr,
+                    id_flagged=float(np.mean(~(a <= thr))), ood_flagged=float(np.mean(~(b <= thr))), n_id=int(a.size), n_ood=int(b.size))
 
     # -- profiling (bench.py roofline leg) ----------------------------------------
     def set_profiling(self, enable: bool):

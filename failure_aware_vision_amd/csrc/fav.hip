@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +27,7 @@
 #include "fav_plan.hpp"
 #include "fav_route.hpp"
 #include "fav_views.hpp"
+#include "fav_ood.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -146,6 +148,16 @@ struct fav_handle {
     int n_views = 0;
     void* view_buf = nullptr;
     size_t view_buf_bytes = 0;
+    // Feature tap (fav_set_feature_tap): while on, every pass copies the rows its fc launch reads into feat_buf, bf16
+    // [T_head][max_batch][feat_D] at most, indexed [sample][frame] like the logits; allocated by the setter.  feat_T / feat_n:
+    // the samples and frames of the last call that filled it (0: none yet)
+    bool tap = false, tap_by_ood = false;
+    void* feat_buf = nullptr;
+    int feat_D = 0, feat_T = 0, feat_n = 0;
+    // OOD model (fav_set_ood): the device copy, P and M transposed (fav_ood.hpp); ood_on: one is set
+    struct OodDev { float *mu = nullptr, *Pt = nullptr, *Mt = nullptr; int32_t* cls = nullptr; int D = 0, k = 0, R = 0; float threshold = 0.f; };
+    OodDev ood;
+    bool ood_on = false;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -977,6 +989,13 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
                     d.relu = o.relu; d.out_f32 = o.out_f32; d.math_mode = c.math_mode;
                     d.drop = dd;
                     const int ldy = o.out_f32 ? L.cout_pad : L.cout;
+                    if (h->tap && last && k + 1 == p.op_end) {
+                        // the feature tap: the rows the fc reads, to [member][virtual frame] of feat_buf, in front of the launch
+                        const size_t row = (size_t)o.C * 2, member_rows = (size_t)n * (p.suffix ? h->plan.T_eff : 1);
+                        for (int g = 0; g < lane.groups; ++g)
+                            HIP_TRY(h, hipMemcpyAsync((char*)h->feat_buf + ((size_t)(lane.member + g) * member_rows + (size_t)v0) * row,
+                                                      (const char*)d.x + (long long)g * G.x, (size_t)cn * row, hipMemcpyDeviceToDevice, s));
+                    }
                     if (const char* e = launch_conv(h, d, L.cout_pad, ldy, false, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 }
@@ -1039,6 +1058,8 @@ void free_all(fav_handle* h) {
     if (h->logits) (void)hipFree(h->logits);
     if (h->host_stage) (void)hipFree(h->host_stage);
     if (h->view_buf) (void)hipFree(h->view_buf);
+    if (h->feat_buf) (void)hipFree(h->feat_buf);
+    for (void* q : {(void*)h->ood.mu, (void*)h->ood.Pt, (void*)h->ood.Mt, (void*)h->ood.cls}) if (q) (void)hipFree(q);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
@@ -1100,6 +1121,8 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
     }
     const LayerWeights& lnf = h->weights[li];
     FAV_VIT_TRY(launch_layernorm(h, B.v_x, (long long)ntok * D, (const float*)lnf.w_m[0], lnf.b_m[0], B.v_cls, n, D, 1e-6f, s));   // class tokens only
+    if (h->tap)   // the feature tap: this part's class tokens, in front of the fc launch
+        HIP_TRY(h, hipMemcpyAsync((char*)h->feat_buf + F * D * 2, B.v_cls, (size_t)n * D * 2, hipMemcpyDeviceToDevice, s));
     FAV_VIT_TRY(gemm(li + 1, B.v_cls, 1, nullptr, 0, B.logits, 1));
 #undef FAV_VIT_TRY
     return FAV_OK;
@@ -1485,6 +1508,7 @@ fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out
     HIP_TRY(h, hipGetLastError());
     h->last_T = T_head;
     h->last_n = n_head;
+    if (h->tap) { h->feat_T = T_head; h->feat_n = n_head; }
     return FAV_OK;
 }
 
@@ -1730,6 +1754,151 @@ fav_status fav_get_logits(fav_handle* h, float* out, int32_t* t_out, int32_t* n_
                                     hipMemcpyDeviceToDevice, (hipStream_t)stream));
         mark_last_use(h, (hipStream_t)stream);
     }
+    return FAV_OK;
+}
+
+// ---- feature tap and OOD scoring (fav_ood.hpp) ------------------------------
+namespace {
+// the width of the row the final fc reads
+int feature_width(const fav_handle* h) { return h->vit ? kVit[h->cfg.arch - 2].dim : h->plan.ops.back().C; }
+
+// The scoring head: one launch, x and g in LDS.  The arguments have been checked (ood_dims_error, the pointers).
+void launch_ood(const void* feat, int S, int n, int D, int k, int R, const float* mu, const float* Pt, const float* Mt,
+                const int32_t* cls, const int32_t* labels, float threshold, fav_ood_record* rec, hipStream_t s) {
+    OodParams p;
+    p.feat = (const uint16_t*)feat; p.mu = mu; p.Pt = Pt; p.Mt = Mt; p.cls = cls; p.labels = labels; p.rec = (int32_t*)rec;
+    p.S = S; p.n = n; p.D = D; p.k = k; p.R = R;
+    p.inv_S = (float)(1.0 / S); p.threshold = threshold;
+    const int fpb = ood_frames_per_block(n, D, k);
+    const size_t lds = (size_t)fpb * (size_t)(D + k) * 4;
+    const dim3 grid((unsigned)((n + fpb - 1) / fpb));
+    if (fpb == 4) hipLaunchKernelGGL(ood_score_kernel<4>, grid, dim3(OOD_THREADS), lds, s, p);
+    else if (fpb == 2) hipLaunchKernelGGL(ood_score_kernel<2>, grid, dim3(OOD_THREADS), lds, s, p);
+    else hipLaunchKernelGGL(ood_score_kernel<1>, grid, dim3(OOD_THREADS), lds, s, p);
+}
+
+void free_ood(fav_handle::OodDev* o) {
+    for (void* q : {(void*)o->mu, (void*)o->Pt, (void*)o->Mt, (void*)o->cls}) if (q) (void)hipFree(q);
+    *o = fav_handle::OodDev{};
+}
+// the host waits for what has been enqueued on the handle (its last call's event)
+fav_status wait_enqueued(fav_handle* h) {
+    if (h->ev_last_set) HIP_TRY(h, hipEventSynchronize(h->ev_last));
+    return FAV_OK;
+}
+fav_status tap_on(fav_handle* h) {
+    if (!h->feat_buf) {
+        const int D = feature_width(h);
+        const size_t rows = (size_t)(h->n_members > 1 ? h->n_members : h->plan.T_eff) * h->cfg.max_batch;
+        HIP_TRY(h, hipSetDevice(h->cfg.device));
+        HIP_TRY(h, hipMalloc(&h->feat_buf, rows * D * 2 + 256));
+        h->feat_D = D;
+    }
+    if (!h->tap) { h->tap = true; h->feat_T = h->feat_n = 0; }
+    return FAV_OK;
+}
+void tap_off(fav_handle* h) { h->tap = false; h->tap_by_ood = false; h->feat_T = h->feat_n = 0; }
+}  // namespace
+
+fav_status fav_set_feature_tap(fav_handle* h, int32_t enable) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!enable) {
+        if (h->ood_on) { h->err = "fav_set_feature_tap: an OOD model is set, which reads the tap; clear it first (fav_set_ood)"; return FAV_ERR_INVALID_ARG; }
+        tap_off(h);
+        return FAV_OK;
+    }
+    h->tap_by_ood = false;      // the caller's own tap outlives a model
+    return tap_on(h);
+}
+
+fav_status fav_get_features(fav_handle* h, float* out, int32_t* s_out, int32_t* n_out, int32_t* d_out, void* stream) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!h->tap) { h->err = "fav_get_features: the feature tap is off (fav_set_feature_tap)"; return FAV_ERR_INVALID_ARG; }
+    if (h->feat_n == 0) { h->err = "fav_get_features: no classify call since the tap was turned on"; return FAV_ERR_INVALID_ARG; }
+    if ((uintptr_t)out & 15) { h->err = "fav_get_features: out_dev must be 16-byte aligned"; return FAV_ERR_INVALID_ARG; }
+    if (s_out) *s_out = h->feat_T;
+    if (n_out) *n_out = h->feat_n;
+    if (d_out) *d_out = h->feat_D;
+    if (out) {
+        hipStream_t s = (hipStream_t)stream;
+        HIP_TRY(h, hipSetDevice(h->cfg.device));
+        if (fav_status st = wait_last_use(h, s)) return st;
+        const long long groups = (long long)h->feat_T * h->feat_n * h->feat_D / 8;
+        hipLaunchKernelGGL(features_to_f32_kernel, dim3(grid_for(groups)), dim3(256), 0, s, (const uint4*)h->feat_buf, (float4*)out, groups);
+        HIP_TRY(h, hipGetLastError());
+        mark_last_use(h, s);
+    }
+    return FAV_OK;
+}
+
+fav_status fav_check_ood_model(const fav_ood_model* m, int32_t D_expected, char* err, size_t err_cap) {
+    static_assert(sizeof(fav_ood_record) == 16, "fav_ood_record is 4 dwords");
+    if (err && err_cap) err[0] = 0;
+    const std::string why = ood_model_error(m, D_expected);
+    if (why.empty()) return FAV_OK;
+    if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
+    return FAV_ERR_INVALID_ARG;
+}
+
+fav_status fav_set_ood(fav_handle* h, const fav_ood_model* m) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!m) {
+        if (!h->ood_on) return FAV_OK;
+        if (fav_status st = wait_enqueued(h)) return st;
+        free_ood(&h->ood);
+        h->ood_on = false;
+        if (h->tap_by_ood) tap_off(h);
+        return FAV_OK;
+    }
+    const std::string why = ood_model_error(m, feature_width(h));
+    if (!why.empty()) { h->err = fmt("fav_set_ood: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (h->n_members > 1) {
+        h->err = "fav_set_ood: the members of a deep ensemble do not share a feature space; an OOD model is not supported on it";
+        return FAV_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    // the new copy first: a failure leaves the handle as it was
+    const size_t D = (size_t)m->D, k = (size_t)m->k, R = (size_t)m->R;
+    std::vector<float> Pt(D * k), Mt(k * R);
+    for (size_t r = 0; r < k; ++r)
+        for (size_t j = 0; j < D; ++j) Pt[j * k + r] = m->P[r * D + j];
+    for (size_t c = 0; c < R; ++c)
+        for (size_t r = 0; r < k; ++r) Mt[r * R + c] = m->M[c * k + r];
+    fav_handle::OodDev nw;
+    nw.D = m->D; nw.k = m->k; nw.R = m->R; nw.threshold = m->threshold;
+    auto upload = [&](void** dst, const void* src, size_t bytes) {
+        return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (!upload((void**)&nw.mu, m->mu, D * 4) || !upload((void**)&nw.Pt, Pt.data(), D * k * 4) ||
+        !upload((void**)&nw.Mt, Mt.data(), k * R * 4) || !upload((void**)&nw.cls, m->class_id, R * 4)) {
+        h->err = fmt("fav_set_ood: cannot copy the model to the device: %s", hipGetErrorString(hipGetLastError()));
+        free_ood(&nw);
+        return FAV_ERR_HIP;
+    }
+    const bool tap_was_on = h->tap;
+    if (fav_status st = tap_on(h)) { free_ood(&nw); return st; }
+    if (!tap_was_on) h->tap_by_ood = true;
+    if (h->ood_on) {
+        if (fav_status st = wait_enqueued(h)) { free_ood(&nw); return st; }
+        free_ood(&h->ood);
+    }
+    h->ood = nw;
+    h->ood_on = true;
+    return FAV_OK;
+}
+
+fav_status fav_classify_ood(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
+                            float* conf, uint8_t* fail, float* score, fav_ood_record* ood, void* stream) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!h->ood_on) { route_clear(); h->err = "fav_classify_ood: no OOD model set (fav_set_ood)"; return FAV_ERR_INVALID_ARG; }
+    if (!ood || ((uintptr_t)ood & 7)) { route_clear(); h->err = fmt("fav_classify_ood: %s", kBadRecords); return FAV_ERR_INVALID_ARG; }
+    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
+    // behind the forward pass on the same stream; feat_T x feat_n are this call's samples and frames
+    hipStream_t s = (hipStream_t)stream;
+    const fav_handle::OodDev& o = h->ood;
+    launch_ood(h->feat_buf, h->feat_T, h->feat_n, o.D, o.k, o.R, o.mu, o.Pt, o.Mt, o.cls, labels, o.threshold, ood, s);
+    HIP_TRY(h, hipGetLastError());
+    mark_last_use(h, s);
     return FAV_OK;
 }
 
@@ -2133,6 +2302,22 @@ fav_status fav_op_views(const void* frames, void* out, int32_t n, int32_t H, int
     const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + (uintptr_t)frame_bytes * (uintptr_t)n * (uintptr_t)n_views;
     if (in_lo < out_hi && out_lo < in_hi) return corruption_rejected(fn, "out overlaps frames");
     launch_views(frames, out, n, H, W, layout, views, n_views, (hipStream_t)stream);
+    return op_done(nullptr);
+}
+
+fav_status fav_op_ood_score(const void* feat, int32_t S, int32_t n, int32_t D, int32_t k, int32_t R, const float* mu, const float* Pt,
+                            const float* Mt, const int32_t* class_id, const int32_t* labels, float threshold,
+                            fav_ood_record* records, void* stream) {
+    const char* fn = "fav_op_ood_score";
+    route_clear();
+    if (!feat || !mu || !Pt || !Mt || !class_id || !records) return corruption_rejected(fn, "null pointer");
+    if (S < 1 || S > OOD_MAX_S) return corruption_rejected(fn, fmt("S=%d outside [1, %d]", S, OOD_MAX_S).c_str());
+    if (n < 1) return corruption_rejected(fn, "n must be at least 1");
+    const std::string why = ood_dims_error(D, k, R);
+    if (!why.empty()) return corruption_rejected(fn, why.c_str());
+    if (std::isnan(threshold)) return corruption_rejected(fn, "threshold is NaN");
+    if ((uintptr_t)records & 7) return corruption_rejected(fn, "records_dev must be 8-byte aligned");
+    launch_ood(feat, S, n, D, k, R, mu, Pt, Mt, class_id, labels, threshold, records, (hipStream_t)stream);
     return op_done(nullptr);
 }
 

@@ -1,0 +1,168 @@
+"""Feature-space OOD scoring (include/fav.h fav_ood_model): a class-conditional Gaussian with a
+tied covariance on the pooled features the final fc layer reads (Mahalanobis distance; Lee et al. 2018).
+
+The fit is host work in float64 and happens once; the model it produces is a whitening projection ``P`` and the projected
+class means ``M``, so that the device head (fav_op_ood_score) computes ``|P (f - mu) - M[c]|^2`` as two plain chains of
+fp32 products and sums.  The metrics below are the usual ones for a detector whose score grows with strangeness."""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import math
+
+import numpy as np
+
+from . import _lib
+
+#: dwords of one fav_ood_record (include/fav.h)
+OOD_RECORD_DWORDS = 4
+
+
+@dataclasses.dataclass(frozen=True)
+class OODModel:
+    """``mu`` fp32[D] global feature mean, ``P`` fp32[k, D] whitening projection, ``M`` fp32[R, k] projected class means,
+    ``class_id`` int32[R] (-1: class-agnostic), ``threshold``: a frame is flagged when not (min_dist <= threshold)."""
+    mu: np.ndarray
+    P: np.ndarray
+    M: np.ndarray
+    class_id: np.ndarray
+    threshold: float = math.inf
+
+    def __post_init__(self):
+        object.__setattr__(self, "mu", np.ascontiguousarray(self.mu, np.float32))
+        object.__setattr__(self, "P", np.ascontiguousarray(self.P, np.float32))
+        object.__setattr__(self, "M", np.ascontiguousarray(self.M, np.float32))
+        object.__setattr__(self, "class_id", np.ascontiguousarray(self.class_id, np.int32))
+        object.__setattr__(self, "threshold", float(self.threshold))
+        if self.mu.ndim != 1 or self.P.ndim != 2 or self.M.ndim != 2 or self.class_id.ndim != 1:
+            raise ValueError("mu and class_id are vectors, P and M matrices")
+        if self.P.shape[1] != self.mu.shape[0] or self.M.shape[1] != self.P.shape[0] or self.class_id.shape[0] != self.M.shape[0]:
+            raise ValueError(f"shapes do not fit: mu {self.mu.shape}, P {self.P.shape}, M {self.M.shape}, class_id {self.class_id.shape}")
+
+    @property
+    def D(self) -> int:
+        return int(self.P.shape[1])
+
+    @property
+    def k(self) -> int:
+        return int(self.P.shape[0])
+
+    @property
+    def R(self) -> int:
+        return int(self.M.shape[0])
+
+    def with_threshold(self, threshold: float) -> "OODModel":
+        return dataclasses.replace(self, threshold=float(threshold))
+
+    def save(self, path):
+        np.savez(path, mu=self.mu, P=self.P, M=self.M, class_id=self.class_id, threshold=np.float32(self.threshold))
+
+    @classmethod
+    def load(cls, path) -> "OODModel":
+        with np.load(path) as z:
+            return cls(z["mu"], z["P"], z["M"], z["class_id"], float(z["threshold"]))
+
+    def to_c(self) -> _lib.FavOodModel:
+        """The fav_ood_model that points into this model's arrays (which it keeps alive)."""
+        m = _lib.FavOodModel()
+        m.struct_size = C.sizeof(_lib.FavOodModel)
+        m.D, m.k, m.R = self.D, self.k, self.R
+        fp = C.POINTER(C.c_float)
+        m.mu, m.P, m.M = self.mu.ctypes.data_as(fp), self.P.ctypes.data_as(fp), self.M.ctypes.data_as(fp)
+        m.class_id = self.class_id.ctypes.data_as(C.POINTER(C.c_int32))
+        m.threshold = self.threshold
+        m._keep = self
+        return m
+
+    def check(self, D_expected: int = -1):
+        """fav_check_ood_model (host only); raises ValueError with the library's message."""
+        err = C.create_string_buffer(256)
+        c = self.to_c()
+        if _lib.load().fav_check_ood_model(C.byref(c), int(D_expected), err, len(err)) != _lib.FAV_OK:
+            raise ValueError(err.value.decode("utf-8", "replace"))
+
+    # -- metrics: a score grows with strangeness; in-distribution frames should score low
+    @staticmethod
+    def threshold_for_tpr(id_scores, tpr: float) -> float:
+        """The ceil(tpr * n)-th smallest in-distribution score: at least ``tpr`` of those frames pass ``score <= threshold``."""
+        s = _scores(id_scores, "id_scores")
+        if not 0.0 < tpr <= 1.0:
+            raise ValueError(f"tpr must be in (0, 1], got {tpr}")
+        rank = min(s.size, max(1, math.ceil(tpr * s.size - 1e-9)))
+        return float(np.sort(s)[rank - 1])
+
+    @staticmethod
+    def auroc(id_scores, ood_scores) -> float:
+        """P(an OOD frame scores above an in-distribution one), ties counting 1/2 (Mann-Whitney)."""
+        a, b = np.sort(_scores(id_scores, "id_scores")), _scores(ood_scores, "ood_scores")
+        below = np.searchsorted(a, b, side="left")
+        equal = np.searchsorted(a, b, side="right") - below
+        return float((below.sum() + 0.5 * equal.sum()) / (a.size * b.size))
+
+    @staticmethod
+    def fpr_at_tpr(id_scores, ood_scores, tpr: float = 0.95) -> float:
+        """The share of OOD frames that pass the threshold which keeps ``tpr`` of the in-distribution frames."""
+        thr = OODModel.threshold_for_tpr(id_scores, tpr)
+        return float(np.mean(_scores(ood_scores, "ood_scores") <= thr))
+
+
+def _scores(v, name: str) -> np.ndarray:
+    s = np.asarray(v, np.float64).ravel()
+    if s.size == 0:
+        raise ValueError(f"{name} is empty")
+    if np.isnan(s).any():
+        raise ValueError(f"{name} holds a NaN")
+    return s
+
+
+def fit_mahalanobis(features, labels, k: int | None = None, shrinkage: float = 0.01) -> OODModel:
+    """features [N, D], labels int[N] -> the model, computed in float64: the global mean ``mu``; one mean per class that
+    occurs; the tied covariance S = (1/N) sum (f - mu_y)(f - mu_y)^T; S' = (1 - rho) S + rho (tr S / D) I with rho =
+    ``shrinkage``; its eigenpairs, eigenvalues descending, the top ``k`` (default D) kept; P = diag(lambda^-1/2) U_k^T and
+    M = (mu_c - mu) P^T, cast to fp32.  With k = D the distance is (f - mu_c)^T S'^-1 (f - mu_c)."""
+    F = np.asarray(features, np.float64)
+    y = np.asarray(labels).ravel()
+    if F.ndim != 2 or y.shape[0] != F.shape[0]:
+        raise ValueError("features must be [N, D] with one label per row")
+    N, D = F.shape
+    if N < 2:
+        raise ValueError(f"at least 2 feature rows are needed, got {N}")
+    if not np.isfinite(F).all():
+        raise ValueError("features hold a non-finite value")
+    if not np.issubdtype(y.dtype, np.integer):
+        raise ValueError("labels must be integers")
+    if (y < 0).any():
+        raise ValueError("labels must not be negative")
+    if not 0.0 <= shrinkage <= 1.0:
+        raise ValueError(f"shrinkage must be in [0, 1], got {shrinkage}")
+    k = D if k is None else int(k)
+    if not 1 <= k <= D:
+        raise ValueError(f"k must be in [1, D={D}], got {k}")
+    mu = F.mean(axis=0)
+    classes, inv = np.unique(y, return_inverse=True)
+    means = np.stack([F[inv == c].mean(axis=0) for c in range(classes.size)])
+    Z = F - means[inv]
+    S = Z.T @ Z / N
+    S = (1.0 - shrinkage) * S + shrinkage * (np.trace(S) / D) * np.eye(D)
+    lam, U = np.linalg.eigh(S)
+    order = np.argsort(lam)[::-1][:k]
+    lam, U = lam[order], U[:, order]
+    if not (lam > 0).all():
+        raise ValueError("the shrunk covariance is singular in the kept directions; raise shrinkage or lower k")
+    P = (U / np.sqrt(lam)).T
+    M = (means - mu) @ P.T
+    return OODModel(mu.astype(np.float32), P.astype(np.float32), M.astype(np.float32), classes.astype(np.int32))
+
+
+def unpack_records(records) -> dict:
+    """int32[n, 4] fav_ood_record records (torch tensor or numpy) -> ``min_dist`` fp32[n], ``nearest_class`` int32[n],
+    ``label_dist`` fp32[n], ``ood`` int32[n]; views of the record buffer."""
+    if records.ndim != 2 or int(records.shape[1]) != OOD_RECORD_DWORDS:
+        raise ValueError(f"expected int32[n, {OOD_RECORD_DWORDS}] records, got shape {tuple(records.shape)}")
+    if isinstance(records, np.ndarray):
+        f32 = np.float32
+    else:
+        import torch
+        f32 = torch.float32
+    return {"min_dist": records[:, 0].view(f32), "nearest_class": records[:, 1], "label_dist": records[:, 2].view(f32),
+            "ood": records[:, 3]}

@@ -290,6 +290,66 @@ fav_status fav_set_views(fav_handle* h, const fav_view* views, int32_t n_views);
 /* The views in force: *n_out (may be NULL) = their number, the first min(cap, number) of them copied to out (may be NULL). */
 fav_status fav_get_views(const fav_handle* h, fav_view* out, int32_t cap, int32_t* n_out);
 
+/* ---- Feature tap and feature-space OOD scoring.  Every other signal of this library is a
+ * function of the logits; these two read the row the final fc GEMM reads - the FEATURE of a sample:
+ *   ResNet archs   the input row of the last convolution of the schedule (the fc): the average-pool output, or the entry
+ *                  dropout's output when the pooled-feature site is the first dropout site.  It is therefore POST-dropout
+ *                  whenever the pooled-feature site is active.  D = 512 (ResNet-18), 2048 (ResNet-50)
+ *   ViT archs      the class token behind the final LayerNorm.  D = 768 (ViT-B/16), 128 (the miniature)
+ * While the tap is on, every pass copies those bf16 rows device to device into a buffer the handle owns, on the stream the
+ * fc launch runs on and in front of it: per chunk at the chunk's virtual-frame offset, per ensemble member (grouped or one
+ * stream a member), per stream part on the ViT path.  The buffer holds [S][n][D] rows with the sample indexing of
+ * fav_get_logits (views included: S = T_head * n_views).  It is allocated by the setter, for max_batch frames; the setter may
+ * synchronise, fav_classify* never allocates or synchronises for it.  The copies are booked in no kernel class.  The tap
+ * changes no result.  With the tap off and no OOD model set a fav_classify* call enqueues exactly what it did before.  Turning
+ * the tap off while an OOD model is set is refused (FAV_ERR_INVALID_ARG): the model reads it. */
+fav_status fav_set_feature_tap(fav_handle* h, int32_t enable);
+/* The features of the last fav_classify* call, converted to fp32 [S][n][D] in out_dev (16-byte aligned; may be NULL: only
+ * the sizes), on hip_stream.  FAV_ERR_INVALID_ARG before the first call made with the tap on, and with the tap off. */
+fav_status fav_get_features(fav_handle* h, float* out_dev, int32_t* s_out, int32_t* n_out, int32_t* d_out, void* hip_stream);
+
+/* A class-conditional Gaussian with a tied covariance on those features (Mahalanobis distance; Lee et al. 2018), stored as a
+ * whitening projection: with Sigma = U diag(lambda) U^T, P = diag(lambda^-1/2) U_k^T and M[c] = P (mu_c - mu), the distance
+ * of a feature f to class c is |P (f - mu) - M[c]|^2.  All pointers are HOST pointers.
+ * Ranges (fav_check_ood_model; FAV_ERR_INVALID_ARG and a message that names the field): struct_size == sizeof(fav_ood_model);
+ * D a multiple of 16 in [16, 4096] (and the arch's feature width when set on a handle); 1 <= k <= 2048; 1 <= R <= 4096; every
+ * value of mu, P and M finite; threshold not NaN (+inf: no frame is ever flagged); class_id >= -1. */
+typedef struct fav_ood_model {
+    uint32_t struct_size; int32_t D, k, R;
+    const float* mu;        /* [D]    global feature mean            (host) */
+    const float* P;         /* [k][D] whitening projection           (host) */
+    const float* M;         /* [R][k] projected class means          (host) */
+    const int32_t* class_id;/* [R]    class of each row, -1 = class-agnostic */
+    float threshold;        /* ood = !(min_dist <= threshold); +inf = never */
+} fav_ood_model;
+/* One frame's score, 16 bytes.  Per frame i, everything fp32, every product and every sum rounded on its own (no FMA
+ * contraction, no re-association):
+ *   1. fbar[j]    +0, plus fp32(feat[s][i][j]) for s = 0 .. S-1 in that order, times (float)(1.0 / S)
+ *   2. x[j]       fbar[j] - mu[j]
+ *   3. g[r]       r < k: +0, then for j = 0 .. D-1 in that order g = g + P[r][j] * x[j]
+ *   4. d[c]       c < R: +0, then for r = 0 .. k-1 in that order t = g[r] - M[c][r], d = d + t * t
+ *   5. best = +inf, row = -1; for c ascending: if (d[c] < best) { best = d[c]; row = c; } - ties go to the lowest row, a NaN
+ *      never wins.  min_dist = best; min_class = row < 0 ? -1 : class_id[row]
+ *   6. label_dist d[c] of the lowest row whose class_id equals labels[i]; NaN when labels is NULL or no row has that class
+ *   7. ood        !(min_dist <= threshold)
+ * Non-finite features have no rule of their own: the chains carry them along and the strict < settles the outcome. */
+typedef struct fav_ood_record { float min_dist; int32_t min_class; float label_dist; int32_t ood; } fav_ood_record;
+/* Host only, no device: the ranges above (D_expected < 0: any width in range), the one place they live; fav_set_ood calls it
+ * first.  err (may be NULL) receives the message. */
+fav_status fav_check_ood_model(const fav_ood_model* m, int32_t D_expected, char* err, size_t err_cap);
+/* The handle's OOD model (copied to the device, P and M transposed on the host; NULL: none).  Setting one turns the feature
+ * tap on; clearing it turns the tap off again if this is what turned it on.  Replacing or clearing a model waits on the
+ * host for the work enqueued on the handle and frees the old copy (hipFree: the whole device).  FAV_ERR_UNSUPPORTED on a
+ * deep-ensemble handle: the members do not share a feature space (the tap itself works there).  A rejected call leaves the
+ * handle as it was. */
+fav_status fav_set_ood(fav_handle* h, const fav_ood_model* m);
+/* fav_classify_ex unchanged, then the scoring head on the tapped features, all on the caller's stream: ood_dev[n] (non-NULL,
+ * 8-byte aligned) gets one fav_ood_record per frame, label_dist being the distance to the class this very call wrote to
+ * labels_dev.  Needs a model (FAV_ERR_INVALID_ARG otherwise).  fail_dev / score_dev may be NULL. */
+fav_status fav_classify_ood(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
+                            int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev,
+                            fav_ood_record* ood_dev, void* hip_stream);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -570,6 +630,20 @@ fav_status fav_op_corrupt_c(const uint8_t* frames_dev, float* out_dev, int32_t n
  * that names the function in fav_last_error(NULL). */
 fav_status fav_op_views(const void* frames_dev, void* out_dev, int32_t n, int32_t H, int32_t W, int32_t layout,
                         const fav_view* views_host, int32_t n_views, void* hip_stream);
+
+/* ---- The scoring head defined beside fav_ood_record, on device arrays: feat_bf16 [S][n][D] bf16, mu_dev [D], Pt_dev [D][k]
+ * and Mt_dev [k][R] (P and M TRANSPOSED, so that the kernel reads them along its thread index), class_id_dev [R], labels_dev
+ * [n] or NULL, records_dev [n] (8-byte aligned).  One launch; no allocation, no workspace (x and g live in LDS), no
+ * synchronisation; vector stores only.  A thread owns one column of the projection, then one row of the means, for the up to
+ * four frames of its block; every chain runs in the contract's order.  The matrix pipe is not used: an fp32-input MFMA is an
+ * fmaf chain, which rounds once where the contract rounds twice.
+ * A refused call (FAV_ERR_INVALID_ARG: a NULL pointer other than labels_dev, S outside [1, 4096], n < 1, D, k or R outside
+ * the ranges of fav_ood_model, a NaN threshold, a misaligned records_dev) launches nothing and leaves a message that names the
+ * function in fav_last_error(NULL). */
+fav_status fav_op_ood_score(const void* feat_bf16, int32_t S, int32_t n, int32_t D, int32_t k, int32_t R,
+                            const float* mu_dev, const float* Pt_dev, const float* Mt_dev,
+                            const int32_t* class_id_dev, const int32_t* labels_dev, float threshold,
+                            fav_ood_record* records_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
