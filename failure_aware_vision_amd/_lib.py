@@ -124,6 +124,18 @@ class FavOodRecord(C.Structure):
     _fields_ = [("min_dist", C.c_float), ("min_class", C.c_int32), ("label_dist", C.c_float), ("ood", C.c_int32)]
 
 
+class FavKnnBank(C.Structure):
+    """fav_knn_bank: a bank of L2-normalised bf16 feature rows, host pointers (ood.KNNBank.to_c fills it)."""
+    _fields_ = [("struct_size", C.c_uint32), ("D", C.c_int32), ("N", C.c_int32), ("k", C.c_int32),
+                ("rows", C.POINTER(C.c_uint16)), ("class_id", C.POINTER(C.c_int32)), ("threshold", C.c_float)]
+
+
+class FavKnnRecord(C.Structure):
+    """fav_knn_record: one 24-byte score per frame (ood.unpack_knn_records reads it as int32[n, 6])."""
+    _fields_ = [("kth_dist", C.c_float), ("kth_sim", C.c_float), ("nn_sim", C.c_float), ("nn_row", C.c_int32),
+                ("nn_class", C.c_int32), ("ood", C.c_int32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -174,6 +186,13 @@ _SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_op_ood_score": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "fav_check_knn_bank": (C.c_int, [C.POINTER(FavKnnBank), C.c_int32, C.c_char_p, C.c_size_t]),
+    "fav_set_knn": (C.c_int, [C.c_void_p, C.POINTER(FavKnnBank)]),
+    "fav_classify_knn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_knn_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "fav_op_knn_score": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),

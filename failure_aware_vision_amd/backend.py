@@ -100,7 +100,7 @@ class Backend:
                 blob, self.weights_info = _weights.make_synthetic(arch, seed=seed_weights, num_classes=cfg.num_classes)
             self.load_weights(blob)
         self._T_head = cfg.n_samples if self.mc else max(1, cfg.n_members)
-        self._tap, self._ood = False, None   # the caller's own feature tap; the ood.OODModel in force
+        self._tap, self._ood, self._knn = False, None, None   # the caller's own feature tap; the ood.OODModel, the ood.KNNBank in force
         self._views = ()
         if views:
             self.set_views(views)
@@ -523,7 +523,7 @@ class Backend:
         lab = np.asarray(labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()).ravel()
         if lab.shape[0] != n:
             raise ValueError("one label per frame")
-        own_tap = self._ood is None and not self._tap
+        own_tap = self._ood is None and self._knn is None and not self._tap
         if own_tap:
             self.set_feature_tap(True)
         try:
@@ -591,6 +591,95 @@ class Backend:
         from .ood import OODModel
         a, b = self._min_dists(id_frames), self._min_dists(ood_frames)
         thr = self.ood_model.threshold
+        return dict(auroc=OODModel.auroc(a, b), fpr_at_tpr95=OODModel.fpr_at_tpr(a, b, 0.95),
+                    id_mean_dist=float(a.mean()), ood_mean_dist=float(b.mean()), threshold=thr,
+                    id_flagged=float(np.mean(~(a <= thr))), ood_flagged=float(np.mean(~(b <= thr))), n_id=int(a.size), n_ood=int(b.size))
+
+    # -- nearest-neighbour OOD scoring (ood.py KNNBank; include/fav.h fav_set_knn) ----------------------------------------
+    @property
+    def knn_bank(self):
+        """The ``ood.KNNBank`` in force, None when off."""
+        return self._knn
+
+    def fit_knn(self, frames, labels=None, **kw):
+        """Build an ``ood.KNNBank`` from in-distribution frames: batches of frames_per_call frames run through the classifier
+        with the tap on, the mean over the samples of each frame's features goes to ``ood.build_knn_bank`` (``k``,
+        ``max_rows``, ``seed``).  The handle is left as it was: see ``set_knn``."""
+        from .ood import build_knn_bank
+        n, mb = int(frames.shape[0]), self.frames_per_call
+        lab = None
+        if labels is not None:
+            lab = np.asarray(labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()).ravel()
+            if lab.shape[0] != n:
+                raise ValueError("one label per frame")
+        own_tap = self._ood is None and self._knn is None and not self._tap
+        if own_tap:
+            self.set_feature_tap(True)
+        try:
+            rows = []
+            for b in range(0, n, mb):
+                self.classify_detect(frames[b:min(n, b + mb)], b)
+                rows.append(self.features().to(self._torch.float64).mean(dim=0).cpu().numpy())
+        finally:
+            if own_tap:
+                self.set_feature_tap(False)
+        return build_knn_bank(np.concatenate(rows), lab, **kw)
+
+    def set_knn(self, bank):
+        """Adopt an ``ood.KNNBank`` (fav_set_knn: copied to the device, the workspace allocated, the tap goes on), or None:
+        off.  Refused on a deep ensemble, and for a bank whose D is not this arch's feature width."""
+        if bank is None:
+            _lib.check(self.lib.fav_set_knn(self._h, None), self._h)
+        else:
+            c = bank.to_c()
+            _lib.check(self.lib.fav_set_knn(self._h, C.byref(c)), self._h)
+        self._knn = bank
+
+    def classify_knn(self, images, first_index: int = 0) -> dict:
+        """frames -> ``label``, ``conf``, ``fail``, ``score`` as ``classify_detect`` gives them, plus the k-NN record of each
+        frame (fav_classify_knn): ``kth_dist`` (squared distance of the normalised feature to its k-th nearest bank row),
+        ``kth_sim``, ``nn_sim``, ``nn_row``, ``nn_class`` (the nearest row, its class or -1) and ``ood`` (not kth_dist <=
+        threshold).  torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out,
+        synchronous."""
+        from .ood import KNN_RECORD_DWORDS, unpack_knn_records
+        torch = self._torch
+        img, host, n, layout, stream = self._classify_args(images)
+        dev = img.device
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        conf = torch.empty(n, dtype=torch.float32, device=dev)
+        fail = torch.empty(n, dtype=torch.uint8, device=dev)
+        score = torch.empty(n, dtype=torch.float32, device=dev)
+        rec = torch.empty((n, KNN_RECORD_DWORDS), dtype=torch.int32, device=dev)
+        _lib.check(self.lib.fav_classify_knn(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
+                                             conf.data_ptr(), fail.data_ptr(), score.data_ptr(), rec.data_ptr(), stream), self._h)
+        if host:
+            labels, conf, fail, score, rec = (t.cpu().numpy() for t in (labels, conf, fail, score, rec))
+        return dict(unpack_knn_records(rec), label=labels, conf=conf, fail=fail, score=score)
+
+    def _kth_dists(self, frames) -> np.ndarray:
+        n, mb = int(frames.shape[0]), self.frames_per_call
+        out = []
+        for b in range(0, n, mb):
+            d = self.classify_knn(frames[b:min(n, b + mb)], b)["kth_dist"]
+            out.append(d if isinstance(d, np.ndarray) else d.cpu().numpy())
+        return np.concatenate(out)
+
+    def calibrate_knn(self, frames, tpr: float = 0.95) -> float:
+        """Set the bank's threshold so that at least ``tpr`` of these in-distribution frames pass, and return it."""
+        if self.knn_bank is None:
+            raise ValueError("calibrate_knn needs a bank: set_knn first")
+        from .ood import OODModel
+        thr = OODModel.threshold_for_tpr(self._kth_dists(frames), tpr)
+        self.set_knn(self.knn_bank.with_threshold(thr))
+        return thr
+
+    def knn_report(self, id_frames, ood_frames) -> dict:
+        """How well kth_dist separates ``ood_frames`` from ``id_frames``: the keys of ``ood_report``."""
+        if self.knn_bank is None:
+            raise ValueError("knn_report needs a bank: set_knn first")
+        from .ood import OODModel
+        a, b = self._kth_dists(id_frames), self._kth_dists(ood_frames)
+        thr = self.knn_bank.threshold
         return dict(auroc=OODModel.auroc(a, b), fpr_at_tpr95=OODModel.fpr_at_tpr(a, b, 0.95),
                     id_mean_dist=float(a.mean()), ood_mean_dist=float(b.mean()), threshold=thr,
                     id_flagged=float(np.mean(~(a <= thr))), ood_flagged=float(np.mean(~(b <= thr))), n_id=int(a.size), n_ood=int(b.size))

@@ -28,6 +28,7 @@
 #include "fav_route.hpp"
 #include "fav_views.hpp"
 #include "fav_ood.hpp"
+#include "fav_knn.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -151,13 +152,19 @@ struct fav_handle {
     // Feature tap (fav_set_feature_tap): while on, every pass copies the rows its fc launch reads into feat_buf, bf16
     // [T_head][max_batch][feat_D] at most, indexed [sample][frame] like the logits; allocated by the setter.  feat_T / feat_n:
     // the samples and frames of the last call that filled it (0: none yet)
-    bool tap = false, tap_by_ood = false;
+    // tap_by_head: a head's setter (fav_set_ood, fav_set_knn) turned it on, not the caller: it goes off with the last of them
+    bool tap = false, tap_by_head = false;
     void* feat_buf = nullptr;
     int feat_D = 0, feat_T = 0, feat_n = 0;
     // OOD model (fav_set_ood): the device copy, P and M transposed (fav_ood.hpp); ood_on: one is set
     struct OodDev { float *mu = nullptr, *Pt = nullptr, *Mt = nullptr; int32_t* cls = nullptr; int D = 0, k = 0, R = 0; float threshold = 0.f; };
     OodDev ood;
     bool ood_on = false;
+    // k-NN bank (fav_set_knn): the device copy, padded with zero rows to Npad, and the head's workspace for max_batch frames
+    // (fav_knn.hpp knn_workspace, its zero bias written once by the setter); knn_on: one is set
+    struct KnnDev { void *bank = nullptr, *ws = nullptr; int32_t* cls = nullptr; int D = 0, N = 0, k = 0; float threshold = 0.f; };
+    KnnDev knn;
+    bool knn_on = false;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -1060,6 +1067,7 @@ void free_all(fav_handle* h) {
     if (h->view_buf) (void)hipFree(h->view_buf);
     if (h->feat_buf) (void)hipFree(h->feat_buf);
     for (void* q : {(void*)h->ood.mu, (void*)h->ood.Pt, (void*)h->ood.Mt, (void*)h->ood.cls}) if (q) (void)hipFree(q);
+    for (void* q : {h->knn.bank, h->knn.ws, (void*)h->knn.cls}) if (q) (void)hipFree(q);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
@@ -1797,17 +1805,29 @@ fav_status tap_on(fav_handle* h) {
     if (!h->tap) { h->tap = true; h->feat_T = h->feat_n = 0; }
     return FAV_OK;
 }
-void tap_off(fav_handle* h) { h->tap = false; h->tap_by_ood = false; h->feat_T = h->feat_n = 0; }
+void tap_off(fav_handle* h) { h->tap = false; h->tap_by_head = false; h->feat_T = h->feat_n = 0; }
+// a head's setter (fav_set_ood, fav_set_knn) needs the tap: on, and the head's own if the caller had not turned it on
+fav_status tap_on_for_head(fav_handle* h) {
+    const bool tap_was_on = h->tap;
+    if (fav_status st = tap_on(h)) return st;
+    if (!tap_was_on) h->tap_by_head = true;
+    return FAV_OK;
+}
+// ... and a head that has just been cleared lets go of it: off, if a head turned it on and no other head reads it
+void tap_release_by_head(fav_handle* h) {
+    if (h->tap_by_head && !h->ood_on && !h->knn_on) tap_off(h);
+}
 }  // namespace
 
 fav_status fav_set_feature_tap(fav_handle* h, int32_t enable) {
     if (!h) return FAV_ERR_INVALID_ARG;
     if (!enable) {
         if (h->ood_on) { h->err = "fav_set_feature_tap: an OOD model is set, which reads the tap; clear it first (fav_set_ood)"; return FAV_ERR_INVALID_ARG; }
+        if (h->knn_on) { h->err = "fav_set_feature_tap: a k-NN bank is set, which reads the tap; clear it first (fav_set_knn)"; return FAV_ERR_INVALID_ARG; }
         tap_off(h);
         return FAV_OK;
     }
-    h->tap_by_ood = false;      // the caller's own tap outlives a model
+    h->tap_by_head = false;     // the caller's own tap outlives a model and a bank
     return tap_on(h);
 }
 
@@ -1847,7 +1867,7 @@ fav_status fav_set_ood(fav_handle* h, const fav_ood_model* m) {
         if (fav_status st = wait_enqueued(h)) return st;
         free_ood(&h->ood);
         h->ood_on = false;
-        if (h->tap_by_ood) tap_off(h);
+        tap_release_by_head(h);
         return FAV_OK;
     }
     const std::string why = ood_model_error(m, feature_width(h));
@@ -1875,9 +1895,7 @@ fav_status fav_set_ood(fav_handle* h, const fav_ood_model* m) {
         free_ood(&nw);
         return FAV_ERR_HIP;
     }
-    const bool tap_was_on = h->tap;
-    if (fav_status st = tap_on(h)) { free_ood(&nw); return st; }
-    if (!tap_was_on) h->tap_by_ood = true;
+    if (fav_status st = tap_on_for_head(h)) { free_ood(&nw); return st; }
     if (h->ood_on) {
         if (fav_status st = wait_enqueued(h)) { free_ood(&nw); return st; }
         free_ood(&h->ood);
@@ -1899,6 +1917,136 @@ fav_status fav_classify_ood(fav_handle* h, const void* images, int32_t n, int32_
     launch_ood(h->feat_buf, h->feat_T, h->feat_n, o.D, o.k, o.R, o.mu, o.Pt, o.Mt, o.cls, labels, o.threshold, ood, s);
     HIP_TRY(h, hipGetLastError());
     mark_last_use(h, s);
+    return FAV_OK;
+}
+
+// ---- nearest-neighbour OOD scoring (fav_knn.hpp) ----------------------------
+namespace {
+// What the head needs of a workspace before its first launch: the zero bias, and the rows of the bank behind its last whole
+// 64 as a zero-padded tile.  A padded bank (the handle's copy) needs the bias only, once.
+fav_status knn_prepare(const KnnWs& w, void* ws, const void* bank, int D, int N, bool padded_bank, hipStream_t s) {
+    if (hipMemsetAsync((char*)ws + w.bias, 0, (size_t)w.Npad * 4, s) != hipSuccess) return FAV_ERR_HIP;
+    const int rest = N % 64;
+    if (rest == 0 || padded_bank) return FAV_OK;
+    const size_t row = (size_t)D * 2;
+    if (hipMemsetAsync((char*)ws + w.tile + rest * row, 0, (size_t)(64 - rest) * row, s) != hipSuccess) return FAV_ERR_HIP;
+    if (hipMemcpyAsync((char*)ws + w.tile, (const char*)bank + (size_t)(N - rest) * row, rest * row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FAV_ERR_HIP;
+    return FAV_OK;
+}
+
+// The head on a prepared workspace: the query kernel, the GEMM (one launch; two when an unpadded bank ends in a part tile),
+// the select.  The arguments have been checked (knn_dims_error, the pointers).  Returns the conv launcher's refusal, if any.
+const char* launch_knn(const void* feat, int S, int n, int D, const void* bank, int N, int k, const int32_t* cls, float threshold,
+                       const KnnWs& w, void* ws, bool padded_bank, fav_knn_record* rec, hipStream_t s) {
+    KnnQueryParams qp;
+    qp.feat = (const uint16_t*)feat; qp.q = (uint16_t*)((char*)ws + w.q); qp.flags = (int32_t*)((char*)ws + w.flags);
+    qp.S = S; qp.n = n; qp.D = D; qp.inv_S = (float)(1.0 / S);
+    hipLaunchKernelGGL(knn_query_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, s, qp);
+    float* const sim = (float*)((char*)ws + w.sim);
+    auto gemm = [&](const void* rows, int col0, int cols) -> const char* {
+        fav_conv_desc d;
+        memset(&d, 0, sizeof d);
+        d.x = qp.q; d.w = rows; d.bias = (const float*)((char*)ws + w.bias) + col0; d.y = sim + col0;
+        d.n_frames = n; d.H = 1; d.W = 1; d.Cin = D; d.Cout = cols;
+        d.kh = 1; d.kw = 1; d.stride = 1; d.pad = 0; d.relu = 0; d.out_f32 = 1; d.math_mode = FAV_MATH_BF16;
+        d.drop.site = -1;
+        return launch_conv(nullptr, d, cols, w.Npad, false, Group{}, s);
+    };
+    const int whole = padded_bank ? w.Npad : (N & ~63);
+    if (whole > 0)
+        if (const char* e = gemm(bank, 0, whole)) return e;
+    if (whole < w.Npad)
+        if (const char* e = gemm((const char*)ws + w.tile, whole, 64)) return e;
+    KnnSelectParams sp;
+    sp.sim = sim; sp.flags = qp.flags; sp.cls = cls; sp.rec = (int32_t*)rec;
+    sp.N = N; sp.ld = w.Npad; sp.k = k; sp.threshold = threshold;
+    hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)n), dim3(KNN_SEL_THREADS), 0, s, sp);
+    return nullptr;
+}
+
+void free_knn(fav_handle::KnnDev* o) {
+    for (void* q : {o->bank, o->ws, (void*)o->cls}) if (q) (void)hipFree(q);
+    *o = fav_handle::KnnDev{};
+}
+}  // namespace
+
+fav_status fav_check_knn_bank(const fav_knn_bank* b, int32_t D_expected, char* err, size_t err_cap) {
+    static_assert(sizeof(fav_knn_record) == 24, "fav_knn_record is 6 dwords");
+    if (err && err_cap) err[0] = 0;
+    const std::string why = knn_bank_error(b, D_expected);
+    if (why.empty()) return FAV_OK;
+    if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
+    return FAV_ERR_INVALID_ARG;
+}
+
+size_t fav_knn_workspace_bytes(int32_t n, int32_t D, int32_t N) {
+    if (n < 1 || !knn_dims_error(D, N, 1).empty()) return 0;
+    return knn_workspace(n, D, N, false).bytes;
+}
+
+fav_status fav_set_knn(fav_handle* h, const fav_knn_bank* b) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!b) {
+        if (!h->knn_on) return FAV_OK;
+        if (fav_status st = wait_enqueued(h)) return st;
+        free_knn(&h->knn);
+        h->knn_on = false;
+        tap_release_by_head(h);
+        return FAV_OK;
+    }
+    const std::string why = knn_bank_error(b, feature_width(h));
+    if (!why.empty()) { h->err = fmt("fav_set_knn: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (h->n_members > 1) {
+        h->err = "fav_set_knn: the members of a deep ensemble do not share a feature space; a k-NN bank is not supported on it";
+        return FAV_ERR_UNSUPPORTED;
+    }
+    const KnnWs w = knn_workspace(h->cfg.max_batch, b->D, b->N, true);
+    if (w.bytes > KNN_MAX_WS_BYTES) {
+        h->err = fmt("fav_set_knn: the workspace of max_batch=%d frames against N=%d rows (%d padded) is %zu bytes, above the limit of %zu",
+                     (int)h->cfg.max_batch, b->N, w.Npad, w.bytes, KNN_MAX_WS_BYTES);
+        return FAV_ERR_INVALID_ARG;
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    // the new copy first: a failure leaves the handle as it was
+    fav_handle::KnnDev nw;
+    nw.D = b->D; nw.N = b->N; nw.k = b->k; nw.threshold = b->threshold;
+    const size_t row = (size_t)b->D * 2, bank_bytes = (size_t)b->N * row, pad_bytes = (size_t)(w.Npad - b->N) * row;
+    bool ok = hipMalloc(&nw.bank, (size_t)w.Npad * row) == hipSuccess && hipMalloc(&nw.ws, w.bytes) == hipSuccess &&
+              hipMemcpy(nw.bank, b->rows, bank_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+              (pad_bytes == 0 || hipMemset((char*)nw.bank + bank_bytes, 0, pad_bytes) == hipSuccess);
+    if (ok && b->class_id)
+        ok = hipMalloc((void**)&nw.cls, (size_t)b->N * 4) == hipSuccess && hipMemcpy(nw.cls, b->class_id, (size_t)b->N * 4, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && knn_prepare(w, nw.ws, nw.bank, b->D, b->N, true, nullptr) == FAV_OK && hipStreamSynchronize(nullptr) == hipSuccess;
+    if (!ok) {
+        h->err = fmt("fav_set_knn: cannot copy the bank to the device: %s", hipGetErrorString(hipGetLastError()));
+        free_knn(&nw);
+        return FAV_ERR_HIP;
+    }
+    if (fav_status st = tap_on_for_head(h)) { free_knn(&nw); return st; }
+    if (h->knn_on) {
+        if (fav_status st = wait_enqueued(h)) { free_knn(&nw); return st; }
+        free_knn(&h->knn);
+    }
+    h->knn = nw;
+    h->knn_on = true;
+    return FAV_OK;
+}
+
+fav_status fav_classify_knn(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
+                            float* conf, uint8_t* fail, float* score, fav_knn_record* knn, void* stream) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!h->knn_on) { route_clear(); h->err = "fav_classify_knn: no k-NN bank set (fav_set_knn)"; return FAV_ERR_INVALID_ARG; }
+    if (!knn || ((uintptr_t)knn & 7)) { route_clear(); h->err = fmt("fav_classify_knn: %s", kBadRecords); return FAV_ERR_INVALID_ARG; }
+    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
+    // behind the forward pass on the same stream; feat_T x feat_n are this call's samples and frames
+    hipStream_t s = (hipStream_t)stream;
+    const fav_handle::KnnDev& o = h->knn;
+    const KnnWs w = knn_workspace(h->cfg.max_batch, o.D, o.N, true);
+    const char* e = launch_knn(h->feat_buf, h->feat_T, h->feat_n, o.D, o.bank, o.N, o.k, o.cls, o.threshold, w, o.ws, true, knn, s);
+    route_clear();            // the report speaks of fav_op_* launches only
+    mark_last_use(h, s);
+    if (e) { h->err = fmt("fav_classify_knn: %s", e); return FAV_ERR_INVALID_ARG; }
+    HIP_TRY(h, hipGetLastError());
     return FAV_OK;
 }
 
@@ -2319,6 +2467,27 @@ fav_status fav_op_ood_score(const void* feat, int32_t S, int32_t n, int32_t D, i
     if ((uintptr_t)records & 7) return corruption_rejected(fn, "records_dev must be 8-byte aligned");
     launch_ood(feat, S, n, D, k, R, mu, Pt, Mt, class_id, labels, threshold, records, (hipStream_t)stream);
     return op_done(nullptr);
+}
+
+fav_status fav_op_knn_score(const void* feat, int32_t S, int32_t n, int32_t D, const void* bank, int32_t N, int32_t k,
+                            const int32_t* class_id, float threshold, void* ws, size_t ws_bytes, fav_knn_record* records,
+                            void* stream) {
+    const char* fn = "fav_op_knn_score";
+    route_clear();
+    if (!feat || !bank || !ws || !records) return corruption_rejected(fn, "null pointer");
+    if (S < 1 || S > KNN_MAX_S) return corruption_rejected(fn, fmt("S=%d outside [1, %d]", S, KNN_MAX_S).c_str());
+    if (n < 1) return corruption_rejected(fn, "n must be at least 1");
+    const std::string why = knn_dims_error(D, N, k);
+    if (!why.empty()) return corruption_rejected(fn, why.c_str());
+    if (std::isnan(threshold)) return corruption_rejected(fn, "threshold is NaN");
+    const KnnWs w = knn_workspace(n, D, N, false);
+    if (ws_bytes < w.bytes) return corruption_rejected(fn, fmt("ws_bytes=%zu is below fav_knn_workspace_bytes=%zu", ws_bytes, w.bytes).c_str());
+    if ((uintptr_t)ws & 255) return corruption_rejected(fn, "ws_dev must be 256-byte aligned");
+    if ((uintptr_t)bank & 15) return corruption_rejected(fn, "bank_dev must be 16-byte aligned");
+    if ((uintptr_t)records & 7) return corruption_rejected(fn, "records_dev must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (knn_prepare(w, ws, bank, D, N, false, s) != FAV_OK) { g_create_error = fmt("%s: cannot prepare the workspace: %s", fn, hipGetErrorString(hipGetLastError())); return FAV_ERR_HIP; }
+    return op_done(fn, launch_knn(feat, S, n, D, bank, N, k, class_id, threshold, w, ws, false, records, s));
 }
 
 }  // extern "C"

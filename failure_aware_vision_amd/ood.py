@@ -3,7 +3,11 @@ tied covariance on the pooled features the final fc layer reads (Mahalanobis dis
 
 The fit is host work in float64 and happens once; the model it produces is a whitening projection ``P`` and the projected
 class means ``M``, so that the device head (fav_op_ood_score) computes ``|P (f - mu) - M[c]|^2`` as two plain chains of
-fp32 products and sums.  The metrics below are the usual ones for a detector whose score grows with strangeness."""
+fp32 products and sums.  The metrics below are the usual ones for a detector whose score grows with strangeness.
+
+Its non-parametric companion (item 5g; deep nearest neighbours, Sun et al. 2022) is at the end of the file: ``KNNBank``, a bank of
+L2-normalised features as bf16 rows that ``build_knn_bank`` makes, scored on the device by fav_op_knn_score as the distance to the
+k-th nearest row, with the same metrics."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,6 +20,8 @@ from . import _lib
 
 #: dwords of one fav_ood_record (include/fav.h)
 OOD_RECORD_DWORDS = 4
+#: dwords of one fav_knn_record
+KNN_RECORD_DWORDS = 6
 
 
 @dataclasses.dataclass(frozen=True)
@@ -166,3 +172,120 @@ def unpack_records(records) -> dict:
         f32 = torch.float32
     return {"min_dist": records[:, 0].view(f32), "nearest_class": records[:, 1], "label_dist": records[:, 2].view(f32),
             "ood": records[:, 3]}
+
+
+# ---- nearest-neighbour scoring (include/fav.h fav_knn_bank) ------------------------------------
+def _bf16_bits(x: np.ndarray) -> np.ndarray:
+    """finite float32 -> bf16 bit patterns, round to nearest even (the integer recipe of the device and the oracle)."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+@dataclasses.dataclass(frozen=True)
+class KNNBank:
+    """``rows`` uint16[N, D]: L2-normalised in-distribution features as bf16 bit patterns, ``class_id`` int32[N] or None, ``k``:
+    which neighbour's distance is the score, ``threshold``: a frame is flagged when not (kth_dist <= threshold)."""
+    rows: np.ndarray
+    class_id: np.ndarray | None = None
+    k: int = 10
+    threshold: float = math.inf
+
+    def __post_init__(self):
+        if np.asarray(self.rows).dtype != np.uint16:
+            raise ValueError("rows are bf16 bit patterns: uint16 (build_knn_bank makes them from features)")
+        object.__setattr__(self, "rows", np.ascontiguousarray(self.rows, np.uint16))
+        if self.class_id is not None:
+            object.__setattr__(self, "class_id", np.ascontiguousarray(self.class_id, np.int32))
+        object.__setattr__(self, "k", int(self.k))
+        object.__setattr__(self, "threshold", float(self.threshold))
+        if self.rows.ndim != 2:
+            raise ValueError("rows is a matrix [N, D]")
+        if self.class_id is not None and self.class_id.shape != (self.rows.shape[0],):
+            raise ValueError(f"shapes do not fit: rows {self.rows.shape}, class_id {self.class_id.shape}")
+
+    @property
+    def N(self) -> int:
+        return int(self.rows.shape[0])
+
+    @property
+    def D(self) -> int:
+        return int(self.rows.shape[1])
+
+    def with_threshold(self, threshold: float) -> "KNNBank":
+        return dataclasses.replace(self, threshold=float(threshold))
+
+    def save(self, path):
+        extra = {} if self.class_id is None else {"class_id": self.class_id}
+        np.savez(path, rows=self.rows, k=np.int32(self.k), threshold=np.float32(self.threshold), **extra)
+
+    @classmethod
+    def load(cls, path) -> "KNNBank":
+        with np.load(path) as z:
+            return cls(z["rows"], z["class_id"] if "class_id" in z.files else None, int(z["k"]), float(z["threshold"]))
+
+    def to_c(self) -> _lib.FavKnnBank:
+        """The fav_knn_bank that points into this bank's arrays (which it keeps alive)."""
+        b = _lib.FavKnnBank()
+        b.struct_size = C.sizeof(_lib.FavKnnBank)
+        b.D, b.N, b.k = self.D, self.N, self.k
+        b.rows = self.rows.ctypes.data_as(C.POINTER(C.c_uint16))
+        if self.class_id is not None:
+            b.class_id = self.class_id.ctypes.data_as(C.POINTER(C.c_int32))
+        b.threshold = self.threshold
+        b._keep = self
+        return b
+
+    def check(self, D_expected: int = -1):
+        """fav_check_knn_bank (host only); raises ValueError with the library's message."""
+        err = C.create_string_buffer(256)
+        c = self.to_c()
+        if _lib.load().fav_check_knn_bank(C.byref(c), int(D_expected), err, len(err)) != _lib.FAV_OK:
+            raise ValueError(err.value.decode("utf-8", "replace"))
+
+
+def build_knn_bank(features, labels=None, k: int = 10, max_rows: int | None = None, seed: int = 0) -> KNNBank:
+    """features [N, D] (one row per in-distribution frame: the mean over the samples of its features), labels int[N] or None
+    -> the bank: every row divided by its Euclidean norm in float64, then rounded to bf16 (nearest even).  ``max_rows``: keep
+    that many rows, drawn without replacement by ``np.random.default_rng(seed)`` and kept in their original order.  Refuses a
+    non-finite value and a zero row."""
+    F = np.asarray(features, np.float64)
+    if F.ndim != 2 or F.shape[0] < 1:
+        raise ValueError("features must be [N, D] with at least one row")
+    if not np.isfinite(F).all():
+        raise ValueError("features hold a non-finite value")
+    y = None
+    if labels is not None:
+        y = np.asarray(labels).ravel()
+        if y.shape[0] != F.shape[0]:
+            raise ValueError("one label per feature row")
+        if not np.issubdtype(y.dtype, np.integer):
+            raise ValueError("labels must be integers")
+        if (y < 0).any():
+            raise ValueError("labels must not be negative")
+    if max_rows is not None:
+        if max_rows < 1:
+            raise ValueError(f"max_rows must be at least 1, got {max_rows}")
+        if max_rows < F.shape[0]:
+            keep = np.sort(np.random.default_rng(seed).choice(F.shape[0], size=int(max_rows), replace=False))
+            F, y = F[keep], (None if y is None else y[keep])
+    norm = np.sqrt((F * F).sum(axis=1))
+    if not (norm > 0).all():
+        raise ValueError(f"feature row {int(np.flatnonzero(~(norm > 0))[0])} is zero: it has no direction")
+    if not 1 <= k <= F.shape[0]:
+        raise ValueError(f"k must be in [1, N={F.shape[0]}], got {k}")
+    rows = _bf16_bits((F / norm[:, None]).astype(np.float32))
+    return KNNBank(rows, None if y is None else y.astype(np.int32), k=k)
+
+
+def unpack_knn_records(records) -> dict:
+    """int32[n, 6] fav_knn_record records (torch tensor or numpy) -> ``kth_dist``, ``kth_sim``, ``nn_sim`` fp32[n], ``nn_row``,
+    ``nn_class``, ``ood`` int32[n]; views of the record buffer."""
+    if records.ndim != 2 or int(records.shape[1]) != KNN_RECORD_DWORDS:
+        raise ValueError(f"expected int32[n, {KNN_RECORD_DWORDS}] records, got shape {tuple(records.shape)}")
+    if isinstance(records, np.ndarray):
+        f32 = np.float32
+    else:
+        import torch
+        f32 = torch.float32
+    return {"kth_dist": records[:, 0].view(f32), "kth_sim": records[:, 1].view(f32), "nn_sim": records[:, 2].view(f32),
+            "nn_row": records[:, 3], "nn_class": records[:, 4], "ood": records[:, 5]}

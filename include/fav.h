@@ -350,6 +350,56 @@ fav_status fav_classify_ood(fav_handle* h, const void* images_dev, int32_t n, in
                             int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev,
                             fav_ood_record* ood_dev, void* hip_stream);
 
+/* ---- Nearest-neighbour OOD scoring (deep nearest neighbours, Sun et al. 2022): the
+ * non-parametric companion of the Mahalanobis model above.  A BANK holds N L2-normalised in-distribution features as bf16
+ * rows; a frame's score is the squared Euclidean distance of its normalised feature to its k-th nearest bank row.  No labels,
+ * no covariance, no assumption about the shape of a class.  All pointers are HOST pointers.
+ * Ranges (fav_check_knn_bank; FAV_ERR_INVALID_ARG and a message that names the field): struct_size == sizeof(fav_knn_bank);
+ * D a multiple of 64 in [64, 4096] (and the arch's feature width when set on a handle); 1 <= N <= 262144; 1 <= k <=
+ * min(N, 256); no row value NaN or inf; class_id NULL or every entry >= -1; threshold not NaN (+inf: no frame is ever
+ * flagged).  The rows are meant to be unit vectors; this is not checked. */
+typedef struct fav_knn_bank {
+    uint32_t struct_size; int32_t D, N, k;
+    const uint16_t* rows;    /* [N][D] bf16 bit patterns                        (host) */
+    const int32_t* class_id; /* [N] class of each row, -1 = none; or NULL       (host) */
+    float threshold;         /* ood = !(kth_dist <= threshold); +inf = never */
+} fav_knn_bank;
+/* One frame's score, 24 bytes, 8-byte aligned.  Per frame i, with the features feat[S][n][D] bf16 indexed as in
+ * fav_get_features, everything fp32, every product and every sum rounded on its own (no FMA contraction):
+ *   1. fbar[j]    step 1 of fav_ood_record: +0, plus fp32(feat[s][i][j]) for s = 0 .. S-1 in that order, times (float)(1.0 / S)
+ *   2. ss         sixteen partial sums: p[l] = +0, then for j = l, l+16, l+32, .. in that order p[l] = p[l] + fbar[j] * fbar[j];
+ *                 ss = (((p[0] + p[1]) + p[2]) + .. + p[15])
+ *   3. q[j]       inv = 1.0f / sqrtf(ss), both correctly rounded; q[j] = bf16_rne(fbar[j] * inv)
+ *   4. sim[b]     b < N: acc[b] + (+0.0f), where acc[b] is the production GEMM accumulator of
+ *                 q . bank[b]: v_mfma_f32_16x16x32_bf16 chained from +0 over ascending k, k in the operand layout of the
+ *                 convolution kernels; K is never split and never re-associated.  The + 0.0f is a conv epilogue's zero bias,
+ *                 and rules out -0
+ *   5. kth_sim    the k-th largest value of the multiset {sim[b]} (a value: no tie rule needed); nn_sim the largest value;
+ *                 nn_row the LOWEST row that holds it; nn_class = class_id[nn_row], -1 when the bank has no class ids
+ *   6. kth_dist   fmaxf(2.0f - 2.0f * kth_sim, +0.0f): the squared distance of two unit vectors; ood = !(kth_dist <= threshold)
+ *   7. a DEGENERATE frame, !(ss > 0 && ss < inf) - a zero feature row, a NaN or inf feature, an overflowed square - gets
+ *      kth_sim = nn_sim = kth_dist = NaN (0x7FC00000), nn_row = nn_class = -1, ood = 1, and touches no other frame of the
+ *      call.  For every other frame |q[j]| <= 1 and the bank is finite, so every sim is finite. */
+typedef struct fav_knn_record { float kth_dist, kth_sim, nn_sim; int32_t nn_row, nn_class, ood; } fav_knn_record;
+/* Host only, no device: the ranges above (D_expected < 0: any width in range), the one place they live; fav_set_knn calls it
+ * first.  err (may be NULL) receives the message. */
+fav_status fav_check_knn_bank(const fav_knn_bank* bank, int32_t D_expected, char* err, size_t err_cap);
+/* The handle's bank (NULL: none), as fav_set_ood in every respect: copied to the device (padded with zero rows to a multiple
+ * of 64, which the GEMM's tiles want), the feature tap goes on; clearing it turns the tap off again only if a head turned it
+ * on and no OOD model still reads it.  A model and a bank may be set together: the tap stays on while either is set or while
+ * the caller turned it on, and fav_set_feature_tap(h, 0) is refused while either reads it.  The setter allocates the whole
+ * workspace, for max_batch frames - fav_classify_knn never allocates or synchronises - and refuses a bank whose workspace
+ * would exceed 1 GiB (the message carries the numbers).  Replacing or clearing a bank waits on the host for the work
+ * enqueued on the handle and frees the old copy.  FAV_ERR_UNSUPPORTED on a deep-ensemble handle.  A rejected call leaves
+ * the handle as it was. */
+fav_status fav_set_knn(fav_handle* h, const fav_knn_bank* bank);
+/* fav_classify_ex unchanged, then the k-NN head on the tapped features, all on the caller's stream: knn_dev[n] (non-NULL,
+ * 8-byte aligned) gets one fav_knn_record per frame.  Needs a bank (FAV_ERR_INVALID_ARG otherwise).  fail_dev / score_dev may
+ * be NULL.  The head's three launches are booked in no kernel class, like fav_classify_ood's. */
+fav_status fav_classify_knn(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
+                            int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev,
+                            fav_knn_record* knn_dev, void* hip_stream);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -644,6 +694,22 @@ fav_status fav_op_ood_score(const void* feat_bf16, int32_t S, int32_t n, int32_t
                             const float* mu_dev, const float* Pt_dev, const float* Mt_dev,
                             const int32_t* class_id_dev, const int32_t* labels_dev, float threshold,
                             fav_ood_record* records_dev, void* hip_stream);
+
+/* ---- The k-NN head defined beside fav_knn_record, on device arrays: feat_bf16 [S][n][D] bf16, bank_dev [N][D] bf16 (16-byte
+ * aligned; exactly N rows - the caller never pads), class_id_dev [N] or NULL, ws_dev a workspace of at least
+ * fav_knn_workspace_bytes(n, D, N) bytes on a 256-byte boundary, records_dev [n] (8-byte aligned).  Three kernels: the query
+ * kernel (q and the degenerate flags), the similarity GEMM through the convolution launcher (1x1, fp32 output, zero bias;
+ * fav_op_last_route names its tile) - in two launches when N is no multiple of 64 and at least 64: the bank in place up to
+ * its last whole 64 rows, the rest from a zero-padded tile in the workspace - and the radix select.  No allocation, no
+ * synchronisation; vector stores only.  Padding columns and degenerate frames' rows of the workspace are never read by the
+ * select.
+ * A refused call (FAV_ERR_INVALID_ARG: a NULL pointer other than class_id_dev, S outside [1, 4096], n < 1, D, N or k outside
+ * the ranges of fav_knn_bank, a NaN threshold, a workspace too small or misaligned, a misaligned bank_dev or records_dev)
+ * launches nothing and leaves a message that names the function in fav_last_error(NULL). */
+size_t fav_knn_workspace_bytes(int32_t n, int32_t D, int32_t N);   /* host only; 0 for sizes out of range */
+fav_status fav_op_knn_score(const void* feat_bf16, int32_t S, int32_t n, int32_t D, const void* bank_dev, int32_t N, int32_t k,
+                            const int32_t* class_id_dev, float threshold, void* ws_dev, size_t ws_bytes,
+                            fav_knn_record* records_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
