@@ -34,6 +34,11 @@ UNCERTAINTY_DWORDS = 18
 _MATH = {"bf16": _lib.MATH_BF16, "f32_exact": _lib.MATH_F32_EXACT}
 
 
+def _to_numpy(x) -> np.ndarray:
+    """A numpy array as it is, a torch tensor copied to the host (which synchronises its stream)."""
+    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
+
+
 class Backend:
     def __init__(self, arch: str = "resnet50", blob: bytes | None = None, *, seed_weights: int = 1, device: int | None = None,
                  in_hw=None, max_batch: int = 256, num_classes: int | None = None,
@@ -206,11 +211,22 @@ class Backend:
             raise ValueError(f"out must be a contiguous int32[n, {width}] tensor on the frames' device")
         return out
 
+    def _batches(self, n: int):
+        """(b, e) over n frames, frames_per_call at a time."""
+        mb = self.frames_per_call
+        return ((b, min(n, b + mb)) for b in range(0, n, mb))
+
+    def _detect_buffers(self, n: int, dev, first: int = 0) -> tuple:
+        """-> new (labels int32[n], conf fp32[n], fail uint8[n], score fp32[n]) on ``dev``: what fav_classify_ex writes.
+        ``first`` = 2: the (fail, score) half alone, for a head that writes labels and confidences into its records."""
+        torch = self._torch
+        dtypes = (torch.int32, torch.float32, torch.uint8, torch.float32)
+        return tuple(torch.empty(n, dtype=dt, device=dev) for dt in dtypes[first:])
+
     def classify_detect(self, images, first_index: int = 0):
         """-> (labels int32[n], confidences fp32[n], fail uint8[n], anomaly_score fp32[n]).
         torch CUDA tensors in -> torch CUDA tensors out (asynchronous on the current
         stream); numpy in -> numpy out (synchronous)."""
-        torch = self._torch
         img, host, n, layout, stream = self._classify_args(images, keep_host=True)
         if host:
             labels = np.empty(n, np.int32); conf = np.empty(n, np.float32)
@@ -219,11 +235,7 @@ class Backend:
                                                   labels.ctypes.data, conf.ctypes.data, fail.ctypes.data,
                                                   score.ctypes.data), self._h)
             return labels, conf, fail, score
-        dev = img.device
-        labels = torch.empty(n, dtype=torch.int32, device=dev)
-        conf = torch.empty(n, dtype=torch.float32, device=dev)
-        fail = torch.empty(n, dtype=torch.uint8, device=dev)
-        score = torch.empty(n, dtype=torch.float32, device=dev)
+        labels, conf, fail, score = self._detect_buffers(n, img.device)
         _lib.check(self.lib.fav_classify_ex(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
                                             conf.data_ptr(), fail.data_ptr(), score.data_ptr(), stream), self._h)
         return labels, conf, fail, score
@@ -248,12 +260,9 @@ class Backend:
         the records into (e.g. this rank's slot of an all-gather send buffer).
         A non-finite frame (include/fav.h: a NaN or +inf among a sample's scaled logits, or a sample -inf throughout):
         label 0, confidence 0, fail 1 whatever tau is, score 1; the other statistics NaN, top_label -1, top_prob 0."""
-        torch = self._torch
         img, host, n, layout, stream = self._classify_args(images)
-        dev = img.device
-        out = self._records_out(out, n, UNCERTAINTY_DWORDS, dev)
-        fail = torch.empty(n, dtype=torch.uint8, device=dev)
-        score = torch.empty(n, dtype=torch.float32, device=dev)
+        out = self._records_out(out, n, UNCERTAINTY_DWORDS, img.device)
+        fail, score = self._detect_buffers(n, img.device, first=2)
         _lib.check(self.lib.fav_classify_uncertainty(self._h, img.data_ptr(), n, layout, int(first_index), out.data_ptr(),
                                                      fail.data_ptr(), score.data_ptr(), stream), self._h)
         if host:
@@ -268,15 +277,10 @@ class Backend:
         asynchronous on the current stream; numpy in -> numpy out, synchronous."""
         torch = self._torch
         img, host, n, layout, stream = self._classify_args(images)
-        if int(np.shape(labels)[0] if isinstance(labels, np.ndarray) else labels.shape[0]) != n:
-            raise ValueError("one label per frame")
-        dev = img.device
-        lab = (torch.from_numpy(np.asarray(labels)) if isinstance(labels, np.ndarray) else labels).to(dev, torch.int32).contiguous()
-        out = torch.empty(n, dtype=torch.float32, device=dev)
+        lab = self._labels_on(labels, n, img.device)
+        out = torch.empty(n, dtype=torch.float32, device=img.device)
         c = cp.to_c()
-        mb = self.frames_per_call
-        for b in range(0, n, mb):
-            e = min(n, b + mb)
+        for b, e in self._batches(n):
             _lib.check(self.lib.fav_conformal_scores(self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b,
                                                      C.byref(c), lab[b:e].data_ptr(), out[b:e].data_ptr(), stream), self._h)
         return out.cpu().numpy() if host else out
@@ -291,8 +295,7 @@ class Backend:
             raise ValueError(f"method must be 'lac', 'aps' or 'raps', got {method!r}")
         kind = "lac" if method == "lac" else "aps"
         cp = Conformal(kind=kind, randomized=bool(randomized) and kind == "aps", lam=float(lam), k_reg=int(k_reg), seed=int(seed))
-        s = self.conformal_scores(images, labels, cp, first_index=first_index)
-        s = s if isinstance(s, np.ndarray) else s.cpu().numpy()
+        s = _to_numpy(self.conformal_scores(images, labels, cp, first_index=first_index))
         return dataclasses.replace(cp, qhat=calibrate_qhat(s, alpha))
 
     def classify_sets(self, images, cp, first_index: int = 0, out=None) -> dict:
@@ -305,12 +308,9 @@ class Backend:
         A non-finite frame (include/fav.h): label 0, confidence 0, fail 1 whatever tau is, score 1, an empty set
         (set_size 0, set_mass 0, hence ambiguous); its calibration score is NaN, which calibrate_conformal refuses."""
         from .conformal import PRED_SET_DWORDS, unpack_sets
-        torch = self._torch
         img, host, n, layout, stream = self._classify_args(images)
-        dev = img.device
-        out = self._records_out(out, n, PRED_SET_DWORDS, dev)
-        fail = torch.empty(n, dtype=torch.uint8, device=dev)
-        score = torch.empty(n, dtype=torch.float32, device=dev)
+        out = self._records_out(out, n, PRED_SET_DWORDS, img.device)
+        fail, score = self._detect_buffers(n, img.device, first=2)
         c = cp.to_c()
         _lib.check(self.lib.fav_classify_sets(self._h, img.data_ptr(), n, layout, int(first_index), C.byref(c),
                                               out.data_ptr(), fail.data_ptr(), score.data_ptr(), stream), self._h)
@@ -357,9 +357,7 @@ class Backend:
         lab = self._labels_on(labels, n, dev)
         t, tp = self._temps_c(temperatures)
         cells = torch.empty((n, t.size, 4), dtype=torch.int32, device=dev)
-        mb = self.frames_per_call
-        for b in range(0, n, mb):
-            e = min(n, b + mb)
+        for b, e in self._batches(n):
             _lib.check(self.lib.fav_classify_sweep(self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b,
                                                    lab[b:e].data_ptr(), tp, t.size, cells[b:e].data_ptr(), stream), self._h)
             if _keep_logits is not None:
@@ -388,8 +386,7 @@ class Backend:
         kept = []
 
         def sum_nll(cells):
-            c = cells if isinstance(cells, np.ndarray) else cells.cpu().numpy()
-            return unpack_cells(c)["nll"].astype(np.float64).sum(axis=0)
+            return unpack_cells(_to_numpy(cells))["nll"].astype(np.float64).sum(axis=0)
 
         def nll_of(temps):
             if not kept:
@@ -399,12 +396,11 @@ class Backend:
 
     def _detect_batched(self, images, first_index: int = 0):
         """classify_detect over batches of frames_per_call frames -> numpy (labels, conf)."""
-        n, mb = int(images.shape[0]), self.frames_per_call
         out_l, out_c = [], []
-        for b in range(0, n, mb):
-            l, c, _, _ = self.classify_detect(images[b:min(n, b + mb)], int(first_index) + b)
-            out_l.append(l if isinstance(l, np.ndarray) else l.cpu().numpy())
-            out_c.append(c if isinstance(c, np.ndarray) else c.cpu().numpy())
+        for b, e in self._batches(int(images.shape[0])):
+            l, c, _, _ = self.classify_detect(images[b:e], int(first_index) + b)
+            out_l.append(_to_numpy(l))
+            out_c.append(_to_numpy(c))
         return np.concatenate(out_l), np.concatenate(out_c)
 
     def calibrate_tau(self, images, labels, target_risk: float, delta: float | None = None, first_index: int = 0) -> dict:
@@ -413,16 +409,14 @@ class Backend:
         the guarantee's failure probability (None: the empirical risk decides).  The handle is not changed."""
         from .calibration import tau_for_risk
         pred, conf = self._detect_batched(images, first_index)
-        lab = labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()
-        return tau_for_risk(conf, pred == np.asarray(lab).ravel(), target_risk, delta)
+        return tau_for_risk(conf, pred == np.asarray(_to_numpy(labels)).ravel(), target_risk, delta)
 
     def calibration_report(self, images, labels, first_index: int = 0) -> dict:
         """What the confidence is worth on labelled frames at the current temperature (a one-temperature sweep):
         accuracy, mean_confidence, nll, brier, ece, mce, aurc."""
         from .calibration import report_from_cells
         cells = self.calibration_sweep(images, labels, [self.cfg.temperature], first_index)
-        lab = labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()
-        return report_from_cells(cells if isinstance(cells, np.ndarray) else cells.cpu().numpy(), lab)
+        return report_from_cells(_to_numpy(cells), _to_numpy(labels))
 
     def robustness_report(self, frames_u8, labels, corruptions=CORRUPTIONS, severities=(1, 2, 3, 4, 5), seed: int = 0,
                           first_index: int = 0) -> dict:
@@ -440,17 +434,15 @@ class Backend:
         if self._layout_of(frames_u8) != _lib.LAYOUT_NHWC_U8:
             raise TypeError("robustness_report takes uint8 frames")
         img, _ = self._frames_on_device(frames_u8)
-        n, mb = int(img.shape[0]), self.frames_per_call
+        n = int(img.shape[0])
         lab = self._labels_on(labels, n, img.device)
         lab_host = lab.cpu().numpy()
         cor = Corruptor(seed=seed)
         temps = [self.cfg.temperature]
 
         def row(make):
-            cells = []
-            for b in range(0, n, mb):
-                e = min(n, b + mb)
-                cells.append(self.calibration_sweep(make(img[b:e], int(first_index) + b), lab[b:e], temps, int(first_index) + b))
+            cells = [self.calibration_sweep(make(img[b:e], int(first_index) + b), lab[b:e], temps, int(first_index) + b)
+                     for b, e in self._batches(n)]
             c = unpack_cells(torch.cat(cells).cpu().numpy())
             return summarize(c["label"][:, 0], c["confidence"][:, 0], c["nll"][:, 0], lab_host, self.cfg.tau)
 
@@ -509,6 +501,46 @@ class Backend:
         _lib.check(self.lib.fav_get_features(self._h, out.data_ptr(), None, None, None, stream), self._h)
         return out
 
+    # what the two feature heads (the Mahalanobis model, the k-NN bank) share
+    @staticmethod
+    def _frame_labels(labels, frames) -> np.ndarray:
+        lab = np.asarray(_to_numpy(labels)).ravel()
+        if lab.shape[0] != int(frames.shape[0]):
+            raise ValueError("one label per frame")
+        return lab
+
+    def _tapped_mean_features(self, frames) -> np.ndarray:
+        """Batches of frames_per_call frames through the classifier with the tap on -> float64 [n, D], the mean over the
+        samples of each frame's features.  A tap that only this call needs goes off again."""
+        own_tap = self._ood is None and self._knn is None and not self._tap
+        if own_tap:
+            self.set_feature_tap(True)
+        try:
+            rows = []
+            for b, e in self._batches(int(frames.shape[0])):
+                self.classify_detect(frames[b:e], b)
+                rows.append(self.features().to(self._torch.float64).mean(dim=0).cpu().numpy())
+        finally:
+            if own_tap:
+                self.set_feature_tap(False)
+        return np.concatenate(rows)
+
+    def _classify_feature_head(self, fn, record_dwords: int, unpack, images, first_index: int) -> dict:
+        """fav_classify_ood / fav_classify_knn (``fn``) -> ``unpack`` of the head's int32[n, record_dwords] records plus
+        ``label``, ``conf``, ``fail``, ``score``; numpy frames in -> numpy out."""
+        img, host, n, layout, stream = self._classify_args(images)
+        labels, conf, fail, score = self._detect_buffers(n, img.device)
+        rec = self._torch.empty((n, record_dwords), dtype=self._torch.int32, device=img.device)
+        _lib.check(fn(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(), conf.data_ptr(), fail.data_ptr(),
+                      score.data_ptr(), rec.data_ptr(), stream), self._h)
+        if host:
+            labels, conf, fail, score, rec = (t.cpu().numpy() for t in (labels, conf, fail, score, rec))
+        return dict(unpack(rec), label=labels, conf=conf, fail=fail, score=score)
+
+    def _head_distances(self, classify, key: str, frames) -> np.ndarray:
+        """``classify`` (classify_ood, classify_knn) over batches of frames_per_call frames -> its ``key`` of every frame."""
+        return np.concatenate([_to_numpy(classify(frames[b:e], b)[key]) for b, e in self._batches(int(frames.shape[0]))])
+
     @property
     def ood_model(self):
         """The ``ood.OODModel`` in force, None when off."""
@@ -519,22 +551,8 @@ class Backend:
         classifier with the tap on, the mean over the samples of each frame's features goes to ``ood.fit_mahalanobis``
         (``k``, ``shrinkage``).  The handle is left as it was: see ``set_ood``."""
         from .ood import fit_mahalanobis
-        n, mb = int(frames.shape[0]), self.frames_per_call
-        lab = np.asarray(labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()).ravel()
-        if lab.shape[0] != n:
-            raise ValueError("one label per frame")
-        own_tap = self._ood is None and self._knn is None and not self._tap
-        if own_tap:
-            self.set_feature_tap(True)
-        try:
-            rows = []
-            for b in range(0, n, mb):
-                self.classify_detect(frames[b:min(n, b + mb)], b)
-                rows.append(self.features().to(self._torch.float64).mean(dim=0).cpu().numpy())
-        finally:
-            if own_tap:
-                self.set_feature_tap(False)
-        return fit_mahalanobis(np.concatenate(rows), lab, **kw)
+        lab = self._frame_labels(labels, frames)
+        return fit_mahalanobis(self._tapped_mean_features(frames), lab, **kw)
 
     def set_ood(self, model):
         """Adopt an ``ood.OODModel`` (fav_set_ood: copied to the device, the tap goes on), or None: off.  Refused on a deep
@@ -553,33 +571,14 @@ class Backend:
         min_dist <= threshold).  torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in ->
         numpy out, synchronous."""
         from .ood import OOD_RECORD_DWORDS, unpack_records
-        torch = self._torch
-        img, host, n, layout, stream = self._classify_args(images)
-        dev = img.device
-        labels = torch.empty(n, dtype=torch.int32, device=dev)
-        conf = torch.empty(n, dtype=torch.float32, device=dev)
-        fail = torch.empty(n, dtype=torch.uint8, device=dev)
-        score = torch.empty(n, dtype=torch.float32, device=dev)
-        rec = torch.empty((n, OOD_RECORD_DWORDS), dtype=torch.int32, device=dev)
-        _lib.check(self.lib.fav_classify_ood(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
-                                             conf.data_ptr(), fail.data_ptr(), score.data_ptr(), rec.data_ptr(), stream), self._h)
-        if host:
-            labels, conf, fail, score, rec = (t.cpu().numpy() for t in (labels, conf, fail, score, rec))
-        return dict(unpack_records(rec), label=labels, conf=conf, fail=fail, score=score)
-
-    def _min_dists(self, frames) -> np.ndarray:
-        n, mb = int(frames.shape[0]), self.frames_per_call
-        out = []
-        for b in range(0, n, mb):
-            d = self.classify_ood(frames[b:min(n, b + mb)], b)["min_dist"]
-            out.append(d if isinstance(d, np.ndarray) else d.cpu().numpy())
-        return np.concatenate(out)
+        return self._classify_feature_head(self.lib.fav_classify_ood, OOD_RECORD_DWORDS, unpack_records, images, first_index)
 
     def calibrate_ood(self, frames, tpr: float = 0.95) -> float:
         """Set the model's threshold so that at least ``tpr`` of these in-distribution frames pass, and return it."""
         if self.ood_model is None:
             raise ValueError("calibrate_ood needs a model: set_ood first")
-        thr = self.ood_model.threshold_for_tpr(self._min_dists(frames), tpr)
+        from .ood import threshold_for_tpr
+        thr = threshold_for_tpr(self._head_distances(self.classify_ood, "min_dist", frames), tpr)
         self.set_ood(self.ood_model.with_threshold(thr))
         return thr
 
@@ -588,12 +587,9 @@ class Backend:
         model's current threshold, the share of each set that is flagged."""
         if self.ood_model is None:
             raise ValueError("ood_report needs a model: set_ood first")
-        from .ood import OODModel
-        a, b = self._min_dists(id_frames), self._min_dists(ood_frames)
-        thr = self.ood_model.threshold
-        return dict(auroc=OODModel.auroc(a, b), fpr_at_tpr95=OODModel.fpr_at_tpr(a, b, 0.95),
-                    id_mean_dist=float(a.mean()), ood_mean_dist=float(b.mean()), threshold=thr,
-                    id_flagged=float(np.mean(~(a <= thr))), ood_flagged=float(np.mean(~(b <= thr))), n_id=int(a.size), n_ood=int(b.size))
+        from .ood import separation_report
+        return separation_report(self._head_distances(self.classify_ood, "min_dist", id_frames),
+                                 self._head_distances(self.classify_ood, "min_dist", ood_frames), self.ood_model.threshold)
 
     # -- nearest-neighbour OOD scoring (ood.py KNNBank; include/fav.h fav_set_knn) ----------------------------------------
     @property
@@ -606,24 +602,8 @@ class Backend:
         with the tap on, the mean over the samples of each frame's features goes to ``ood.build_knn_bank`` (``k``,
         ``max_rows``, ``seed``).  The handle is left as it was: see ``set_knn``."""
         from .ood import build_knn_bank
-        n, mb = int(frames.shape[0]), self.frames_per_call
-        lab = None
-        if labels is not None:
-            lab = np.asarray(labels if isinstance(labels, np.ndarray) else labels.cpu().numpy()).ravel()
-            if lab.shape[0] != n:
-                raise ValueError("one label per frame")
-        own_tap = self._ood is None and self._knn is None and not self._tap
-        if own_tap:
-            self.set_feature_tap(True)
-        try:
-            rows = []
-            for b in range(0, n, mb):
-                self.classify_detect(frames[b:min(n, b + mb)], b)
-                rows.append(self.features().to(self._torch.float64).mean(dim=0).cpu().numpy())
-        finally:
-            if own_tap:
-                self.set_feature_tap(False)
-        return build_knn_bank(np.concatenate(rows), lab, **kw)
+        lab = None if labels is None else self._frame_labels(labels, frames)
+        return build_knn_bank(self._tapped_mean_features(frames), lab, **kw)
 
     def set_knn(self, bank):
         """Adopt an ``ood.KNNBank`` (fav_set_knn: copied to the device, the workspace allocated, the tap goes on), or None:
@@ -642,34 +622,14 @@ class Backend:
         threshold).  torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out,
         synchronous."""
         from .ood import KNN_RECORD_DWORDS, unpack_knn_records
-        torch = self._torch
-        img, host, n, layout, stream = self._classify_args(images)
-        dev = img.device
-        labels = torch.empty(n, dtype=torch.int32, device=dev)
-        conf = torch.empty(n, dtype=torch.float32, device=dev)
-        fail = torch.empty(n, dtype=torch.uint8, device=dev)
-        score = torch.empty(n, dtype=torch.float32, device=dev)
-        rec = torch.empty((n, KNN_RECORD_DWORDS), dtype=torch.int32, device=dev)
-        _lib.check(self.lib.fav_classify_knn(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
-                                             conf.data_ptr(), fail.data_ptr(), score.data_ptr(), rec.data_ptr(), stream), self._h)
-        if host:
-            labels, conf, fail, score, rec = (t.cpu().numpy() for t in (labels, conf, fail, score, rec))
-        return dict(unpack_knn_records(rec), label=labels, conf=conf, fail=fail, score=score)
-
-    def _kth_dists(self, frames) -> np.ndarray:
-        n, mb = int(frames.shape[0]), self.frames_per_call
-        out = []
-        for b in range(0, n, mb):
-            d = self.classify_knn(frames[b:min(n, b + mb)], b)["kth_dist"]
-            out.append(d if isinstance(d, np.ndarray) else d.cpu().numpy())
-        return np.concatenate(out)
+        return self._classify_feature_head(self.lib.fav_classify_knn, KNN_RECORD_DWORDS, unpack_knn_records, images, first_index)
 
     def calibrate_knn(self, frames, tpr: float = 0.95) -> float:
         """Set the bank's threshold so that at least ``tpr`` of these in-distribution frames pass, and return it."""
         if self.knn_bank is None:
             raise ValueError("calibrate_knn needs a bank: set_knn first")
-        from .ood import OODModel
-        thr = OODModel.threshold_for_tpr(self._kth_dists(frames), tpr)
+        from .ood import threshold_for_tpr
+        thr = threshold_for_tpr(self._head_distances(self.classify_knn, "kth_dist", frames), tpr)
         self.set_knn(self.knn_bank.with_threshold(thr))
         return thr
 
@@ -677,12 +637,9 @@ class Backend:
         """How well kth_dist separates ``ood_frames`` from ``id_frames``: the keys of ``ood_report``."""
         if self.knn_bank is None:
             raise ValueError("knn_report needs a bank: set_knn first")
-        from .ood import OODModel
-        a, b = self._kth_dists(id_frames), self._kth_dists(ood_frames)
-        thr = self.knn_bank.threshold
-        return dict(auroc=OODModel.auroc(a, b), fpr_at_tpr95=OODModel.fpr_at_tpr(a, b, 0.95),
-                    id_mean_dist=float(a.mean()), ood_mean_dist=float(b.mean()), threshold=thr,
-                    id_flagged=float(np.mean(~(a <= thr))), ood_flagged=float(np.mean(~(b <= thr))), n_id=int(a.size), n_ood=int(b.size))
+        from .ood import separation_report
+        return separation_report(self._head_distances(self.classify_knn, "kth_dist", id_frames),
+                                 self._head_distances(self.classify_knn, "kth_dist", ood_frames), self.knn_bank.threshold)
 
     # -- profiling (bench.py roofline leg) ----------------------------------------
     def set_profiling(self, enable: bool):

@@ -151,9 +151,9 @@ struct fav_handle {
     size_t view_buf_bytes = 0;
     // Feature tap (fav_set_feature_tap): while on, every pass copies the rows its fc launch reads into feat_buf, bf16
     // [T_head][max_batch][feat_D] at most, indexed [sample][frame] like the logits; allocated by the setter.  feat_T / feat_n:
-    // the samples and frames of the last call that filled it (0: none yet)
-    // tap_by_head: a head's setter (fav_set_ood, fav_set_knn) turned it on, not the caller: it goes off with the last of them
-    bool tap = false, tap_by_head = false;
+    // the samples and frames of the last call that filled it (0: none yet).  tap_user: fav_set_feature_tap(1) is in force.
+    // tap is derived: tap_user || ood_on || knn_on, as tap_sync last brought it in line
+    bool tap = false, tap_user = false;
     void* feat_buf = nullptr;
     int feat_D = 0, feat_T = 0, feat_n = 0;
     // OOD model (fav_set_ood): the device copy, P and M transposed (fav_ood.hpp); ood_on: one is set
@@ -1647,16 +1647,17 @@ namespace {
 int head_samples(const fav_handle* h, int n_views) {
     return (h->n_members > 1 ? h->n_members : h->plan.T_eff) * std::max(1, n_views);
 }
+// what a host-only check (fav_check_views, fav_check_ood_model, fav_check_knn_bank) answers: `why` in err, "" and FAV_OK when fine
+fav_status check_reply(const std::string& why, char* err, size_t cap) {
+    if (err && cap) snprintf(err, cap, "%s", why.c_str());
+    return why.empty() ? FAV_OK : FAV_ERR_INVALID_ARG;
+}
 }  // namespace
 
 fav_status fav_check_views(const fav_view* views, int32_t n_views, int32_t H, int32_t W, char* err, size_t err_cap) {
     static_assert(sizeof(fav_view) == 24, "fav_view is 6 dwords");
     static_assert(FAV_MAX_VIEWS == VW_MAX_VIEWS && sizeof(ViewsArg) <= 2048, "the views travel in the kernel arguments");
-    if (err && err_cap) err[0] = 0;
-    const std::string why = views_error(views, n_views, H, W);
-    if (why.empty()) return FAV_OK;
-    if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
-    return FAV_ERR_INVALID_ARG;
+    return check_reply(views_error(views, n_views, H, W), err, err_cap);
 }
 
 fav_status fav_set_views(fav_handle* h, const fav_view* views, int32_t n_views) {
@@ -1794,41 +1795,89 @@ fav_status wait_enqueued(fav_handle* h) {
     if (h->ev_last_set) HIP_TRY(h, hipEventSynchronize(h->ev_last));
     return FAV_OK;
 }
-fav_status tap_on(fav_handle* h) {
-    if (!h->feat_buf) {
+// The tap is on iff the caller asked for it or a head reads it.  tap_sync brings the handle in line with `on`: tap_wanted
+// once one of the three facts has changed, or true in front of a fact that is about to (only that can fail, and then nothing
+// has changed).  Every transition forgets the last call's sizes: fav_get_features has nothing until the next call.
+bool tap_wanted(const fav_handle* h) { return h->tap_user || h->ood_on || h->knn_on; }
+fav_status tap_sync(fav_handle* h, bool on) {
+    if (on && !h->feat_buf) {
         const int D = feature_width(h);
         const size_t rows = (size_t)(h->n_members > 1 ? h->n_members : h->plan.T_eff) * h->cfg.max_batch;
         HIP_TRY(h, hipSetDevice(h->cfg.device));
         HIP_TRY(h, hipMalloc(&h->feat_buf, rows * D * 2 + 256));
         h->feat_D = D;
     }
-    if (!h->tap) { h->tap = true; h->feat_T = h->feat_n = 0; }
+    if (on != h->tap) { h->tap = on; h->feat_T = h->feat_n = 0; }
     return FAV_OK;
 }
-void tap_off(fav_handle* h) { h->tap = false; h->tap_by_head = false; h->feat_T = h->feat_n = 0; }
-// a head's setter (fav_set_ood, fav_set_knn) needs the tap: on, and the head's own if the caller had not turned it on
-fav_status tap_on_for_head(fav_handle* h) {
-    const bool tap_was_on = h->tap;
-    if (fav_status st = tap_on(h)) return st;
-    if (!tap_was_on) h->tap_by_head = true;
+
+// ---- the frames the two feature heads share (fav_set_ood / fav_set_knn, fav_classify_ood / fav_classify_knn)
+// the members of a deep ensemble have a feature space each: `what` ("an OOD model", "a k-NN bank") is refused on one
+fav_status refuse_ensemble(fav_handle* h, const char* fn, const char* what) {
+    if (h->n_members <= 1) return FAV_OK;
+    h->err = fmt("%s: the members of a deep ensemble do not share a feature space; %s is not supported on it", fn, what);
+    return FAV_ERR_UNSUPPORTED;
+}
+extern "C++" {   // templates
+// a setter's NULL argument: the head `cur` goes, and with the last reader the tap
+template <class Dev>
+fav_status head_clear(fav_handle* h, Dev& cur, bool& on, void (*free_dev)(Dev*)) {
+    if (!on) return FAV_OK;
+    if (fav_status st = wait_enqueued(h)) return st;
+    free_dev(&cur);
+    on = false;
+    return tap_sync(h, tap_wanted(h));
+}
+// ... and its last step: `fresh`, the device copy it built (`built`; false: it failed and has written h->err), becomes the
+// head.  Any failure frees `fresh` and leaves the handle, the tap included, as it was.
+template <class Dev>
+fav_status head_commit(fav_handle* h, Dev& cur, bool& on, Dev& fresh, void (*free_dev)(Dev*), bool built) {
+    fav_status st = built ? tap_sync(h, true) : FAV_ERR_HIP;
+    if (st == FAV_OK && on) st = wait_enqueued(h);
+    if (st != FAV_OK) {
+        free_dev(&fresh);
+        (void)tap_sync(h, tap_wanted(h));
+        return st;
+    }
+    if (on) free_dev(&cur);
+    cur = fresh;
+    on = true;
     return FAV_OK;
 }
-// ... and a head that has just been cleared lets go of it: off, if a head turned it on and no other head reads it
-void tap_release_by_head(fav_handle* h) {
-    if (h->tap_by_head && !h->ood_on && !h->knn_on) tap_off(h);
+
+// A classify call with a feature head behind it: fav_classify_ex, then `launch(stream)` on the same stream, which reads the
+// tap (feat_T x feat_n are this call's samples and frames) and returns its launcher's refusal, if it has one.  `on`: the
+// head's flag; `what` and `setter` name what is missing when it is off.
+template <class Launch>
+fav_status classify_feature_head(fav_handle* h, bool fav_handle::*on, const char* fn, const char* what, const char* setter,
+                                 const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels, float* conf,
+                                 uint8_t* fail, float* score, const void* records, void* stream, Launch launch) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!(h->*on)) { route_clear(); h->err = fmt("%s: no %s set (%s)", fn, what, setter); return FAV_ERR_INVALID_ARG; }
+    if (!records || ((uintptr_t)records & 7)) { route_clear(); h->err = fmt("%s: %s", fn, kBadRecords); return FAV_ERR_INVALID_ARG; }
+    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
+    hipStream_t s = (hipStream_t)stream;
+    const char* e = launch(s);
+    route_clear();            // the report speaks of fav_op_* launches only
+    mark_last_use(h, s);
+    if (e) { h->err = fmt("%s: %s", fn, e); return FAV_ERR_INVALID_ARG; }
+    HIP_TRY(h, hipGetLastError());
+    return FAV_OK;
 }
+}  // extern "C++"
 }  // namespace
 
 fav_status fav_set_feature_tap(fav_handle* h, int32_t enable) {
     if (!h) return FAV_ERR_INVALID_ARG;
-    if (!enable) {
-        if (h->ood_on) { h->err = "fav_set_feature_tap: an OOD model is set, which reads the tap; clear it first (fav_set_ood)"; return FAV_ERR_INVALID_ARG; }
-        if (h->knn_on) { h->err = "fav_set_feature_tap: a k-NN bank is set, which reads the tap; clear it first (fav_set_knn)"; return FAV_ERR_INVALID_ARG; }
-        tap_off(h);
+    if (enable) {
+        if (fav_status st = tap_sync(h, true)) return st;
+        h->tap_user = true;     // the caller's own tap outlives a model and a bank
         return FAV_OK;
     }
-    h->tap_by_head = false;     // the caller's own tap outlives a model and a bank
-    return tap_on(h);
+    if (h->ood_on) { h->err = "fav_set_feature_tap: an OOD model is set, which reads the tap; clear it first (fav_set_ood)"; return FAV_ERR_INVALID_ARG; }
+    if (h->knn_on) { h->err = "fav_set_feature_tap: a k-NN bank is set, which reads the tap; clear it first (fav_set_knn)"; return FAV_ERR_INVALID_ARG; }
+    h->tap_user = false;
+    return tap_sync(h, false);
 }
 
 fav_status fav_get_features(fav_handle* h, float* out, int32_t* s_out, int32_t* n_out, int32_t* d_out, void* stream) {
@@ -1853,29 +1902,15 @@ fav_status fav_get_features(fav_handle* h, float* out, int32_t* s_out, int32_t* 
 
 fav_status fav_check_ood_model(const fav_ood_model* m, int32_t D_expected, char* err, size_t err_cap) {
     static_assert(sizeof(fav_ood_record) == 16, "fav_ood_record is 4 dwords");
-    if (err && err_cap) err[0] = 0;
-    const std::string why = ood_model_error(m, D_expected);
-    if (why.empty()) return FAV_OK;
-    if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
-    return FAV_ERR_INVALID_ARG;
+    return check_reply(ood_model_error(m, D_expected), err, err_cap);
 }
 
 fav_status fav_set_ood(fav_handle* h, const fav_ood_model* m) {
     if (!h) return FAV_ERR_INVALID_ARG;
-    if (!m) {
-        if (!h->ood_on) return FAV_OK;
-        if (fav_status st = wait_enqueued(h)) return st;
-        free_ood(&h->ood);
-        h->ood_on = false;
-        tap_release_by_head(h);
-        return FAV_OK;
-    }
+    if (!m) return head_clear(h, h->ood, h->ood_on, free_ood);
     const std::string why = ood_model_error(m, feature_width(h));
     if (!why.empty()) { h->err = fmt("fav_set_ood: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
-    if (h->n_members > 1) {
-        h->err = "fav_set_ood: the members of a deep ensemble do not share a feature space; an OOD model is not supported on it";
-        return FAV_ERR_UNSUPPORTED;
-    }
+    if (fav_status st = refuse_ensemble(h, "fav_set_ood", "an OOD model")) return st;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     // the new copy first: a failure leaves the handle as it was
     const size_t D = (size_t)m->D, k = (size_t)m->k, R = (size_t)m->R;
@@ -1889,35 +1924,20 @@ fav_status fav_set_ood(fav_handle* h, const fav_ood_model* m) {
     auto upload = [&](void** dst, const void* src, size_t bytes) {
         return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
     };
-    if (!upload((void**)&nw.mu, m->mu, D * 4) || !upload((void**)&nw.Pt, Pt.data(), D * k * 4) ||
-        !upload((void**)&nw.Mt, Mt.data(), k * R * 4) || !upload((void**)&nw.cls, m->class_id, R * 4)) {
-        h->err = fmt("fav_set_ood: cannot copy the model to the device: %s", hipGetErrorString(hipGetLastError()));
-        free_ood(&nw);
-        return FAV_ERR_HIP;
-    }
-    if (fav_status st = tap_on_for_head(h)) { free_ood(&nw); return st; }
-    if (h->ood_on) {
-        if (fav_status st = wait_enqueued(h)) { free_ood(&nw); return st; }
-        free_ood(&h->ood);
-    }
-    h->ood = nw;
-    h->ood_on = true;
-    return FAV_OK;
+    const bool ok = upload((void**)&nw.mu, m->mu, D * 4) && upload((void**)&nw.Pt, Pt.data(), D * k * 4) &&
+                    upload((void**)&nw.Mt, Mt.data(), k * R * 4) && upload((void**)&nw.cls, m->class_id, R * 4);
+    if (!ok) h->err = fmt("fav_set_ood: cannot copy the model to the device: %s", hipGetErrorString(hipGetLastError()));
+    return head_commit(h, h->ood, h->ood_on, nw, free_ood, ok);
 }
 
 fav_status fav_classify_ood(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
                             float* conf, uint8_t* fail, float* score, fav_ood_record* ood, void* stream) {
-    if (!h) return FAV_ERR_INVALID_ARG;
-    if (!h->ood_on) { route_clear(); h->err = "fav_classify_ood: no OOD model set (fav_set_ood)"; return FAV_ERR_INVALID_ARG; }
-    if (!ood || ((uintptr_t)ood & 7)) { route_clear(); h->err = fmt("fav_classify_ood: %s", kBadRecords); return FAV_ERR_INVALID_ARG; }
-    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
-    // behind the forward pass on the same stream; feat_T x feat_n are this call's samples and frames
-    hipStream_t s = (hipStream_t)stream;
-    const fav_handle::OodDev& o = h->ood;
-    launch_ood(h->feat_buf, h->feat_T, h->feat_n, o.D, o.k, o.R, o.mu, o.Pt, o.Mt, o.cls, labels, o.threshold, ood, s);
-    HIP_TRY(h, hipGetLastError());
-    mark_last_use(h, s);
-    return FAV_OK;
+    return classify_feature_head(h, &fav_handle::ood_on, "fav_classify_ood", "OOD model", "fav_set_ood", images, n, layout, first_index,
+                                 labels, conf, fail, score, ood, stream, [&](hipStream_t s) -> const char* {
+        const fav_handle::OodDev& o = h->ood;
+        launch_ood(h->feat_buf, h->feat_T, h->feat_n, o.D, o.k, o.R, o.mu, o.Pt, o.Mt, o.cls, labels, o.threshold, ood, s);
+        return nullptr;
+    });
 }
 
 // ---- nearest-neighbour OOD scoring (fav_knn.hpp) ----------------------------
@@ -1972,11 +1992,7 @@ void free_knn(fav_handle::KnnDev* o) {
 
 fav_status fav_check_knn_bank(const fav_knn_bank* b, int32_t D_expected, char* err, size_t err_cap) {
     static_assert(sizeof(fav_knn_record) == 24, "fav_knn_record is 6 dwords");
-    if (err && err_cap) err[0] = 0;
-    const std::string why = knn_bank_error(b, D_expected);
-    if (why.empty()) return FAV_OK;
-    if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
-    return FAV_ERR_INVALID_ARG;
+    return check_reply(knn_bank_error(b, D_expected), err, err_cap);
 }
 
 size_t fav_knn_workspace_bytes(int32_t n, int32_t D, int32_t N) {
@@ -1986,20 +2002,10 @@ size_t fav_knn_workspace_bytes(int32_t n, int32_t D, int32_t N) {
 
 fav_status fav_set_knn(fav_handle* h, const fav_knn_bank* b) {
     if (!h) return FAV_ERR_INVALID_ARG;
-    if (!b) {
-        if (!h->knn_on) return FAV_OK;
-        if (fav_status st = wait_enqueued(h)) return st;
-        free_knn(&h->knn);
-        h->knn_on = false;
-        tap_release_by_head(h);
-        return FAV_OK;
-    }
+    if (!b) return head_clear(h, h->knn, h->knn_on, free_knn);
     const std::string why = knn_bank_error(b, feature_width(h));
     if (!why.empty()) { h->err = fmt("fav_set_knn: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
-    if (h->n_members > 1) {
-        h->err = "fav_set_knn: the members of a deep ensemble do not share a feature space; a k-NN bank is not supported on it";
-        return FAV_ERR_UNSUPPORTED;
-    }
+    if (fav_status st = refuse_ensemble(h, "fav_set_knn", "a k-NN bank")) return st;
     const KnnWs w = knn_workspace(h->cfg.max_batch, b->D, b->N, true);
     if (w.bytes > KNN_MAX_WS_BYTES) {
         h->err = fmt("fav_set_knn: the workspace of max_batch=%d frames against N=%d rows (%d padded) is %zu bytes, above the limit of %zu",
@@ -2017,37 +2023,18 @@ fav_status fav_set_knn(fav_handle* h, const fav_knn_bank* b) {
     if (ok && b->class_id)
         ok = hipMalloc((void**)&nw.cls, (size_t)b->N * 4) == hipSuccess && hipMemcpy(nw.cls, b->class_id, (size_t)b->N * 4, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && knn_prepare(w, nw.ws, nw.bank, b->D, b->N, true, nullptr) == FAV_OK && hipStreamSynchronize(nullptr) == hipSuccess;
-    if (!ok) {
-        h->err = fmt("fav_set_knn: cannot copy the bank to the device: %s", hipGetErrorString(hipGetLastError()));
-        free_knn(&nw);
-        return FAV_ERR_HIP;
-    }
-    if (fav_status st = tap_on_for_head(h)) { free_knn(&nw); return st; }
-    if (h->knn_on) {
-        if (fav_status st = wait_enqueued(h)) { free_knn(&nw); return st; }
-        free_knn(&h->knn);
-    }
-    h->knn = nw;
-    h->knn_on = true;
-    return FAV_OK;
+    if (!ok) h->err = fmt("fav_set_knn: cannot copy the bank to the device: %s", hipGetErrorString(hipGetLastError()));
+    return head_commit(h, h->knn, h->knn_on, nw, free_knn, ok);
 }
 
 fav_status fav_classify_knn(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
                             float* conf, uint8_t* fail, float* score, fav_knn_record* knn, void* stream) {
-    if (!h) return FAV_ERR_INVALID_ARG;
-    if (!h->knn_on) { route_clear(); h->err = "fav_classify_knn: no k-NN bank set (fav_set_knn)"; return FAV_ERR_INVALID_ARG; }
-    if (!knn || ((uintptr_t)knn & 7)) { route_clear(); h->err = fmt("fav_classify_knn: %s", kBadRecords); return FAV_ERR_INVALID_ARG; }
-    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
-    // behind the forward pass on the same stream; feat_T x feat_n are this call's samples and frames
-    hipStream_t s = (hipStream_t)stream;
-    const fav_handle::KnnDev& o = h->knn;
-    const KnnWs w = knn_workspace(h->cfg.max_batch, o.D, o.N, true);
-    const char* e = launch_knn(h->feat_buf, h->feat_T, h->feat_n, o.D, o.bank, o.N, o.k, o.cls, o.threshold, w, o.ws, true, knn, s);
-    route_clear();            // the report speaks of fav_op_* launches only
-    mark_last_use(h, s);
-    if (e) { h->err = fmt("fav_classify_knn: %s", e); return FAV_ERR_INVALID_ARG; }
-    HIP_TRY(h, hipGetLastError());
-    return FAV_OK;
+    return classify_feature_head(h, &fav_handle::knn_on, "fav_classify_knn", "k-NN bank", "fav_set_knn", images, n, layout, first_index,
+                                 labels, conf, fail, score, knn, stream, [&](hipStream_t s) {
+        const fav_handle::KnnDev& o = h->knn;
+        const KnnWs w = knn_workspace(h->cfg.max_batch, o.D, o.N, true);
+        return launch_knn(h->feat_buf, h->feat_T, h->feat_n, o.D, o.bank, o.N, o.k, o.cls, o.threshold, w, o.ws, true, knn, s);
+    });
 }
 
 fav_status fav_set_profiling(fav_handle* h, int32_t enable) {
@@ -2331,28 +2318,44 @@ static int corrupt_c_store_mode() {
     return v ? std::max(0, std::min(2, atoi(v))) : CC_STORE_STAGED;
 }
 
-static fav_status corruption_rejected(const char* fn, const char* why) {
+// an operator that refuses its arguments, before anything is launched
+static fav_status op_rejected(const char* fn, const char* why) {
     g_create_error = fmt("%s: %s", fn, why);
     return FAV_ERR_INVALID_ARG;
 }
 
+// The gate in front of a scoring head's launch: what fav_op_ood_score and fav_op_knn_score refuse alike, in the order both
+// report it, or "".  dims: the head's *_dims_error; own(): the checks only that head has, which stand in front of the records'.
+extern "C++" {   // a template
+template <class Own>
+static std::string score_gate(int S, int max_S, int n, const std::string& dims, float threshold, const void* records, Own own) {
+    if (S < 1 || S > max_S) return fmt("S=%d outside [1, %d]", S, max_S);
+    if (n < 1) return "n must be at least 1";
+    if (!dims.empty()) return dims;
+    if (std::isnan(threshold)) return "threshold is NaN";
+    const std::string why = own();
+    if (!why.empty()) return why;
+    return (uintptr_t)records & 7 ? "records_dev must be 8-byte aligned" : "";
+}
+}  // extern "C++"
+
 fav_status fav_corruption_params(int32_t kind, int32_t severity, float* a, float* b) {
-    if (!a || !b) return corruption_rejected("fav_corruption_params", "null pointer");
-    if (kind < 0 || kind >= FAV_C_COUNT) return corruption_rejected("fav_corruption_params", "kind outside [0, FAV_C_COUNT)");
-    if (severity < 1 || severity > 5) return corruption_rejected("fav_corruption_params", "severity outside 1..5");
+    if (!a || !b) return op_rejected("fav_corruption_params", "null pointer");
+    if (kind < 0 || kind >= FAV_C_COUNT) return op_rejected("fav_corruption_params", "kind outside [0, FAV_C_COUNT)");
+    if (severity < 1 || severity > 5) return op_rejected("fav_corruption_params", "severity outside 1..5");
     *a = kCorruptionSeverity[kind][severity - 1][0];
     *b = kCorruptionSeverity[kind][severity - 1][1];
     return FAV_OK;
 }
 
 fav_status fav_corruption_taps(int32_t kind, float a, float b, float* taps, int32_t cap, int32_t* radius) {
-    if (!taps || !radius) return corruption_rejected("fav_corruption_taps", "null pointer");
+    if (!taps || !radius) return op_rejected("fav_corruption_taps", "null pointer");
     if (kind != FAV_C_GAUSSIAN_BLUR && kind != FAV_C_DEFOCUS_BLUR)
-        return corruption_rejected("fav_corruption_taps", "only the two blur kinds have taps");
-    if (const char* why = corruption_params_error(kind, a, b)) return corruption_rejected("fav_corruption_taps", why);
+        return op_rejected("fav_corruption_taps", "only the two blur kinds have taps");
+    if (const char* why = corruption_params_error(kind, a, b)) return op_rejected("fav_corruption_taps", why);
     const int R = kind == FAV_C_GAUSSIAN_BLUR ? gauss_radius(a) : disk_radius(a);
     const int count = kind == FAV_C_GAUSSIAN_BLUR ? 2 * R + 1 : (2 * R + 1) * (2 * R + 1);
-    if (cap < count) return corruption_rejected("fav_corruption_taps", "cap is smaller than the number of taps");
+    if (cap < count) return op_rejected("fav_corruption_taps", "cap is smaller than the number of taps");
     if (kind == FAV_C_GAUSSIAN_BLUR) gauss_taps(a, R, taps);
     else disk_taps(a, b, taps);
     *radius = R;
@@ -2364,11 +2367,11 @@ fav_status fav_op_corrupt_c(const uint8_t* frames, float* out, int32_t n, int32_
     static_assert(sizeof(fav_corruption_desc) == 32, "fav_corruption_desc layout");
     const char* fn = "fav_op_corrupt_c";
     route_clear();
-    if (!frames || !out || !d) return corruption_rejected(fn, "null pointer");
-    if (n < 1 || H < 1 || W < 1) return corruption_rejected(fn, "n, H and W must be at least 1");
-    if (d->struct_size != sizeof(fav_corruption_desc)) return corruption_rejected(fn, "struct_size is not sizeof(fav_corruption_desc)");
-    if (const char* why = corruption_params_error(d->kind, d->a, d->b)) return corruption_rejected(fn, why);
-    if ((uintptr_t)out % 4 != 0) return corruption_rejected(fn, "out must be 4-byte aligned");
+    if (!frames || !out || !d) return op_rejected(fn, "null pointer");
+    if (n < 1 || H < 1 || W < 1) return op_rejected(fn, "n, H and W must be at least 1");
+    if (d->struct_size != sizeof(fav_corruption_desc)) return op_rejected(fn, "struct_size is not sizeof(fav_corruption_desc)");
+    if (const char* why = corruption_params_error(d->kind, d->a, d->b)) return op_rejected(fn, why);
+    if ((uintptr_t)out % 4 != 0) return op_rejected(fn, "out must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const long long npx = (long long)H * W, total = npx * n;
     const long long max_grid = (1ll << 24) - 1;
@@ -2395,13 +2398,13 @@ fav_status fav_op_corrupt_c(const uint8_t* frames, float* out, int32_t n, int32_
     case FAV_C_CONTRAST: {
         // blocks per frame: one per 4096 pixels, at most 16 (each of them reads the whole frame once for the sums)
         const int per_frame = (int)std::max<long long>(1, std::min<long long>((npx + 4095) / 4096, 16));
-        if ((long long)n * per_frame > 0x7FFFFFFFll) return corruption_rejected(fn, "too many frames for one contrast launch");
+        if ((long long)n * per_frame > 0x7FFFFFFFll) return op_rejected(fn, "too many frames for one contrast launch");
         hipLaunchKernelGGL(contrast_kernel, dim3((unsigned)(n * per_frame)), dim3(256), 0, s, frames, out, npx, per_frame,
                            (double)H * W * 255.0, d->a, corrupt_c_store_mode());
         break;
     }
     case FAV_C_PIXELATE: {
-        if (W > CC_PIXELATE_MAX_W) return corruption_rejected(fn, "pixelate takes frames up to 2048 pixels wide");
+        if (W > CC_PIXELATE_MAX_W) return op_rejected(fn, "pixelate takes frames up to 2048 pixels wide");
         const int hd = std::max(1, (int)((double)H * (double)d->a)), wd = std::max(1, (int)((double)W * (double)d->a));
         const long long items = (long long)n * hd;
         const size_t lds = (size_t)4 * W * 4 + (size_t)3 * wd * 4;
@@ -2435,20 +2438,20 @@ fav_status fav_op_views(const void* frames, void* out, int32_t n, int32_t H, int
                         int32_t n_views, void* stream) {
     const char* fn = "fav_op_views";
     route_clear();
-    if (!frames || !out) return corruption_rejected(fn, "null pointer");
-    if (n < 1 || H < 1 || W < 1) return corruption_rejected(fn, "n, H and W must be at least 1");
-    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return corruption_rejected(fn, "unknown layout");
+    if (!frames || !out) return op_rejected(fn, "null pointer");
+    if (n < 1 || H < 1 || W < 1) return op_rejected(fn, "n, H and W must be at least 1");
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return op_rejected(fn, "unknown layout");
     const std::string why = views_error(views, n_views, H, W);
-    if (!why.empty()) return corruption_rejected(fn, why.c_str());
+    if (!why.empty()) return op_rejected(fn, why.c_str());
     const size_t esz = layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4;
-    if (((uintptr_t)frames | (uintptr_t)out) % esz != 0) return corruption_rejected(fn, "fp32 frames and out must be 4-byte aligned");
+    if (((uintptr_t)frames | (uintptr_t)out) % esz != 0) return op_rejected(fn, "fp32 frames and out must be 4-byte aligned");
     // the kernels hold a frame's work items in 32 bits: H * (1 + ceil(W / 4)) <= H * W / 4 + 2 H stays below 2^31
-    if ((long long)H * W > 0x7FFFFFFFll / 12) return corruption_rejected(fn, "H * W above (2^31 - 1) / 12 pixels");
+    if ((long long)H * W > 0x7FFFFFFFll / 12) return op_rejected(fn, "H * W above (2^31 - 1) / 12 pixels");
     const long long frame_bytes = (long long)H * W * 3 * (long long)esz;
-    if ((long long)n * n_views > 0x7FFFFFFFll) return corruption_rejected(fn, "n * n_views above 2^31 - 1");
+    if ((long long)n * n_views > 0x7FFFFFFFll) return op_rejected(fn, "n * n_views above 2^31 - 1");
     const uintptr_t in_lo = (uintptr_t)frames, in_hi = in_lo + (uintptr_t)frame_bytes * (uintptr_t)n;
     const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + (uintptr_t)frame_bytes * (uintptr_t)n * (uintptr_t)n_views;
-    if (in_lo < out_hi && out_lo < in_hi) return corruption_rejected(fn, "out overlaps frames");
+    if (in_lo < out_hi && out_lo < in_hi) return op_rejected(fn, "out overlaps frames");
     launch_views(frames, out, n, H, W, layout, views, n_views, (hipStream_t)stream);
     return op_done(nullptr);
 }
@@ -2458,13 +2461,9 @@ fav_status fav_op_ood_score(const void* feat, int32_t S, int32_t n, int32_t D, i
                             fav_ood_record* records, void* stream) {
     const char* fn = "fav_op_ood_score";
     route_clear();
-    if (!feat || !mu || !Pt || !Mt || !class_id || !records) return corruption_rejected(fn, "null pointer");
-    if (S < 1 || S > OOD_MAX_S) return corruption_rejected(fn, fmt("S=%d outside [1, %d]", S, OOD_MAX_S).c_str());
-    if (n < 1) return corruption_rejected(fn, "n must be at least 1");
-    const std::string why = ood_dims_error(D, k, R);
-    if (!why.empty()) return corruption_rejected(fn, why.c_str());
-    if (std::isnan(threshold)) return corruption_rejected(fn, "threshold is NaN");
-    if ((uintptr_t)records & 7) return corruption_rejected(fn, "records_dev must be 8-byte aligned");
+    if (!feat || !mu || !Pt || !Mt || !class_id || !records) return op_rejected(fn, "null pointer");
+    const std::string why = score_gate(S, OOD_MAX_S, n, ood_dims_error(D, k, R), threshold, records, [] { return std::string(); });
+    if (!why.empty()) return op_rejected(fn, why.c_str());
     launch_ood(feat, S, n, D, k, R, mu, Pt, Mt, class_id, labels, threshold, records, (hipStream_t)stream);
     return op_done(nullptr);
 }
@@ -2474,17 +2473,15 @@ fav_status fav_op_knn_score(const void* feat, int32_t S, int32_t n, int32_t D, c
                             void* stream) {
     const char* fn = "fav_op_knn_score";
     route_clear();
-    if (!feat || !bank || !ws || !records) return corruption_rejected(fn, "null pointer");
-    if (S < 1 || S > KNN_MAX_S) return corruption_rejected(fn, fmt("S=%d outside [1, %d]", S, KNN_MAX_S).c_str());
-    if (n < 1) return corruption_rejected(fn, "n must be at least 1");
-    const std::string why = knn_dims_error(D, N, k);
-    if (!why.empty()) return corruption_rejected(fn, why.c_str());
-    if (std::isnan(threshold)) return corruption_rejected(fn, "threshold is NaN");
-    const KnnWs w = knn_workspace(n, D, N, false);
-    if (ws_bytes < w.bytes) return corruption_rejected(fn, fmt("ws_bytes=%zu is below fav_knn_workspace_bytes=%zu", ws_bytes, w.bytes).c_str());
-    if ((uintptr_t)ws & 255) return corruption_rejected(fn, "ws_dev must be 256-byte aligned");
-    if ((uintptr_t)bank & 15) return corruption_rejected(fn, "bank_dev must be 16-byte aligned");
-    if ((uintptr_t)records & 7) return corruption_rejected(fn, "records_dev must be 8-byte aligned");
+    if (!feat || !bank || !ws || !records) return op_rejected(fn, "null pointer");
+    KnnWs w;
+    const std::string why = score_gate(S, KNN_MAX_S, n, knn_dims_error(D, N, k), threshold, records, [&]() -> std::string {
+        w = knn_workspace(n, D, N, false);
+        if (ws_bytes < w.bytes) return fmt("ws_bytes=%zu is below fav_knn_workspace_bytes=%zu", ws_bytes, w.bytes);
+        if ((uintptr_t)ws & 255) return "ws_dev must be 256-byte aligned";
+        return (uintptr_t)bank & 15 ? "bank_dev must be 16-byte aligned" : "";
+    });
+    if (!why.empty()) return op_rejected(fn, why.c_str());
     hipStream_t s = (hipStream_t)stream;
     if (knn_prepare(w, ws, bank, D, N, false, s) != FAV_OK) { g_create_error = fmt("%s: cannot prepare the workspace: %s", fn, hipGetErrorString(hipGetLastError())); return FAV_ERR_HIP; }
     return op_done(fn, launch_knn(feat, S, n, D, bank, N, k, class_id, threshold, w, ws, false, records, s));

@@ -23,6 +23,66 @@ OOD_RECORD_DWORDS = 4
 #: dwords of one fav_knn_record
 KNN_RECORD_DWORDS = 6
 
+# ---- metrics: a score grows with strangeness; in-distribution frames should score low ------------------------------------------
+def _scores(v, name: str) -> np.ndarray:
+    s = np.asarray(v, np.float64).ravel()
+    if s.size == 0:
+        raise ValueError(f"{name} is empty")
+    if np.isnan(s).any():
+        raise ValueError(f"{name} holds a NaN")
+    return s
+
+
+def threshold_for_tpr(id_scores, tpr: float) -> float:
+    """The ceil(tpr * n)-th smallest in-distribution score: at least ``tpr`` of those frames pass ``score <= threshold``."""
+    s = _scores(id_scores, "id_scores")
+    if not 0.0 < tpr <= 1.0:
+        raise ValueError(f"tpr must be in (0, 1], got {tpr}")
+    rank = min(s.size, max(1, math.ceil(tpr * s.size - 1e-9)))
+    return float(np.sort(s)[rank - 1])
+
+
+def auroc(id_scores, ood_scores) -> float:
+    """P(an OOD frame scores above an in-distribution one), ties counting 1/2 (Mann-Whitney)."""
+    a, b = np.sort(_scores(id_scores, "id_scores")), _scores(ood_scores, "ood_scores")
+    below = np.searchsorted(a, b, side="left")
+    equal = np.searchsorted(a, b, side="right") - below
+    return float((below.sum() + 0.5 * equal.sum()) / (a.size * b.size))
+
+
+def fpr_at_tpr(id_scores, ood_scores, tpr: float = 0.95) -> float:
+    """The share of OOD frames that pass the threshold which keeps ``tpr`` of the in-distribution frames."""
+    thr = threshold_for_tpr(id_scores, tpr)
+    return float(np.mean(_scores(ood_scores, "ood_scores") <= thr))
+
+
+def separation_report(id_scores, ood_scores, threshold: float) -> dict:
+    """How well a score separates OOD frames from in-distribution ones: auroc, fpr_at_tpr95, the mean scores and, at
+    ``threshold``, the share of each set that is flagged (not score <= threshold)."""
+    a, b = np.asarray(id_scores), np.asarray(ood_scores)
+    return dict(auroc=auroc(a, b), fpr_at_tpr95=fpr_at_tpr(a, b, 0.95),
+                id_mean_dist=float(a.mean()), ood_mean_dist=float(b.mean()), threshold=threshold,
+                id_flagged=float(np.mean(~(a <= threshold))), ood_flagged=float(np.mean(~(b <= threshold))),
+                n_id=int(a.size), n_ood=int(b.size))
+
+
+def _check(fn: str, c, D_expected: int):
+    """The library's host-only check ``fn`` of the C struct ``c``; raises ValueError with the library's message."""
+    err = C.create_string_buffer(256)
+    if getattr(_lib.load(), fn)(C.byref(c), int(D_expected), err, len(err)) != _lib.FAV_OK:
+        raise ValueError(err.value.decode("utf-8", "replace"))
+
+
+def _f32_of(records, dwords: int):
+    """int32[n, dwords] records (torch tensor or numpy), or ValueError -> the fp32 type their float fields are viewed as."""
+    if records.ndim != 2 or int(records.shape[1]) != dwords:
+        raise ValueError(f"expected int32[n, {dwords}] records, got shape {tuple(records.shape)}")
+    if isinstance(records, np.ndarray):
+        return np.float32
+    import torch
+    return torch.float32
+
+
 
 @dataclasses.dataclass(frozen=True)
 class OODModel:
@@ -82,43 +142,12 @@ class OODModel:
 
     def check(self, D_expected: int = -1):
         """fav_check_ood_model (host only); raises ValueError with the library's message."""
-        err = C.create_string_buffer(256)
-        c = self.to_c()
-        if _lib.load().fav_check_ood_model(C.byref(c), int(D_expected), err, len(err)) != _lib.FAV_OK:
-            raise ValueError(err.value.decode("utf-8", "replace"))
+        _check("fav_check_ood_model", self.to_c(), D_expected)
 
-    # -- metrics: a score grows with strangeness; in-distribution frames should score low
-    @staticmethod
-    def threshold_for_tpr(id_scores, tpr: float) -> float:
-        """The ceil(tpr * n)-th smallest in-distribution score: at least ``tpr`` of those frames pass ``score <= threshold``."""
-        s = _scores(id_scores, "id_scores")
-        if not 0.0 < tpr <= 1.0:
-            raise ValueError(f"tpr must be in (0, 1], got {tpr}")
-        rank = min(s.size, max(1, math.ceil(tpr * s.size - 1e-9)))
-        return float(np.sort(s)[rank - 1])
-
-    @staticmethod
-    def auroc(id_scores, ood_scores) -> float:
-        """P(an OOD frame scores above an in-distribution one), ties counting 1/2 (Mann-Whitney)."""
-        a, b = np.sort(_scores(id_scores, "id_scores")), _scores(ood_scores, "ood_scores")
-        below = np.searchsorted(a, b, side="left")
-        equal = np.searchsorted(a, b, side="right") - below
-        return float((below.sum() + 0.5 * equal.sum()) / (a.size * b.size))
-
-    @staticmethod
-    def fpr_at_tpr(id_scores, ood_scores, tpr: float = 0.95) -> float:
-        """The share of OOD frames that pass the threshold which keeps ``tpr`` of the in-distribution frames."""
-        thr = OODModel.threshold_for_tpr(id_scores, tpr)
-        return float(np.mean(_scores(ood_scores, "ood_scores") <= thr))
-
-
-def _scores(v, name: str) -> np.ndarray:
-    s = np.asarray(v, np.float64).ravel()
-    if s.size == 0:
-        raise ValueError(f"{name} is empty")
-    if np.isnan(s).any():
-        raise ValueError(f"{name} holds a NaN")
-    return s
+    # the metrics below, under the names they have always had here
+    threshold_for_tpr = staticmethod(threshold_for_tpr)
+    auroc = staticmethod(auroc)
+    fpr_at_tpr = staticmethod(fpr_at_tpr)
 
 
 def fit_mahalanobis(features, labels, k: int | None = None, shrinkage: float = 0.01) -> OODModel:
@@ -163,13 +192,7 @@ def fit_mahalanobis(features, labels, k: int | None = None, shrinkage: float = 0
 def unpack_records(records) -> dict:
     """int32[n, 4] fav_ood_record records (torch tensor or numpy) -> ``min_dist`` fp32[n], ``nearest_class`` int32[n],
     ``label_dist`` fp32[n], ``ood`` int32[n]; views of the record buffer."""
-    if records.ndim != 2 or int(records.shape[1]) != OOD_RECORD_DWORDS:
-        raise ValueError(f"expected int32[n, {OOD_RECORD_DWORDS}] records, got shape {tuple(records.shape)}")
-    if isinstance(records, np.ndarray):
-        f32 = np.float32
-    else:
-        import torch
-        f32 = torch.float32
+    f32 = _f32_of(records, OOD_RECORD_DWORDS)
     return {"min_dist": records[:, 0].view(f32), "nearest_class": records[:, 1], "label_dist": records[:, 2].view(f32),
             "ood": records[:, 3]}
 
@@ -237,10 +260,7 @@ class KNNBank:
 
     def check(self, D_expected: int = -1):
         """fav_check_knn_bank (host only); raises ValueError with the library's message."""
-        err = C.create_string_buffer(256)
-        c = self.to_c()
-        if _lib.load().fav_check_knn_bank(C.byref(c), int(D_expected), err, len(err)) != _lib.FAV_OK:
-            raise ValueError(err.value.decode("utf-8", "replace"))
+        _check("fav_check_knn_bank", self.to_c(), D_expected)
 
 
 def build_knn_bank(features, labels=None, k: int = 10, max_rows: int | None = None, seed: int = 0) -> KNNBank:
@@ -280,12 +300,6 @@ def build_knn_bank(features, labels=None, k: int = 10, max_rows: int | None = No
 def unpack_knn_records(records) -> dict:
     """int32[n, 6] fav_knn_record records (torch tensor or numpy) -> ``kth_dist``, ``kth_sim``, ``nn_sim`` fp32[n], ``nn_row``,
     ``nn_class``, ``ood`` int32[n]; views of the record buffer."""
-    if records.ndim != 2 or int(records.shape[1]) != KNN_RECORD_DWORDS:
-        raise ValueError(f"expected int32[n, {KNN_RECORD_DWORDS}] records, got shape {tuple(records.shape)}")
-    if isinstance(records, np.ndarray):
-        f32 = np.float32
-    else:
-        import torch
-        f32 = torch.float32
+    f32 = _f32_of(records, KNN_RECORD_DWORDS)
     return {"kth_dist": records[:, 0].view(f32), "kth_sim": records[:, 1].view(f32), "nn_sim": records[:, 2].view(f32),
             "nn_row": records[:, 3], "nn_class": records[:, 4], "ood": records[:, 5]}

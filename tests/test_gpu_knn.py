@@ -402,3 +402,59 @@ def test_a_workspace_above_the_limit_is_refused_with_the_numbers(lib):
     be.classify(dev(synth.synthetic_frames_u8(2, 64, 64, seed=1)))
     assert not tap_is_on(be, lib)
     be.close()
+
+
+# ---- the tap's ownership: on iff the caller asked for it or a head reads it -------------------------------------------------
+def tap_heads():
+    """(setter name, head) of the two heads that read the tap, each as small as its checks allow."""
+    return (("set_knn", KNNBank(unit_rows(np.random.default_rng(0), 7, 512), k=2)),
+            ("set_ood", OODModel(np.zeros(512), np.eye(2, 512), np.zeros((1, 2)), np.zeros(1))))
+
+
+def tap_sizes(be, lib):
+    """fav_get_features without a buffer -> (status, (S, n, D) as it reported them)."""
+    s, n, d = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    st = lib.fav_get_features(be._h, None, C.byref(s), C.byref(n), C.byref(d), None)
+    return st, (s.value, n.value, d.value)
+
+
+def test_a_tap_the_caller_adopts_outlives_the_head_that_turned_it_on(lib, r18_b):
+    frames = synth.synthetic_frames_u8(3, 32, 32, seed=21)
+    be = Backend("resnet18_cifar", r18_b, max_batch=4)
+    for setter, head in tap_heads():
+        set_head = getattr(be, setter)
+        set_head(head)                                                               # the head turns the tap on
+        be.classify(dev(frames))
+        assert tap_is_on(be, lib)
+        be.set_feature_tap(True)                                                     # ... and the caller makes it their own
+        set_head(None)
+        assert tap_is_on(be, lib) and features_of(be, frames).shape == (1, 3, 512)
+        be.set_feature_tap(False)
+        be.classify(dev(frames))
+        assert not tap_is_on(be, lib), setter
+    be.close()
+
+
+def test_the_tap_forgets_the_last_call_when_it_goes_on_and_at_no_other_time(lib, r18_b):
+    frames = synth.synthetic_frames_u8(3, 32, 32, seed=22)
+    (_, bank), (_, model) = tap_heads()
+    be = Backend("resnet18_cifar", r18_b, max_batch=4)
+    be.set_ood(model)
+    be.classify(dev(frames))
+    assert tap_sizes(be, lib) == (0, (1, 3, 512))
+    be.set_knn(bank)                                                                 # a second head on a tap that is on
+    assert tap_sizes(be, lib) == (0, (1, 3, 512))
+    be.set_ood(None)
+    assert tap_sizes(be, lib) == (0, (1, 3, 512))                                    # the bank still reads it
+    be.set_knn(None)                                                                 # off with the last head ...
+    assert tap_sizes(be, lib)[0] == 1 and "the feature tap is off" in lib.fav_last_error(be._h).decode()
+    be.set_ood(model)                                                                # ... and on again: nothing to read yet
+    assert tap_sizes(be, lib) == (1, (-1, -1, -1))
+    assert "no classify call since the tap was turned on" in lib.fav_last_error(be._h).decode()
+    be.classify(dev(frames[:2]))
+    assert tap_sizes(be, lib) == (0, (1, 2, 512))
+    be.set_feature_tap(True)                                                         # the caller adopts a tap that is on
+    assert tap_sizes(be, lib) == (0, (1, 2, 512))
+    be.set_ood(None)
+    assert tap_sizes(be, lib) == (0, (1, 2, 512))
+    be.close()

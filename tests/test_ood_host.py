@@ -253,6 +253,47 @@ def test_auroc_and_fpr_with_ties():
         OODModel.auroc([1.0], [np.nan])
 
 
+def test_separation_report_on_hand_made_scores():
+    from failure_aware_vision_amd.ood import OODModel, separation_report
+    a, b = [0, 1, 1, 2, 5], [1, 3, 5, 6]
+    # above + half the ties, OOD score by OOD score: 1: 1 + 2/2; 3: 4; 5: 4 + 1/2; 6: 5
+    rep = separation_report(a, b, 2)
+    assert rep["auroc"] == 15.5 / 20 and rep["fpr_at_tpr95"] == OODModel.fpr_at_tpr(a, b) == 0.75   # the 5th smallest, 5: 1, 3, 5 pass
+    assert rep["id_flagged"] == 0.2 and rep["ood_flagged"] == 0.75 and (rep["n_id"], rep["n_ood"]) == (5, 4)
+    assert rep["id_mean_dist"] == 1.8 and rep["ood_mean_dist"] == 3.75 and rep["threshold"] == 2
+    assert set(rep) == {"auroc", "fpr_at_tpr95", "id_mean_dist", "ood_mean_dist", "threshold", "id_flagged", "ood_flagged",
+                        "n_id", "n_ood"}
+    assert separation_report(a, b, math.inf)["ood_flagged"] == 0.0 and separation_report(a, b, -1.0)["id_flagged"] == 1.0
+
+
+def test_module_level_metrics_are_the_static_methods():
+    from failure_aware_vision_amd import ood
+    rng = np.random.default_rng(5)
+    for _ in range(20):
+        a, b = rng.integers(0, 6, 40).astype(np.float64), rng.integers(2, 9, 31).astype(np.float32)   # ties within and across
+        assert ood.auroc(a, b) == ood.OODModel.auroc(a, b) == R.auroc(a, b)
+        for tpr in (0.05, 0.5, 0.95, 1.0):
+            assert ood.threshold_for_tpr(a, tpr) == ood.OODModel.threshold_for_tpr(a, tpr)
+            assert ood.fpr_at_tpr(a, b, tpr) == ood.OODModel.fpr_at_tpr(a, b, tpr)
+    m = model(16, 2, 3)
+    assert m.threshold_for_tpr([3.0, 1.0, 2.0], 0.5) == 2.0                         # on an instance, as Backend.calibrate_ood did
+    for fn in (ood.auroc, ood.OODModel.auroc, ood.fpr_at_tpr, ood.OODModel.fpr_at_tpr,
+               lambda x, y: ood.separation_report(x, y, 1.0)):
+        with pytest.raises(ValueError, match="id_scores is empty"):
+            fn([], [1.0])
+        with pytest.raises(ValueError, match="ood_scores is empty"):
+            fn([1.0], [])
+        with pytest.raises(ValueError, match="id_scores holds a NaN"):
+            fn([1.0, np.nan], [1.0])
+        with pytest.raises(ValueError, match="ood_scores holds a NaN"):
+            fn([1.0], [np.nan, 2.0])
+    for fn in (ood.threshold_for_tpr, ood.OODModel.threshold_for_tpr):
+        with pytest.raises(ValueError, match="id_scores is empty"):
+            fn([], 0.5)
+        with pytest.raises(ValueError, match="id_scores holds a NaN"):
+            fn([np.nan], 0.5)
+
+
 def test_npz_round_trip_and_records(tmp_path):
     from failure_aware_vision_amd.ood import OODModel, unpack_records
     m = model(48, 5, 7, threshold=12.5, class_id=np.array([3, 3, -1, 0, 9, 2, 2]))
