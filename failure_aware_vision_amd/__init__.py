@@ -12,6 +12,7 @@ from .calibration import (Calibration, fit_temperature, reliability, risk_covera
 from .corrupt import CORRUPTIONS, SEVERITY, Corruptor  # noqa: F401
 from .distributed import classify_sharded, shard_range  # noqa: F401
 from . import ood, robustness, synth, views, weights  # noqa: F401
-from .ood import KNNBank, OODModel, build_knn_bank, fit_mahalanobis  # noqa: F401
+from .ood import (DriftReference, KNNBank, OODModel, build_drift_reference, build_knn_bank, fit_mahalanobis,  # noqa: F401
+                  unpack_drift_record)
 from .views import View  # noqa: F401
 from .robustness import summarize  # noqa: F401

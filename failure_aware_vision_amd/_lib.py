@@ -136,6 +136,18 @@ class FavKnnRecord(C.Structure):
                 ("nn_class", C.c_int32), ("ood", C.c_int32)]
 
 
+class FavDriftRef(C.Structure):
+    """fav_drift_ref: a reference of L2-normalised bf16 feature rows, host pointers (ood.DriftReference.to_c fills it)."""
+    _fields_ = [("struct_size", C.c_uint32), ("D", C.c_int32), ("R", C.c_int32), ("n_perm", C.c_int32),
+                ("rows", C.POINTER(C.c_uint16)), ("seed", C.c_uint64), ("alpha", C.c_float)]
+
+
+class FavDriftRecord(C.Structure):
+    """fav_drift_record: one 48-byte record per call (ood.unpack_drift_record reads it as int32[12])."""
+    _fields_ = [("statistic", C.c_double), ("s_ab", C.c_int64), ("s_aa", C.c_int64), ("s_bb", C.c_int64),
+                ("p_value", C.c_float), ("n_exceed", C.c_int32), ("drift", C.c_int32), ("n_degenerate", C.c_int32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -193,6 +205,13 @@ _SIGNATURES = {
     "fav_knn_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "fav_op_knn_score": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "fav_check_drift_ref": (C.c_int, [C.POINTER(FavDriftRef), C.c_int32, C.c_char_p, C.c_size_t]),
+    "fav_set_drift": (C.c_int, [C.c_void_p, C.POINTER(FavDriftRef)]),
+    "fav_classify_drift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_drift_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "fav_op_drift_test": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64,
+                                    C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),

@@ -106,6 +106,7 @@ class Backend:
             self.load_weights(blob)
         self._T_head = cfg.n_samples if self.mc else max(1, cfg.n_members)
         self._tap, self._ood, self._knn = False, None, None   # the caller's own feature tap; the ood.OODModel, the ood.KNNBank in force
+        self._drift = None                                    # the ood.DriftReference in force
         self._views = ()
         if views:
             self.set_views(views)
@@ -512,7 +513,7 @@ class Backend:
     def _tapped_mean_features(self, frames) -> np.ndarray:
         """Batches of frames_per_call frames through the classifier with the tap on -> float64 [n, D], the mean over the
         samples of each frame's features.  A tap that only this call needs goes off again."""
-        own_tap = self._ood is None and self._knn is None and not self._tap
+        own_tap = self._ood is None and self._knn is None and self._drift is None and not self._tap
         if own_tap:
             self.set_feature_tap(True)
         try:
@@ -640,6 +641,72 @@ class Backend:
         from .ood import separation_report
         return separation_report(self._head_distances(self.classify_knn, "kth_dist", id_frames),
                                  self._head_distances(self.classify_knn, "kth_dist", ood_frames), self.knn_bank.threshold)
+
+    # -- window-level drift detection (ood.py DriftReference; include/fav.h fav_set_drift) -------------------------------
+    @property
+    def drift_reference(self):
+        """The ``ood.DriftReference`` in force, None when off."""
+        return self._drift
+
+    def fit_drift(self, frames, **kw):
+        """Build an ``ood.DriftReference`` from held-out in-distribution frames, as ``fit_knn`` builds a bank: the mean over
+        the samples of each frame's tapped features goes to ``ood.build_drift_reference`` (``max_rows``, ``n_perm``,
+        ``alpha``, ``seed``).  The handle is left as it was: see ``set_drift``."""
+        from .ood import build_drift_reference
+        return build_drift_reference(self._tapped_mean_features(frames), **kw)
+
+    def set_drift(self, ref):
+        """Adopt an ``ood.DriftReference`` (fav_set_drift: copied to the device, its own block of distances computed, the
+        workspace allocated, the tap goes on), or None: off.  Refused on a deep ensemble, for a reference whose D is not this
+        arch's feature width, and on a handle whose max_batch lies outside [2, 1024]."""
+        if ref is None:
+            _lib.check(self.lib.fav_set_drift(self._h, None), self._h)
+        else:
+            c = ref.to_c()
+            _lib.check(self.lib.fav_set_drift(self._h, C.byref(c)), self._h)
+        self._drift = ref
+
+    def classify_drift(self, images, first_index: int = 0) -> dict:
+        """frames -> ``label``, ``conf``, ``fail``, ``score`` as ``classify_detect`` gives them, plus ``record``: the one
+        fav_drift_record of the call as int32[12] (``ood.unpack_drift_record`` reads it).  One call is one window: the
+        permutation test is between the reference and exactly these frames, 2 to ``frames_per_call`` of them; more is a
+        ValueError.  torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out,
+        synchronous."""
+        from .ood import DRIFT_RECORD_DWORDS
+        n = int(images.shape[0])
+        if n > self.frames_per_call:
+            raise ValueError(f"classify_drift: a call is one window and takes at most frames_per_call={self.frames_per_call} "
+                             f"frames, got {n}")
+        img, host, n, layout, stream = self._classify_args(images)
+        labels, conf, fail, score = self._detect_buffers(n, img.device)
+        rec = self._torch.empty((DRIFT_RECORD_DWORDS,), dtype=self._torch.int32, device=img.device)
+        _lib.check(self.lib.fav_classify_drift(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
+                                               conf.data_ptr(), fail.data_ptr(), score.data_ptr(), rec.data_ptr(), stream), self._h)
+        if host:
+            labels, conf, fail, score, rec = (t.cpu().numpy() for t in (labels, conf, fail, score, rec))
+        return dict(record=rec, label=labels, conf=conf, fail=fail, score=score)
+
+    def drift_report(self, id_frames, shifted_frames, window: int) -> dict:
+        """Cut both sets into windows of ``window`` frames (a rest shorter than that is dropped), test each: ``id_p`` and
+        ``shifted_p`` (the p-values), ``false_alarm_rate`` and ``detection_rate`` (the share of each set's windows with
+        drift set, at the reference's alpha), ``alpha``, ``window``."""
+        if self.drift_reference is None:
+            raise ValueError("drift_report needs a reference: set_drift first")
+        if not 2 <= window <= self.frames_per_call:
+            raise ValueError(f"window must be in [2, frames_per_call={self.frames_per_call}], got {window}")
+        from .ood import unpack_drift_record
+
+        def run(frames):
+            recs = [unpack_drift_record(self.classify_drift(frames[b:b + window], b)["record"])
+                    for b in range(0, int(frames.shape[0]) - window + 1, window)]
+            if not recs:
+                raise ValueError(f"fewer than window={window} frames")
+            return np.array([r["p_value"] for r in recs], np.float32), float(np.mean([r["drift"] for r in recs]))
+
+        id_p, far = run(id_frames)
+        sh_p, det = run(shifted_frames)
+        return dict(id_p=id_p, shifted_p=sh_p, false_alarm_rate=far, detection_rate=det, alpha=self.drift_reference.alpha,
+                    window=int(window))
 
     # -- profiling (bench.py roofline leg) ----------------------------------------
     def set_profiling(self, enable: bool):

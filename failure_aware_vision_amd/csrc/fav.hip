@@ -29,6 +29,7 @@
 #include "fav_views.hpp"
 #include "fav_ood.hpp"
 #include "fav_knn.hpp"
+#include "fav_drift.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -152,7 +153,7 @@ struct fav_handle {
     // Feature tap (fav_set_feature_tap): while on, every pass copies the rows its fc launch reads into feat_buf, bf16
     // [T_head][max_batch][feat_D] at most, indexed [sample][frame] like the logits; allocated by the setter.  feat_T / feat_n:
     // the samples and frames of the last call that filled it (0: none yet).  tap_user: fav_set_feature_tap(1) is in force.
-    // tap is derived: tap_user || ood_on || knn_on, as tap_sync last brought it in line
+    // tap is derived: tap_user || ood_on || knn_on || drift_on, as tap_sync last brought it in line
     bool tap = false, tap_user = false;
     void* feat_buf = nullptr;
     int feat_D = 0, feat_T = 0, feat_n = 0;
@@ -165,6 +166,11 @@ struct fav_handle {
     struct KnnDev { void *bank = nullptr, *ws = nullptr; int32_t* cls = nullptr; int D = 0, N = 0, k = 0; float threshold = 0.f; };
     KnnDev knn;
     bool knn_on = false;
+    // drift reference (fav_set_drift): the workspace for max_batch frames (fav_drift.hpp drift_workspace, cached_ref), its
+    // pool holding the reference and U the reference's block of distances, both written once by the setter; drift_on: one is set
+    struct DriftDev { void* ws = nullptr; int D = 0, R = 0, n_perm = 0; uint64_t seed = 0; float alpha = 0.f; };
+    DriftDev drift;
+    bool drift_on = false;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -1068,6 +1074,7 @@ void free_all(fav_handle* h) {
     if (h->feat_buf) (void)hipFree(h->feat_buf);
     for (void* q : {(void*)h->ood.mu, (void*)h->ood.Pt, (void*)h->ood.Mt, (void*)h->ood.cls}) if (q) (void)hipFree(q);
     for (void* q : {h->knn.bank, h->knn.ws, (void*)h->knn.cls}) if (q) (void)hipFree(q);
+    if (h->drift.ws) (void)hipFree(h->drift.ws);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
@@ -1796,9 +1803,9 @@ fav_status wait_enqueued(fav_handle* h) {
     return FAV_OK;
 }
 // The tap is on iff the caller asked for it or a head reads it.  tap_sync brings the handle in line with `on`: tap_wanted
-// once one of the three facts has changed, or true in front of a fact that is about to (only that can fail, and then nothing
+// once one of the four facts has changed, or true in front of a fact that is about to (only that can fail, and then nothing
 // has changed).  Every transition forgets the last call's sizes: fav_get_features has nothing until the next call.
-bool tap_wanted(const fav_handle* h) { return h->tap_user || h->ood_on || h->knn_on; }
+bool tap_wanted(const fav_handle* h) { return h->tap_user || h->ood_on || h->knn_on || h->drift_on; }
 fav_status tap_sync(fav_handle* h, bool on) {
     if (on && !h->feat_buf) {
         const int D = feature_width(h);
@@ -1811,8 +1818,8 @@ fav_status tap_sync(fav_handle* h, bool on) {
     return FAV_OK;
 }
 
-// ---- the frames the two feature heads share (fav_set_ood / fav_set_knn, fav_classify_ood / fav_classify_knn)
-// the members of a deep ensemble have a feature space each: `what` ("an OOD model", "a k-NN bank") is refused on one
+// ---- the frames the three feature heads share (fav_set_ood / fav_set_knn / fav_set_drift and their fav_classify_*)
+// the members of a deep ensemble have a feature space each: `what` ("an OOD model", "a k-NN bank", ..) is refused on one
 fav_status refuse_ensemble(fav_handle* h, const char* fn, const char* what) {
     if (h->n_members <= 1) return FAV_OK;
     h->err = fmt("%s: the members of a deep ensemble do not share a feature space; %s is not supported on it", fn, what);
@@ -1876,6 +1883,7 @@ fav_status fav_set_feature_tap(fav_handle* h, int32_t enable) {
     }
     if (h->ood_on) { h->err = "fav_set_feature_tap: an OOD model is set, which reads the tap; clear it first (fav_set_ood)"; return FAV_ERR_INVALID_ARG; }
     if (h->knn_on) { h->err = "fav_set_feature_tap: a k-NN bank is set, which reads the tap; clear it first (fav_set_knn)"; return FAV_ERR_INVALID_ARG; }
+    if (h->drift_on) { h->err = "fav_set_feature_tap: a drift reference is set, which reads the tap; clear it first (fav_set_drift)"; return FAV_ERR_INVALID_ARG; }
     h->tap_user = false;
     return tap_sync(h, false);
 }
@@ -2034,6 +2042,120 @@ fav_status fav_classify_knn(fav_handle* h, const void* images, int32_t n, int32_
         const fav_handle::KnnDev& o = h->knn;
         const KnnWs w = knn_workspace(h->cfg.max_batch, o.D, o.N, true);
         return launch_knn(h->feat_buf, h->feat_T, h->feat_n, o.D, o.bank, o.N, o.k, o.cls, o.threshold, w, o.ws, true, knn, s);
+    });
+}
+
+// ---- window-level drift detection (fav_drift.hpp) ---------------------------
+namespace {
+// The test on a prepared workspace (the pool's reference rows, its zero rows and the zero bias are there; with cached_ref
+// also the reference's block of U and its diagonal): the query kernel, one GEMM, the quantise, row-sum, permutation and final
+// kernels.  The arguments have been checked (drift_dims_error, the pointers).  Returns the conv launcher's refusal, if any.
+const char* drift_gemm(const DriftWs& w, void* ws, int D, int row0, int rows, int cols, int ldg, float* G, hipStream_t s) {
+    fav_conv_desc d;
+    memset(&d, 0, sizeof d);
+    d.x = (const char*)ws + w.pool + (size_t)row0 * D * 2; d.w = (const char*)ws + w.pool;
+    d.bias = (const float*)((char*)ws + w.bias); d.y = G;
+    d.n_frames = rows; d.H = 1; d.W = 1; d.Cin = D; d.Cout = cols;
+    d.kh = 1; d.kw = 1; d.stride = 1; d.pad = 0; d.relu = 0; d.out_f32 = 1; d.math_mode = FAV_MATH_BF16;
+    d.drop.site = -1;
+    return launch_conv(nullptr, d, cols, ldg, false, Group{}, s);
+}
+void drift_quant(const DriftWs& w, void* ws, int row0, int rows, const float* G, int ldg, hipStream_t s) {
+    DriftQuantParams qp;
+    qp.G = G; qp.diag = (float*)((char*)ws + w.diag); qp.U = (uint32_t*)((char*)ws + w.U);
+    qp.row0 = row0; qp.rows = rows; qp.ldg = ldg; qp.ldu = w.ld;
+    hipLaunchKernelGGL(drift_quant_kernel, dim3((unsigned)rows), dim3(256), 0, s, qp);
+}
+const char* launch_drift(const void* feat, int S, int n, int D, int R, int n_perm, uint64_t seed, float alpha, const DriftWs& w,
+                         void* ws, bool cached_ref, fav_drift_record* rec, int64_t* perm_sums, hipStream_t s) {
+    const int Np = R + n;
+    KnnQueryParams qp;
+    qp.feat = (const uint16_t*)feat; qp.q = (uint16_t*)((char*)ws + w.pool) + (size_t)R * D; qp.flags = (int32_t*)((char*)ws + w.flags);
+    qp.S = S; qp.n = n; qp.D = D; qp.inv_S = (float)(1.0 / S);
+    hipLaunchKernelGGL(knn_query_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, s, qp);
+    float* const G = (float*)((char*)ws + w.G);
+    const int row0 = cached_ref ? R : 0, rows = Np - row0;
+    if (const char* e = drift_gemm(w, ws, D, row0, rows, (Np + 63) & ~63, w.ld, G, s)) return e;
+    drift_quant(w, ws, row0, rows, G, w.ld, s);
+    long long* const r = (long long*)((char*)ws + w.r);
+    hipLaunchKernelGGL(drift_rowsum_kernel, dim3((unsigned)((Np + 3) / 4)), dim3(256), 0, s, (const uint32_t*)((char*)ws + w.U), r, Np, w.ld);
+    DriftPermParams pp;
+    pp.U = (const uint32_t*)((char*)ws + w.U); pp.r = r; pp.flags = qp.flags;
+    pp.sums = (long long*)((char*)ws + w.sums); pp.user_sums = (long long*)perm_sums;
+    pp.R = R; pp.n = n; pp.Np = Np; pp.ld = w.ld; pp.P = n_perm;
+    pp.sort_n = 4;
+    while (pp.sort_n < Np) pp.sort_n <<= 1;
+    pp.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); pp.seed_hi = (uint32_t)(seed >> 32);
+    hipLaunchKernelGGL(drift_perm_kernel, dim3((unsigned)(n_perm + 1)), dim3(DRIFT_PERM_THREADS), 0, s, pp);
+    DriftFinalParams fp;
+    fp.r = r; fp.sums = pp.sums; fp.flags = qp.flags; fp.rec = (unsigned long long*)rec;
+    fp.R = R; fp.n = n; fp.Np = Np; fp.P = n_perm; fp.alpha = alpha;
+    hipLaunchKernelGGL(drift_final_kernel, dim3(1), dim3(DRIFT_FINAL_THREADS), 0, s, fp);
+    return nullptr;
+}
+
+void free_drift(fav_handle::DriftDev* o) {
+    if (o->ws) (void)hipFree(o->ws);
+    *o = fav_handle::DriftDev{};
+}
+}  // namespace
+
+fav_status fav_check_drift_ref(const fav_drift_ref* b, int32_t D_expected, char* err, size_t err_cap) {
+    static_assert(sizeof(fav_drift_record) == 48 && alignof(fav_drift_record) == 8, "fav_drift_record is six 8-byte words");
+    return check_reply(drift_ref_error(b, D_expected), err, err_cap);
+}
+
+size_t fav_drift_workspace_bytes(int32_t n, int32_t D, int32_t R, int32_t n_perm) {
+    if (!drift_dims_error(D, R, n_perm, 0.f, &n).empty()) return 0;
+    return drift_workspace(n, D, R, n_perm, false).bytes;
+}
+
+fav_status fav_set_drift(fav_handle* h, const fav_drift_ref* b) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!b) return head_clear(h, h->drift, h->drift_on, free_drift);
+    const std::string why = drift_ref_error(b, feature_width(h));
+    if (!why.empty()) { h->err = fmt("fav_set_drift: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (fav_status st = refuse_ensemble(h, "fav_set_drift", "a drift reference")) return st;
+    if (h->cfg.max_batch < 2 || h->cfg.max_batch > DRIFT_MAX_N) {
+        h->err = fmt("fav_set_drift: max_batch=%d outside [2, %d]: a window is 2 to %d frames", (int)h->cfg.max_batch, DRIFT_MAX_N, DRIFT_MAX_N);
+        return FAV_ERR_INVALID_ARG;
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    // the new copy first: a failure leaves the handle as it was
+    const DriftWs w = drift_workspace(h->cfg.max_batch, b->D, b->R, b->n_perm, true);
+    fav_handle::DriftDev nw;
+    nw.D = b->D; nw.R = b->R; nw.n_perm = b->n_perm; nw.seed = b->seed; nw.alpha = b->alpha;
+    const int Rpad = (b->R + 63) & ~63;
+    float* G = nullptr;
+    bool ok = hipMalloc(&nw.ws, w.bytes) == hipSuccess && hipMalloc((void**)&G, (size_t)b->R * Rpad * 4) == hipSuccess &&
+              hipMemset((char*)nw.ws + w.pool, 0, (size_t)w.ld * b->D * 2) == hipSuccess &&
+              hipMemset((char*)nw.ws + w.bias, 0, (size_t)w.ld * 4) == hipSuccess &&
+              hipMemcpy((char*)nw.ws + w.pool, b->rows, (size_t)b->R * b->D * 2, hipMemcpyHostToDevice) == hipSuccess;
+    const char* e = nullptr;
+    if (ok) {
+        // the reference's own block of distances, once: R rows against pad64(R) rows of the pool
+        e = drift_gemm(w, nw.ws, b->D, 0, b->R, Rpad, Rpad, G, nullptr);
+        route_clear();
+        if (!e) drift_quant(w, nw.ws, 0, b->R, G, Rpad, nullptr);
+        ok = !e && hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
+    }
+    if (G) (void)hipFree(G);
+    if (!ok) h->err = e ? fmt("fav_set_drift: %s", e) : fmt("fav_set_drift: cannot copy the reference to the device: %s", hipGetErrorString(hipGetLastError()));
+    return head_commit(h, h->drift, h->drift_on, nw, free_drift, ok);
+}
+
+fav_status fav_classify_drift(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
+                              float* conf, uint8_t* fail, float* score, fav_drift_record* drift, void* stream) {
+    if (h && h->drift_on && n < 2) {
+        route_clear();
+        h->err = fmt("fav_classify_drift: n=%d is below 2: a window needs two frames", (int)n);
+        return FAV_ERR_INVALID_ARG;
+    }
+    return classify_feature_head(h, &fav_handle::drift_on, "fav_classify_drift", "drift reference", "fav_set_drift", images, n, layout,
+                                 first_index, labels, conf, fail, score, drift, stream, [&](hipStream_t s) {
+        const fav_handle::DriftDev& o = h->drift;
+        const DriftWs w = drift_workspace(h->cfg.max_batch, o.D, o.R, o.n_perm, true);
+        return launch_drift(h->feat_buf, h->feat_T, h->feat_n, o.D, o.R, o.n_perm, o.seed, o.alpha, w, o.ws, true, drift, nullptr, s);
     });
 }
 
@@ -2485,6 +2607,34 @@ fav_status fav_op_knn_score(const void* feat, int32_t S, int32_t n, int32_t D, c
     hipStream_t s = (hipStream_t)stream;
     if (knn_prepare(w, ws, bank, D, N, false, s) != FAV_OK) { g_create_error = fmt("%s: cannot prepare the workspace: %s", fn, hipGetErrorString(hipGetLastError())); return FAV_ERR_HIP; }
     return op_done(fn, launch_knn(feat, S, n, D, bank, N, k, class_id, threshold, w, ws, false, records, s));
+}
+
+fav_status fav_op_drift_test(const void* feat, int32_t S, int32_t n, int32_t D, const void* ref, int32_t R, int32_t n_perm,
+                             uint64_t seed, float alpha, void* ws, size_t ws_bytes, fav_drift_record* record, int64_t* perm_sums,
+                             void* stream) {
+    const char* fn = "fav_op_drift_test";
+    route_clear();
+    if (!feat || !ref || !ws || !record) return op_rejected(fn, "null pointer");
+    DriftWs w;
+    const std::string why = score_gate(S, DRIFT_MAX_S, n, drift_dims_error(D, R, n_perm, alpha, &n), 0.f, record, [&]() -> std::string {
+        w = drift_workspace(n, D, R, n_perm, false);
+        if (ws_bytes < w.bytes) return fmt("ws_bytes=%zu is below fav_drift_workspace_bytes=%zu", ws_bytes, w.bytes);
+        if ((uintptr_t)ws & 255) return "ws_dev must be 256-byte aligned";
+        if ((uintptr_t)perm_sums & 7) return "perm_sums_dev must be 8-byte aligned";
+        return (uintptr_t)ref & 15 ? "ref_dev must be 16-byte aligned" : "";
+    });
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    hipStream_t s = (hipStream_t)stream;
+    // the pool: the reference at the front, zero rows behind the window's; and the zero bias
+    const size_t row = (size_t)D * 2, Np = (size_t)R + n;
+    char* const pool = (char*)ws + w.pool;
+    if (hipMemcpyAsync(pool, ref, R * row, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        ((size_t)w.ld > Np && hipMemsetAsync(pool + Np * row, 0, ((size_t)w.ld - Np) * row, s) != hipSuccess) ||
+        hipMemsetAsync((char*)ws + w.bias, 0, (size_t)w.ld * 4, s) != hipSuccess) {
+        g_create_error = fmt("%s: cannot prepare the workspace: %s", fn, hipGetErrorString(hipGetLastError()));
+        return FAV_ERR_HIP;
+    }
+    return op_done(fn, launch_drift(feat, S, n, D, R, n_perm, seed, alpha, w, ws, false, record, perm_sums, s));
 }
 
 }  // extern "C"

@@ -7,7 +7,10 @@ fp32 products and sums.  The metrics below are the usual ones for a detector who
 
 Its non-parametric companion (item 5g; deep nearest neighbours, Sun et al. 2022) is at the end of the file: ``KNNBank``, a bank of
 L2-normalised features as bf16 rows that ``build_knn_bank`` makes, scored on the device by fav_op_knn_score as the distance to the
-k-th nearest row, with the same metrics."""
+k-th nearest row, with the same metrics.
+
+Behind it (item 5h) what judges a window of frames and not a frame: ``DriftReference``, held-out in-distribution rows made the same
+way by ``build_drift_reference``, against which fav_op_drift_test runs a permutation test on the energy distance of a call's frames."""
 from __future__ import annotations
 
 import ctypes as C
@@ -282,19 +285,35 @@ def build_knn_bank(features, labels=None, k: int = 10, max_rows: int | None = No
             raise ValueError("labels must be integers")
         if (y < 0).any():
             raise ValueError("labels must not be negative")
-    if max_rows is not None:
-        if max_rows < 1:
-            raise ValueError(f"max_rows must be at least 1, got {max_rows}")
-        if max_rows < F.shape[0]:
-            keep = np.sort(np.random.default_rng(seed).choice(F.shape[0], size=int(max_rows), replace=False))
-            F, y = F[keep], (None if y is None else y[keep])
+    F, keep = _subsample(F, max_rows, seed)
+    if keep is not None and y is not None:
+        y = y[keep]
+    rows = _unit_rows_bf16(F)
+    if not 1 <= k <= F.shape[0]:
+        raise ValueError(f"k must be in [1, N={F.shape[0]}], got {k}")
+    return KNNBank(rows, None if y is None else y.astype(np.int32), k=k)
+
+
+def _subsample(F: np.ndarray, max_rows, seed: int):
+    """-> (the rows kept, their indices or None when all are): ``max_rows`` of them, drawn without replacement by
+    ``np.random.default_rng(seed)`` and kept in their original order."""
+    if max_rows is None:
+        return F, None
+    if max_rows < 1:
+        raise ValueError(f"max_rows must be at least 1, got {max_rows}")
+    if max_rows >= F.shape[0]:
+        return F, None
+    keep = np.sort(np.random.default_rng(seed).choice(F.shape[0], size=int(max_rows), replace=False))
+    return F[keep], keep
+
+
+def _unit_rows_bf16(F: np.ndarray) -> np.ndarray:
+    """float64 [N, D] -> every row divided by its Euclidean norm in float64, then rounded to bf16 bits (nearest even): what a
+    bank and a drift reference hold.  Refuses a zero row."""
     norm = np.sqrt((F * F).sum(axis=1))
     if not (norm > 0).all():
         raise ValueError(f"feature row {int(np.flatnonzero(~(norm > 0))[0])} is zero: it has no direction")
-    if not 1 <= k <= F.shape[0]:
-        raise ValueError(f"k must be in [1, N={F.shape[0]}], got {k}")
-    rows = _bf16_bits((F / norm[:, None]).astype(np.float32))
-    return KNNBank(rows, None if y is None else y.astype(np.int32), k=k)
+    return _bf16_bits((F / norm[:, None]).astype(np.float32))
 
 
 def unpack_knn_records(records) -> dict:
@@ -303,3 +322,92 @@ def unpack_knn_records(records) -> dict:
     f32 = _f32_of(records, KNN_RECORD_DWORDS)
     return {"kth_dist": records[:, 0].view(f32), "kth_sim": records[:, 1].view(f32), "nn_sim": records[:, 2].view(f32),
             "nn_row": records[:, 3], "nn_class": records[:, 4], "ood": records[:, 5]}
+
+
+# ---- window-level drift detection (include/fav.h fav_drift_ref) ---------------------------------
+#: dwords of the one fav_drift_record of a call
+DRIFT_RECORD_DWORDS = 12
+
+
+@dataclasses.dataclass(frozen=True)
+class DriftReference:
+    """``rows`` uint16[R, D]: L2-normalised held-out in-distribution features as bf16 bit patterns, ``n_perm``: permutations of
+    the test, ``alpha``: a window is flagged when p_value <= alpha, ``seed``: the Philox key of the permutations."""
+    rows: np.ndarray
+    n_perm: int = 999
+    alpha: float = 0.01
+    seed: int = 0
+
+    def __post_init__(self):
+        if np.asarray(self.rows).dtype != np.uint16:
+            raise ValueError("rows are bf16 bit patterns: uint16 (build_drift_reference makes them from features)")
+        object.__setattr__(self, "rows", np.ascontiguousarray(self.rows, np.uint16))
+        object.__setattr__(self, "n_perm", int(self.n_perm))
+        object.__setattr__(self, "alpha", float(self.alpha))
+        object.__setattr__(self, "seed", int(self.seed))
+        if self.rows.ndim != 2:
+            raise ValueError("rows is a matrix [R, D]")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError("seed is a 64-bit unsigned integer")
+
+    @property
+    def R(self) -> int:
+        return int(self.rows.shape[0])
+
+    @property
+    def D(self) -> int:
+        return int(self.rows.shape[1])
+
+    def with_alpha(self, alpha: float) -> "DriftReference":
+        return dataclasses.replace(self, alpha=float(alpha))
+
+    def save(self, path):
+        np.savez(path, rows=self.rows, n_perm=np.int32(self.n_perm), alpha=np.float32(self.alpha), seed=np.uint64(self.seed))
+
+    @classmethod
+    def load(cls, path) -> "DriftReference":
+        with np.load(path) as z:
+            return cls(z["rows"], int(z["n_perm"]), float(z["alpha"]), int(z["seed"]))
+
+    def to_c(self) -> _lib.FavDriftRef:
+        """The fav_drift_ref that points into this reference's rows (which it keeps alive)."""
+        b = _lib.FavDriftRef()
+        b.struct_size = C.sizeof(_lib.FavDriftRef)
+        b.D, b.R, b.n_perm = self.D, self.R, self.n_perm
+        b.rows = self.rows.ctypes.data_as(C.POINTER(C.c_uint16))
+        b.seed = self.seed
+        b.alpha = self.alpha
+        b._keep = self
+        return b
+
+    def check(self, D_expected: int = -1):
+        """fav_check_drift_ref (host only); raises ValueError with the library's message."""
+        _check("fav_check_drift_ref", self.to_c(), D_expected)
+
+
+def build_drift_reference(features, max_rows: int | None = 1024, n_perm: int = 999, alpha: float = 0.01, seed: int = 0) -> DriftReference:
+    """features [N, D] (one row per held-out in-distribution frame: the mean over the samples of its features) -> the
+    reference: rows normalised and rounded exactly as ``build_knn_bank``'s, at most ``max_rows`` of them, drawn as there.
+    ``seed`` draws the rows and keys the permutations.  Refuses a non-finite value and a zero row."""
+    F = np.asarray(features, np.float64)
+    if F.ndim != 2 or F.shape[0] < 2:
+        raise ValueError("features must be [N, D] with at least two rows")
+    if not np.isfinite(F).all():
+        raise ValueError("features hold a non-finite value")
+    F, _ = _subsample(F, max_rows, seed)
+    return DriftReference(_unit_rows_bf16(F), n_perm=n_perm, alpha=alpha, seed=seed)
+
+
+def unpack_drift_record(record) -> dict:
+    """int32[12] (or [1, 12]) fav_drift_record (torch tensor or numpy) -> ``statistic`` (float), ``s_ab``, ``s_aa``, ``s_bb``,
+    ``n_exceed``, ``n_degenerate`` (int), ``p_value`` (float), ``drift`` (bool).  Reads the record on the host: a device
+    tensor is copied, which waits for the call that wrote it."""
+    if not isinstance(record, np.ndarray):
+        record = record.cpu().numpy()
+    rec = np.ascontiguousarray(record, np.int32).ravel()
+    if rec.shape[0] != DRIFT_RECORD_DWORDS:
+        raise ValueError(f"expected the int32[{DRIFT_RECORD_DWORDS}] of one fav_drift_record, got shape {tuple(record.shape)}")
+    q = rec[:8].view(np.int64)
+    return {"statistic": float(rec[:2].view(np.float64)[0]), "s_ab": int(q[1]), "s_aa": int(q[2]), "s_bb": int(q[3]),
+            "p_value": float(rec[8:9].view(np.float32)[0]), "n_exceed": int(rec[9]), "drift": bool(rec[10]),
+            "n_degenerate": int(rec[11])}

@@ -400,6 +400,69 @@ fav_status fav_classify_knn(fav_handle* h, const void* images_dev, int32_t n, in
                             int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev,
                             fav_knn_record* knn_dev, void* hip_stream);
 
+/* ---- Window-level drift detection (Rabanser et al. 2019, "Failing Loudly"): a two-sample
+ * permutation test on the energy distance between a REFERENCE of R L2-normalised in-distribution features, bf16 rows, and the
+ * n frames of one call - the window.  Every other output of this library describes a frame; this one describes a call.  All
+ * pointers are HOST pointers.
+ * Ranges (fav_check_drift_ref; FAV_ERR_INVALID_ARG and a message that names the field): struct_size == sizeof(fav_drift_ref);
+ * D a multiple of 64 in [64, 4096] (and the arch's feature width when set on a handle); 2 <= R <= 2048; 1 <= n_perm <= 9999;
+ * alpha in [0, 1] (a NaN is outside); no row value NaN or inf; every row's squared norm, summed in float64 over its bf16
+ * values in index order, inside [0.5, 2].  A call takes 2 <= n <= 1024 frames. */
+typedef struct fav_drift_ref {
+    uint32_t struct_size; int32_t D, R, n_perm;
+    const uint16_t* rows;    /* [R][D] bf16 bit patterns, meant to be unit vectors  (host) */
+    uint64_t seed;           /* the Philox key of the permutations */
+    float alpha;             /* drift = p_value <= alpha */
+} fav_drift_ref;
+/* One call's test, 48 bytes, 8-byte aligned.  With the features feat[S][n][D] bf16 indexed as in fav_get_features, P = n_perm:
+ *   1. q[i]       the window's rows: steps 1 to 3 of fav_knn_record, unchanged.  If any frame is DEGENERATE (step 7 there) the
+ *                 test is not run: statistic = NaN (0x7FF8000000000000), p_value = NaN (0x7FC00000), s_ab = s_aa = s_bb = 0,
+ *                 n_exceed = -1, drift = 1, n_degenerate = their number; the permutation kernel's blocks return before they
+ *                 compute anything, perm_sums is not written, and nothing a later call reads has been changed.  Otherwise
+ *                 n_degenerate = 0 and:
+ *   2. the pool   rows 0 .. R-1 the reference, rows R .. R+n-1 the q[i]; Np = R + n
+ *   3. G[i][j]    j <= i: acc + (+0.0f), acc the production GEMM accumulator of fav_knn_record's step 4, K never split, pool
+ *                 row i its activation row and pool row j its weight row.  Only j <= i is ever used: symmetry of the matrix
+ *                 pipe is not assumed, it is defined away
+ *   4. u[i][j]    fp32, every operation rounded on its own: d2 = fmaxf((G[i][i] + G[j][j]) - 2.0f * G[i][j], +0.0f);
+ *                 dd = sqrtf(d2), correctly rounded; u[i][j] = u[j][i] = (uint32) rintf(dd * 1048576.0f) for j < i; u[i][i] = 0.
+ *                 Identical rows are at distance exactly 0.  With the norm band above every u is below 2^22, and with
+ *                 Np <= 3072 every sum below is below 2^45
+ *   5. the sums   integers, exact, hence independent of order.  For a group B of n pool indices, A the other R:
+ *                 S_BB the sum of u over the unordered pairs inside B, S_AB over the pairs across, S_AA over those inside A.
+ *                 With r[i] = sum_j u[i][j] and S_tot = (sum_i r[i]) / 2: S_AB = sum_{i in B} r[i] - 2 S_BB and
+ *                 S_AA = S_tot - S_BB - S_AB.  The observed group is B = {R .. Np-1}; s_ab, s_aa, s_bb are its sums
+ *   6. B_p        permutation p < P: x0(i) the first word of Philox4x32-10 with counter (i, p, 0, 0x5F17) and key (seed low,
+ *                 seed high); key(i) = (uint64) x0(i) << 32 | i, which are unique; B_p the n pool indices with the smallest keys
+ *   7. n_exceed   T = S_AB (R n) - S_AA n^2 - S_BB R^2 as a 128-bit integer (R n (R + n) / 2 times the energy distance);
+ *                 n_exceed = #{p : T_p >= T_obs}
+ *   8. statistic  float64, every operation rounded on its own:
+ *                 (((2.0 * S_AB) / (double)(R n) - (2.0 * S_AA) / (double)(R R)) - (2.0 * S_BB) / (double)(n n)) * 2^-20
+ *                 from the observed sums: 2 E|a - b| - E|a - a'| - E|b - b'| with the V-statistic's divisors;
+ *                 p_value = (float)((double)(1 + n_exceed) / (double)(P + 1)); drift = p_value <= alpha */
+typedef struct fav_drift_record {
+    double statistic; int64_t s_ab, s_aa, s_bb; float p_value; int32_t n_exceed, drift, n_degenerate;
+} fav_drift_record;
+/* Host only, no device: the ranges above (D_expected < 0: any width in range), the one place they live; fav_set_drift calls
+ * it first.  err (may be NULL) receives the message. */
+fav_status fav_check_drift_ref(const fav_drift_ref* ref, int32_t D_expected, char* err, size_t err_cap);
+/* The handle's drift reference (NULL: none), as fav_set_knn in every respect: the feature tap goes on and is derived from the
+ * three heads and the caller's own wish - a model, a bank and a reference may be set together, and fav_set_feature_tap(h, 0)
+ * is refused while any of them reads the tap.  The setter allocates the whole workspace for max_batch frames (the pool
+ * [pad64(R + max_batch)][D] with the reference at its front, the quantised distances of the whole pool), computes the
+ * reference's own block of distances once, and synchronises; fav_classify_drift never allocates or synchronises.  A handle
+ * whose max_batch lies outside [2, 1024] is refused (the message carries the numbers).  Replacing or clearing waits on the
+ * host for the work enqueued on the handle and frees the old copy.  FAV_ERR_UNSUPPORTED on a deep-ensemble handle.  A
+ * rejected call leaves the handle as it was. */
+fav_status fav_set_drift(fav_handle* h, const fav_drift_ref* ref);
+/* fav_classify_ex unchanged, then the test on the tapped features of these n frames, all on the caller's stream: drift_dev
+ * (non-NULL, 8-byte aligned) gets ONE fav_drift_record: the call is the window.  Needs a reference, and n >= 2: both are
+ * refused (FAV_ERR_INVALID_ARG) before anything is enqueued.  fail_dev / score_dev may be NULL.  The head's launches are
+ * booked in no kernel class. */
+fav_status fav_classify_drift(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
+                              int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev,
+                              fav_drift_record* drift_dev, void* hip_stream);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -710,6 +773,21 @@ size_t fav_knn_workspace_bytes(int32_t n, int32_t D, int32_t N);   /* host only;
 fav_status fav_op_knn_score(const void* feat_bf16, int32_t S, int32_t n, int32_t D, const void* bank_dev, int32_t N, int32_t k,
                             const int32_t* class_id_dev, float threshold, void* ws_dev, size_t ws_bytes,
                             fav_knn_record* records_dev, void* hip_stream);
+
+/* ---- The whole drift test defined beside fav_drift_record, on device arrays: feat_bf16 [S][n][D] bf16, ref_dev [R][D] bf16
+ * (16-byte aligned; exactly R rows), ws_dev a workspace of at least fav_drift_workspace_bytes(n, D, R, n_perm) bytes on a
+ * 256-byte boundary, record_dev one record (8-byte aligned), perm_sums_dev int64 [n_perm][2] (8-byte aligned) or NULL: the
+ * pair (S_BB, S_AB) of every permutation.  The reference's block of distances is computed in the call: one GEMM of the whole
+ * pool against itself through the convolution launcher (1x1, fp32 output, zero bias; fav_op_last_route names its tile), then
+ * the quantise, row-sum, permutation (n_perm + 1 blocks) and final kernels.  No allocation, no synchronisation; vector stores
+ * only.  The reference's norms are not checked here (fav_check_drift_ref is host work on host rows).
+ * A refused call (FAV_ERR_INVALID_ARG: a NULL pointer other than perm_sums_dev, S outside [1, 4096], n outside [2, 1024], D, R,
+ * n_perm or alpha outside the ranges of fav_drift_ref, a workspace too small or misaligned, a misaligned ref_dev, record_dev
+ * or perm_sums_dev) launches nothing and leaves a message that names the function in fav_last_error(NULL). */
+size_t fav_drift_workspace_bytes(int32_t n, int32_t D, int32_t R, int32_t n_perm);   /* host only; 0 for sizes out of range */
+fav_status fav_op_drift_test(const void* feat_bf16, int32_t S, int32_t n, int32_t D, const void* ref_dev, int32_t R,
+                             int32_t n_perm, uint64_t seed, float alpha, void* ws_dev, size_t ws_bytes,
+                             fav_drift_record* record_dev, int64_t* perm_sums_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
