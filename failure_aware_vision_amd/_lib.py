@@ -148,6 +148,12 @@ class FavDriftRecord(C.Structure):
                 ("p_value", C.c_float), ("n_exceed", C.c_int32), ("drift", C.c_int32), ("n_degenerate", C.c_int32)]
 
 
+class FavCamRecord(C.Structure):
+    """fav_cam_record: one 32-byte summary per (frame, class) map (cam.unpack_cam_records reads it as int32[..., 8])."""
+    _fields_ = [("class_id", C.c_int32), ("logit_mean", C.c_float), ("peak", C.c_float), ("peak_cell", C.c_int32),
+                ("floor", C.c_float), ("pos_sum", C.c_float), ("n_above", C.c_int32), ("box", C.c_int32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -212,6 +218,18 @@ _SIGNATURES = {
     "fav_drift_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "fav_op_drift_test": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64,
                                     C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_set_map_tap": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t]),
+    "fav_get_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
+    "fav_map_tap_info": (C.c_int, [C.POINTER(FavConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    "fav_cam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_classify_cam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_cam": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                             C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_cam_heatmap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),

@@ -107,6 +107,7 @@ class Backend:
         self._T_head = cfg.n_samples if self.mc else max(1, cfg.n_members)
         self._tap, self._ood, self._knn = False, None, None   # the caller's own feature tap; the ood.OODModel, the ood.KNNBank in force
         self._drift = None                                    # the ood.DriftReference in force
+        self._map_hw = None                                   # (Hf, Wf) of the map tap, known from the first set_map_tap(True) on
         self._views = ()
         if views:
             self.set_views(views)
@@ -501,6 +502,105 @@ class Backend:
         stream = torch.cuda.current_stream(out.device).cuda_stream
         _lib.check(self.lib.fav_get_features(self._h, out.data_ptr(), None, None, None, stream), self._h)
         return out
+
+    # -- class activation maps (cam.py; include/fav.h fav_set_map_tap, fav_cam) ---------------------------------------------
+    def set_map_tap(self, enable: bool, budget_bytes: int = 2 << 30):
+        """Keep the feature maps the average pool reads (fav_set_map_tap) from the next call on; ``maps()``, ``cam()`` and
+        ``classify_cam()`` read them.  The buffer is allocated here, for max_batch frames (``map_tap_info()['bytes']``), and
+        refused above ``budget_bytes``; turning the tap off frees it.  Refused on a ViT arch and on a deep ensemble."""
+        _lib.check(self.lib.fav_set_map_tap(self._h, 1 if enable else 0, int(budget_bytes)), self._h)
+        if enable and self._map_hw is None:
+            info = self.map_tap_info()                 # the planner, once: classify_cam sizes its outputs from this
+            self._map_hw = (info["hf"], info["wf"])
+
+    def map_tap_info(self) -> dict:
+        """What the map tap of this configuration holds, from the planner alone (fav_map_tap_info; no device work):
+        ``bytes`` of the buffer, ``samples`` a frame has in it (without views), and the map's ``hf``, ``wf``, ``c``."""
+        nbytes, s, hf, wf, c = C.c_size_t(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        err = C.create_string_buffer(256)
+        st = self.lib.fav_map_tap_info(C.byref(self.cfg), C.byref(nbytes), C.byref(s), C.byref(hf), C.byref(wf), C.byref(c), err,
+                                       len(err))
+        if st != _lib.FAV_OK:
+            raise _lib.FavError(st, err.value.decode("utf-8", "replace"))
+        return dict(bytes=nbytes.value, samples=s.value, hf=hf.value, wf=wf.value, c=c.value)
+
+    def _map_sizes(self) -> tuple:
+        """(S, n, Hf, Wf, C) of the maps the last tapped call left."""
+        v = [C.c_int32() for _ in range(5)]
+        _lib.check(self.lib.fav_get_maps(self._h, None, *(C.byref(x) for x in v), None), self._h)
+        return tuple(x.value for x in v)
+
+    def maps(self):
+        """bf16 [S, n, Hf, Wf, C] feature maps of the last classify call made with the map tap on (torch CUDA tensor),
+        indexed like ``logits()``: what the average pool read - behind the dropout of every block site, in front of the
+        pooled-feature site's (S = 1 when that is the only site)."""
+        torch = self._torch
+        shape = self._map_sizes()
+        out = torch.empty(shape, dtype=torch.bfloat16, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        _lib.check(self.lib.fav_get_maps(self._h, out.data_ptr(), None, None, None, None, None, stream), self._h)
+        return out
+
+    def cam(self, classes) -> dict:
+        """Class activation maps of the LAST classify call for the classes named per frame (fav_cam; no second forward
+        pass): ``classes`` int [n, K] or [n], K <= 8 -> ``map`` fp32 [n, K, Hf, Wf] (the mean over the samples of
+        w_c . F(h, w): its spatial mean plus the bias is the class's mean logit) plus the record fields of
+        ``cam.unpack_cam_records``, each [n, K]: ``class_id``, ``logit_mean``, ``peak``, ``peak_cell``, ``floor``, ``pos_sum``,
+        ``n_above`` (cells at 20 % of the peak or more), ``box`` and its ``x0``, ``y0``, ``x1``, ``y1``.  A class outside
+        [0, num_classes) gives a NaN map and class_id -1.  torch CUDA classes in -> CUDA tensors out, asynchronous on the
+        current stream; numpy in -> numpy out.  Needs the map tap; refused while views are set."""
+        from .cam import CAM_RECORD_DWORDS, unpack_cam_records
+        torch = self._torch
+        host = isinstance(classes, np.ndarray) or not hasattr(classes, "is_cuda")
+        dev = torch.device(f"cuda:{self.device}")
+        cls = torch.as_tensor(np.asarray(classes) if host else classes).to(device=dev, dtype=torch.int32)
+        if cls.ndim == 1:
+            cls = cls[:, None]
+        cls = cls.contiguous()
+        v = [C.c_int32() for _ in range(5)]
+        if self.lib.fav_get_maps(self._h, None, *(C.byref(x) for x in v), None) != _lib.FAV_OK:
+            # no maps to size the outputs by (the tap is off, or no call since it went on): fav_cam says so in its own words
+            _lib.check(self.lib.fav_cam(self._h, cls.data_ptr(), 1, cls.data_ptr(), cls.data_ptr(), None), self._h)
+            raise RuntimeError("fav_get_maps has no maps, yet fav_cam accepted the call")
+        _, n, hf, wf, _ = (x.value for x in v)
+        if cls.ndim != 2 or int(cls.shape[0]) != n:
+            raise ValueError(f"classes must be [n, K] or [n] for the n={n} frames of the last call, got {tuple(cls.shape)}")
+        K = int(cls.shape[1])
+        cam = torch.empty((n, K, hf, wf), dtype=torch.float32, device=dev)
+        rec = torch.empty((n, K, CAM_RECORD_DWORDS), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self.lib.fav_cam(self._h, cls.data_ptr(), K, cam.data_ptr(), rec.data_ptr(), stream), self._h)
+        if host:
+            cam, rec = cam.cpu().numpy(), rec.cpu().numpy()
+        return dict(unpack_cam_records(rec), map=cam)
+
+    def classify_cam(self, images, heatmap: bool = False, first_index: int = 0) -> dict:
+        """frames -> ``label``, ``conf``, ``fail``, ``score`` as ``classify_detect`` gives them, plus the class activation
+        map of each frame's predicted class (fav_classify_cam: the class is read on the device, nothing synchronises):
+        ``map`` fp32 [n, Hf, Wf] and the record fields of ``cam()``, each [n].  ``heatmap``: also ``heatmap`` uint8 [n, H, W],
+        the map resized to the frame (bilinear) and normalised from its floor to its peak - the overlay a dashboard draws.
+        torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out, synchronous.
+        Needs the map tap; refused while views are set."""
+        from .cam import CAM_RECORD_DWORDS, unpack_cam_records
+        torch = self._torch
+        img, host, n, layout, stream = self._classify_args(images)
+        hf, wf = self._map_hw or (1, 1)                # never tapped: fav_classify_cam refuses before it writes anything
+        labels, conf, fail, score = self._detect_buffers(n, img.device)
+        cam = torch.empty((n, hf, wf), dtype=torch.float32, device=img.device)
+        rec = torch.empty((n, CAM_RECORD_DWORDS), dtype=torch.int32, device=img.device)
+        _lib.check(self.lib.fav_classify_cam(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
+                                             conf.data_ptr(), fail.data_ptr(), score.data_ptr(), cam.data_ptr(), rec.data_ptr(),
+                                             stream), self._h)
+        out = dict(label=labels, conf=conf, fail=fail, score=score, map=cam)
+        if heatmap:
+            H, W = int(self.cfg.in_h), int(self.cfg.in_w)
+            heat = torch.empty((n, H, W), dtype=torch.uint8, device=img.device)
+            _lib.check(self.lib.fav_op_cam_heatmap(cam.data_ptr(), rec.data_ptr(), n, hf, wf, H, W, heat.data_ptr(), stream))
+            out["heatmap"] = heat
+        if host:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+            rec = rec.cpu().numpy()
+        return dict(unpack_cam_records(rec), **out)
 
     # what the two feature heads (the Mahalanobis model, the k-NN bank) share
     @staticmethod

@@ -30,6 +30,7 @@
 #include "fav_ood.hpp"
 #include "fav_knn.hpp"
 #include "fav_drift.hpp"
+#include "fav_cam.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -171,6 +172,14 @@ struct fav_handle {
     struct DriftDev { void* ws = nullptr; int D = 0, R = 0, n_perm = 0; uint64_t seed = 0; float alpha = 0.f; };
     DriftDev drift;
     bool drift_on = false;
+    // Map tap (fav_set_map_tap): while on, every pass copies the frames its average pool reads into map_buf, bf16
+    // [map.S][max_batch][Hf * Wf][C] at most (map: fav_cam.hpp map_tap_dims of the plan), indexed [sample][frame] like the
+    // logits; allocated by the setter, freed when the tap goes off.  map_S / map_n: the samples and frames of the last call
+    // that filled it (0: none yet); map_views: the views that call ran under
+    bool map_tap = false;
+    void* map_buf = nullptr;
+    fav::MapTapDims map;
+    int map_S = 0, map_n = 0, map_views = 0;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -1033,6 +1042,12 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
                     if (const char* e = launch_maxpool(h, buf(o.in, o), buf(o.out, o), cn, o.H, o.W, o.C, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 case OP_AVGPOOL:
+                    if (h->map_tap) {
+                        // the map tap: the frames the pool reads, to [virtual frame] of map_buf, in front of the launch
+                        const size_t frame = (size_t)o.H * o.W * o.C * 2;
+                        HIP_TRY(h, hipMemcpyAsync((char*)h->map_buf + (size_t)v0 * frame, buf(o.in, o), (size_t)cn * frame,
+                                                  hipMemcpyDeviceToDevice, s));
+                    }
                     if (const char* e = launch_avgpool(h, buf(o.in, o), buf(o.out, o), cn, o.H * o.W, o.C, &dd, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 case OP_ENTRY_DROPOUT:
@@ -1075,6 +1090,7 @@ void free_all(fav_handle* h) {
     for (void* q : {(void*)h->ood.mu, (void*)h->ood.Pt, (void*)h->ood.Mt, (void*)h->ood.cls}) if (q) (void)hipFree(q);
     for (void* q : {h->knn.bank, h->knn.ws, (void*)h->knn.cls}) if (q) (void)hipFree(q);
     if (h->drift.ws) (void)hipFree(h->drift.ws);
+    if (h->map_buf) (void)hipFree(h->map_buf);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
@@ -1524,6 +1540,7 @@ fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out
     h->last_T = T_head;
     h->last_n = n_head;
     if (h->tap) { h->feat_T = T_head; h->feat_n = n_head; }
+    if (h->map_tap) { h->map_S = h->map.S * views; h->map_n = n_head; h->map_views = h->n_views; }
     return FAV_OK;
 }
 
@@ -2159,6 +2176,161 @@ fav_status fav_classify_drift(fav_handle* h, const void* images, int32_t n, int3
     });
 }
 
+// ---- class activation maps (fav_cam.hpp) -------------------------------------
+namespace {
+// The head: one launch, a block a frame, the weight rows and the maps in LDS.  The arguments have been checked
+// (cam_dims_error, the pointers).  Returns a refusal of the runtime's, if it has one.
+const char* launch_cam(const void* maps, int S, int n, int Hf, int Wf, int C, const void* w, long long ldw, const float* bias,
+                       int n_classes, const int32_t* classes, int K, float* cam, fav_cam_record* rec, hipStream_t s) {
+    CamParams p;
+    p.maps = (const uint16_t*)maps; p.w = (const uint16_t*)w; p.bias = bias; p.classes = classes; p.cam = cam; p.rec = (int32_t*)rec;
+    p.S = S; p.n = n; p.HW = Hf * Wf; p.Wf = Wf; p.C = C; p.K = K; p.n_classes = n_classes; p.ldw = ldw;
+    p.inv_S = (float)(1.0 / S); p.inv_HW = (float)(1.0 / (Hf * Wf));
+    const size_t lds = (size_t)K * C * 2 + (size_t)K * p.HW * 4;     // at most 96 KB
+    void (*const fn)(const CamParams) = K == 1 ? cam_kernel<1> : cam_kernel<CAM_MAX_K>;
+    if (lds + CAM_STATIC_LDS > 64 * 1024) {      // the kernel's static LDS counts towards the default limit too
+        static DeviceFlags attr_set[2];   // hipFuncSetAttribute applies to the CURRENT device only
+        DeviceFlags& done = attr_set[K == 1 ? 0 : 1];
+        if (!done.test_current()) {
+            if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
+                return "cannot reserve LDS for the weight rows and the maps";
+            done.set_current();
+        }
+    }
+    hipLaunchKernelGGL(fn, dim3((unsigned)n), dim3(CAM_THREADS), lds, s, p);
+    return nullptr;
+}
+
+void launch_cam_heatmap(const float* cam, const fav_cam_record* rec, int m, int Hf, int Wf, int H, int W, uint8_t* out, hipStream_t s) {
+    CamHeatParams p;
+    p.cam = cam; p.rec = (const int32_t*)rec; p.out = out; p.m = m; p.Hf = Hf; p.Wf = Wf; p.H = H; p.W = W;
+    p.scale_y = (float)Hf / (float)H; p.scale_x = (float)Wf / (float)W;
+    hipLaunchKernelGGL(cam_heatmap_kernel, dim3(grid_for((long long)m * H * W)), dim3(256), 0, s, p);
+}
+
+// the row pitch of the fc's weights: the last layer of the plan, whose rows the head reads
+int fc_pitch(const fav_handle* h) { return h->plan.layers.back().k; }
+
+// What fav_cam and fav_classify_cam refuse alike about the handle's state, before anything is enqueued (FAV_OK: nothing)
+fav_status cam_gate(fav_handle* h, const char* fn, int K, const void* classes, const void* cam, const void* rec) {
+    if (!h->map_tap) { h->err = fmt("%s: the map tap is off (fav_set_map_tap)", fn); return FAV_ERR_INVALID_ARG; }
+    if (h->n_views > 0) {
+        h->err = fmt("%s: views are set; a view's map lies in that view's frame and averaging them mis-registers (fav_get_maps still works)", fn);
+        return FAV_ERR_UNSUPPORTED;
+    }
+    if (!classes || !cam || !rec || ((uintptr_t)classes & 3) || ((uintptr_t)cam & 3) || ((uintptr_t)rec & 7)) {
+        h->err = fmt("%s: %s", fn, kBadRecords);
+        return FAV_ERR_INVALID_ARG;
+    }
+    const std::string why = cam_dims_error(h->map.S, 1, h->map.Hf, h->map.Wf, h->map.C, fc_pitch(h), h->cfg.num_classes, K);
+    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
+    return FAV_OK;
+}
+// the head on the maps of the last call, behind whatever used the handle's buffers last
+fav_status cam_on_stream(fav_handle* h, const char* fn, const int32_t* classes, int K, float* cam, fav_cam_record* rec, hipStream_t s) {
+    const size_t fc = h->plan.layers.size() - 1;
+    const char* e = launch_cam(h->map_buf, h->map_S, h->map_n, h->map.Hf, h->map.Wf, h->map.C, h->weights[fc].w_m[0], fc_pitch(h),
+                               h->weights[fc].b_m[0], h->cfg.num_classes, classes, K, cam, rec, s);
+    route_clear();            // the report speaks of fav_op_* launches only
+    mark_last_use(h, s);
+    if (e) { h->err = fmt("%s: %s", fn, e); return FAV_ERR_HIP; }
+    HIP_TRY(h, hipGetLastError());
+    return FAV_OK;
+}
+}  // namespace
+
+fav_status fav_map_tap_info(const fav_config* cfg, size_t* bytes, int32_t* s_map, int32_t* hf, int32_t* wf, int32_t* c, char* err,
+                            size_t err_cap) {
+    auto reply = [&](fav_status st, const std::string& why) {
+        if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
+        return st;
+    };
+    if (!cfg || cfg->struct_size != sizeof(fav_config)) return reply(FAV_ERR_INVALID_ARG, "fav_map_tap_info: null config or struct_size mismatch");
+    if (cfg->arch < 0 || cfg->arch > 3) return reply(FAV_ERR_UNSUPPORTED, "fav_map_tap_info: unknown arch");
+    if (const char* why = map_tap_unsupported(cfg->arch, cfg->n_members)) return reply(FAV_ERR_UNSUPPORTED, fmt("fav_map_tap_info: %s", why));
+    if (cfg->max_batch < 1 || cfg->n_samples < 1 || cfg->n_samples > 4096 || cfg->in_h < 8 || cfg->in_w < 8 || cfg->num_classes < 1)
+        return reply(FAV_ERR_INVALID_ARG, "fav_map_tap_info: config value out of range");
+    Plan P;
+    std::string why;
+    if (fav_status st = plan_resnet(*cfg, 1, false, &P, &why)) return reply(st, fmt("fav_map_tap_info: %s", why.c_str()));
+    const MapTapDims d = map_tap_dims(P, cfg->max_batch);
+    if (bytes) *bytes = d.bytes;
+    if (s_map) *s_map = d.S;
+    if (hf) *hf = d.Hf;
+    if (wf) *wf = d.Wf;
+    if (c) *c = d.C;
+    return reply(FAV_OK, "");
+}
+
+fav_status fav_set_map_tap(fav_handle* h, int32_t enable, size_t max_bytes) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!enable) {
+        if (!h->map_tap) return FAV_OK;
+        h->map_tap = false;
+        h->map_S = h->map_n = h->map_views = 0;
+        HIP_TRY(h, hipSetDevice(h->cfg.device));
+        if (fav_status st = wait_enqueued(h)) return st;
+        void* buf = h->map_buf;
+        h->map_buf = nullptr;
+        if (buf) HIP_TRY(h, hipFree(buf));
+        return FAV_OK;
+    }
+    if (const char* why = map_tap_unsupported(h->cfg.arch, h->n_members)) { h->err = fmt("fav_set_map_tap: %s", why); return FAV_ERR_UNSUPPORTED; }
+    const MapTapDims d = map_tap_dims(h->plan, h->cfg.max_batch);
+    const std::string why = map_tap_budget_error(d.bytes, max_bytes);
+    if (!why.empty()) { h->err = fmt("fav_set_map_tap: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (h->map_tap) return FAV_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipMalloc(&h->map_buf, d.bytes + 256));
+    h->map = d;
+    h->map_S = h->map_n = h->map_views = 0;
+    h->map_tap = true;
+    return FAV_OK;
+}
+
+fav_status fav_get_maps(fav_handle* h, void* out, int32_t* s_out, int32_t* n_out, int32_t* hf_out, int32_t* wf_out, int32_t* c_out,
+                        void* stream) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!h->map_tap) { h->err = "fav_get_maps: the map tap is off (fav_set_map_tap)"; return FAV_ERR_INVALID_ARG; }
+    if (h->map_n == 0) { h->err = "fav_get_maps: no classify call since the tap was turned on"; return FAV_ERR_INVALID_ARG; }
+    if (s_out) *s_out = h->map_S;
+    if (n_out) *n_out = h->map_n;
+    if (hf_out) *hf_out = h->map.Hf;
+    if (wf_out) *wf_out = h->map.Wf;
+    if (c_out) *c_out = h->map.C;
+    if (out) {
+        hipStream_t s = (hipStream_t)stream;
+        HIP_TRY(h, hipSetDevice(h->cfg.device));
+        if (fav_status st = wait_last_use(h, s)) return st;
+        const size_t bytes = (size_t)h->map_S * h->map_n * h->map.Hf * h->map.Wf * h->map.C * 2;
+        HIP_TRY(h, hipMemcpyAsync(out, h->map_buf, bytes, hipMemcpyDeviceToDevice, s));
+        mark_last_use(h, s);
+    }
+    return FAV_OK;
+}
+
+fav_status fav_cam(fav_handle* h, const int32_t* classes, int32_t K, float* cam, fav_cam_record* rec, void* stream) {
+    static_assert(sizeof(fav_cam_record) == 32, "fav_cam_record is 8 dwords");
+    route_clear();
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (fav_status st = cam_gate(h, "fav_cam", K, classes, cam, rec)) return st;
+    if (h->map_n == 0) { h->err = "fav_cam: no classify call since the tap was turned on"; return FAV_ERR_INVALID_ARG; }
+    if (h->map_views > 0) { h->err = "fav_cam: the last call ran under views; their maps lie in each view's own frame"; return FAV_ERR_UNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_last_use(h, s)) return st;
+    return cam_on_stream(h, "fav_cam", classes, K, cam, rec, s);
+}
+
+fav_status fav_classify_cam(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
+                            float* conf, uint8_t* fail, float* score, float* cam, fav_cam_record* rec, void* stream) {
+    route_clear();
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (fav_status st = cam_gate(h, "fav_classify_cam", 1, labels, cam, rec)) return st;
+    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
+    return cam_on_stream(h, "fav_classify_cam", labels, 1, cam, rec, (hipStream_t)stream);
+}
+
 fav_status fav_set_profiling(fav_handle* h, int32_t enable) {
     if (!h) return FAV_ERR_INVALID_ARG;
     h->profiling = enable != 0;
@@ -2635,6 +2807,33 @@ fav_status fav_op_drift_test(const void* feat, int32_t S, int32_t n, int32_t D, 
         return FAV_ERR_HIP;
     }
     return op_done(fn, launch_drift(feat, S, n, D, R, n_perm, seed, alpha, w, ws, false, record, perm_sums, s));
+}
+
+fav_status fav_op_cam(const void* maps, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C, const void* w, int32_t ldw,
+                      const float* bias, int32_t n_classes, const int32_t* classes, int32_t K, float* cam, fav_cam_record* rec,
+                      void* stream) {
+    const char* fn = "fav_op_cam";
+    route_clear();
+    if (!maps || !w || !bias || !classes || !cam || !rec) return op_rejected(fn, "null pointer");
+    const std::string why = cam_dims_error(S, n, Hf, Wf, C, ldw, n_classes, K);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    if (((uintptr_t)maps | (uintptr_t)w) & 15) return op_rejected(fn, "maps_bf16 and w_bf16 must be 16-byte aligned");
+    if (((uintptr_t)bias | (uintptr_t)classes | (uintptr_t)cam) & 3) return op_rejected(fn, "bias, classes_dev and cam_dev must be 4-byte aligned");
+    if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
+    return op_done(fn, launch_cam(maps, S, n, Hf, Wf, C, w, ldw, bias, n_classes, classes, K, cam, rec, (hipStream_t)stream));
+}
+
+fav_status fav_op_cam_heatmap(const float* cam, const fav_cam_record* rec, int32_t m, int32_t Hf, int32_t Wf, int32_t H, int32_t W,
+                              uint8_t* out, void* stream) {
+    const char* fn = "fav_op_cam_heatmap";
+    route_clear();
+    if (!cam || !rec || !out) return op_rejected(fn, "null pointer");
+    const std::string why = cam_heatmap_dims_error(m, Hf, Wf, H, W);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    if ((uintptr_t)cam & 3) return op_rejected(fn, "cam_dev must be 4-byte aligned");
+    if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
+    launch_cam_heatmap(cam, rec, m, Hf, Wf, H, W, out, (hipStream_t)stream);
+    return op_done(nullptr);
 }
 
 }  // extern "C"

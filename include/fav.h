@@ -463,6 +463,73 @@ fav_status fav_classify_drift(fav_handle* h, const void* images_dev, int32_t n, 
                               int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev,
                               fav_drift_record* drift_dev, void* hip_stream);
 
+/* ---- Class activation maps (Zhou et al. 2016).  Every signal above says WHETHER a frame can
+ * be trusted; this one says WHERE in the frame the decision comes from.  On a ResNet the logit of class c is the spatial mean
+ * of w_c . F(h, w) over the last feature map F, plus the bias, so M_c(h, w) = w_c . F(h, w) is an exact additive
+ * decomposition of the logit over the cells of the map: no backward pass, and linear in the MC-Dropout samples, so the mean
+ * map over the samples decomposes the mean logit.
+ *
+ * The MAP TAP.  While it is on, every pass copies the input of its average-pool launch - cn frames x Hf*Wf cells x C
+ * channels, bf16 - device to device into a buffer the handle owns, on the stream of that launch and in front of it, per
+ * chunk at the chunk's virtual-frame offset.  The buffer holds [S_map][n][Hf*Wf][C] with the sample indexing of
+ * fav_get_logits: S_map = the MC-Dropout samples when the pool runs once a sample, 1 when it runs once a frame (the
+ * pooled-feature site is the only dropout site: the map is then the same for every sample), times the views when views are
+ * set.  WHICH MAPS: those the pool reads - POST-dropout for every block site, PRE-dropout for the pooled-feature site, whose
+ * mask falls on the pooled feature behind the pool.
+ * The setter allocates S_map * max_batch * Hf*Wf * C * 2 bytes (with A views a call takes at most max_batch / A frames) and
+ * may synchronise; fav_classify* never allocates or synchronises for it.  It refuses (FAV_ERR_INVALID_ARG, the message
+ * carries both numbers) a buffer above max_bytes (0: 2 GiB), and (FAV_ERR_UNSUPPORTED) a ViT arch, which has no pooled
+ * convolutional map, and a deep-ensemble handle.  Turning the tap off is never refused; it waits for the work enqueued on
+ * the handle and frees the buffer.  The copies are booked in no kernel class.  The tap changes no result, and it is
+ * independent of the feature tap.  With the tap off a fav_classify* call enqueues exactly what it did before. */
+fav_status fav_set_map_tap(fav_handle* h, int32_t enable, size_t max_bytes);
+/* The maps of the last fav_classify* call made with the tap on, copied as they are - bf16 [S][n][Hf*Wf][C] - to out_dev (may
+ * be NULL: only the sizes; every size pointer may be NULL), on hip_stream.  FAV_ERR_INVALID_ARG with the tap off and before
+ * the first call made with it on. */
+fav_status fav_get_maps(fav_handle* h, void* out_dev, int32_t* s_out, int32_t* n_out, int32_t* hf_out, int32_t* wf_out,
+                        int32_t* c_out, void* hip_stream);
+/* Host only, no device: what fav_set_map_tap would allocate for this configuration, from the planner - *bytes, *s_map (the
+ * samples without views), *hf, *wf, *c (each may be NULL).  FAV_ERR_UNSUPPORTED for a ViT arch and for n_members > 1,
+ * FAV_ERR_INVALID_ARG for a configuration the planner refuses; err (may be NULL) receives the message. */
+fav_status fav_map_tap_info(const fav_config* cfg, size_t* bytes, int32_t* s_map, int32_t* hf, int32_t* wf, int32_t* c,
+                            char* err, size_t err_cap);
+
+/* One (frame, class) map's summary, 32 bytes, 8-byte aligned.  For frame i and class c = classes[i][k], with x the maps
+ * [S][n][HW][C] and w the weight rows, everything fp32, every product and every sum rounded on its own (no FMA contraction,
+ * no re-association); the partition is fixed and does not depend on the grid or the block:
+ *   1. lane partials   l < 64: p[l] = +0; then for s = 0 .. S-1, for m = 0 .. C/512-1, for e = 0 .. 7, in that order, with
+ *                      ch = 512 m + 8 l + e:  p[l] = p[l] + fp32(w[c][ch]) * fp32(x[s][i][hw][ch])
+ *   2. six halvings    for h = 32, 16, 8, 4, 2, 1: p[l] = p[l] + p[l + h] for l < h.  M[hw] = p[0] * (float)(1.0 / S)
+ *   3. logit_mean      +0 plus M[hw] in index order, times (float)(1.0 / HW), plus bias[c]
+ *   4. peak, peak_cell best = -inf, cell = -1; for hw ascending: if (M[hw] > best) { best = M[hw]; cell = hw; } - ties go to
+ *                      the lowest cell, a NaN never wins.  floor: the same from +inf with <
+ *   5. pos_sum         +0 plus fmaxf(M[hw], +0) in index order.  With thr = 0.2f * peak (the 20 % rule of the CAM paper),
+ *                      n_above = the number of cells with M[hw] >= thr, counted only when peak > 0 (else 0); box = the
+ *                      inclusive extent of those cells, x0 | y0 << 8 | x1 << 16 | y1 << 24 with x = hw % Wf, y = hw / Wf,
+ *                      -1 when n_above == 0.  It is the bounding box of ALL such cells, not of the largest connected
+ *                      component
+ *   6. a class id outside [0, n_classes): the slot's map is all 0x7FC00000, class_id = -1, peak_cell = -1, n_above = 0,
+ *                      box = -1, the floats of the record NaN; other slots are untouched
+ * Non-finite map values have no rule of their own: the chains carry them (a NaN's payload and sign are not part of the
+ * contract). */
+typedef struct fav_cam_record { int32_t class_id; float logit_mean, peak; int32_t peak_cell; float floor, pos_sum;
+                                int32_t n_above, box; } fav_cam_record;
+/* The head on the maps of the LAST fav_classify* call, with the handle's own fc weights and bias, for any classes the caller
+ * names: classes_dev int32 [n][K], 1 <= K <= 8, cam_dev fp32 [n][K][Hf*Wf] (4-byte aligned), rec_dev [n][K] (8-byte aligned),
+ * n the frames of that call.  One small launch on hip_stream, no second forward pass, no allocation, no synchronisation.
+ * FAV_ERR_INVALID_ARG with the tap off, before the first tapped call, for a NULL or misaligned buffer and for a map outside
+ * the head's ranges (fav_op_cam).  FAV_ERR_UNSUPPORTED while views are set or when the last call ran under views: a mirrored
+ * or turned view's map lies in that view's frame, and averaging them mis-registers (fav_get_maps still works there). */
+fav_status fav_cam(fav_handle* h, const int32_t* classes_dev, int32_t K, float* cam_dev, fav_cam_record* rec_dev,
+                   void* hip_stream);
+/* fav_classify_ex unchanged, then the head with K = 1 on the class this very call wrote to labels_dev (non-NULL; read on the
+ * device, so nothing synchronises): cam_dev fp32 [n][Hf*Wf], rec_dev [n].  Needs the map tap on (FAV_ERR_INVALID_ARG
+ * otherwise); FAV_ERR_UNSUPPORTED while views are set.  Never allocates or synchronises.  fail_dev / score_dev may be NULL.
+ * The head's launch is booked in no kernel class. */
+fav_status fav_classify_cam(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
+                            int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev, float* cam_dev,
+                            fav_cam_record* rec_dev, void* hip_stream);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -788,6 +855,28 @@ size_t fav_drift_workspace_bytes(int32_t n, int32_t D, int32_t R, int32_t n_perm
 fav_status fav_op_drift_test(const void* feat_bf16, int32_t S, int32_t n, int32_t D, const void* ref_dev, int32_t R,
                              int32_t n_perm, uint64_t seed, float alpha, void* ws_dev, size_t ws_bytes,
                              fav_drift_record* record_dev, int64_t* perm_sums_dev, void* hip_stream);
+
+/* ---- The CAM head defined beside fav_cam_record, on device arrays: maps_bf16 [S][n][Hf*Wf][C] bf16 and w_bf16 rows of ldw
+ * bf16 (both 16-byte aligned), bias fp32 [n_classes], classes_dev int32 [n][K], cam_dev fp32 [n][K][Hf*Wf], rec_dev [n][K]
+ * (8-byte aligned).  One launch, one block a frame, no global workspace, no allocation, no synchronisation; vector stores
+ * only.  Ranges: 1 <= S <= 4096; n >= 1; 1 <= Hf*Wf <= 1024 with Hf, Wf <= 256 (the box packs a byte a coordinate); C a
+ * multiple of 512, at most 4096; ldw >= C, a multiple of 8; n_classes >= 1; 1 <= K <= 8.  A refused call
+ * (FAV_ERR_INVALID_ARG: a NULL pointer, a size out of range, a misaligned buffer) launches nothing and leaves a message that
+ * names the function in fav_last_error(NULL). */
+fav_status fav_op_cam(const void* maps_bf16, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C, const void* w_bf16,
+                      int32_t ldw, const float* bias, int32_t n_classes, const int32_t* classes_dev, int32_t K, float* cam_dev,
+                      fav_cam_record* rec_dev, void* hip_stream);
+/* The overlay a dashboard draws: each of m maps (cam_dev fp32 [m][Hf*Wf], rec_dev [m] for its floor and peak) resized to
+ * H x W and normalised to a byte, out_u8 [m][H][W].  Bilinear, half-pixel centres, clamped edges (align_corners = False).
+ * Per output pixel (y, x), everything fp32, every operation rounded on its own:
+ *   1. sy = fmaxf(((float)y + 0.5f) * ((float)Hf / (float)H) - 0.5f, 0);  y0 = min((int)sy, Hf - 1);  y1 = min(y0 + 1, Hf - 1);
+ *      ly = sy - (float)y0;  hy = 1 - ly;  likewise sx, x0, x1, lx, hx from x, Wf and W
+ *   2. top = hx * M[y0][x0] + lx * M[y0][x1];  bot = hx * M[y1][x0] + lx * M[y1][x1];  v = hy * top + ly * bot
+ *   3. t = (v - floor) / (peak - floor);  byte = rintf(fminf(fmaxf(t, 0), 1) * 255) (fmaxf drops a NaN: byte 0)
+ *   4. a map with !(peak > floor) - flat, all NaN, a class out of range - is all 0
+ * Ranges: m >= 1; 1 <= Hf*Wf <= 1024; 1 <= H*W <= 2^31 - 1.  Refusals as fav_op_cam. */
+fav_status fav_op_cam_heatmap(const float* cam_dev, const fav_cam_record* rec_dev, int32_t m, int32_t Hf, int32_t Wf,
+                              int32_t H, int32_t W, uint8_t* out_u8, void* hip_stream);
 
 #ifdef __cplusplus
 }
