@@ -29,8 +29,11 @@ typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4_t;
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t b) { return __uint_as_float(b << 16); }
 
-// round-to-nearest-even fp32 -> bf16 bits (same integer recipe as the oracle;
-// no NaN can reach it on this path: pixels are sanitised where they enter (fav_sanitize_px), weights are checked finite when loaded)
+// round-to-nearest-even fp32 -> bf16 bits (same integer recipe as the oracle).  Only for values that are finite by construction:
+// the stem kernels round sanitised pixels (fav_sanitize_px) with it, the k-NN head a normalised feature it has checked.  The
+// recipe turns a NaN with a full payload into a zero, and activations CAN be non-finite from the first convolution on (finite
+// weights overflow bf16, and +inf times weights of mixed sign is a NaN), so every epilogue rounds with pack_bf16x2, whose
+// v_cvt_pk_bf16_f32 keeps NaN and +-inf and turns a finite fp32 above the bf16 range into +-inf.
 __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
     uint32_t u = __float_as_uint(f);
     return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
@@ -44,12 +47,18 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     const f32x2_t v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
-// ReLU on a PACKED pair of bf16 values: as signed 16-bit integers every negative float (and -0) is negative, every non-negative one
-// keeps its pattern, so max(x, 0) per half is ONE v_pk_max_i16 for two elements.  Rounding first and clamping afterwards gives the same
-// bits as clamping the fp32 value first: a negative value rounds to a negative bf16 (or -0) and becomes +0 either way.
-typedef short s16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, v), (s16x2_t){0, 0}));
+// THE ReLU of every epilogue, on the fp32 value in front of the one rounding: IEEE 754-2019 maximum(v, +0), ONE v_maximum3_f32
+// on gfx950.  It keeps a NaN of either sign, maps -inf and -0 to +0 and keeps +inf; every finite value gets the bits fmaxf(v, 0)
+// gave it.  fmaxf (v_max_f32) answers 0 for a NaN, and so does an integer maximum on the bits for a NaN whose sign bit is set -
+// which is the NaN v_mfma_f32_16x16x32_bf16 produces (0xFFC00000, measured: DESIGN.md section 2, item 2b).  Either would turn a
+// frame whose activations overflowed into a finite, confident one, so no site may use them: one function, the same bits everywhere.
+__device__ __forceinline__ float relu_f32(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+// Two fp32 additions as ONE v_pk_add_f32 - the same two IEEE results as two v_add_f32.  The epilogues whose ReLU used to be a
+// packed integer maximum on the rounded pair (half an instruction per element; it dropped sign-set NaNs) add their bias with
+// it, which pays for relu_f32's whole instruction per element.
+__device__ __forceinline__ void add_pair(float& o0, float& o1, float a0, float a1, float b0, float b1) {
+    const f32x2_t s = (f32x2_t){a0, a1} + (f32x2_t){b0, b1};
+    o0 = s.x; o1 = s.y;
 }
 
 // fp32 frames come from the caller: a NaN pixel counts as 0, everything else is clamped to [-64, 64] (far outside any image range;
@@ -164,6 +173,17 @@ __device__ __forceinline__ uint4 drop_draws16_ti(const DropParams& d, uint32_t t
 // v = keep(byte j of the draws) ? v * scale : 0
 #define FAV_DROP_APPLY(V, DRAWS, J, D) \
     ((((DRAWS)[(J) >> 2] >> (8 * ((J) & 3))) & 0xFFu) >= (D).thr ? __fmul_rn((V), (D).scale) : 0.f)
+// The same on eight values at once, the scaling as four v_pk_mul_f32 in front of the selects (same products, same selects: a
+// dropped NaN is 0, a kept one stays NaN)
+#define FAV_DROP_APPLY8(V, DRAWS, J0, D)                                                                          \
+    do {                                                                                                          \
+        _Pragma("unroll") for (int k_ = 0; k_ < 8; k_ += 2) {                                                     \
+            const f32x2_t p_ = (f32x2_t){(V)[k_], (V)[k_ + 1]} * (f32x2_t){(D).scale, (D).scale};                 \
+            (V)[k_] = p_.x; (V)[k_ + 1] = p_.y;                                                                   \
+        }                                                                                                         \
+        _Pragma("unroll") for (int k_ = 0; k_ < 8; ++k_)                                                          \
+            (V)[k_] = (((DRAWS)[((J0) + k_) >> 2] >> (8 * (((J0) + k_) & 3))) & 0xFFu) >= (D).thr ? (V)[k_] : 0.f; \
+    } while (0)
 
 // ---------------------------------------------------------------------------
 // Stem: frames (u8 / fp32 NHWC3) -> normalised bf16 im2col rows [n*Ho*Wo][kpad]
@@ -454,9 +474,10 @@ __global__ __launch_bounds__(256, 2) void stem7_pool_kernel(StemPoolParams p) {
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 const float4 bq = *(const float4*)(bias_s + 16 * a + 4 * fq);
-                const float v0 = __fadd_rn(acc[a][0], bq.x), v1 = __fadd_rn(acc[a][1], bq.y);
-                const float v2 = __fadd_rn(acc[a][2], bq.z), v3 = __fadd_rn(acc[a][3], bq.w);
-                *(uint2*)(crow + (((2 * a + (fq >> 1)) ^ (q & 7)) << 4)) = make_uint2(relu_bf16x2(pack_bf16x2(v0, v1)), relu_bf16x2(pack_bf16x2(v2, v3)));
+                float v0, v1, v2, v3;
+                add_pair(v0, v1, acc[a][0], acc[a][1], bq.x, bq.y);
+                add_pair(v2, v3, acc[a][2], acc[a][3], bq.z, bq.w);
+                *(uint2*)(crow + (((2 * a + (fq >> 1)) ^ (q & 7)) << 4)) = make_uint2(pack_bf16x2(relu_f32(v0), relu_f32(v1)), pack_bf16x2(relu_f32(v2), relu_f32(v3)));
             }
         }
         __syncthreads();
@@ -1019,7 +1040,9 @@ __global__ __launch_bounds__((BM / 64) * WN * 64, OCCW ? OCCW : conv_waves_per_s
                 for (int h8 = 0; h8 < CPL / 8; ++h8) {
                     float v[8];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = __fadd_rn(acc[g * (GS / 16) + 2 * h8 + (k >> 2)][b][k & 3], bia[g][8 * h8 + k]);
+                    for (int k = 0; k < 8; k += 2)
+                        add_pair(v[k], v[k + 1], acc[g * (GS / 16) + 2 * h8 + (k >> 2)][b][k & 3], acc[g * (GS / 16) + 2 * h8 + (k >> 2)][b][(k & 3) + 1],
+                                 bia[g][8 * h8 + k], bia[g][8 * h8 + k + 1]);
                     if (p.res) {
                         const uint32_t rw[4] = {rr1[slot][g][h8][0], rr1[slot][g][h8][1], rr1[slot][g][h8][2], rr1[slot][g][h8][3]};
 #pragma unroll
@@ -1028,9 +1051,9 @@ __global__ __launch_bounds__((BM / 64) * WN * 64, OCCW ? OCCW : conv_waves_per_s
                             v[2 * k + 1] = __fadd_rn(v[2 * k + 1], bf16_bits_to_f32(rw[k] >> 16));
                         }
                     }
-                    if (p.relu == 1 && p.out_f32) {        // (bf16 output: ReLU on the packed pairs below)
+                    if (p.relu == 1 && p.out_f32) {        // (bf16 output: behind the dropout below)
 #pragma unroll
-                        for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
+                        for (int k = 0; k < 8; ++k) v[k] = relu_f32(v[k]);
                     } else if (GELU && p.relu == 2) {
 #pragma unroll
                         for (int k = 0; k < 8; ++k) v[k] = fav_gelu(v[k]);
@@ -1044,15 +1067,12 @@ __global__ __launch_bounds__((BM / 64) * WN * 64, OCCW ? OCCW : conv_waves_per_s
                                     *(float4*)(yo + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
                         }
                     } else {
-                        if (p.drop.site >= 0) {
-#pragma unroll
-                            for (int k = 0; k < 8; ++k) v[k] = FAV_DROP_APPLY(v[k], draws, 8 * h8 + k, p.drop);
-                        }
-                        u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+                        if (p.drop.site >= 0) FAV_DROP_APPLY8(v, draws, 8 * h8, p.drop);
                         if (p.relu == 1) {
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) o[k] = relu_bf16x2(o[k]);
+                            for (int k = 0; k < 8; ++k) v[k] = relu_f32(v[k]);
                         }
+                        const u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
                         if (LSTORE) {
                             const int r = b * 16 + frow, c16 = (g * GS + CPL * fq + 8 * h8) >> 3;   // row / 16-byte chunk inside the wave tile
                             *(u32x4_t*)(ytile + r * (WTN * 2) + ((c16 ^ (r & 15)) << 4)) = o;
@@ -1135,7 +1155,7 @@ __global__ __launch_bounds__((BM / 64) * WN * 64, OCCW ? OCCW : conv_waves_per_s
                 }
                 if (p.relu == 1) {
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
+                    for (int j = 0; j < 8; ++j) v[j] = relu_f32(v[j]);
                 } else if (GELU && p.relu == 2) {   // GELU (ViT MLP)
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = fav_gelu(v[j]);
@@ -1426,7 +1446,7 @@ __global__ __launch_bounds__(BM * 2, OCC) void conv3x3_halo_kernel(const ConvPar
                 const float4 t4 = *(const float4*)(outs + ml * OUT_LD + n + 4 * q);
                 const float4 bq = *(const float4*)(bias_s + ec * 20 + 4 * q);
                 float v0 = __fadd_rn(t4.x, bq.x), v1 = __fadd_rn(t4.y, bq.y), v2 = __fadd_rn(t4.z, bq.z), v3 = __fadd_rn(t4.w, bq.w);
-                if (p.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
+                if (p.relu) { v0 = relu_f32(v0); v1 = relu_f32(v1); v2 = relu_f32(v2); v3 = relu_f32(v3); }
                 o[2 * q] = pack_bf16x2(v0, v1);
                 o[2 * q + 1] = pack_bf16x2(v2, v3);
             }
@@ -1893,11 +1913,12 @@ __global__ __launch_bounds__(NW * 64, 2) void bottleneck_tail_kernel(const TailP
                 const int row = wm * 64 + b * 16 + frow;
                 const int c0 = wn * (CMID / WN1) + a * 16 + fq * 4;
                 const float4 bq = *(const float4*)(bias_b_s + (c0 >> 4) * 20 + (c0 & 15));
-                const float v0 = __fadd_rn(acc[a][b][0], bq.x), v1 = __fadd_rn(acc[a][b][1], bq.y);
-                const float v2 = __fadd_rn(acc[a][b][2], bq.z), v3 = __fadd_rn(acc[a][b][3], bq.w);
+                float v0, v1, v2, v3;
+                add_pair(v0, v1, acc[a][b][0], acc[a][b][1], bq.x, bq.y);
+                add_pair(v2, v3, acc[a][b][2], acc[a][b][3], bq.z, bq.w);
                 const int sw = tail_sw<CPR>(row);
                 *(uint2*)(tsm + row * ROWB + (((c0 >> 3) ^ sw) << 4) + ((c0 >> 2) & 1) * 8) =
-                    make_uint2(relu_bf16x2(pack_bf16x2(v0, v1)), relu_bf16x2(pack_bf16x2(v2, v3)));
+                    make_uint2(pack_bf16x2(relu_f32(v0), relu_f32(v1)), pack_bf16x2(relu_f32(v2), relu_f32(v3)));
             }
     }
     // wave w owns pixel rows [w*RP, w*RP + RP): their T2 fragments (all CMID k) live in registers from here on
@@ -2053,7 +2074,8 @@ __global__ __launch_bounds__(NW * 64, 2) void bottleneck_tail_kernel(const TailP
                 for (int g = 0; g < 2; ++g) {
                     float v[8];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = __fadd_rn(acc2[2 * g + (k >> 2)][b][k & 3], bia[8 * g + k]);
+                    for (int k = 0; k < 8; k += 2)
+                        add_pair(v[k], v[k + 1], acc2[2 * g + (k >> 2)][b][k & 3], acc2[2 * g + (k >> 2)][b][(k & 3) + 1], bia[8 * g + k], bia[8 * g + k + 1]);
                     if (HAS_RES) {
                         uint32_t rw[4] = {rcur[b][g][0], rcur[b][g][1], rcur[b][g][2], rcur[b][g][3]};
                         if constexpr (RESE) {     // cached pixel -> the bf16 the entry dropout would have stored for this sample
@@ -2070,15 +2092,12 @@ __global__ __launch_bounds__(NW * 64, 2) void bottleneck_tail_kernel(const TailP
                             v[2 * k + 1] = __fadd_rn(v[2 * k + 1], bf16_bits_to_f32(rw[k] >> 16));
                         }
                     }
-                    if (p.drop.site >= 0) {
+                    if (p.drop.site >= 0) FAV_DROP_APPLY8(v, draws, 8 * g, p.drop);
+                    if (RELU) {      // (scale > 0: the sign is the value's own, so the ReLU may follow the dropout)
 #pragma unroll
-                        for (int k = 0; k < 8; ++k) v[k] = FAV_DROP_APPLY(v[k], draws, 8 * g + k, p.drop);
+                        for (int k = 0; k < 8; ++k) v[k] = relu_f32(v[k]);
                     }
-                    u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-                    if (RELU) {      // on the packed pairs: half the instructions of eight v_max_f32 (scale > 0: the sign is the value's own)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = relu_bf16x2(o[k]);
-                    }
+                    const u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
                     if (!LINEST) __builtin_amdgcn_raw_buffer_store_b128(o, srd_y, (row * COUT + n + 8 * g) * 2, 0, 0);
                     if (LINEST) *(u32x4_t*)(ych + row * 128 + (((2 * fq + g) ^ (row & 7)) << 4)) = o;
                 }
@@ -2162,9 +2181,11 @@ __global__ __launch_bounds__(NW * 64, 2) void bottleneck_tail_kernel(const TailP
                 for (int g = 0; g < 2; ++g) {
                     float v[8];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = __fadd_rn(acc3[g3 * 4 + 2 * g + (k >> 2)][b][k & 3], bia[8 * g + k]);
-                    const u32x4_t o = {relu_bf16x2(pack_bf16x2(v[0], v[1])), relu_bf16x2(pack_bf16x2(v[2], v[3])), relu_bf16x2(pack_bf16x2(v[4], v[5])),
-                                       relu_bf16x2(pack_bf16x2(v[6], v[7]))};
+                    for (int k = 0; k < 8; k += 2)
+                        add_pair(v[k], v[k + 1], acc3[g3 * 4 + 2 * g + (k >> 2)][b][k & 3], acc3[g3 * 4 + 2 * g + (k >> 2)][b][(k & 3) + 1], bia[8 * g + k], bia[8 * g + k + 1]);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) v[k] = relu_f32(v[k]);
+                    const u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
                     __builtin_amdgcn_raw_buffer_store_b128(o, srd_t, (row * NRED + g3 * 64 + fq * 16 + 8 * g) * 2, 0, 0);
                 }
             }
@@ -2179,7 +2200,8 @@ __global__ __launch_bounds__(NW * 64, 2) void bottleneck_tail_kernel(const TailP
 
 // ---------------------------------------------------------------------------
 // 3x3 stride-2 pad-1 max pool, NHWC bf16; one thread = 8 channels of one output
-// pixel (16-B loads/stores).  HBM-bound.
+// pixel (16-B loads/stores).  HBM-bound.  A NaN tap inside the frame makes the output NaN (fmaxf alone would drop it
+// beside a finite tap): the taps' NaN-ness is collected per channel and decides at the end.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const uint4* __restrict__ x, uint4* __restrict__ y, int n,
                                                            int H, int W, int C, int Ho, int Wo) {
@@ -2191,6 +2213,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const uint4* __restri
         const int ow = (int)(pix % Wo), oh = (int)((pix / Wo) % Ho);
         const long long img = pix / ((long long)Wo * Ho);
         float best[8];
+        uint32_t nan_taps = 0;      // bit j: channel j met a NaN
 #pragma unroll
         for (int j = 0; j < 8; ++j) best[j] = -INFINITY;
 #pragma unroll
@@ -2205,11 +2228,15 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const uint4* __restri
                 const uint32_t vw[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    best[2 * j] = fmaxf(best[2 * j], bf16_bits_to_f32(vw[j] & 0xFFFFu));
-                    best[2 * j + 1] = fmaxf(best[2 * j + 1], bf16_bits_to_f32(vw[j] >> 16));
+                    const float lo = bf16_bits_to_f32(vw[j] & 0xFFFFu), hi = bf16_bits_to_f32(vw[j] >> 16);
+                    nan_taps |= (uint32_t)(lo != lo) << (2 * j) | (uint32_t)(hi != hi) << (2 * j + 1);
+                    best[2 * j] = fmaxf(best[2 * j], lo);
+                    best[2 * j + 1] = fmaxf(best[2 * j + 1], hi);
                 }
             }
         }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) best[j] = (nan_taps >> j) & 1u ? __uint_as_float(0x7FC00000u) : best[j];
         y[idx] = make_uint4(pack_bf16x2(best[0], best[1]), pack_bf16x2(best[2], best[3]),
                             pack_bf16x2(best[4], best[5]), pack_bf16x2(best[6], best[7]));
     }
@@ -2450,9 +2477,11 @@ __global__ __launch_bounds__(256, 2) void entry_reduce_kernel(const EntryReduceP
                 for (int g = 0; g < 2; ++g) {
                     float v[8];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = __fadd_rn(acc3[g3 * 4 + 2 * g + (k >> 2)][b][k & 3], bia[8 * g + k]);
-                    const u32x4_t o = {relu_bf16x2(pack_bf16x2(v[0], v[1])), relu_bf16x2(pack_bf16x2(v[2], v[3])), relu_bf16x2(pack_bf16x2(v[4], v[5])),
-                                       relu_bf16x2(pack_bf16x2(v[6], v[7]))};
+                    for (int k = 0; k < 8; k += 2)
+                        add_pair(v[k], v[k + 1], acc3[g3 * 4 + 2 * g + (k >> 2)][b][k & 3], acc3[g3 * 4 + 2 * g + (k >> 2)][b][(k & 3) + 1], bia[8 * g + k], bia[8 * g + k + 1]);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) v[k] = relu_f32(v[k]);
+                    const u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
                     __builtin_amdgcn_raw_buffer_store_b128(o, srd_t, (int)(orow[b] * (uint32_t)(NRED * 2)) + (g3 * 64 + fq * 16 + 8 * g) * 2, 0, 0);
                 }
         }
@@ -2742,7 +2771,7 @@ __global__ __launch_bounds__(256, 3) void gemm_streamk_kernel(const GemmSkParams
                         }
                         if ((p.act & 0xff) == 1) {
 #pragma unroll
-                            for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
+                            for (int k = 0; k < 8; ++k) v[k] = relu_f32(v[k]);
                         } else if ((p.act & 0xff) == 2) {
 #pragma unroll
                             for (int k = 0; k < 8; ++k) v[k] = fav_gelu(v[k]);
@@ -2917,7 +2946,9 @@ __device__ __forceinline__ int attn_vsw(int row) { return 2 * ((row >> 1) & 3); 
 // degree-4 polynomial for 2^r on [-0.5, 0.5] (relative error 2.9e-6: the probabilities are rounded to bf16), 2^k added into the exponent
 // field.  7 packed + 1 scalar instruction per pair; oracle/fav_exact.c: fav_attn_exp2_ref is the same sequence.
 __device__ __forceinline__ f32x2_t fav_attn_exp2(f32x2_t z) {
-    z.x = fmaxf(z.x, -125.0f); z.y = fmaxf(z.y, -125.0f);
+    // a compare and a select, not fmaxf: a NaN score (a NaN in Q or K, or +inf - inf behind a +inf row max, or a row of -inf) must stay
+    // a NaN - it makes the row's sum, hence every probability of the row, NaN; fmaxf would turn it into the smallest weight
+    z.x = z.x < -125.0f ? -125.0f : z.x; z.y = z.y < -125.0f ? -125.0f : z.y;
     const f32x2_t M = {12582912.0f, 12582912.0f};
     const f32x2_t zk = z + M;
     const f32x2_t r = z - (zk - M);

@@ -608,6 +608,14 @@ typedef struct fav_conv_desc {
     int32_t relu, out_f32, math_mode;   /* relu: 0 = none, 1 = ReLU, 2 = GELU (ViT MLP) */
     fav_dropout_desc drop;
 } fav_conv_desc;
+/* Non-finite values.  Every fav_op_* between the stem and the logits is IEEE arithmetic: a NaN
+ * in x, res or made inside (+inf - inf, inf x 0) stays a NaN and +-inf behave as in float64, on every route and in both math
+ * modes.  ReLU maps -inf to +0 and keeps +inf and a NaN of either sign; GELU is its fixed sequence (-inf gives NaN); a dropped
+ * NaN is +0, a kept one stays NaN; the one rounding to bf16 turns a finite fp32 above the bf16 range into +-inf; the max pool
+ * is NaN when any tap inside the frame is; a LayerNorm row with a non-finite value is NaN throughout; an attention query whose
+ * scores hold a NaN or +inf has NaN outputs.  The NaN the device makes is 0xFFC00000 (sign set, measured on MI355X); which NaN
+ * pattern comes out is not part of the contract.  A frame whose activations overflow ends in the non-finite frame rule above
+ * fav_classify, whatever the batch size and the schedule fields of fav_config. */
 fav_status fav_op_conv2d(const fav_conv_desc* d, void* hip_stream);
 
 /* Bottleneck tail (one launch): conv_b 3x3/1/1 Cmid->Cmid + ReLU (skipped when wb == NULL: x is then conv_c's

@@ -52,6 +52,7 @@ def bf16_round(x: np.ndarray) -> np.ndarray:
     x = np.ascontiguousarray(x, dtype=np.float32)
     u = x.view(np.uint32).astype(np.uint64)
     r = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    r = np.where(np.isnan(x), (u & 0xFFFF0000) | 0x00400000, r)      # a NaN stays a NaN whatever its payload
     return r.astype(np.uint32).view(np.float32).reshape(x.shape)
 
 
@@ -629,8 +630,25 @@ def mean_softmax(logits: np.ndarray, temperature: float = 1.0) -> np.ndarray:
     return acc * np.float32(1.0 / p.shape[0])
 
 
+def nonfinite_frames(logits: np.ndarray, temperature: float = 1.0) -> np.ndarray:
+    """bool[B]: the frames of logits [T,B,C] under the non-finite frame rule: in some sample the
+    scaled row holds a NaN or +inf, or is -inf throughout."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        z = logits.astype(np.float32) * np.float32(1.0 / temperature)
+    bad_row = np.isnan(z).any(axis=-1) | (z == np.inf).any(axis=-1) | (z == -np.inf).all(axis=-1)
+    return bad_row.any(axis=0)
+
+
 def confidence_head(logits: np.ndarray, temperature: float = 1.0, kind: int = CONF_MAX_SOFTMAX):
-    """-> (labels int32[B], confidence fp32[B], pbar fp32[B,C]).  argmax tie -> lowest index."""
+    """-> (labels int32[B], confidence fp32[B], pbar fp32[B,C]).  argmax tie -> lowest index.
+    A non-finite frame (nonfinite_frames): label 0, confidence 0, its pbar NaN - hence fail = 1 and score 1 from
+    failure_detect at any tau above 0 (the device writes fail = 1 whatever tau is)."""
+    bad = nonfinite_frames(logits, temperature)
+    if bad.any():
+        logits = np.where(bad[None, :, None], np.float32(0.0), logits.astype(np.float32))
+        labels, conf, pbar = confidence_head(logits, temperature, kind)
+        pbar = np.where(bad[:, None], np.float32(np.nan), pbar)
+        return np.where(bad, 0, labels).astype(np.int32), np.where(bad, np.float32(0.0), conf).astype(np.float32), pbar
     pbar = mean_softmax(logits, temperature)
     labels = pbar.argmax(axis=-1).astype(np.int32)
     if kind == CONF_MAX_SOFTMAX:

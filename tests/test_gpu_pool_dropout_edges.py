@@ -101,7 +101,7 @@ def maxpool_taps(x):
 
 
 def maxpool_ref(x):
-    return maxpool_taps(x).max(axis=0)           # order-free; the pool rounds nothing
+    return maxpool_taps(x).max(axis=0)           # order-free; the pool rounds nothing; a NaN tap inside the frame gives NaN (np.max)
 
 
 def maxpool_inputs(rng, n, H, W, Cc):
@@ -118,6 +118,17 @@ def maxpool_inputs(rng, n, H, W, Cc):
     x[rng.random(shape) < 0.2] = -BF16_MAX
     out["largest_finite"] = x
     out["subnormals"] = subnormals(rng, shape)                        # must come through unchanged, not flushed
+    # NaNs of either sign (0x7FC0, 0xFFC0 - the matrix unit makes the latter) beside finite values and both infinities: a window
+    # with a NaN tap is NaN whatever else it holds; channel 1 of frame 0 has none
+    x = spread(rng, shape)
+    x[rng.random(shape) < 0.1] = np.inf
+    x[rng.random(shape) < 0.1] = -np.inf
+    nans = O.bf16_from_bits(np.array([0x7FC0, 0xFFC0], np.uint16))
+    sel = rng.random(shape)
+    x[sel < 0.08], x[sel > 0.92] = nans[0], nans[1]
+    if Cc > 1:
+        x[0, :, :, 1] = spread(rng, (H, W))
+    out["nans"] = x
     # every (frame, channel) plane a permutation of distinct integers (exact in bf16 up to 256): the maximum of a window
     # is at exactly one tap, and which one changes from window to window
     assert H * W <= 256
@@ -148,8 +159,10 @@ def test_maxpool_small_frames_bit_exact(lib, H, W):
                 ref = maxpool_ref(x)
                 got = run_maxpool(lib, x)
                 assert got.shape == ref.shape
-                # by value: -0 == +0 (fmaxf does not order them); no NaN anywhere (the pool's input is a ReLU of sanitised frames)
-                assert np.array_equal(got, ref), f"{kind} n={n} C={Cc}: {np.mean(got != ref):.4f} of elements differ"
+                # by value: -0 == +0 (fmaxf does not order them); a NaN equals a NaN whatever its pattern
+                assert np.array_equal(got, ref, equal_nan=True), f"{kind} n={n} C={Cc}: {np.mean(got != ref):.4f} of elements differ"
+                if kind == "nans":
+                    assert np.isnan(ref).any() == np.isnan(x).any() and not np.isnan(ref[0, :, :, 1]).any()
                 if kind == "subnormals":
                     assert np.all(got != 0) and np.all(np.abs(got) < np.finfo(np.float32).tiny)
                 if kind == "all_negative":
@@ -165,7 +178,7 @@ def test_maxpool_ragged_launch_and_every_tap(lib):
     rng = np.random.default_rng(911)
     for kind, x in maxpool_inputs(rng, n, H, W, Cc).items():
         got = run_maxpool(lib, x)
-        assert np.array_equal(got, maxpool_ref(x)), kind
+        assert np.array_equal(got, maxpool_ref(x), equal_nan=True), kind
     taps = maxpool_taps(maxpool_inputs(rng, n, H, W, Cc)["distinct"])
     assert set(np.unique(taps.argmax(axis=0))) == set(range(9))
 

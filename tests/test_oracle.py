@@ -273,3 +273,106 @@ def test_committed_fixtures_belong_to_the_current_checkpoint_and_oracle(r50_blob
         assert same.sum() >= floor, (name, int(same.sum()))
         assert (prod["labels"][~same] == ind["second"][~same]).mean() >= 0.9          # disagreements sit on the other model's runner-up
         assert np.abs(prod["conf"] - ind["conf"]).max() < dmax
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# NaN and the infinities (the float64 reference of the classes is tests/nonfinite_ref.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def test_c_epilogue_equals_the_numpy_specification_on_non_finite_values():
+    """np.maximum keeps a NaN; so does the C restatement: bit for bit the specification, a NaN counting as equal whatever
+    its payload, on an accumulator that holds both NaNs, both infinities, +inf under a residual of -inf and a finite fp32
+    above the bf16 range."""
+    import nonfinite_ref as N
+    rng = np.random.default_rng(4)
+    acc = rng.standard_normal((2, 3, 5, 64)).astype(np.float32)
+    res = O.bf16_round(rng.standard_normal(acc.shape).astype(np.float32))
+    acc[0, 0, 0, :6] = [N.special("nan"), N.special("nan_neg"), np.inf, -np.inf, np.inf, 3.4e38]
+    res[0, 0, 0, 4] = -np.inf
+    acc[1, ..., 7], acc[1, ..., 8], acc[1, ..., 9] = np.nan, np.inf, -np.inf
+    bias = rng.standard_normal(64).astype(np.float32)
+    keep = rng.random(acc.shape) > 0.3
+    scale = O.dropout_scale(O.dropout_threshold(0.3))
+    with np.errstate(all="ignore"):
+        for kw in (dict(), dict(res=res), dict(res=res, keep=keep, scale=scale), dict(relu=False), dict(res=res, relu=False), dict(keep=keep, scale=scale)):
+            a, b = O.epilogue(acc, bias, **kw), O.epilogue_numpy(acc, bias, **kw)
+            nan = np.isnan(b)
+            assert np.array_equal(np.isnan(a), nan) and np.array_equal(a.view(np.uint32)[~nan], b.view(np.uint32)[~nan]), kw.keys()
+            relu = kw.get("relu", True)
+            want = [N.NAN, N.NAN, N.PINF, N.FIN if relu else N.NINF, N.NAN if "res" in kw else N.PINF, N.PINF]
+            kept = keep[0, 0, 0, :6] if "keep" in kw else np.ones(6, bool)
+            assert N.classes(a[0, 0, 0, :6]).tolist() == [w if k else N.FIN for w, k in zip(want, kept)], kw.keys()
+            assert np.isnan(a).sum() > 10 or "keep" in kw
+
+
+@pytest.mark.parametrize("kh,stride,pad", [(1, 1, 0), (3, 1, 1), (3, 2, 1)])
+def test_mfma_model_gives_the_ieee_class_for_non_finite_operands(kh, stride, pad):
+    """fav_bf16mfma_conv_acc on inputs that hold NaN and the infinities: every output's class is float64's (the rule of
+    tests/nonfinite_ref.py) and the f32-chain mode's, and a pixel with a clean receptive field keeps the bits it has on the
+    clean input.  Also an accumulator that overflows on finite operands, and products beyond the fp32 range."""
+    import nonfinite_ref as N
+    rng = np.random.default_rng(kh * 10 + stride)
+    x = O.bf16_round(np.clip(rng.standard_normal((2, 9, 10, 64)), -4, 4).astype(np.float32))
+    x = np.where(rng.random(x.shape) < 0.3, np.float32(0), x)            # ReLU zeros: inf x 0 on the weight side stays out, 0 x w is 0
+    w = O.bf16_round((rng.standard_normal((40, kh, kh, 64)) * 0.1).astype(np.float32))
+    w[:, :, :, ::9] = 0                                                   # zero weights: inf x 0 is a NaN
+    p = x.copy()
+    for i, kind in enumerate(("+inf", "-inf", "nan", "nan_neg")):
+        p[0, 2 * i + 1, 2, 3 * i + 1] = N.special(kind)
+    p[0, 4, 7, 0] = np.inf                                                # on a zero weight (channel 0)
+    p[0, 7, 6, 11], p[0, 7, 6, 12] = np.inf, -np.inf
+    cols, ho, wo = N.im2col(p, kh, kh, stride, pad)
+    ref, _ = N.dot_classes(cols, w.reshape(40, -1))
+    ref = ref.reshape(2, ho, wo, 40)
+    assert set(np.unique(ref).tolist()) == {N.NAN, N.PINF, N.NINF, N.FIN}
+    clean_acc = O.conv_acc_exact(x, w, kh, kh, stride, pad, mode="mfma")
+    got = O.conv_acc_exact(p, w, kh, kh, stride, pad, mode="mfma")
+    chain = O.conv_acc_exact(p, w, kh, kh, stride, pad, mode=True)
+    assert np.array_equal(N.classes(got), ref) and np.array_equal(N.classes(chain), ref)
+    untouched = ref == N.FIN
+    dirty, _, _ = N.im2col((p.view(np.uint32) != x.view(np.uint32)).any(axis=3, keepdims=True), kh, kh, stride, pad)
+    untouched = np.broadcast_to((dirty.sum(axis=1) == 0).reshape(2, ho, wo, 1), ref.shape)
+    assert untouched.mean() > 0.5 and np.array_equal(got.view(np.uint32)[untouched], clean_acc.view(np.uint32)[untouched])
+    assert np.array_equal(got[1].view(np.uint32), clean_acc[1].view(np.uint32))                # the frame without poison
+    if kh == 1:
+        # finite operands: an accumulator that overflows stays infinite (finite products cannot move it) ...
+        big = np.full((1, 1, 1, 64), 2.0 ** 60, np.float32)
+        wb = np.zeros((3, 1, 1, 64), np.float32)
+        wb[0, ..., :32], wb[0, ..., 32:] = 2.0 ** 64, -(2.0 ** 20)
+        wb[1] = -wb[0]
+        wb[2, ..., :8] = 1.0
+        out = O.conv_acc_exact(big, wb, 1, 1, 1, 0, mode="mfma").ravel()
+        assert out[0] == np.inf and out[1] == -np.inf and out[2] == np.float32(2.0 ** 63)
+        assert np.array_equal(N.classes(O.conv_acc_exact(big, wb, 1, 1, 1, 0, mode=True).ravel()), N.classes(out))
+        # ... and a product beyond the fp32 range is an infinity of its sign: both signs in one accumulator are a NaN
+        # (measured on the matrix unit; the fmaf chain rounds once per step and answers with the first infinity it reaches)
+        px = np.full((1, 1, 1, 64), 2.25, np.float32)
+        wh = np.zeros((3, 1, 1, 64), np.float32)
+        wh[0], wh[1] = 2.0 ** 127, 2.0 ** 127
+        wh[1, ..., 40:] = -(2.0 ** 127)
+        wh[2] = 2.0 ** 126                                                 # 2.25 x 2^126 < 2^128: finite products, the sum overflows
+        out = O.conv_acc_exact(px, wh, 1, 1, 1, 0, mode="mfma").ravel()
+        assert out[0] == np.inf and np.isnan(out[1]) and out[2] == np.inf
+
+
+@pytest.mark.parametrize("exact", ["mfma", True], ids=["mfma", "f32-chain"])
+def test_overflowing_checkpoint_ends_in_the_non_finite_frame_rule(r18_blob, exact):
+    """layer2.0.conv1 and layer2.0.conv2 of the ResNet-18 fixture scaled by 2^100: every weight is finite, the activations
+    overflow bf16, +inf meets weights of both signs.  O.classify answers with non-finite logits and the non-finite frame
+    rule - label 0, confidence 0, hence fail and score 1 - on every frame, in both exact modes; it used to answer label 0 with
+    a confidence of 0.75 - 0.84."""
+    import nonfinite_ref as N
+    blob = N.scale_layer(N.scale_layer(r18_blob[0], 5, 100), 6, 100)
+    model = O.parse_blob(blob)
+    assert all(np.isfinite(L.w).all() and np.isfinite(L.b).all() for L in model.layers)
+    frames = synth.synthetic_frames_u8(3, 32, 32, seed=11)
+    labels, conf, lg, pbar = O.classify(model, frames, O.ClassifyConfig(exact=exact), return_logits=True)
+    assert not np.isfinite(lg).any(axis=-1).all() and O.nonfinite_frames(lg).all()
+    assert (labels == 0).all() and (conf == 0).all() and np.isnan(pbar).all()
+    fail, score = O.failure_detect(conf, 0.5)
+    assert (fail == 1).all() and (score == 1).all()
+    # a finite frame beside it keeps what it had: the rule touches the non-finite frames alone
+    mixed = np.concatenate([lg, np.zeros_like(lg[:, :1])], axis=1)
+    mixed[0, -1, 3] = 5.0
+    l2, c2, p2 = O.confidence_head(mixed)
+    l1, c1, p1 = O.confidence_head(mixed[:, -1:])
+    assert l2[-1] == l1[0] == 3 and c2[-1] == c1[0] > 0.5 and (l2[:-1] == 0).all() and (c2[:-1] == 0).all()
