@@ -154,6 +154,13 @@ class FavCamRecord(C.Structure):
                 ("floor", C.c_float), ("pos_sum", C.c_float), ("n_above", C.c_int32), ("box", C.c_int32)]
 
 
+class FavRolloutRecord(C.Structure):
+    """fav_rollout_record: one 32-byte summary per frame (rollout.unpack_rollout_records reads it as int32[..., 8]); peak and
+    floor stand where FavCamRecord has them."""
+    _fields_ = [("n_layers", C.c_int32), ("cls_mass", C.c_float), ("peak", C.c_float), ("peak_cell", C.c_int32),
+                ("floor", C.c_float), ("patch_sum", C.c_float), ("n_above", C.c_int32), ("box", C.c_int32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -230,6 +237,17 @@ _SIGNATURES = {
                              C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_op_cam_heatmap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p]),
+    "fav_set_attn_tap": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t]),
+    "fav_get_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32), C.c_void_p]),
+    "fav_attn_tap_info": (C.c_int, [C.POINTER(FavConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    "fav_rollout": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_classify_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_attn_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "fav_op_attn_rollout": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),

@@ -108,6 +108,7 @@ class Backend:
         self._tap, self._ood, self._knn = False, None, None   # the caller's own feature tap; the ood.OODModel, the ood.KNNBank in force
         self._drift = None                                    # the ood.DriftReference in force
         self._map_hw = None                                   # (Hf, Wf) of the map tap, known from the first set_map_tap(True) on
+        self._attn_grid = None                                # (gh, gw) of the attention tap, known from the first set_attn_tap(True) on
         self._views = ()
         if views:
             self.set_views(views)
@@ -601,6 +602,92 @@ class Backend:
             out = {k: v.cpu().numpy() for k, v in out.items()}
             rec = rec.cpu().numpy()
         return dict(unpack_cam_records(rec), **out)
+
+    # -- attention rollout (rollout.py; include/fav.h fav_set_attn_tap, fav_rollout) --------------------------------------------
+    def set_attn_tap(self, enable: bool, budget_bytes: int = 2 << 30):
+        """Keep every encoder layer's head-mean attention (fav_set_attn_tap) from the next call on; ``attention()``,
+        ``rollout()`` and ``classify_rollout()`` read it.  The buffer is allocated here, for max_batch frames
+        (``attn_tap_info()['bytes']``), and refused above ``budget_bytes``; turning the tap off frees it.  Refused on a ResNet
+        arch, on a deep ensemble and in the exact math mode."""
+        _lib.check(self.lib.fav_set_attn_tap(self._h, 1 if enable else 0, int(budget_bytes)), self._h)
+        if enable and self._attn_grid is None:
+            info = self.attn_tap_info()                # the planner, once: classify_rollout sizes its outputs from this
+            from .rollout import VIT_PATCH
+            self._attn_grid = (int(self.cfg.in_h) // VIT_PATCH, int(self.cfg.in_w) // VIT_PATCH)
+            assert self._attn_grid[0] * self._attn_grid[1] + 1 == info["tokens"]
+
+    def attn_tap_info(self) -> dict:
+        """What the attention tap of this configuration holds, from the planner alone (fav_attn_tap_info; no device work):
+        ``bytes`` of the buffer, its ``layers``, the ``tokens`` of a frame and the row pitch ``ld`` (tokens rounded up to 16)."""
+        nbytes, layers, tokens, ld = C.c_size_t(), C.c_int32(), C.c_int32(), C.c_int32()
+        err = C.create_string_buffer(256)
+        st = self.lib.fav_attn_tap_info(C.byref(self.cfg), C.byref(nbytes), C.byref(layers), C.byref(tokens), C.byref(ld), err, len(err))
+        if st != _lib.FAV_OK:
+            raise _lib.FavError(st, err.value.decode("utf-8", "replace"))
+        return dict(bytes=nbytes.value, layers=layers.value, tokens=tokens.value, ld=ld.value)
+
+    def attention(self):
+        """fp32 [L, n, T, T] head-mean attention of the last classify call made with the attention tap on (torch CUDA tensor,
+        a view of the padded buffer with the padding cut off): row t of layer l is how query token t spreads over the keys,
+        token 0 the class token.  Under views n is frames x views, indexed like ``logits()``."""
+        torch = self._torch
+        v = [C.c_int32() for _ in range(4)]
+        _lib.check(self.lib.fav_get_attention(self._h, None, *(C.byref(x) for x in v), None), self._h)
+        L, n, T, ld = (x.value for x in v)
+        out = torch.empty((L, n, T, ld), dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        _lib.check(self.lib.fav_get_attention(self._h, out.data_ptr(), None, None, None, None, stream), self._h)
+        return out[..., :T]
+
+    def rollout(self, first_layer: int = 0) -> dict:
+        """Attention rollout of the LAST classify call (fav_rollout; no second forward pass), over the layers
+        ``first_layer`` .. L-1: ``map`` fp32 [n, gh, gw] (how much each patch fed the class token) plus the record fields of
+        ``rollout.unpack_rollout_records``, each [n].  CUDA tensors, asynchronous on the current stream.  Needs the attention
+        tap; refused while views are set."""
+        from .rollout import ROLLOUT_RECORD_DWORDS, unpack_rollout_records
+        torch = self._torch
+        dev = torch.device(f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        v = [C.c_int32() for _ in range(4)]
+        if self.lib.fav_get_attention(self._h, None, *(C.byref(x) for x in v), None) != _lib.FAV_OK:
+            # nothing to size the outputs by (the tap is off, or no call since it went on): fav_rollout says so in its own words
+            dummy = torch.empty(8, dtype=torch.int32, device=dev)
+            _lib.check(self.lib.fav_rollout(self._h, int(first_layer), dummy.data_ptr(), dummy.data_ptr(), stream), self._h)
+            raise RuntimeError("fav_get_attention has nothing, yet fav_rollout accepted the call")
+        n = v[1].value
+        gh, gw = self._attn_grid
+        m = torch.empty((n, gh, gw), dtype=torch.float32, device=dev)
+        rec = torch.empty((n, ROLLOUT_RECORD_DWORDS), dtype=torch.int32, device=dev)
+        _lib.check(self.lib.fav_rollout(self._h, int(first_layer), m.data_ptr(), rec.data_ptr(), stream), self._h)
+        return dict(unpack_rollout_records(rec), map=m)
+
+    def classify_rollout(self, images, heatmap: bool = False, first_layer: int = 0, first_index: int = 0) -> dict:
+        """frames -> ``label``, ``conf``, ``fail``, ``score`` as ``classify_detect`` gives them, plus the attention rollout of
+        each frame (fav_classify_rollout; nothing synchronises): ``map`` fp32 [n, gh, gw] and the record fields of
+        ``rollout()``, each [n].  ``heatmap``: also ``heatmap`` uint8 [n, H, W], the map resized to the frame (bilinear) and
+        normalised from its floor to its peak by fav_op_cam_heatmap - the overlay a dashboard draws.  torch CUDA frames in ->
+        CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out, synchronous.  Needs the attention tap;
+        refused while views are set."""
+        from .rollout import ROLLOUT_RECORD_DWORDS, unpack_rollout_records
+        torch = self._torch
+        img, host, n, layout, stream = self._classify_args(images)
+        gh, gw = self._attn_grid or (1, 1)             # never tapped: fav_classify_rollout refuses before it writes anything
+        labels, conf, fail, score = self._detect_buffers(n, img.device)
+        m = torch.empty((n, gh, gw), dtype=torch.float32, device=img.device)
+        rec = torch.empty((n, ROLLOUT_RECORD_DWORDS), dtype=torch.int32, device=img.device)
+        _lib.check(self.lib.fav_classify_rollout(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
+                                                 conf.data_ptr(), fail.data_ptr(), score.data_ptr(), int(first_layer), m.data_ptr(),
+                                                 rec.data_ptr(), stream), self._h)
+        out = dict(label=labels, conf=conf, fail=fail, score=score, map=m)
+        if heatmap:
+            H, W = int(self.cfg.in_h), int(self.cfg.in_w)
+            heat = torch.empty((n, H, W), dtype=torch.uint8, device=img.device)
+            _lib.check(self.lib.fav_op_cam_heatmap(m.data_ptr(), rec.data_ptr(), n, gh, gw, H, W, heat.data_ptr(), stream))
+            out["heatmap"] = heat
+        if host:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+            rec = rec.cpu().numpy()
+        return dict(unpack_rollout_records(rec), **out)
 
     # what the two feature heads (the Mahalanobis model, the k-NN bank) share
     @staticmethod

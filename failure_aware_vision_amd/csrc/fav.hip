@@ -31,6 +31,7 @@
 #include "fav_knn.hpp"
 #include "fav_drift.hpp"
 #include "fav_cam.hpp"
+#include "fav_rollout.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -180,6 +181,14 @@ struct fav_handle {
     void* map_buf = nullptr;
     fav::MapTapDims map;
     int map_S = 0, map_n = 0, map_views = 0;
+    // Attention tap (fav_set_attn_tap; ViT only): while on, every encoder layer of every run_vit part launches attn_mean_kernel
+    // (fav_rollout.hpp) in front of its attention launch; attn_buf holds fp32 [attn.L][n][attn.T][attn.ld] for the n frame rows of
+    // the call (at most max_batch), a part at its frame offset; allocated by the setter, freed when the tap goes off.
+    // attn_n: the frame rows of the last call that filled it (0: none yet); attn_views: the views that call ran under
+    bool attn_tap = false;
+    float* attn_buf = nullptr;
+    fav::AttnTapDims attn;
+    int attn_n = 0, attn_views = 0;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -1091,16 +1100,29 @@ void free_all(fav_handle* h) {
     for (void* q : {h->knn.bank, h->knn.ws, (void*)h->knn.cls}) if (q) (void)hipFree(q);
     if (h->drift.ws) (void)hipFree(h->drift.ws);
     if (h->map_buf) (void)hipFree(h->map_buf);
+    if (h->attn_buf) (void)hipFree(h->attn_buf);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
     for (auto& e : h->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
 }
 
+// The attention tap's launch: the head-mean attention of n frames' qkv rows, to a [n][T][attn_ld(T)] (fav_rollout.hpp).  Booked in
+// no kernel class and in no route report.  The arguments have been checked (attn_mean_dims_error, the pointers).
+void launch_attn_mean(const void* qkv, float* a, int n, int T, int D, int heads, hipStream_t s) {
+    const int nkt = (T + 15) / 16, groups = (nkt + ATTN_MEAN_WAVES - 1) / ATTN_MEAN_WAVES;
+    void (*const fn)(const uint16_t*, float*, int, int, int, float) =
+        nkt <= 2 ? attn_mean_kernel<2, false> : nkt == 13 ? attn_mean_kernel<13, true> : nkt == 16 ? attn_mean_kernel<16, true>
+                                                                                          : attn_mean_kernel<16, false>;
+    const size_t lds = (size_t)2 * nkt * 16 * 128;      // two K buffers: at most 64 KB
+    hipLaunchKernelGGL(fn, dim3((unsigned)(n * groups)), dim3(64 * ATTN_MEAN_WAVES), lds, s, (const uint16_t*)qkv, a, T, D, heads,
+                       (float)(1.0 / heads));
+}
+
 // One forward pass of the ViT encoder over n frames -> fp32 logits [n][cpad].
-// Frames [f0, f0 + n) of the call: every buffer is indexed by frame, so two halves of a batch can run side by side
+// Frames [f0, f0 + n) of the call's n_call: every buffer is indexed by frame, so two halves of a batch can run side by side
 // on two streams (fav_classify_ex).
-fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, int n, hipStream_t s) {
+fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, int n, int n_call, hipStream_t s) {
     const fav_config& c = h->cfg;
     const VitDef& V = kVit[c.arch - 2];
     const int ntok = h->plan.ntok, D = V.dim, gh = c.in_h / V.patch, gw = c.in_w / V.patch;
@@ -1144,6 +1166,8 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
         const LayerWeights &ln1 = h->weights[li], &ln2 = h->weights[li + 3];
         FAV_VIT_TRY(launch_layernorm(h, B.v_x, D, (const float*)ln1.w_m[0], ln1.b_m[0], B.v_y, (long long)n * ntok, D, 1e-6f, s));
         FAV_VIT_TRY(gemm(li + 1, B.v_y, ntok, nullptr, 0, B.v_qkv, 0));
+        if (h->attn_tap)   // the attention tap: layer blk of this part's frames, at [blk][f0] of the call's n_call rows
+            launch_attn_mean(B.v_qkv, h->attn_buf + ((size_t)blk * n_call + F) * ntok * h->attn.ld, n, ntok, D, V.heads, s);
         FAV_VIT_TRY(launch_attention(h, B.v_qkv, B.v_y, n, ntok, D, V.heads, c.math_mode, s));
         FAV_VIT_TRY(gemm(li + 2, B.v_y, ntok, B.v_x, 0, B.v_x, 0));                 // x = x + proj(attn), in place tile by tile
         FAV_VIT_TRY(launch_layernorm(h, B.v_x, D, (const float*)ln2.w_m[0], ln2.b_m[0], B.v_y, (long long)n * ntok, D, 1e-6f, s));
@@ -1457,7 +1481,7 @@ fav_status run_vit_call(fav_handle* h, const Frames& f, hipStream_t s) {
     const int vit_streams = h->cfg.vit_streams <= 0 ? 2 : std::min(4, (int)h->cfg.vit_streams);
     if (!(vit_streams > 1 && n >= 8 * vit_streams)) {
         h->sk_slot = 0;
-        return run_vit(h, f.images, f.layout, 0, n, s);
+        return run_vit(h, f.images, f.layout, 0, n, n, s);
     }
     if (!h->ev_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     while ((int)h->vit_streams.size() < vit_streams) {
@@ -1472,7 +1496,7 @@ fav_status run_vit_call(fav_handle* h, const Frames& f, hipStream_t s) {
         const int f0 = (int)((long long)n * part / vit_streams), f1 = (int)((long long)n * (part + 1) / vit_streams);
         HIP_KEEP(h, st, hipStreamWaitEvent(h->vit_streams[part], h->ev_fork, 0));
         h->sk_slot = 1 + part;
-        if (st == FAV_OK) st = run_vit(h, f.images, f.layout, f0, f1 - f0, h->vit_streams[part]);
+        if (st == FAV_OK) st = run_vit(h, f.images, f.layout, f0, f1 - f0, n, h->vit_streams[part]);
         HIP_KEEP(h, st, hipEventRecord(h->vit_done[part], h->vit_streams[part]));
         HIP_KEEP(h, st, hipStreamWaitEvent(s, h->vit_done[part], 0));
     }
@@ -1541,6 +1565,7 @@ fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out
     h->last_n = n_head;
     if (h->tap) { h->feat_T = T_head; h->feat_n = n_head; }
     if (h->map_tap) { h->map_S = h->map.S * views; h->map_n = n_head; h->map_views = h->n_views; }
+    if (h->attn_tap) { h->attn_n = f.n; h->attn_views = h->n_views; }
     return FAV_OK;
 }
 
@@ -2331,6 +2356,140 @@ fav_status fav_classify_cam(fav_handle* h, const void* images, int32_t n, int32_
     return cam_on_stream(h, "fav_classify_cam", labels, 1, cam, rec, (hipStream_t)stream);
 }
 
+// ---- attention rollout (fav_rollout.hpp) ---------------------------------------
+namespace {
+// The head: one launch, a block a frame.  The arguments have been checked (rollout_dims_error, the pointers).
+void launch_rollout(const float* a, long long layer_stride, int L, int n, int gh, int gw, int ld, int first_layer, float* map,
+                    fav_rollout_record* rec, hipStream_t s) {
+    RolloutParams p;
+    p.a = a; p.map = map; p.rec = (int32_t*)rec; p.layer_stride = layer_stride;
+    p.L = L; p.T = gh * gw + 1; p.gw = gw; p.ld = ld; p.first_layer = first_layer;
+    hipLaunchKernelGGL(attn_rollout_kernel, dim3((unsigned)n), dim3(ROLL_THREADS), 0, s, p);
+}
+// the patch grid of a ViT handle
+void vit_grid(const fav_handle* h, int* gh, int* gw) {
+    const VitDef& V = kVit[h->cfg.arch - 2];
+    *gh = h->cfg.in_h / V.patch; *gw = h->cfg.in_w / V.patch;
+}
+// What fav_rollout and fav_classify_rollout refuse alike about the handle's state, before anything is enqueued (FAV_OK: nothing)
+fav_status rollout_gate(fav_handle* h, const char* fn, int first_layer, const void* map, const void* rec) {
+    if (!h->attn_tap) { h->err = fmt("%s: the attention tap is off (fav_set_attn_tap)", fn); return FAV_ERR_INVALID_ARG; }
+    if (h->n_views > 0) {
+        h->err = fmt("%s: views are set; a view's rollout lies in that view's frame and averaging them mis-registers (fav_get_attention still works)", fn);
+        return FAV_ERR_UNSUPPORTED;
+    }
+    if (!map || !rec || ((uintptr_t)map & 3) || ((uintptr_t)rec & 7)) { h->err = fmt("%s: %s", fn, kBadRecords); return FAV_ERR_INVALID_ARG; }
+    int gh, gw;
+    vit_grid(h, &gh, &gw);
+    const std::string why = rollout_dims_error(h->attn.L, 1, gh, gw, h->attn.ld, first_layer);
+    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
+    return FAV_OK;
+}
+// the head on the attention of the last call, behind whatever used the handle's buffers last
+fav_status rollout_on_stream(fav_handle* h, int first_layer, float* map, fav_rollout_record* rec, hipStream_t s) {
+    int gh, gw;
+    vit_grid(h, &gh, &gw);
+    launch_rollout(h->attn_buf, (long long)h->attn_n * h->attn.T * h->attn.ld, h->attn.L, h->attn_n, gh, gw, h->attn.ld, first_layer, map, rec, s);
+    route_clear();            // the report speaks of fav_op_* launches only
+    mark_last_use(h, s);
+    HIP_TRY(h, hipGetLastError());
+    return FAV_OK;
+}
+}  // namespace
+
+fav_status fav_attn_tap_info(const fav_config* cfg, size_t* bytes, int32_t* layers, int32_t* tokens, int32_t* ld, char* err, size_t err_cap) {
+    auto reply = [&](fav_status st, const std::string& why) {
+        if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
+        return st;
+    };
+    if (!cfg || cfg->struct_size != sizeof(fav_config)) return reply(FAV_ERR_INVALID_ARG, "fav_attn_tap_info: null config or struct_size mismatch");
+    if (cfg->arch < 0 || cfg->arch > 3) return reply(FAV_ERR_UNSUPPORTED, "fav_attn_tap_info: unknown arch");
+    if (const char* why = attn_tap_unsupported(cfg->arch, cfg->n_members, cfg->math_mode)) return reply(FAV_ERR_UNSUPPORTED, fmt("fav_attn_tap_info: %s", why));
+    if (cfg->max_batch < 1 || cfg->in_h < 8 || cfg->in_w < 8 || cfg->num_classes < 1)
+        return reply(FAV_ERR_INVALID_ARG, "fav_attn_tap_info: config value out of range");
+    Plan P;
+    std::string why;
+    if (fav_status st = plan_vit(*cfg, &P, &why)) return reply(st, fmt("fav_attn_tap_info: %s", why.c_str()));
+    const AttnTapDims d = attn_tap_dims(kVit[cfg->arch - 2].depth, P.ntok, cfg->max_batch);
+    if (bytes) *bytes = d.bytes;
+    if (layers) *layers = d.L;
+    if (tokens) *tokens = d.T;
+    if (ld) *ld = d.ld;
+    return reply(FAV_OK, "");
+}
+
+fav_status fav_set_attn_tap(fav_handle* h, int32_t enable, size_t max_bytes) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!enable) {
+        if (!h->attn_tap) return FAV_OK;
+        h->attn_tap = false;
+        h->attn_n = h->attn_views = 0;
+        HIP_TRY(h, hipSetDevice(h->cfg.device));
+        if (fav_status st = wait_enqueued(h)) return st;
+        void* buf = h->attn_buf;
+        h->attn_buf = nullptr;
+        if (buf) HIP_TRY(h, hipFree(buf));
+        return FAV_OK;
+    }
+    if (const char* why = attn_tap_unsupported(h->cfg.arch, h->n_members, h->cfg.math_mode)) { h->err = fmt("fav_set_attn_tap: %s", why); return FAV_ERR_UNSUPPORTED; }
+    const AttnTapDims d = attn_tap_dims(kVit[h->cfg.arch - 2].depth, h->plan.ntok, h->cfg.max_batch);
+    const std::string why = attn_tap_budget_error(d.bytes, max_bytes);
+    if (!why.empty()) { h->err = fmt("fav_set_attn_tap: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (h->attn_tap) return FAV_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    void* buf = nullptr;
+    HIP_TRY(h, hipMalloc(&buf, d.bytes + 256));
+    h->attn_buf = (float*)buf;
+    h->attn = d;
+    h->attn_n = h->attn_views = 0;
+    h->attn_tap = true;
+    return FAV_OK;
+}
+
+fav_status fav_get_attention(fav_handle* h, float* out, int32_t* l_out, int32_t* n_out, int32_t* t_out, int32_t* ld_out, void* stream) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!h->attn_tap) { h->err = "fav_get_attention: the attention tap is off (fav_set_attn_tap)"; return FAV_ERR_INVALID_ARG; }
+    if (h->attn_n == 0) { h->err = "fav_get_attention: no classify call since the tap was turned on"; return FAV_ERR_INVALID_ARG; }
+    if (l_out) *l_out = h->attn.L;
+    if (n_out) *n_out = h->attn_n;
+    if (t_out) *t_out = h->attn.T;
+    if (ld_out) *ld_out = h->attn.ld;
+    if (out) {
+        hipStream_t s = (hipStream_t)stream;
+        HIP_TRY(h, hipSetDevice(h->cfg.device));
+        if (fav_status st = wait_last_use(h, s)) return st;
+        const size_t bytes = (size_t)h->attn.L * h->attn_n * h->attn.T * h->attn.ld * 4;
+        HIP_TRY(h, hipMemcpyAsync(out, h->attn_buf, bytes, hipMemcpyDeviceToDevice, s));
+        mark_last_use(h, s);
+    }
+    return FAV_OK;
+}
+
+fav_status fav_rollout(fav_handle* h, int32_t first_layer, float* map, fav_rollout_record* rec, void* stream) {
+    static_assert(sizeof(fav_rollout_record) == 32, "fav_rollout_record is 8 dwords");
+    static_assert(offsetof(fav_rollout_record, peak) == offsetof(fav_cam_record, peak) && offsetof(fav_rollout_record, floor) == offsetof(fav_cam_record, floor),
+                  "fav_op_cam_heatmap reads peak and floor of either record");
+    route_clear();
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (fav_status st = rollout_gate(h, "fav_rollout", first_layer, map, rec)) return st;
+    if (h->attn_n == 0) { h->err = "fav_rollout: no classify call since the tap was turned on"; return FAV_ERR_INVALID_ARG; }
+    if (h->attn_views > 0) { h->err = "fav_rollout: the last call ran under views; their rollouts lie in each view's own frame"; return FAV_ERR_UNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_last_use(h, s)) return st;
+    return rollout_on_stream(h, first_layer, map, rec, s);
+}
+
+fav_status fav_classify_rollout(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
+                                float* conf, uint8_t* fail, float* score, int32_t first_layer, float* map, fav_rollout_record* rec,
+                                void* stream) {
+    route_clear();
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (fav_status st = rollout_gate(h, "fav_classify_rollout", first_layer, map, rec)) return st;
+    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
+    return rollout_on_stream(h, first_layer, map, rec, (hipStream_t)stream);
+}
+
 fav_status fav_set_profiling(fav_handle* h, int32_t enable) {
     if (!h) return FAV_ERR_INVALID_ARG;
     h->profiling = enable != 0;
@@ -2833,6 +2992,30 @@ fav_status fav_op_cam_heatmap(const float* cam, const fav_cam_record* rec, int32
     if ((uintptr_t)cam & 3) return op_rejected(fn, "cam_dev must be 4-byte aligned");
     if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
     launch_cam_heatmap(cam, rec, m, Hf, Wf, H, W, out, (hipStream_t)stream);
+    return op_done(nullptr);
+}
+
+fav_status fav_op_attn_mean(const void* qkv, float* a, int32_t n, int32_t T, int32_t D, int32_t heads, void* stream) {
+    const char* fn = "fav_op_attn_mean";
+    route_clear();
+    if (!qkv || !a) return op_rejected(fn, "null pointer");
+    const std::string why = attn_mean_dims_error(n, T, D, heads);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    if (((uintptr_t)qkv | (uintptr_t)a) & 15) return op_rejected(fn, "qkv_bf16 and a_dev must be 16-byte aligned");
+    launch_attn_mean(qkv, a, n, T, D, heads, (hipStream_t)stream);
+    return op_done(nullptr);
+}
+
+fav_status fav_op_attn_rollout(const float* a, int32_t L, int32_t n, int32_t gh, int32_t gw, int32_t ld, int32_t first_layer, float* map,
+                               fav_rollout_record* rec, void* stream) {
+    const char* fn = "fav_op_attn_rollout";
+    route_clear();
+    if (!a || !map || !rec) return op_rejected(fn, "null pointer");
+    const std::string why = rollout_dims_error(L, n, gh, gw, ld, first_layer);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    if (((uintptr_t)a | (uintptr_t)map) & 3) return op_rejected(fn, "a_dev and map_dev must be 4-byte aligned");
+    if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
+    launch_rollout(a, (long long)n * (gh * gw + 1) * ld, L, n, gh, gw, ld, first_layer, map, rec, (hipStream_t)stream);
     return op_done(nullptr);
 }
 

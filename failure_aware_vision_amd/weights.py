@@ -132,11 +132,13 @@ def _conv64(x, w, stride, pad):
 
 
 def make_synthetic_vit(arch="vit_b16", seed: int = 1, num_classes: int = 1000, in_hw=None,
-                       mean=DEFAULT_MEAN, std=DEFAULT_STD, logit_std: float = 5.0):
+                       mean=DEFAULT_MEAN, std=DEFAULT_STD, logit_std: float = 5.0, qk_gain: float = 1.0):
     """Seeded synthetic ViT checkpoint (pre-norm encoder, class token, learned positions,
     GELU MLP).  LayerNorm keeps activations in range, so no calibration pass is needed:
     linear layers are N(0, 1/fan_in) (x0.5 where they feed the residual stream) and the head is
-    scaled for logits of standard deviation `logit_std`.  Returns (blob, info)."""
+    scaled for logits of standard deviation `logit_std`.  `qk_gain` scales the query and key rows of every qkv layer (weights
+    and biases): the attention scores grow with its square, so a gain above 1 gives peaked attention where the default's is
+    nearly flat; 1.0 leaves the checkpoint as it always was.  Returns (blob, info)."""
     aid = ARCH_IDS[arch] if isinstance(arch, str) else int(arch)
     cfg = VIT_CFG[aid]
     D, depth, mlp, P = cfg["dim"], cfg["depth"], cfg["mlp"], cfg["patch"]
@@ -147,9 +149,12 @@ def make_synthetic_vit(arch="vit_b16", seed: int = 1, num_classes: int = 1000, i
     rng = np.random.default_rng(seed)
     specs, folded = [], []
 
-    def linear(cout, cin, gain, kh=1, kw=1, stride=1):
+    def linear(cout, cin, gain, kh=1, kw=1, stride=1, lead_rows=0, lead_gain=1.0):
         w = (rng.standard_normal((cout, kh, kw, cin)) * (gain / np.sqrt(kh * kw * cin))).astype(np.float32)
         b = (rng.standard_normal(cout) * 0.02).astype(np.float32)
+        if lead_gain != 1.0:
+            w[:lead_rows] *= np.float32(lead_gain)
+            b[:lead_rows] *= np.float32(lead_gain)
         specs.append(dict(cout=cout, cin=cin, kh=kh, kw=kw, stride=stride, pad=0))
         folded.append((_bf16(w), b))
 
@@ -165,7 +170,7 @@ def make_synthetic_vit(arch="vit_b16", seed: int = 1, num_classes: int = 1000, i
     pos[0] += (0.2 * rng.standard_normal(D)).astype(np.float32)   # class token
     vectors(pos.reshape(-1), np.zeros(ntok * D, np.float32))
     for _ in range(depth):
-        layernorm(); linear(3 * D, D, 1.0); linear(D, D, 0.5)
+        layernorm(); linear(3 * D, D, 1.0, lead_rows=2 * D, lead_gain=qk_gain); linear(D, D, 0.5)
         layernorm(); linear(mlp, D, 1.0); linear(D, mlp, 0.5)
     layernorm()
     linear(num_classes, D, logit_std)

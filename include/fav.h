@@ -530,6 +530,78 @@ fav_status fav_classify_cam(fav_handle* h, const void* images_dev, int32_t n, in
                             int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev, float* cam_dev,
                             fav_cam_record* rec_dev, void* hip_stream);
 
+/* ---- Attention rollout (Abnar & Zuidema 2020): the ViT counterpart of the class activation map.  Average each encoder
+ * layer's attention over its heads, mix in the identity for the residual connection, multiply the layers together; the class
+ * token's row of the product says how much each patch fed the decision.  No backward pass.  What the tests of this library
+ * verify is that algebra and its bits on synthetic checkpoints; whether the maps localise objects is a property of trained
+ * weights.
+ *
+ * The ATTENTION TAP.  The production attention kernel keeps its probabilities in registers and never writes them.  While the
+ * tap is on, every encoder layer of every part of a ViT call launches one more kernel on that part's stream, between the
+ * layer's qkv GEMM and its attention launch; it reads the part's qkv rows and writes the head-mean attention of layer l into
+ * a buffer the handle owns: A[L][n][T][ldT] fp32, n the frame rows of the call (frames x views when views are set, in the
+ * indexing of fav_get_logits), T the tokens, ldT = 16 * ceil(T / 16) so that every row starts 16-byte aligned; columns
+ * u >= T hold +0.  A part writes at its frame offset.
+ * For frame i, layer l, head h < heads, query t and key u, with q_h, k_h the 64 bf16 columns of the head in qkv:
+ *   1. s_h[t][u]  the production score accumulator: v_mfma_f32_16x16x32_bf16 chained from +0 over the two 32-channel steps,
+ *                 K rows the A operand, the query's fragment B (oracle/fav_oracle.py: gemm_acc(q_h, k_h, "mfma"))
+ *   2. p_h[t][.]  the production softmax in front of its rounding to bf16 (oracle: attn_softmax_exact): the row max of the raw
+ *                 scores; e = 2^fma(s, log2(e) / 8, -(max * log2(e) / 8)) by the kernels' own exponential; the row sum from eight partial sums
+ *                 (lane group (u >> 2) & 3, parity u & 1, each in ascending key order) combined as
+ *                 ((s00 + s01) + (s10 + s11)) + ((s20 + s21) + (s30 + s31)); ONE 1.0f / sum, then a multiplication per
+ *                 element.  Keys >= T are masked as production masks them (-inf for the max, 0 for the sum)
+ *   3. A[t][u]    +0, plus p_h[t][u] for h = 0 .. heads-1 in that order, times (float)(1.0 / heads); every operation rounded
+ *                 on its own
+ * Non-finite qkv values have no rule of their own: the chains carry them.  Padded columns are +0 whenever the row is finite.
+ * The setter allocates L * max_batch * T * ldT * 4 bytes and may synchronise; fav_classify* never allocates or synchronises
+ * for the tap.  It refuses (FAV_ERR_INVALID_ARG, the message carries both numbers) a buffer above max_bytes (0: 2 GiB), and
+ * (FAV_ERR_UNSUPPORTED) a ResNet arch, a deep-ensemble handle and a handle in FAV_MATH_F32_EXACT (the tap restates the
+ * production score product only).  Turning the tap off is never refused; it waits for the work enqueued on the handle and
+ * frees the buffer.  The tap's launches are booked in no kernel class (fav_get_profile does not see them).  The tap changes
+ * no result, and it is independent of the feature tap and of the map tap.  With the tap off a fav_classify* call enqueues
+ * exactly what it did before. */
+fav_status fav_set_attn_tap(fav_handle* h, int32_t enable, size_t max_bytes);
+/* The head-mean attention of the last fav_classify* call made with the tap on, copied as it is - fp32 [L][n][T][ld] - to
+ * out_dev (may be NULL: only the sizes; every size pointer may be NULL), on hip_stream.  FAV_ERR_INVALID_ARG with the tap off
+ * and before the first call made with it on.  Works under views (n = frames x views). */
+fav_status fav_get_attention(fav_handle* h, float* out_dev, int32_t* l_out, int32_t* n_out, int32_t* t_out, int32_t* ld_out,
+                             void* hip_stream);
+/* Host only, no device: what fav_set_attn_tap would allocate for this configuration, from the planner - *bytes, *layers,
+ * *tokens, *ld (each may be NULL).  FAV_ERR_UNSUPPORTED for a ResNet arch, for n_members > 1 and for FAV_MATH_F32_EXACT,
+ * FAV_ERR_INVALID_ARG for a configuration the planner refuses; err (may be NULL) receives the message. */
+fav_status fav_attn_tap_info(const fav_config* cfg, size_t* bytes, int32_t* layers, int32_t* tokens, int32_t* ld, char* err,
+                             size_t err_cap);
+
+/* One frame's rollout summary, 32 bytes, 8-byte aligned.  peak (byte 8) and floor (byte 16) stand where fav_cam_record has
+ * them, so fav_op_cam_heatmap accepts an array of these records unchanged: that is how the overlay is made.
+ * For frame i with T = gh * gw + 1 tokens and A_l = A[l][i], everything fp32, every product and every sum rounded on its own
+ * (no FMA contraction, no re-association); a thread owns a column u, and the partition does not depend on the grid:
+ *   1. A~_l[t][u] = 0.5f * A_l[t][u] + (t == u ? 0.5f : +0.0f).  The rows of A sum to 1 within rounding, so the rollout does
+ *      not renormalise
+ *   2. r[u] = A~_{L-1}[0][u]
+ *   3. for l = L-2 down to first_layer: r'[u] = +0, then for t = 0 .. T-1 in that order r'[u] = r'[u] + r[t] * A~_l[t][u];
+ *      r = r'.  first_layer = L-1 gives the raw last-layer class-token attention
+ *   4. map M[p] = r[1 + p];  cls_mass = r[0];  patch_sum = +0 plus M[p] in index order;  n_layers = L - first_layer
+ *   5. peak, peak_cell, floor as step 4 of fav_cam_record: strict scans in index order from -inf / +inf; a NaN never wins
+ *   6. thr = floor + 0.5f * (peak - floor); n_above = the number of cells with M[p] >= thr, counted only when peak > floor
+ *      (else 0); box as fav_cam_record over the gh x gw grid (x = p % gw, y = p / gw), -1 when n_above == 0.  (The 20 % rule
+ *      of CAM would take in nearly every cell of an all-positive map, hence the midpoint.) */
+typedef struct fav_rollout_record { int32_t n_layers; float cls_mass, peak; int32_t peak_cell; float floor, patch_sum;
+                                    int32_t n_above, box; } fav_rollout_record;
+/* The head on the attention of the LAST fav_classify* call made with the tap on: map_dev fp32 [n][gh*gw] (4-byte aligned),
+ * rec_dev [n] (8-byte aligned), n the frames of that call, 0 <= first_layer < L.  One small launch on hip_stream, no second
+ * forward pass, no allocation, no synchronisation.  FAV_ERR_INVALID_ARG with the tap off, before the first tapped call, for a
+ * NULL or misaligned buffer and for first_layer out of range.  FAV_ERR_UNSUPPORTED while views are set or when the last call
+ * ran under views: a mirrored or turned view's rollout lies in that view's frame, and averaging them mis-registers
+ * (fav_get_attention still works there). */
+fav_status fav_rollout(fav_handle* h, int32_t first_layer, float* map_dev, fav_rollout_record* rec_dev, void* hip_stream);
+/* fav_classify_ex unchanged, then the head on this very call's attention.  Needs the attention tap on (FAV_ERR_INVALID_ARG
+ * otherwise); FAV_ERR_UNSUPPORTED while views are set.  Never allocates or synchronises.  fail_dev / score_dev may be NULL.
+ * The head's launch is booked in no kernel class. */
+fav_status fav_classify_rollout(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
+                                int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev, int32_t first_layer,
+                                float* map_dev, fav_rollout_record* rec_dev, void* hip_stream);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -885,6 +957,19 @@ fav_status fav_op_cam(const void* maps_bf16, int32_t S, int32_t n, int32_t Hf, i
  * Ranges: m >= 1; 1 <= Hf*Wf <= 1024; 1 <= H*W <= 2^31 - 1.  Refusals as fav_op_cam. */
 fav_status fav_op_cam_heatmap(const float* cam_dev, const fav_cam_record* rec_dev, int32_t m, int32_t Hf, int32_t Wf,
                               int32_t H, int32_t W, uint8_t* out_u8, void* hip_stream);
+
+/* ---- The attention tap's launch on caller buffers (the contract stands beside fav_set_attn_tap): qkv_bf16 [n][T][3 D] bf16
+ * (Q | K | V, head h = columns 64 h .. 64 h + 63 of each), a_dev fp32 [n][T][ldT] with ldT = 16 * ceil(T / 16), both 16-byte
+ * aligned.  One launch, no workspace, no allocation, no synchronisation; vector stores only.  Ranges: n >= 1; 2 <= T <= 256;
+ * 1 <= heads <= 64; D == 64 * heads.  A refused call (FAV_ERR_INVALID_ARG) launches nothing and leaves a message that names
+ * the function in fav_last_error(NULL). */
+fav_status fav_op_attn_mean(const void* qkv_bf16, float* a_dev, int32_t n, int32_t T, int32_t D, int32_t heads, void* hip_stream);
+/* The rollout head defined beside fav_rollout_record, on device arrays: a_dev fp32 [L][n][T][ld] with T = gh * gw + 1, map_dev
+ * fp32 [n][gh*gw] (both 4-byte aligned), rec_dev [n] (8-byte aligned).  One launch, one block a frame, no workspace, no
+ * allocation, no synchronisation.  Ranges: 1 <= L <= 64; 0 <= first_layer < L; n >= 1; 1 <= gh, gw <= 255 with
+ * gh * gw + 1 <= 256; ld >= T, a multiple of 4.  Refusals as fav_op_attn_mean. */
+fav_status fav_op_attn_rollout(const float* a_dev, int32_t L, int32_t n, int32_t gh, int32_t gw, int32_t ld, int32_t first_layer,
+                               float* map_dev, fav_rollout_record* rec_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
