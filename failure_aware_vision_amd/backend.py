@@ -78,7 +78,8 @@ class Backend:
         cfg.tau = float(tau)
         cfg.math_mode = _MATH[math_mode]
         cfg.chunk_a, cfg.chunk_b, cfg.regroup_block = int(chunk_a), int(chunk_b), int(regroup_block)
-        # schedule choices (fav_config, ABI 2): 0 = the build's measured default; results never depend on them
+        # schedule choices (fav_config, ABI 2): 0 = the build's measured default; results never depend on them, nor on the
+        # chunks and the regroup point above (tests/test_gpu_schedule_sweep.py sweeps them all on the device, bit for bit)
         cfg.tail_min_rows, cfg.ens_grouped_max = int(tail_min_rows), int(ens_grouped_max)
         cfg.vit_streams, cfg.stem_fused = int(vit_streams), int(stem_fused)
         members = list(blob) if isinstance(blob, (list, tuple)) else None   # deep ensemble: one blob per member
