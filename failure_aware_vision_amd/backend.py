@@ -518,13 +518,7 @@ class Backend:
     def map_tap_info(self) -> dict:
         """What the map tap of this configuration holds, from the planner alone (fav_map_tap_info; no device work):
         ``bytes`` of the buffer, ``samples`` a frame has in it (without views), and the map's ``hf``, ``wf``, ``c``."""
-        nbytes, s, hf, wf, c = C.c_size_t(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
-        err = C.create_string_buffer(256)
-        st = self.lib.fav_map_tap_info(C.byref(self.cfg), C.byref(nbytes), C.byref(s), C.byref(hf), C.byref(wf), C.byref(c), err,
-                                       len(err))
-        if st != _lib.FAV_OK:
-            raise _lib.FavError(st, err.value.decode("utf-8", "replace"))
-        return dict(bytes=nbytes.value, samples=s.value, hf=hf.value, wf=wf.value, c=c.value)
+        return self._tap_info(self.lib.fav_map_tap_info, ("samples", "hf", "wf", "c"))
 
     def _map_sizes(self) -> tuple:
         """(S, n, Hf, Wf, C) of the maps the last tapped call left."""
@@ -584,25 +578,9 @@ class Backend:
         torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out, synchronous.
         Needs the map tap; refused while views are set."""
         from .cam import CAM_RECORD_DWORDS, unpack_cam_records
-        torch = self._torch
-        img, host, n, layout, stream = self._classify_args(images)
-        hf, wf = self._map_hw or (1, 1)                # never tapped: fav_classify_cam refuses before it writes anything
-        labels, conf, fail, score = self._detect_buffers(n, img.device)
-        cam = torch.empty((n, hf, wf), dtype=torch.float32, device=img.device)
-        rec = torch.empty((n, CAM_RECORD_DWORDS), dtype=torch.int32, device=img.device)
-        _lib.check(self.lib.fav_classify_cam(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
-                                             conf.data_ptr(), fail.data_ptr(), score.data_ptr(), cam.data_ptr(), rec.data_ptr(),
-                                             stream), self._h)
-        out = dict(label=labels, conf=conf, fail=fail, score=score, map=cam)
-        if heatmap:
-            H, W = int(self.cfg.in_h), int(self.cfg.in_w)
-            heat = torch.empty((n, H, W), dtype=torch.uint8, device=img.device)
-            _lib.check(self.lib.fav_op_cam_heatmap(cam.data_ptr(), rec.data_ptr(), n, hf, wf, H, W, heat.data_ptr(), stream))
-            out["heatmap"] = heat
-        if host:
-            out = {k: v.cpu().numpy() for k, v in out.items()}
-            rec = rec.cpu().numpy()
-        return dict(unpack_cam_records(rec), **out)
+        # never tapped: fav_classify_cam refuses before it writes anything
+        return self._classify_map_head(self.lib.fav_classify_cam, (), self._map_hw or (1, 1), CAM_RECORD_DWORDS, unpack_cam_records,
+                                       images, heatmap, first_index)
 
     # -- attention rollout (rollout.py; include/fav.h fav_set_attn_tap, fav_rollout) --------------------------------------------
     def set_attn_tap(self, enable: bool, budget_bytes: int = 2 << 30):
@@ -620,12 +598,7 @@ class Backend:
     def attn_tap_info(self) -> dict:
         """What the attention tap of this configuration holds, from the planner alone (fav_attn_tap_info; no device work):
         ``bytes`` of the buffer, its ``layers``, the ``tokens`` of a frame and the row pitch ``ld`` (tokens rounded up to 16)."""
-        nbytes, layers, tokens, ld = C.c_size_t(), C.c_int32(), C.c_int32(), C.c_int32()
-        err = C.create_string_buffer(256)
-        st = self.lib.fav_attn_tap_info(C.byref(self.cfg), C.byref(nbytes), C.byref(layers), C.byref(tokens), C.byref(ld), err, len(err))
-        if st != _lib.FAV_OK:
-            raise _lib.FavError(st, err.value.decode("utf-8", "replace"))
-        return dict(bytes=nbytes.value, layers=layers.value, tokens=tokens.value, ld=ld.value)
+        return self._tap_info(self.lib.fav_attn_tap_info, ("layers", "tokens", "ld"))
 
     def attention(self):
         """fp32 [L, n, T, T] head-mean attention of the last classify call made with the attention tap on (torch CUDA tensor,
@@ -670,25 +643,43 @@ class Backend:
         CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out, synchronous.  Needs the attention tap;
         refused while views are set."""
         from .rollout import ROLLOUT_RECORD_DWORDS, unpack_rollout_records
+        # never tapped: fav_classify_rollout refuses before it writes anything
+        return self._classify_map_head(self.lib.fav_classify_rollout, (int(first_layer),), self._attn_grid or (1, 1),
+                                       ROLLOUT_RECORD_DWORDS, unpack_rollout_records, images, heatmap, first_index)
+
+    # what the two localisation taps (the map tap with its CAM head, the attention tap with its rollout head) share
+    def _tap_info(self, fn, names) -> dict:
+        """fav_map_tap_info / fav_attn_tap_info (``fn``) -> ``bytes`` of the buffer and the int32 sizes under ``names``."""
+        nbytes, sizes = C.c_size_t(), [C.c_int32() for _ in names]
+        err = C.create_string_buffer(256)
+        st = fn(C.byref(self.cfg), C.byref(nbytes), *(C.byref(x) for x in sizes), err, len(err))
+        if st != _lib.FAV_OK:
+            raise _lib.FavError(st, err.value.decode("utf-8", "replace"))
+        return dict(bytes=nbytes.value, **{name: x.value for name, x in zip(names, sizes)})
+
+    def _classify_map_head(self, fn, head_args: tuple, map_hw: tuple, record_dwords: int, unpack, images, heatmap: bool,
+                           first_index: int) -> dict:
+        """fav_classify_cam / fav_classify_rollout (``fn``; ``head_args``: the head's own integers, in front of its outputs) ->
+        ``unpack`` of the head's int32[n, record_dwords] records plus ``label``, ``conf``, ``fail``, ``score``, ``map`` fp32
+        [n, *map_hw] and, with ``heatmap``, the overlay fav_op_cam_heatmap draws from either record; numpy frames in -> numpy
+        out.  The counterpart of ``_classify_feature_head``."""
         torch = self._torch
         img, host, n, layout, stream = self._classify_args(images)
-        gh, gw = self._attn_grid or (1, 1)             # never tapped: fav_classify_rollout refuses before it writes anything
         labels, conf, fail, score = self._detect_buffers(n, img.device)
-        m = torch.empty((n, gh, gw), dtype=torch.float32, device=img.device)
-        rec = torch.empty((n, ROLLOUT_RECORD_DWORDS), dtype=torch.int32, device=img.device)
-        _lib.check(self.lib.fav_classify_rollout(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(),
-                                                 conf.data_ptr(), fail.data_ptr(), score.data_ptr(), int(first_layer), m.data_ptr(),
-                                                 rec.data_ptr(), stream), self._h)
+        m = torch.empty((n, *map_hw), dtype=torch.float32, device=img.device)
+        rec = torch.empty((n, record_dwords), dtype=torch.int32, device=img.device)
+        _lib.check(fn(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(), conf.data_ptr(), fail.data_ptr(),
+                      score.data_ptr(), *head_args, m.data_ptr(), rec.data_ptr(), stream), self._h)
         out = dict(label=labels, conf=conf, fail=fail, score=score, map=m)
         if heatmap:
             H, W = int(self.cfg.in_h), int(self.cfg.in_w)
             heat = torch.empty((n, H, W), dtype=torch.uint8, device=img.device)
-            _lib.check(self.lib.fav_op_cam_heatmap(m.data_ptr(), rec.data_ptr(), n, gh, gw, H, W, heat.data_ptr(), stream))
+            _lib.check(self.lib.fav_op_cam_heatmap(m.data_ptr(), rec.data_ptr(), n, *map_hw, H, W, heat.data_ptr(), stream))
             out["heatmap"] = heat
         if host:
             out = {k: v.cpu().numpy() for k, v in out.items()}
             rec = rec.cpu().numpy()
-        return dict(unpack_rollout_records(rec), **out)
+        return dict(unpack(rec), **out)
 
     # what the two feature heads (the Mahalanobis model, the k-NN bank) share
     @staticmethod

@@ -15,13 +15,11 @@ CAM_RECORD_DWORDS = 8
 CAM_MAX_CLASSES = 8
 
 
-def unpack_cam_records(records) -> dict:
-    """int32[..., 8] fav_cam_record records (torch tensor or numpy) -> ``class_id`` int32, ``logit_mean``, ``peak`` fp32,
-    ``peak_cell`` int32, ``floor``, ``pos_sum`` fp32, ``n_above`` int32, ``box`` int32 (packed; -1: none), each [...] and a view
-    of the record buffer, plus the box unpacked to ``x0``, ``y0``, ``x1``, ``y1`` (int32, inclusive map cells; all -1 when the
-    box is -1)."""
-    if records.ndim < 1 or int(records.shape[-1]) != CAM_RECORD_DWORDS:
-        raise ValueError(f"expected int32[..., {CAM_RECORD_DWORDS}] records, got shape {tuple(records.shape)}")
+def _unpack_map_records(records, names) -> dict:
+    """The layout fav_cam_record and fav_rollout_record share, under the eight field ``names`` of one of them: dwords 1, 2, 4
+    and 5 are fp32, the others int32, the last the packed box (-1: none), which also comes unpacked to ``x0`` .. ``y1``."""
+    if records.ndim < 1 or int(records.shape[-1]) != len(names):
+        raise ValueError(f"expected int32[..., {len(names)}] records, got shape {tuple(records.shape)}")
     if isinstance(records, np.ndarray):
         f32 = np.float32
         where = np.where
@@ -29,14 +27,20 @@ def unpack_cam_records(records) -> dict:
         import torch
         f32 = torch.float32
         where = torch.where
-    box = records[..., 7]
+    out = {name: records[..., j].view(f32) if j in (1, 2, 4, 5) else records[..., j] for j, name in enumerate(names)}
+    box = out[names[7]]
     none = box == -1
-    out = {"class_id": records[..., 0], "logit_mean": records[..., 1].view(f32), "peak": records[..., 2].view(f32),
-           "peak_cell": records[..., 3], "floor": records[..., 4].view(f32), "pos_sum": records[..., 5].view(f32),
-           "n_above": records[..., 6], "box": box}
     for name, shift in (("x0", 0), ("y0", 8), ("x1", 16), ("y1", 24)):
         out[name] = where(none, box, (box >> shift) & 0xFF)
     return out
+
+
+def unpack_cam_records(records) -> dict:
+    """int32[..., 8] fav_cam_record records (torch tensor or numpy) -> ``class_id`` int32, ``logit_mean``, ``peak`` fp32,
+    ``peak_cell`` int32, ``floor``, ``pos_sum`` fp32, ``n_above`` int32, ``box`` int32 (packed; -1: none), each [...] and a view
+    of the record buffer, plus the box unpacked to ``x0``, ``y0``, ``x1``, ``y1`` (int32, inclusive map cells; all -1 when the
+    box is -1)."""
+    return _unpack_map_records(records, ("class_id", "logit_mean", "peak", "peak_cell", "floor", "pos_sum", "n_above", "box"))
 
 
 def box_to_pixels(box, in_hw, map_hw):

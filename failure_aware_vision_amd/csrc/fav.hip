@@ -30,6 +30,7 @@
 #include "fav_ood.hpp"
 #include "fav_knn.hpp"
 #include "fav_drift.hpp"
+#include "fav_mapbox.hpp"
 #include "fav_cam.hpp"
 #include "fav_rollout.hpp"
 
@@ -173,22 +174,20 @@ struct fav_handle {
     struct DriftDev { void* ws = nullptr; int D = 0, R = 0, n_perm = 0; uint64_t seed = 0; float alpha = 0.f; };
     DriftDev drift;
     bool drift_on = false;
-    // Map tap (fav_set_map_tap): while on, every pass copies the frames its average pool reads into map_buf, bf16
-    // [map.S][max_batch][Hf * Wf][C] at most (map: fav_cam.hpp map_tap_dims of the plan), indexed [sample][frame] like the
-    // logits; allocated by the setter, freed when the tap goes off.  map_S / map_n: the samples and frames of the last call
-    // that filled it (0: none yet); map_views: the views that call ran under
-    bool map_tap = false;
-    void* map_buf = nullptr;
+    // The two localisation taps, each the caller's own (the feature tap above is derived from its readers), share one record:
+    // on, the buffer (allocated by the setter for max_batch frames, freed when the tap goes off), and what the last call that
+    // filled it left - S x n: its samples and frame rows (n = 0: none yet; S stays 0 where a frame has no samples), views: the
+    // views it ran under.  The steps on it: tap_off .. classify_map_head below.
+    struct LocTap { bool on = false; void* buf = nullptr; int S = 0, n = 0, views = 0; };
+    // Map tap (fav_set_map_tap): while on, every pass copies the frames its average pool reads into map_tap.buf, bf16
+    // [map.S][max_batch][Hf * Wf][C] at most (map: fav_cam.hpp map_tap_dims of the plan), indexed [sample][frame] like the logits
+    LocTap map_tap;
     fav::MapTapDims map;
-    int map_S = 0, map_n = 0, map_views = 0;
     // Attention tap (fav_set_attn_tap; ViT only): while on, every encoder layer of every run_vit part launches attn_mean_kernel
-    // (fav_rollout.hpp) in front of its attention launch; attn_buf holds fp32 [attn.L][n][attn.T][attn.ld] for the n frame rows of
-    // the call (at most max_batch), a part at its frame offset; allocated by the setter, freed when the tap goes off.
-    // attn_n: the frame rows of the last call that filled it (0: none yet); attn_views: the views that call ran under
-    bool attn_tap = false;
-    float* attn_buf = nullptr;
+    // (fav_rollout.hpp) in front of its attention launch; attn_tap.buf holds fp32 [attn.L][n][attn.T][attn.ld] for the n frame
+    // rows of the call (at most max_batch), a part at its frame offset
+    LocTap attn_tap;
     fav::AttnTapDims attn;
-    int attn_n = 0, attn_views = 0;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -1051,10 +1050,10 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
                     if (const char* e = launch_maxpool(h, buf(o.in, o), buf(o.out, o), cn, o.H, o.W, o.C, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 case OP_AVGPOOL:
-                    if (h->map_tap) {
-                        // the map tap: the frames the pool reads, to [virtual frame] of map_buf, in front of the launch
+                    if (h->map_tap.on) {
+                        // the map tap: the frames the pool reads, to [virtual frame] of its buffer, in front of the launch
                         const size_t frame = (size_t)o.H * o.W * o.C * 2;
-                        HIP_TRY(h, hipMemcpyAsync((char*)h->map_buf + (size_t)v0 * frame, buf(o.in, o), (size_t)cn * frame,
+                        HIP_TRY(h, hipMemcpyAsync((char*)h->map_tap.buf + (size_t)v0 * frame, buf(o.in, o), (size_t)cn * frame,
                                                   hipMemcpyDeviceToDevice, s));
                     }
                     if (const char* e = launch_avgpool(h, buf(o.in, o), buf(o.out, o), cn, o.H * o.W, o.C, &dd, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
@@ -1099,8 +1098,7 @@ void free_all(fav_handle* h) {
     for (void* q : {(void*)h->ood.mu, (void*)h->ood.Pt, (void*)h->ood.Mt, (void*)h->ood.cls}) if (q) (void)hipFree(q);
     for (void* q : {h->knn.bank, h->knn.ws, (void*)h->knn.cls}) if (q) (void)hipFree(q);
     if (h->drift.ws) (void)hipFree(h->drift.ws);
-    if (h->map_buf) (void)hipFree(h->map_buf);
-    if (h->attn_buf) (void)hipFree(h->attn_buf);
+    for (void* q : {h->map_tap.buf, h->attn_tap.buf}) if (q) (void)hipFree(q);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
@@ -1166,8 +1164,8 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
         const LayerWeights &ln1 = h->weights[li], &ln2 = h->weights[li + 3];
         FAV_VIT_TRY(launch_layernorm(h, B.v_x, D, (const float*)ln1.w_m[0], ln1.b_m[0], B.v_y, (long long)n * ntok, D, 1e-6f, s));
         FAV_VIT_TRY(gemm(li + 1, B.v_y, ntok, nullptr, 0, B.v_qkv, 0));
-        if (h->attn_tap)   // the attention tap: layer blk of this part's frames, at [blk][f0] of the call's n_call rows
-            launch_attn_mean(B.v_qkv, h->attn_buf + ((size_t)blk * n_call + F) * ntok * h->attn.ld, n, ntok, D, V.heads, s);
+        if (h->attn_tap.on)   // the attention tap: layer blk of this part's frames, at [blk][f0] of the call's n_call rows
+            launch_attn_mean(B.v_qkv, (float*)h->attn_tap.buf + ((size_t)blk * n_call + F) * ntok * h->attn.ld, n, ntok, D, V.heads, s);
         FAV_VIT_TRY(launch_attention(h, B.v_qkv, B.v_y, n, ntok, D, V.heads, c.math_mode, s));
         FAV_VIT_TRY(gemm(li + 2, B.v_y, ntok, B.v_x, 0, B.v_x, 0));                 // x = x + proj(attn), in place tile by tile
         FAV_VIT_TRY(launch_layernorm(h, B.v_x, D, (const float*)ln2.w_m[0], ln2.b_m[0], B.v_y, (long long)n * ntok, D, 1e-6f, s));
@@ -1564,8 +1562,8 @@ fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out
     h->last_T = T_head;
     h->last_n = n_head;
     if (h->tap) { h->feat_T = T_head; h->feat_n = n_head; }
-    if (h->map_tap) { h->map_S = h->map.S * views; h->map_n = n_head; h->map_views = h->n_views; }
-    if (h->attn_tap) { h->attn_n = f.n; h->attn_views = h->n_views; }
+    if (h->map_tap.on) { h->map_tap.S = h->map.S * views; h->map_tap.n = n_head; h->map_tap.views = h->n_views; }
+    if (h->attn_tap.on) { h->attn_tap.n = f.n; h->attn_tap.views = h->n_views; }
     return FAV_OK;
 }
 
@@ -1913,6 +1911,127 @@ fav_status classify_feature_head(fav_handle* h, bool fav_handle::*on, const char
     HIP_TRY(h, hipGetLastError());
     return FAV_OK;
 }
+
+// ---- the steps the two localisation taps and their heads share (fav_handle::LocTap: the map tap with fav_cam and
+//      fav_classify_cam, the attention tap with fav_rollout and fav_classify_rollout).  The nouns of a tap in its refusals:
+struct TapWords { const char *tap, *setter, *getter, *thing; };
+const TapWords kMapWords = {"map", "fav_set_map_tap", "fav_get_maps", "map"};
+const TapWords kAttnWords = {"attention", "fav_set_attn_tap", "fav_get_attention", "rollout"};
+// sizes for the caller: each pointer may be NULL
+using Sizes = std::initializer_list<std::pair<int32_t*, int>>;
+void put_sizes(Sizes sizes) { for (const auto& s : sizes) if (s.first) *s.first = s.second; }
+// A fav_*_tap_info: the config checks, then `fill(&why)` plans the configuration and writes the sizes; the reply goes into err.
+// unsupported: the tap's refusals from the config alone; samples: n_samples counts (the maps are one a sample)
+template <class Fill>
+fav_status tap_info(const char* fn, const fav_config* cfg, const char* (*unsupported)(int, int, int), bool samples, char* err,
+                    size_t err_cap, Fill fill) {
+    auto reply = [&](fav_status st, const char* why) {
+        if (err && err_cap) snprintf(err, err_cap, "%s", st ? fmt("%s: %s", fn, why).c_str() : "");
+        return st;
+    };
+    if (!cfg || cfg->struct_size != sizeof(fav_config)) return reply(FAV_ERR_INVALID_ARG, "null config or struct_size mismatch");
+    if (cfg->arch < 0 || cfg->arch > 3) return reply(FAV_ERR_UNSUPPORTED, "unknown arch");
+    if (const char* why = unsupported(cfg->arch, cfg->n_members, cfg->math_mode)) return reply(FAV_ERR_UNSUPPORTED, why);
+    if (cfg->max_batch < 1 || (samples && (cfg->n_samples < 1 || cfg->n_samples > 4096)) || cfg->in_h < 8 || cfg->in_w < 8 || cfg->num_classes < 1)
+        return reply(FAV_ERR_INVALID_ARG, "config value out of range");
+    std::string why;
+    const fav_status st = fill(&why);
+    return reply(st, why.c_str());
+}
+// The tap goes off: the flag and the last call's counts first, then the wait for what is enqueued, then the buffer
+fav_status tap_off(fav_handle* h, fav_handle::LocTap& t) {
+    if (!t.on) return FAV_OK;
+    t.on = false;
+    t.S = t.n = t.views = 0;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_enqueued(h)) return st;
+    void* buf = t.buf;
+    t.buf = nullptr;
+    if (buf) HIP_TRY(h, hipFree(buf));
+    return FAV_OK;
+}
+// The tap goes on (a tap that is on stays as it is, once the checks have passed).  unsupported: the tap's refusal of this
+// handle, if any; `make_dims()`: what the tap holds (only a supported handle has any), kept in `dims`; what: tap_budget_error's
+template <class Dims, class MakeDims>
+fav_status tap_on(fav_handle* h, const char* fn, fav_handle::LocTap& t, Dims& dims, const char* unsupported, const char* what,
+                  size_t max_bytes, size_t default_budget, MakeDims make_dims) {
+    if (unsupported) { h->err = fmt("%s: %s", fn, unsupported); return FAV_ERR_UNSUPPORTED; }
+    const Dims d = make_dims();
+    const std::string why = tap_budget_error(what, d.bytes, max_bytes, default_budget);
+    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (t.on) return FAV_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipMalloc(&t.buf, d.bytes + 256));
+    dims = d;
+    t.S = t.n = t.views = 0;
+    t.on = true;
+    return FAV_OK;
+}
+// What the last call left in the tap: its sizes, and with `out` the first `bytes` of the buffer, behind the buffer's last use
+fav_status tap_get(fav_handle* h, const char* fn, const TapWords& w, const fav_handle::LocTap& t, Sizes sizes, void* out, size_t bytes,
+                   void* stream) {
+    if (!t.on) { h->err = fmt("%s: the %s tap is off (%s)", fn, w.tap, w.setter); return FAV_ERR_INVALID_ARG; }
+    if (t.n == 0) { h->err = fmt("%s: no classify call since the tap was turned on", fn); return FAV_ERR_INVALID_ARG; }
+    put_sizes(sizes);
+    if (out) {
+        hipStream_t s = (hipStream_t)stream;
+        HIP_TRY(h, hipSetDevice(h->cfg.device));
+        if (fav_status st = wait_last_use(h, s)) return st;
+        HIP_TRY(h, hipMemcpyAsync(out, t.buf, bytes, hipMemcpyDeviceToDevice, s));
+        mark_last_use(h, s);
+    }
+    return FAV_OK;
+}
+// What a head's two entry points refuse alike about the handle's state, before anything is enqueued (FAV_OK: nothing).
+// bad_buffers: an output is null or misaligned; `dims_error()`: the head's own ranges, asked only once the tap is known to be on
+template <class DimsError>
+fav_status map_head_gate(fav_handle* h, const char* fn, const TapWords& w, const fav_handle::LocTap& t, bool bad_buffers, DimsError dims_error) {
+    if (!t.on) { h->err = fmt("%s: the %s tap is off (%s)", fn, w.tap, w.setter); return FAV_ERR_INVALID_ARG; }
+    if (h->n_views > 0) {
+        h->err = fmt("%s: views are set; a view's %s lies in that view's frame and averaging them mis-registers (%s still works)", fn, w.thing, w.getter);
+        return FAV_ERR_UNSUPPORTED;
+    }
+    if (bad_buffers) { h->err = fmt("%s: %s", fn, kBadRecords); return FAV_ERR_INVALID_ARG; }
+    const std::string why = dims_error();
+    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
+    return FAV_OK;
+}
+// the head's `launch(stream)` on what the tap holds (its launcher's refusal, or nullptr), booked as the buffers' last use
+template <class Launch>
+fav_status map_head_on_stream(fav_handle* h, const char* fn, Launch launch, hipStream_t s) {
+    const char* e = launch(s);
+    route_clear();            // the report speaks of fav_op_* launches only
+    mark_last_use(h, s);
+    if (e) { h->err = fmt("%s: %s", fn, e); return FAV_ERR_HIP; }
+    HIP_TRY(h, hipGetLastError());
+    return FAV_OK;
+}
+// fav_cam, fav_rollout: the head on what the LAST call left in the tap, behind whatever used the handle's buffers last
+template <class DimsError, class Launch>
+fav_status map_head_on_last_call(fav_handle* h, const char* fn, const TapWords& w, fav_handle::LocTap fav_handle::*tap, bool bad_buffers,
+                                 DimsError dims_error, void* stream, Launch launch) {
+    route_clear();
+    if (!h) return FAV_ERR_INVALID_ARG;
+    const fav_handle::LocTap& t = h->*tap;
+    if (fav_status st = map_head_gate(h, fn, w, t, bad_buffers, dims_error)) return st;
+    if (t.n == 0) { h->err = fmt("%s: no classify call since the tap was turned on", fn); return FAV_ERR_INVALID_ARG; }
+    if (t.views > 0) { h->err = fmt("%s: the last call ran under views; their %ss lie in each view's own frame", fn, w.thing); return FAV_ERR_UNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_last_use(h, s)) return st;
+    return map_head_on_stream(h, fn, launch, s);
+}
+// fav_classify_cam, fav_classify_rollout: fav_classify_ex, then the head on the same stream
+template <class DimsError, class Launch>
+fav_status classify_map_head(fav_handle* h, const char* fn, const TapWords& w, fav_handle::LocTap fav_handle::*tap, bool bad_buffers,
+                             DimsError dims_error, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
+                             float* conf, uint8_t* fail, float* score, void* stream, Launch launch) {
+    route_clear();
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (fav_status st = map_head_gate(h, fn, w, h->*tap, bad_buffers, dims_error)) return st;
+    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
+    return map_head_on_stream(h, fn, launch, (hipStream_t)stream);
+}
 }  // extern "C++"
 }  // namespace
 
@@ -2236,124 +2355,60 @@ void launch_cam_heatmap(const float* cam, const fav_cam_record* rec, int m, int 
 // the row pitch of the fc's weights: the last layer of the plan, whose rows the head reads
 int fc_pitch(const fav_handle* h) { return h->plan.layers.back().k; }
 
-// What fav_cam and fav_classify_cam refuse alike about the handle's state, before anything is enqueued (FAV_OK: nothing)
-fav_status cam_gate(fav_handle* h, const char* fn, int K, const void* classes, const void* cam, const void* rec) {
-    if (!h->map_tap) { h->err = fmt("%s: the map tap is off (fav_set_map_tap)", fn); return FAV_ERR_INVALID_ARG; }
-    if (h->n_views > 0) {
-        h->err = fmt("%s: views are set; a view's map lies in that view's frame and averaging them mis-registers (fav_get_maps still works)", fn);
-        return FAV_ERR_UNSUPPORTED;
-    }
-    if (!classes || !cam || !rec || ((uintptr_t)classes & 3) || ((uintptr_t)cam & 3) || ((uintptr_t)rec & 7)) {
-        h->err = fmt("%s: %s", fn, kBadRecords);
-        return FAV_ERR_INVALID_ARG;
-    }
-    const std::string why = cam_dims_error(h->map.S, 1, h->map.Hf, h->map.Wf, h->map.C, fc_pitch(h), h->cfg.num_classes, K);
-    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
-    return FAV_OK;
+// the head's own ranges on a handle whose map tap is on, and its launch on the maps the tap holds
+extern "C++" std::string cam_handle_dims_error(const fav_handle* h, int K) {
+    return cam_dims_error(h->map.S, 1, h->map.Hf, h->map.Wf, h->map.C, fc_pitch(h), h->cfg.num_classes, K);
 }
-// the head on the maps of the last call, behind whatever used the handle's buffers last
-fav_status cam_on_stream(fav_handle* h, const char* fn, const int32_t* classes, int K, float* cam, fav_cam_record* rec, hipStream_t s) {
+const char* cam_on_tap(const fav_handle* h, const int32_t* classes, int K, float* cam, fav_cam_record* rec, hipStream_t s) {
     const size_t fc = h->plan.layers.size() - 1;
-    const char* e = launch_cam(h->map_buf, h->map_S, h->map_n, h->map.Hf, h->map.Wf, h->map.C, h->weights[fc].w_m[0], fc_pitch(h),
-                               h->weights[fc].b_m[0], h->cfg.num_classes, classes, K, cam, rec, s);
-    route_clear();            // the report speaks of fav_op_* launches only
-    mark_last_use(h, s);
-    if (e) { h->err = fmt("%s: %s", fn, e); return FAV_ERR_HIP; }
-    HIP_TRY(h, hipGetLastError());
-    return FAV_OK;
+    return launch_cam(h->map_tap.buf, h->map_tap.S, h->map_tap.n, h->map.Hf, h->map.Wf, h->map.C, h->weights[fc].w_m[0], fc_pitch(h),
+                      h->weights[fc].b_m[0], h->cfg.num_classes, classes, K, cam, rec, s);
+}
+bool bad_cam_buffers(const void* classes, const void* cam, const void* rec) {
+    return !classes || !cam || !rec || ((uintptr_t)classes & 3) || ((uintptr_t)cam & 3) || ((uintptr_t)rec & 7);
 }
 }  // namespace
 
 fav_status fav_map_tap_info(const fav_config* cfg, size_t* bytes, int32_t* s_map, int32_t* hf, int32_t* wf, int32_t* c, char* err,
                             size_t err_cap) {
-    auto reply = [&](fav_status st, const std::string& why) {
-        if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
-        return st;
-    };
-    if (!cfg || cfg->struct_size != sizeof(fav_config)) return reply(FAV_ERR_INVALID_ARG, "fav_map_tap_info: null config or struct_size mismatch");
-    if (cfg->arch < 0 || cfg->arch > 3) return reply(FAV_ERR_UNSUPPORTED, "fav_map_tap_info: unknown arch");
-    if (const char* why = map_tap_unsupported(cfg->arch, cfg->n_members)) return reply(FAV_ERR_UNSUPPORTED, fmt("fav_map_tap_info: %s", why));
-    if (cfg->max_batch < 1 || cfg->n_samples < 1 || cfg->n_samples > 4096 || cfg->in_h < 8 || cfg->in_w < 8 || cfg->num_classes < 1)
-        return reply(FAV_ERR_INVALID_ARG, "fav_map_tap_info: config value out of range");
-    Plan P;
-    std::string why;
-    if (fav_status st = plan_resnet(*cfg, 1, false, &P, &why)) return reply(st, fmt("fav_map_tap_info: %s", why.c_str()));
-    const MapTapDims d = map_tap_dims(P, cfg->max_batch);
-    if (bytes) *bytes = d.bytes;
-    if (s_map) *s_map = d.S;
-    if (hf) *hf = d.Hf;
-    if (wf) *wf = d.Wf;
-    if (c) *c = d.C;
-    return reply(FAV_OK, "");
+    return tap_info("fav_map_tap_info", cfg, map_tap_unsupported, true, err, err_cap, [&](std::string* why) -> fav_status {
+        Plan P;
+        if (fav_status st = plan_resnet(*cfg, 1, false, &P, why)) return st;
+        const MapTapDims d = map_tap_dims(P, cfg->max_batch);
+        if (bytes) *bytes = d.bytes;
+        put_sizes({{s_map, d.S}, {hf, d.Hf}, {wf, d.Wf}, {c, d.C}});
+        return FAV_OK;
+    });
 }
 
 fav_status fav_set_map_tap(fav_handle* h, int32_t enable, size_t max_bytes) {
     if (!h) return FAV_ERR_INVALID_ARG;
-    if (!enable) {
-        if (!h->map_tap) return FAV_OK;
-        h->map_tap = false;
-        h->map_S = h->map_n = h->map_views = 0;
-        HIP_TRY(h, hipSetDevice(h->cfg.device));
-        if (fav_status st = wait_enqueued(h)) return st;
-        void* buf = h->map_buf;
-        h->map_buf = nullptr;
-        if (buf) HIP_TRY(h, hipFree(buf));
-        return FAV_OK;
-    }
-    if (const char* why = map_tap_unsupported(h->cfg.arch, h->n_members)) { h->err = fmt("fav_set_map_tap: %s", why); return FAV_ERR_UNSUPPORTED; }
-    const MapTapDims d = map_tap_dims(h->plan, h->cfg.max_batch);
-    const std::string why = map_tap_budget_error(d.bytes, max_bytes);
-    if (!why.empty()) { h->err = fmt("fav_set_map_tap: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
-    if (h->map_tap) return FAV_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipMalloc(&h->map_buf, d.bytes + 256));
-    h->map = d;
-    h->map_S = h->map_n = h->map_views = 0;
-    h->map_tap = true;
-    return FAV_OK;
+    if (!enable) return tap_off(h, h->map_tap);
+    return tap_on(h, "fav_set_map_tap", h->map_tap, h->map, map_tap_unsupported(h->cfg.arch, h->n_members, h->cfg.math_mode),
+                  "maps of max_batch frames take", max_bytes, CAM_DEFAULT_BUDGET, [&] { return map_tap_dims(h->plan, h->cfg.max_batch); });
 }
 
 fav_status fav_get_maps(fav_handle* h, void* out, int32_t* s_out, int32_t* n_out, int32_t* hf_out, int32_t* wf_out, int32_t* c_out,
                         void* stream) {
     if (!h) return FAV_ERR_INVALID_ARG;
-    if (!h->map_tap) { h->err = "fav_get_maps: the map tap is off (fav_set_map_tap)"; return FAV_ERR_INVALID_ARG; }
-    if (h->map_n == 0) { h->err = "fav_get_maps: no classify call since the tap was turned on"; return FAV_ERR_INVALID_ARG; }
-    if (s_out) *s_out = h->map_S;
-    if (n_out) *n_out = h->map_n;
-    if (hf_out) *hf_out = h->map.Hf;
-    if (wf_out) *wf_out = h->map.Wf;
-    if (c_out) *c_out = h->map.C;
-    if (out) {
-        hipStream_t s = (hipStream_t)stream;
-        HIP_TRY(h, hipSetDevice(h->cfg.device));
-        if (fav_status st = wait_last_use(h, s)) return st;
-        const size_t bytes = (size_t)h->map_S * h->map_n * h->map.Hf * h->map.Wf * h->map.C * 2;
-        HIP_TRY(h, hipMemcpyAsync(out, h->map_buf, bytes, hipMemcpyDeviceToDevice, s));
-        mark_last_use(h, s);
-    }
-    return FAV_OK;
+    const fav_handle::LocTap& t = h->map_tap;
+    const MapTapDims& d = h->map;
+    return tap_get(h, "fav_get_maps", kMapWords, t, {{s_out, t.S}, {n_out, t.n}, {hf_out, d.Hf}, {wf_out, d.Wf}, {c_out, d.C}}, out,
+                   (size_t)t.S * t.n * d.Hf * d.Wf * d.C * 2, stream);
 }
 
 fav_status fav_cam(fav_handle* h, const int32_t* classes, int32_t K, float* cam, fav_cam_record* rec, void* stream) {
     static_assert(sizeof(fav_cam_record) == 32, "fav_cam_record is 8 dwords");
-    route_clear();
-    if (!h) return FAV_ERR_INVALID_ARG;
-    if (fav_status st = cam_gate(h, "fav_cam", K, classes, cam, rec)) return st;
-    if (h->map_n == 0) { h->err = "fav_cam: no classify call since the tap was turned on"; return FAV_ERR_INVALID_ARG; }
-    if (h->map_views > 0) { h->err = "fav_cam: the last call ran under views; their maps lie in each view's own frame"; return FAV_ERR_UNSUPPORTED; }
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (fav_status st = wait_last_use(h, s)) return st;
-    return cam_on_stream(h, "fav_cam", classes, K, cam, rec, s);
+    return map_head_on_last_call(h, "fav_cam", kMapWords, &fav_handle::map_tap, bad_cam_buffers(classes, cam, rec),
+                                 [&] { return cam_handle_dims_error(h, K); }, stream,
+                                 [&](hipStream_t s) { return cam_on_tap(h, classes, K, cam, rec, s); });
 }
 
 fav_status fav_classify_cam(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
                             float* conf, uint8_t* fail, float* score, float* cam, fav_cam_record* rec, void* stream) {
-    route_clear();
-    if (!h) return FAV_ERR_INVALID_ARG;
-    if (fav_status st = cam_gate(h, "fav_classify_cam", 1, labels, cam, rec)) return st;
-    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
-    return cam_on_stream(h, "fav_classify_cam", labels, 1, cam, rec, (hipStream_t)stream);
+    return classify_map_head(h, "fav_classify_cam", kMapWords, &fav_handle::map_tap, bad_cam_buffers(labels, cam, rec),
+                             [&] { return cam_handle_dims_error(h, 1); }, images, n, layout, first_index, labels, conf, fail, score, stream,
+                             [&](hipStream_t s) { return cam_on_tap(h, labels, 1, cam, rec, s); });
 }
 
 // ---- attention rollout (fav_rollout.hpp) ---------------------------------------
@@ -2371,123 +2426,64 @@ void vit_grid(const fav_handle* h, int* gh, int* gw) {
     const VitDef& V = kVit[h->cfg.arch - 2];
     *gh = h->cfg.in_h / V.patch; *gw = h->cfg.in_w / V.patch;
 }
-// What fav_rollout and fav_classify_rollout refuse alike about the handle's state, before anything is enqueued (FAV_OK: nothing)
-fav_status rollout_gate(fav_handle* h, const char* fn, int first_layer, const void* map, const void* rec) {
-    if (!h->attn_tap) { h->err = fmt("%s: the attention tap is off (fav_set_attn_tap)", fn); return FAV_ERR_INVALID_ARG; }
-    if (h->n_views > 0) {
-        h->err = fmt("%s: views are set; a view's rollout lies in that view's frame and averaging them mis-registers (fav_get_attention still works)", fn);
-        return FAV_ERR_UNSUPPORTED;
-    }
-    if (!map || !rec || ((uintptr_t)map & 3) || ((uintptr_t)rec & 7)) { h->err = fmt("%s: %s", fn, kBadRecords); return FAV_ERR_INVALID_ARG; }
+// the head's own ranges on a handle whose attention tap is on, and its launch on the attention the tap holds
+extern "C++" std::string rollout_handle_dims_error(const fav_handle* h, int first_layer) {
     int gh, gw;
     vit_grid(h, &gh, &gw);
-    const std::string why = rollout_dims_error(h->attn.L, 1, gh, gw, h->attn.ld, first_layer);
-    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
-    return FAV_OK;
+    return rollout_dims_error(h->attn.L, 1, gh, gw, h->attn.ld, first_layer);
 }
-// the head on the attention of the last call, behind whatever used the handle's buffers last
-fav_status rollout_on_stream(fav_handle* h, int first_layer, float* map, fav_rollout_record* rec, hipStream_t s) {
+const char* rollout_on_tap(const fav_handle* h, int first_layer, float* map, fav_rollout_record* rec, hipStream_t s) {
     int gh, gw;
     vit_grid(h, &gh, &gw);
-    launch_rollout(h->attn_buf, (long long)h->attn_n * h->attn.T * h->attn.ld, h->attn.L, h->attn_n, gh, gw, h->attn.ld, first_layer, map, rec, s);
-    route_clear();            // the report speaks of fav_op_* launches only
-    mark_last_use(h, s);
-    HIP_TRY(h, hipGetLastError());
-    return FAV_OK;
+    const int n = h->attn_tap.n;
+    launch_rollout((const float*)h->attn_tap.buf, (long long)n * h->attn.T * h->attn.ld, h->attn.L, n, gh, gw, h->attn.ld, first_layer, map, rec, s);
+    return nullptr;
 }
+bool bad_rollout_buffers(const void* map, const void* rec) { return !map || !rec || ((uintptr_t)map & 3) || ((uintptr_t)rec & 7); }
 }  // namespace
 
 fav_status fav_attn_tap_info(const fav_config* cfg, size_t* bytes, int32_t* layers, int32_t* tokens, int32_t* ld, char* err, size_t err_cap) {
-    auto reply = [&](fav_status st, const std::string& why) {
-        if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
-        return st;
-    };
-    if (!cfg || cfg->struct_size != sizeof(fav_config)) return reply(FAV_ERR_INVALID_ARG, "fav_attn_tap_info: null config or struct_size mismatch");
-    if (cfg->arch < 0 || cfg->arch > 3) return reply(FAV_ERR_UNSUPPORTED, "fav_attn_tap_info: unknown arch");
-    if (const char* why = attn_tap_unsupported(cfg->arch, cfg->n_members, cfg->math_mode)) return reply(FAV_ERR_UNSUPPORTED, fmt("fav_attn_tap_info: %s", why));
-    if (cfg->max_batch < 1 || cfg->in_h < 8 || cfg->in_w < 8 || cfg->num_classes < 1)
-        return reply(FAV_ERR_INVALID_ARG, "fav_attn_tap_info: config value out of range");
-    Plan P;
-    std::string why;
-    if (fav_status st = plan_vit(*cfg, &P, &why)) return reply(st, fmt("fav_attn_tap_info: %s", why.c_str()));
-    const AttnTapDims d = attn_tap_dims(kVit[cfg->arch - 2].depth, P.ntok, cfg->max_batch);
-    if (bytes) *bytes = d.bytes;
-    if (layers) *layers = d.L;
-    if (tokens) *tokens = d.T;
-    if (ld) *ld = d.ld;
-    return reply(FAV_OK, "");
+    return tap_info("fav_attn_tap_info", cfg, attn_tap_unsupported, false, err, err_cap, [&](std::string* why) -> fav_status {
+        Plan P;
+        if (fav_status st = plan_vit(*cfg, &P, why)) return st;
+        const AttnTapDims d = attn_tap_dims(kVit[cfg->arch - 2].depth, P.ntok, cfg->max_batch);
+        if (bytes) *bytes = d.bytes;
+        put_sizes({{layers, d.L}, {tokens, d.T}, {ld, d.ld}});
+        return FAV_OK;
+    });
 }
 
 fav_status fav_set_attn_tap(fav_handle* h, int32_t enable, size_t max_bytes) {
     if (!h) return FAV_ERR_INVALID_ARG;
-    if (!enable) {
-        if (!h->attn_tap) return FAV_OK;
-        h->attn_tap = false;
-        h->attn_n = h->attn_views = 0;
-        HIP_TRY(h, hipSetDevice(h->cfg.device));
-        if (fav_status st = wait_enqueued(h)) return st;
-        void* buf = h->attn_buf;
-        h->attn_buf = nullptr;
-        if (buf) HIP_TRY(h, hipFree(buf));
-        return FAV_OK;
-    }
-    if (const char* why = attn_tap_unsupported(h->cfg.arch, h->n_members, h->cfg.math_mode)) { h->err = fmt("fav_set_attn_tap: %s", why); return FAV_ERR_UNSUPPORTED; }
-    const AttnTapDims d = attn_tap_dims(kVit[h->cfg.arch - 2].depth, h->plan.ntok, h->cfg.max_batch);
-    const std::string why = attn_tap_budget_error(d.bytes, max_bytes);
-    if (!why.empty()) { h->err = fmt("fav_set_attn_tap: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
-    if (h->attn_tap) return FAV_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    void* buf = nullptr;
-    HIP_TRY(h, hipMalloc(&buf, d.bytes + 256));
-    h->attn_buf = (float*)buf;
-    h->attn = d;
-    h->attn_n = h->attn_views = 0;
-    h->attn_tap = true;
-    return FAV_OK;
+    if (!enable) return tap_off(h, h->attn_tap);
+    return tap_on(h, "fav_set_attn_tap", h->attn_tap, h->attn, attn_tap_unsupported(h->cfg.arch, h->n_members, h->cfg.math_mode),
+                  "attention of max_batch frames takes", max_bytes, ATTN_TAP_DEFAULT_BUDGET,
+                  [&] { return attn_tap_dims(kVit[h->cfg.arch - 2].depth, h->plan.ntok, h->cfg.max_batch); });
 }
 
 fav_status fav_get_attention(fav_handle* h, float* out, int32_t* l_out, int32_t* n_out, int32_t* t_out, int32_t* ld_out, void* stream) {
     if (!h) return FAV_ERR_INVALID_ARG;
-    if (!h->attn_tap) { h->err = "fav_get_attention: the attention tap is off (fav_set_attn_tap)"; return FAV_ERR_INVALID_ARG; }
-    if (h->attn_n == 0) { h->err = "fav_get_attention: no classify call since the tap was turned on"; return FAV_ERR_INVALID_ARG; }
-    if (l_out) *l_out = h->attn.L;
-    if (n_out) *n_out = h->attn_n;
-    if (t_out) *t_out = h->attn.T;
-    if (ld_out) *ld_out = h->attn.ld;
-    if (out) {
-        hipStream_t s = (hipStream_t)stream;
-        HIP_TRY(h, hipSetDevice(h->cfg.device));
-        if (fav_status st = wait_last_use(h, s)) return st;
-        const size_t bytes = (size_t)h->attn.L * h->attn_n * h->attn.T * h->attn.ld * 4;
-        HIP_TRY(h, hipMemcpyAsync(out, h->attn_buf, bytes, hipMemcpyDeviceToDevice, s));
-        mark_last_use(h, s);
-    }
-    return FAV_OK;
+    const fav_handle::LocTap& t = h->attn_tap;
+    const AttnTapDims& d = h->attn;
+    return tap_get(h, "fav_get_attention", kAttnWords, t, {{l_out, d.L}, {n_out, t.n}, {t_out, d.T}, {ld_out, d.ld}}, out,
+                   (size_t)d.L * t.n * d.T * d.ld * 4, stream);
 }
 
 fav_status fav_rollout(fav_handle* h, int32_t first_layer, float* map, fav_rollout_record* rec, void* stream) {
     static_assert(sizeof(fav_rollout_record) == 32, "fav_rollout_record is 8 dwords");
     static_assert(offsetof(fav_rollout_record, peak) == offsetof(fav_cam_record, peak) && offsetof(fav_rollout_record, floor) == offsetof(fav_cam_record, floor),
                   "fav_op_cam_heatmap reads peak and floor of either record");
-    route_clear();
-    if (!h) return FAV_ERR_INVALID_ARG;
-    if (fav_status st = rollout_gate(h, "fav_rollout", first_layer, map, rec)) return st;
-    if (h->attn_n == 0) { h->err = "fav_rollout: no classify call since the tap was turned on"; return FAV_ERR_INVALID_ARG; }
-    if (h->attn_views > 0) { h->err = "fav_rollout: the last call ran under views; their rollouts lie in each view's own frame"; return FAV_ERR_UNSUPPORTED; }
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (fav_status st = wait_last_use(h, s)) return st;
-    return rollout_on_stream(h, first_layer, map, rec, s);
+    return map_head_on_last_call(h, "fav_rollout", kAttnWords, &fav_handle::attn_tap, bad_rollout_buffers(map, rec),
+                                 [&] { return rollout_handle_dims_error(h, first_layer); }, stream,
+                                 [&](hipStream_t s) { return rollout_on_tap(h, first_layer, map, rec, s); });
 }
 
 fav_status fav_classify_rollout(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
                                 float* conf, uint8_t* fail, float* score, int32_t first_layer, float* map, fav_rollout_record* rec,
                                 void* stream) {
-    route_clear();
-    if (!h) return FAV_ERR_INVALID_ARG;
-    if (fav_status st = rollout_gate(h, "fav_classify_rollout", first_layer, map, rec)) return st;
-    if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
-    return rollout_on_stream(h, first_layer, map, rec, (hipStream_t)stream);
+    return classify_map_head(h, "fav_classify_rollout", kAttnWords, &fav_handle::attn_tap, bad_rollout_buffers(map, rec),
+                             [&] { return rollout_handle_dims_error(h, first_layer); }, images, n, layout, first_index, labels, conf, fail,
+                             score, stream, [&](hipStream_t s) { return rollout_on_tap(h, first_layer, map, rec, s); });
 }
 
 fav_status fav_set_profiling(fav_handle* h, int32_t enable) {

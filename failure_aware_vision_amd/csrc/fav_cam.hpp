@@ -4,7 +4,8 @@
 // the map - no backward pass, and linear in the MC-Dropout samples.  The contract (fav.h, beside fav_cam_record) fixes every
 // operation - fp32, one rounding per product and per sum, a fixed partition of the channels over 64 lanes, sums in index
 // order - so the result is the bits of a numpy restatement (tests/cam_ref.py).
-// Included by fav.hip after fav_plan.hpp (Plan) and fav_route.hpp (fmt).
+// Included by fav.hip after fav_plan.hpp (Plan), fav_route.hpp (fmt) and fav_mapbox.hpp (what the record shares with the
+// rollout head's: the box scan, the record store, the tap's budget check).
 //
 //   cam_kernel<KT>      : one block of 1024 threads a frame, ONE launch and no global workspace, so the S x HW x C bf16 of a
 //                         frame are read once for all K classes.  The K weight rows lie in LDS as bf16 (at most 64 KB), the K
@@ -13,7 +14,8 @@
 //                         issued ahead of their chain - and K running sums; six shuffle steps fold the 64 partials.  The head
 //                         is bandwidth-bound (7.7 GFLOP against 1.5 GB at the headline shape), so the products and sums are
 //                         plain v_mul_f32 / v_add_f32: the matrix pipe would buy nothing and would cost the fixed order.  The
-//                         records are K serial scans in index order over a map in LDS, one lane each.
+//                         records are K serial scans in index order over a map in LDS, one lane each: the kernel's own
+//                         for the sums, the peak and the floor, then map_box_scan at 20 % of a positive peak.
 //   cam_heatmap_kernel  : a thread a pixel of the overlay: bilinear taps of the map, the record's floor and peak, one byte.
 #pragma once
 
@@ -60,16 +62,11 @@ inline MapTapDims map_tap_dims(const fav_plan::Plan& P, int max_batch) {
         }
     return d;
 }
-// the configurations the tap refuses, from the config alone ("" : none)
-inline const char* map_tap_unsupported(int arch, int n_members) {
+// the configurations the tap refuses, from the config alone (nullptr: none); the math mode makes no difference to it
+inline const char* map_tap_unsupported(int arch, int n_members, int /*math_mode*/) {
     if (arch == 2 || arch == 3) return "a ViT arch has no pooled convolutional map";
     if (n_members > 1) return "the members of a deep ensemble have a map each; the map tap is not supported on it";
     return nullptr;
-}
-inline std::string map_tap_budget_error(size_t bytes, size_t max_bytes) {
-    const size_t cap = max_bytes ? max_bytes : CAM_DEFAULT_BUDGET;
-    if (bytes > cap) return fmt("the maps of max_batch frames take %zu bytes, above max_bytes=%zu", bytes, cap);
-    return std::string();
 }
 
 // ---- device
@@ -179,23 +176,10 @@ __global__ __launch_bounds__(CAM_THREADS) void cam_kernel(const CamParams p) {
                 pos = __fadd_rn(pos, fmaxf(v, 0.f));
             }
             logit = __fadd_rn(__fmul_rn(sum, p.inv_HW), p.bias[c]);
-            if (peak > 0.f) {
-                const float thr = __fmul_rn(0.2f, peak);
-                int x0 = INT_MAX, y0 = INT_MAX, x1 = -1, y1 = -1;
-                for (int hw = 0; hw < HW; ++hw) {
-                    if (!(Mk[hw] >= thr)) continue;
-                    const int y = hw / p.Wf, x = hw - y * p.Wf;
-                    ++n_above;
-                    x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
-                }
-                if (n_above > 0) box = (int)((uint32_t)x0 | ((uint32_t)y0 << 8) | ((uint32_t)x1 << 16) | ((uint32_t)y1 << 24));
-            }
+            if (peak > 0.f) n_above = map_box_scan(Mk, HW, p.Wf, __fmul_rn(0.2f, peak), &box);
         }
-        int2* out = (int2*)(p.rec + 8 * ((size_t)i * K + k));
-        out[0] = make_int2(c, __float_as_int(logit));
-        out[1] = make_int2(__float_as_int(peak), peak_cell);
-        out[2] = make_int2(__float_as_int(flo), __float_as_int(pos));
-        out[3] = make_int2(n_above, box);
+        map_record_store(p.rec + 8 * ((size_t)i * K + k), c, __float_as_int(logit), __float_as_int(peak), peak_cell,
+                         __float_as_int(flo), __float_as_int(pos), n_above, box);
     }
 }
 

@@ -2962,6 +2962,55 @@ __device__ __forceinline__ f32x2_t fav_attn_exp2(f32x2_t z) {
     return e;
 }
 
+// The attention softmax of one query row in the S layout (the lane: keys 16 kt + 4 fq .. + 3 of its query in sc[kt]), as the
+// tap calls it (fav_rollout.hpp attn_mean_kernel); attention_kernel below holds the same statements in place (see there).
+// In: the raw scores of nkt <= NKT key tiles; out: sc holds the unnormalised exponentials and the result is 1 / their row sum.
+// Only the last key tile reaches past T: its padded keys are -inf for the max and 0 afterwards.
+template <int NKT, bool FULL>
+__device__ __forceinline__ float fav_attn_softmax(f32x4_t (&sc)[NKT], int nkt, int T, int fq) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+        if (kt < nkt) {
+            if (FULL ? kt == NKT - 1 : kt == nkt - 1) {
+                const int key = kt * 16 + fq * 4;
+                sc[kt][0] = key < T ? sc[kt][0] : -INFINITY;
+                sc[kt][1] = key + 1 < T ? sc[kt][1] : -INFINITY;
+                sc[kt][2] = key + 2 < T ? sc[kt][2] : -INFINITY;
+                sc[kt][3] = key + 3 < T ? sc[kt][3] : -INFINITY;
+            }
+            mx = fmaxf(fmaxf(mx, sc[kt][0]), sc[kt][1]);     // v_max3_f32
+            mx = fmaxf(fmaxf(mx, sc[kt][2]), sc[kt][3]);
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    // e = 2^((s - max) / 8 * log2 e) = 2^fma(s, c, -(max * c)), c = log2(e) / 8
+    const float C2 = 0x1.715476p-3f;
+    const float nmc = -__fmul_rn(mx, C2);
+    const f32x2_t c2v = {C2, C2}, nmcv = {nmc, nmc};
+    f32x2_t sum2 = {0.f, 0.f};
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+        if (kt < nkt) {
+            f32x2_t lo = fav_attn_exp2(__builtin_elementwise_fma((f32x2_t){sc[kt][0], sc[kt][1]}, c2v, nmcv));
+            f32x2_t hi = fav_attn_exp2(__builtin_elementwise_fma((f32x2_t){sc[kt][2], sc[kt][3]}, c2v, nmcv));
+            if (FULL ? kt == NKT - 1 : kt == nkt - 1) {
+                const int key = kt * 16 + fq * 4;
+                lo.x = key < T ? lo.x : 0.f;
+                lo.y = key + 1 < T ? lo.y : 0.f;
+                hi.x = key + 2 < T ? hi.x : 0.f;
+                hi.y = key + 3 < T ? hi.y : 0.f;
+            }
+            sum2 = sum2 + lo;
+            sum2 = sum2 + hi;
+            sc[kt] = (f32x4_t){lo.x, lo.y, hi.x, hi.y};
+        }
+    float sum = __fadd_rn(sum2.x, sum2.y);
+    sum = __fadd_rn(sum, __shfl_xor(sum, 16, 64));
+    sum = __fadd_rn(sum, __shfl_xor(sum, 32, 64));
+    return __fdiv_rn(1.0f, sum);   // one IEEE division per query row, then multiplications
+}
+
 // NKT = key tiles the kernel is built for (T <= 16 NKT): 13 for ViT-B/16's 197 tokens, 12 score registers fewer than 16.
 // FULL: T needs exactly NKT tiles, so every tile guard and the position of the masked tile are compile-time (the production shape).
 template <int MODE, int NKT = 16, bool FULL = false>
@@ -3051,7 +3100,8 @@ __global__ __launch_bounds__(512, 4) void attention_kernel(const uint16_t* __res
             // straight-line code (FULL): without a fence the scheduler hoists every K fragment read to the top - 104 registers
             if (FULL && (kt & 3) == 3) __builtin_amdgcn_sched_barrier(0);
         }
-        // row max of the raw scores (only the last key tile reaches past T: its padded keys are -inf for the max and 0 afterwards)
+        // The softmax, fav_attn_softmax's statements in place: a call compiled to another schedule, 0.2 % slower on the ViT
+        // benchmark (profiles/localisation_seam_ab.txt).  An edit goes to both.  First the row max of the raw scores
         float mx = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt)

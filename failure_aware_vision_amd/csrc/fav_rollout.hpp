@@ -4,12 +4,15 @@
 // connection, the layers multiplied together; the class token's row of the product says how much each patch fed the decision.
 // No backward pass.  The contract (fav.h, beside fav_set_attn_tap and fav_rollout_record) fixes every operation, so both
 // kernels give the bits of a numpy restatement (tests/rollout_ref.py).
-// Included by fav.hip after fav_kernels.hpp (fav_attn_exp2, the MFMA vector types) and fav_route.hpp (fmt).
+// Included by fav.hip after fav_kernels.hpp (fav_attn_softmax, the MFMA vector types), fav_route.hpp (fmt) and fav_mapbox.hpp
+// (what the head's record shares with cam_kernel's: the box scan, the record store, the tap's budget check).
 //
 //   attn_mean_kernel       : the tap.  attention_kernel keeps its probabilities in registers and never writes them, so this
-//                            kernel repeats its score product and its softmax - the same MFMA chain with the same operands (K
-//                            rows A, the lane's Q fragment B), the same mask, max, exponential, partial sums and reciprocal,
-//                            copied statement by statement - and stops in front of the rounding to bf16.  A block takes one
+//                            kernel repeats its score product - the same MFMA chain with the same operands (K rows A, the
+//                            lane's Q fragment B), without production's scheduling fences - calls fav_attn_softmax, which
+//                            stands beside attention_kernel and holds its mask, max, exponential, partial sums and
+//                            reciprocal (production keeps the statements in place: a call moved its schedule), and stops in
+//                            front of the rounding to bf16.  A block takes one
 //                            frame and up to four 16-query tiles, a wave a tile, and loops over the heads: the head's K lies
 //                            in LDS (16 nkt rows of 128 B, the production swizzle), in two buffers - the next head's K and Q
 //                            travel to registers under this head's MFMAs and exponentials and go to the other buffer behind
@@ -17,7 +20,8 @@
 //                            them the running head sum, 4 NKT registers more; one 16-byte store per lane and key tile.
 //   attn_rollout_kernel    : the head.  A block a frame, a thread a column u of the running row r (in LDS, two buffers): the
 //                            chain r'[u] = r'[u] + r[t] * A~[t][u] over t in index order, loads of eight t ahead of it.  The
-//                            record is one lane's serial scans over the row, as cam_kernel's.
+//                            record is one lane's serial scans over the row: the kernel's own for the sum, the peak and the
+//                            floor, then map_box_scan at the midpoint of a peak above the floor.
 #pragma once
 
 namespace fav {
@@ -64,11 +68,6 @@ inline const char* attn_tap_unsupported(int arch, int n_members, int math_mode) 
     if (arch != 2 && arch != 3) return "a ResNet arch has no attention; its localisation signal is the class activation map (fav_set_map_tap)";
     if (math_mode != 0) return "FAV_MATH_F32_EXACT is not supported: the tap restates the production score product only";
     return nullptr;
-}
-inline std::string attn_tap_budget_error(size_t bytes, size_t max_bytes) {
-    const size_t cap = max_bytes ? max_bytes : ATTN_TAP_DEFAULT_BUDGET;
-    if (bytes > cap) return fmt("the attention of max_batch frames takes %zu bytes, above max_bytes=%zu", bytes, cap);
-    return std::string();
 }
 
 // ---- device: the tap
@@ -147,48 +146,8 @@ __global__ __launch_bounds__(64 * ATTN_MEAN_WAVES) void attn_mean_kernel(const u
                     }
                 }
             }
-            // ---- attention_kernel's softmax: row max of the raw scores (the padded keys of the last tile are -inf for the max and
-            //      0 afterwards)
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < NKT; ++kt)
-                if (kt < nkt) {
-                    if (FULL ? kt == NKT - 1 : kt == nkt - 1) {
-                        const int key = kt * 16 + fq * 4;
-                        sc[kt][0] = key < T ? sc[kt][0] : -INFINITY;
-                        sc[kt][1] = key + 1 < T ? sc[kt][1] : -INFINITY;
-                        sc[kt][2] = key + 2 < T ? sc[kt][2] : -INFINITY;
-                        sc[kt][3] = key + 3 < T ? sc[kt][3] : -INFINITY;
-                    }
-                    mx = fmaxf(fmaxf(mx, sc[kt][0]), sc[kt][1]);
-                    mx = fmaxf(fmaxf(mx, sc[kt][2]), sc[kt][3]);
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float C2 = 0x1.715476p-3f;
-            const float nmc = -__fmul_rn(mx, C2);
-            const f32x2_t c2v = {C2, C2}, nmcv = {nmc, nmc};
-            f32x2_t sum2 = {0.f, 0.f};
-#pragma unroll
-            for (int kt = 0; kt < NKT; ++kt)
-                if (kt < nkt) {
-                    f32x2_t lo = fav_attn_exp2(__builtin_elementwise_fma((f32x2_t){sc[kt][0], sc[kt][1]}, c2v, nmcv));
-                    f32x2_t hi = fav_attn_exp2(__builtin_elementwise_fma((f32x2_t){sc[kt][2], sc[kt][3]}, c2v, nmcv));
-                    if (FULL ? kt == NKT - 1 : kt == nkt - 1) {
-                        const int key = kt * 16 + fq * 4;
-                        lo.x = key < T ? lo.x : 0.f;
-                        lo.y = key + 1 < T ? lo.y : 0.f;
-                        hi.x = key + 2 < T ? hi.x : 0.f;
-                        hi.y = key + 3 < T ? hi.y : 0.f;
-                    }
-                    sum2 = sum2 + lo;
-                    sum2 = sum2 + hi;
-                    sc[kt] = (f32x4_t){lo.x, lo.y, hi.x, hi.y};
-                }
-            float sum = __fadd_rn(sum2.x, sum2.y);
-            sum = __fadd_rn(sum, __shfl_xor(sum, 16, 64));
-            sum = __fadd_rn(sum, __shfl_xor(sum, 32, 64));
-            const float inv_sum = __fdiv_rn(1.0f, sum);
+            // ---- attention_kernel's softmax: sc becomes the exponentials
+            const float inv_sum = fav_attn_softmax<NKT, FULL>(sc, nkt, T, fq);
             // ---- the fp32 probability in front of production's rounding to bf16, added to the head sum: a product, then a sum
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt)
@@ -262,22 +221,9 @@ __global__ __launch_bounds__(ROLL_THREADS) void attn_rollout_kernel(const Rollou
             if (v > peak) { peak = v; peak_cell = c; }
             if (v < flo) flo = v;
         }
-        if (peak > flo) {
-            const float thr = __fadd_rn(flo, __fmul_rn(0.5f, __fsub_rn(peak, flo)));
-            int x0 = INT_MAX, y0 = INT_MAX, x1 = -1, y1 = -1;
-            for (int c = 0; c < HW; ++c) {
-                if (!(r[1 + c] >= thr)) continue;
-                const int y = c / p.gw, x = c - y * p.gw;
-                ++n_above;
-                x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
-            }
-            if (n_above > 0) box = (int)((uint32_t)x0 | ((uint32_t)y0 << 8) | ((uint32_t)x1 << 16) | ((uint32_t)y1 << 24));
-        }
-        int2* out = (int2*)(p.rec + 8 * (size_t)i);
-        out[0] = make_int2(p.L - p.first_layer, __float_as_int(r[0]));
-        out[1] = make_int2(__float_as_int(peak), peak_cell);
-        out[2] = make_int2(__float_as_int(flo), __float_as_int(sum));
-        out[3] = make_int2(n_above, box);
+        if (peak > flo) n_above = map_box_scan(r + 1, HW, p.gw, __fadd_rn(flo, __fmul_rn(0.5f, __fsub_rn(peak, flo))), &box);
+        map_record_store(p.rec + 8 * (size_t)i, p.L - p.first_layer, __float_as_int(r[0]), __float_as_int(peak), peak_cell,
+                         __float_as_int(flo), __float_as_int(sum), n_above, box);
     }
 }
 

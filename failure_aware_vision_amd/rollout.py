@@ -7,7 +7,7 @@ the tests of this package verify is that algebra and its bits on synthetic check
 property of trained weights."""
 from __future__ import annotations
 
-import numpy as np
+from .cam import _unpack_map_records
 
 #: dwords of one fav_rollout_record
 ROLLOUT_RECORD_DWORDS = 8
@@ -20,23 +20,7 @@ def unpack_rollout_records(records) -> dict:
     ``peak_cell`` int32, ``floor``, ``patch_sum`` fp32, ``n_above`` int32 (cells at the midpoint between floor and peak or
     above), ``box`` int32 (packed; -1: none), each [...] and a view of the record buffer, plus the box unpacked to ``x0``,
     ``y0``, ``x1``, ``y1`` (int32, inclusive patch cells; all -1 when the box is -1)."""
-    if records.ndim < 1 or int(records.shape[-1]) != ROLLOUT_RECORD_DWORDS:
-        raise ValueError(f"expected int32[..., {ROLLOUT_RECORD_DWORDS}] records, got shape {tuple(records.shape)}")
-    if isinstance(records, np.ndarray):
-        f32 = np.float32
-        where = np.where
-    else:
-        import torch
-        f32 = torch.float32
-        where = torch.where
-    box = records[..., 7]
-    none = box == -1
-    out = {"n_layers": records[..., 0], "cls_mass": records[..., 1].view(f32), "peak": records[..., 2].view(f32),
-           "peak_cell": records[..., 3], "floor": records[..., 4].view(f32), "patch_sum": records[..., 5].view(f32),
-           "n_above": records[..., 6], "box": box}
-    for name, shift in (("x0", 0), ("y0", 8), ("x1", 16), ("y1", 24)):
-        out[name] = where(none, box, (box >> shift) & 0xFF)
-    return out
+    return _unpack_map_records(records, ("n_layers", "cls_mass", "peak", "peak_cell", "floor", "patch_sum", "n_above", "box"))
 
 
 def patch_box_to_pixels(box, patch: int = VIT_PATCH):

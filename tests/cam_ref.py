@@ -14,6 +14,8 @@ The partition does not depend on any grid or block geometry.  A NaN's payload an
 ``same_bits`` compares bits everywhere else and NaN-ness where either side is a NaN."""
 import numpy as np
 
+from map_ref import cells_above, same_bits  # noqa: F401  (same_bits: for the tests that compare with this module)
+
 F32 = np.float32
 QNAN_BITS = 0x7FC00000
 RECORD_DWORDS = 8
@@ -27,17 +29,6 @@ def f32_to_bf16_bits(x) -> np.ndarray:
     """finite float32 -> bf16 bit patterns, round to nearest even."""
     u = np.ascontiguousarray(x, np.float32).view(np.uint32)
     return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-
-
-def same_bits(a, b) -> bool:
-    """Equal shapes, equal bits wherever neither value is a NaN, and NaNs in the same places."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    if a.dtype != np.float32:
-        return bool(np.array_equal(a, b))
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
 
 
 def cam_maps(x_bits, w_bits, classes, n_classes) -> np.ndarray:
@@ -94,13 +85,7 @@ def cam_records(M, classes, bias, n_classes, Wf) -> np.ndarray:
                 logit = total * F32(1.0 / HW) + bias[c]
                 n_above, box = 0, -1
                 if peak > 0:
-                    thr = F32(0.2) * peak
-                    cells = np.nonzero(m >= thr)[0]
-                    n_above = int(cells.size)
-                    if n_above:
-                        xs, ys = cells % Wf, cells // Wf
-                        packed = int(xs.min()) | int(ys.min()) << 8 | int(xs.max()) << 16 | int(ys.max()) << 24
-                        box = packed - (1 << 32) if packed >= 1 << 31 else packed
+                    n_above, box = cells_above(m, F32(0.2) * peak, Wf)
                 rec[i, k, 0], rec[i, k, 3], rec[i, k, 6], rec[i, k, 7] = c, cell, n_above, box
                 f[i, k, 1], f[i, k, 2], f[i, k, 4], f[i, k, 5] = logit, peak, floor, pos
     return rec

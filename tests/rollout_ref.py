@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 import vit_ref as V
+from map_ref import cells_above, same_bits  # noqa: F401  (same_bits: for the tests that compare with this module)
 from oracle import fav_oracle as O
 
 F32 = np.float32
@@ -77,13 +78,7 @@ def rollout_records(M, r0, n_layers, gw) -> np.ndarray:
                     floor = v
             n_above, box = 0, -1
             if peak > floor:
-                thr = floor + F32(0.5) * (peak - floor)
-                cells = np.nonzero(m >= thr)[0]
-                n_above = int(cells.size)
-                if n_above:
-                    xs, ys = cells % gw, cells // gw
-                    packed = int(xs.min()) | int(ys.min()) << 8 | int(xs.max()) << 16 | int(ys.max()) << 24
-                    box = packed - (1 << 32) if packed >= 1 << 31 else packed
+                n_above, box = cells_above(m, floor + F32(0.5) * (peak - floor), gw)
             rec[i, 0], rec[i, 3], rec[i, 6], rec[i, 7] = n_layers, cell, n_above, box
             f[i, 1], f[i, 2], f[i, 4], f[i, 5] = r0[i], peak, floor, total
     return rec
@@ -96,17 +91,6 @@ def rollout(A, gh, gw, first_layer=0):
     r = rollout_rows(A, first_layer)
     M = np.ascontiguousarray(r[:, 1:])
     return M, rollout_records(M, r[:, 0], A.shape[0] - first_layer, gw)
-
-
-def same_bits(a, b) -> bool:
-    """Equal shapes, equal bits wherever neither value is a NaN, and NaNs in the same places."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    if a.dtype != np.float32:
-        return bool(np.array_equal(a, b))
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
 
 
 # ---- 2. from the definitions, in float64 ----------------------------------------------------------------------------------------

@@ -103,6 +103,48 @@ def test_op_attn_mean_matches_the_reference(lib, T, heads, n):
         assert A[:, :, :T].max() > 4.0 / T                       # one head's rows are peaked, not flat
 
 
+def poisoned_qkv(seed, n, T, heads):
+    """qkv_problem with, in every head of every frame, one query row whose scores are all NaN (a NaN in Q) and one whose scores
+    are all -inf (+inf in a Q channel where every key holds -1): both rows come out NaN, every other row stays finite."""
+    qkv = qkv_problem(seed, n, T, heads)
+    D = 64 * heads
+    for h in range(heads):
+        qkv[:, :, D + 64 * h + 7] = -1.0
+        qkv[:, 0, 64 * h + 3] = np.nan
+        qkv[:, T - 1, 64 * h + 7] = np.inf
+    return qkv
+
+
+# The tap calls fav_attn_softmax; attention_kernel holds the same statements in place.  The tap's four instantiations - T = 2
+# and 17: up to 2 key tiles (one masked tile with one real key beside the class token; two tiles, one live key in the last);
+# 197: exactly 13; 250: 16 with run-time guards; 256: exactly 16 - and the production route of the same shape, each against its
+# oracle on an input with a NaN score row and a -inf score row: NaNs where the oracle has them, its bits everywhere else.
+@pytest.mark.parametrize("T", [2, 17, 197, 250, 256])
+def test_the_tap_and_production_attention_share_their_softmax(lib, T):
+    from oracle import fav_oracle as O
+    n, heads = 2, 2
+    D = 64 * heads
+    qkv = poisoned_qkv(T, n, T, heads)
+    bad = np.zeros(T, bool)
+    bad[[0, T - 1]] = True
+    # the tap
+    st, A, guards, _ = run_attn_mean(lib, qkv, heads)
+    assert st == 0 and guards
+    want = R.attn_mean(qkv, heads)
+    assert np.isnan(want[:, bad, :T]).all() and np.isfinite(want[:, ~bad]).all()
+    assert R.same_bits(A[:, :, :T], want[:, :, :T])
+    assert not A[:, ~bad, T:].view(np.uint32).any()
+    # production, mode 0: the tap restates its score product
+    q = torch.from_numpy(qkv).cuda().to(torch.bfloat16).contiguous()
+    out = torch.empty((n, T, D), dtype=torch.bfloat16, device="cuda")
+    _lib.check(lib.fav_op_attention(q.data_ptr(), out.data_ptr(), n, T, D, heads, 0, None))
+    assert _lib.route_attention(n, T, D, heads, 0) == (0, _lib.last_route())
+    torch.cuda.synchronize()
+    exp = O.attention(qkv, heads, exact="mfma")
+    assert np.isnan(exp[:, bad]).all() and np.isfinite(exp[:, ~bad]).all()
+    assert R.same_bits(out.float().cpu().numpy(), exp)
+
+
 def test_op_attn_mean_refusals_launch_nothing(lib):
     qkv = qkv_problem(1, 2, 17, 2)
     assert run_attn_mean(lib, qkv, 2)[0] == 0
