@@ -11,9 +11,10 @@ from .calibration import (Calibration, fit_temperature, reliability, risk_covera
                           unpack_cells)
 from .corrupt import CORRUPTIONS, SEVERITY, Corruptor  # noqa: F401
 from .distributed import classify_sharded, shard_range  # noqa: F401
-from . import cam, ood, robustness, rollout, synth, views, weights  # noqa: F401
+from . import cam, faithfulness, ood, robustness, rollout, synth, views, weights  # noqa: F401
 from .cam import box_to_pixels, evidence_share, unpack_cam_records  # noqa: F401
 from .rollout import patch_box_to_pixels, unpack_rollout_records  # noqa: F401
+from .faithfulness import random_maps, unpack_curve_records  # noqa: F401
 from .ood import (DriftReference, KNNBank, OODModel, build_drift_reference, build_knn_bank, fit_mahalanobis,  # noqa: F401
                   unpack_drift_record)
 from .views import View  # noqa: F401

@@ -161,6 +161,21 @@ class FavRolloutRecord(C.Structure):
                 ("floor", C.c_float), ("patch_sum", C.c_float), ("n_above", C.c_int32), ("box", C.c_int32)]
 
 
+CURVE_DELETION, CURVE_INSERTION = 0, 1
+CURVE_MODES = ("deletion", "insertion")
+
+
+class FavCurve(C.Structure):
+    """fav_curve: the steps of a deletion / insertion curve and the fill of an occluded pixel in either layout (32 bytes)."""
+    _fields_ = [("struct_size", C.c_uint32), ("steps", C.c_int32), ("fill_u8", C.c_uint32 * 3), ("fill_f32_bits", C.c_uint32 * 3)]
+
+
+class FavCurveRecord(C.Structure):
+    """fav_curve_record: one 32-byte summary per frame (faithfulness.unpack_curve_records reads it as int32[..., 8])."""
+    _fields_ = [("class_id", C.c_int32), ("auc", C.c_float), ("p_first", C.c_float), ("flip_step", C.c_int32),
+                ("p_last", C.c_float), ("p_min", C.c_float), ("flip_cells", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -248,6 +263,17 @@ _SIGNATURES = {
     "fav_op_attn_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "fav_op_attn_rollout": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "fav_check_curve": (C.c_int, [C.POINTER(FavCurve), C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    "fav_set_curve": (C.c_int, [C.c_void_p, C.POINTER(FavCurve)]),
+    "fav_classify_curve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_rank_cells": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "fav_op_occlude": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.c_void_p]),
+    "fav_op_head_class_prob": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_curve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                               C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),

@@ -110,6 +110,8 @@ class Backend:
         self._drift = None                                    # the ood.DriftReference in force
         self._map_hw = None                                   # (Hf, Wf) of the map tap, known from the first set_map_tap(True) on
         self._attn_grid = None                                # (gh, gw) of the attention tap, known from the first set_attn_tap(True) on
+        self._map_tap_on = self._attn_tap_on = False          # the two localisation taps as this object last set them
+        self._curve_steps = None                              # the steps of the curve descriptor in force (set_curve)
         self._views = ()
         if views:
             self.set_views(views)
@@ -511,6 +513,7 @@ class Backend:
         ``classify_cam()`` read them.  The buffer is allocated here, for max_batch frames (``map_tap_info()['bytes']``), and
         refused above ``budget_bytes``; turning the tap off frees it.  Refused on a ViT arch and on a deep ensemble."""
         _lib.check(self.lib.fav_set_map_tap(self._h, 1 if enable else 0, int(budget_bytes)), self._h)
+        self._map_tap_on = bool(enable)
         if enable and self._map_hw is None:
             info = self.map_tap_info()                 # the planner, once: classify_cam sizes its outputs from this
             self._map_hw = (info["hf"], info["wf"])
@@ -589,6 +592,7 @@ class Backend:
         (``attn_tap_info()['bytes']``), and refused above ``budget_bytes``; turning the tap off frees it.  Refused on a ResNet
         arch, on a deep ensemble and in the exact math mode."""
         _lib.check(self.lib.fav_set_attn_tap(self._h, 1 if enable else 0, int(budget_bytes)), self._h)
+        self._attn_tap_on = bool(enable)
         if enable and self._attn_grid is None:
             info = self.attn_tap_info()                # the planner, once: classify_rollout sizes its outputs from this
             from .rollout import VIT_PATCH
@@ -646,6 +650,110 @@ class Backend:
         # never tapped: fav_classify_rollout refuses before it writes anything
         return self._classify_map_head(self.lib.fav_classify_rollout, (int(first_layer),), self._attn_grid or (1, 1),
                                        ROLLOUT_RECORD_DWORDS, unpack_rollout_records, images, heatmap, first_index)
+
+    # -- deletion / insertion curves (faithfulness.py; include/fav.h fav_set_curve, fav_classify_curve) -------------------------
+    def set_curve(self, steps: int | None = 16, fill=None):
+        """Prepare the handle for ``classify_curve`` (fav_set_curve): curves of ``steps`` steps (1 .. 256), an occluded pixel
+        becoming ``fill`` - a number in [0, 1] or a 3-tuple of them, stored as round(255 fill) in uint8 frames and as the fp32
+        itself in fp32 frames; default 128 / 255 for uint8 frames, 0.5 for fp32 ones.  Everything a later call needs is allocated
+        here, for max_batch frames.  ``steps`` None: clear.  Refused while views are set, and views are refused while this is."""
+        if steps is None:
+            _lib.check(self.lib.fav_set_curve(self._h, None), self._h)
+            self._curve_steps = None
+            return
+        d = _lib.FavCurve()
+        d.struct_size = C.sizeof(_lib.FavCurve)
+        d.steps = int(steps)
+        if fill is None:
+            u8, f32 = (128, 128, 128), (0.5, 0.5, 0.5)
+        else:
+            f32 = tuple(float(v) for v in (fill if np.ndim(fill) else (fill,) * 3))
+            if len(f32) != 3:
+                raise ValueError("fill is a number or a 3-tuple")
+            u8 = tuple(int(round(255.0 * v)) for v in f32)
+        for c in range(3):
+            d.fill_u8[c] = u8[c] & 0xFFFFFFFF
+            d.fill_f32_bits[c] = int(np.float32(f32[c]).view(np.uint32))
+        _lib.check(self.lib.fav_set_curve(self._h, C.byref(d)), self._h)
+        self._curve_steps = int(steps)
+
+    def classify_curve(self, frames, maps, classes=None, mode: str = "deletion", first_index: int = 0) -> dict:
+        """The deletion or insertion curve of every frame under its map (fav_classify_curve): ``maps`` fp32 [n, mh, mw], at most
+        1024 cells (``classify_cam()['map']``, ``classify_rollout()['map']`` or the caller's own); ``classes`` int [n], or None:
+        each frame's label on the unoccluded frame, read on the device.  -> ``curve`` fp32 [n, steps + 1] (the class probability
+        after each step), the record fields of ``faithfulness.unpack_curve_records``, each [n], and ``label``, ``confidence`` of
+        the unoccluded pass.  Costs steps + 1 forward passes a frame; every pass of a frame draws the same MC-Dropout masks.
+        Frames beyond ``frames_per_call`` go in further calls with ``first_index`` advanced.  torch CUDA frames in -> CUDA tensors
+        out, asynchronous on the current stream; numpy in -> numpy out.  Needs ``set_curve``."""
+        from .faithfulness import CURVE_RECORD_DWORDS, unpack_curve_records
+        torch = self._torch
+        if mode not in _lib.CURVE_MODES:
+            raise ValueError(f"mode must be one of {_lib.CURVE_MODES}, got {mode!r}")
+        img, host, n, layout, stream = self._classify_args(frames)
+        dev = img.device
+        m = torch.as_tensor(maps).to(device=dev, dtype=torch.float32).contiguous()
+        if m.ndim != 3 or int(m.shape[0]) != n:
+            raise ValueError(f"maps must be [n, mh, mw] for the n={n} frames, got {tuple(m.shape)}")
+        mh, mw = int(m.shape[1]), int(m.shape[2])
+        cls = None
+        if classes is not None:
+            cls = torch.as_tensor(np.asarray(classes) if not hasattr(classes, "is_cuda") else classes).to(device=dev, dtype=torch.int32)
+            cls = cls.contiguous()
+            if tuple(cls.shape) != (n,):
+                raise ValueError(f"classes must be [n] for the n={n} frames, got {tuple(cls.shape)}")
+        S = self._curve_steps if self._curve_steps is not None else 0     # never set: fav_classify_curve refuses before it writes
+        curve = torch.empty((n, S + 1), dtype=torch.float32, device=dev)
+        rec = torch.empty((n, CURVE_RECORD_DWORDS), dtype=torch.int32, device=dev)
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        conf = torch.empty(n, dtype=torch.float32, device=dev)
+        for b, e in (self._batches(n) if n else ()):
+            _lib.check(self.lib.fav_classify_curve(
+                self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b, m[b:e].data_ptr(), mh, mw,
+                cls[b:e].data_ptr() if cls is not None else None, _lib.CURVE_MODES.index(mode), labels[b:e].data_ptr(),
+                conf[b:e].data_ptr(), curve[b:e].data_ptr(), rec[b:e].data_ptr(), stream), self._h)
+        out = dict(curve=curve, label=labels, confidence=conf)
+        if host:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+            rec = rec.cpu().numpy()
+        return dict(unpack_curve_records(rec), **out)
+
+    def faithfulness_report(self, frames, steps: int = 16, seed: int = 0, fill=None, maps=None) -> dict:
+        """Is this checkpoint's saliency map faithful on these frames?  The maps come from ``classify_cam`` (ResNet) or
+        ``classify_rollout`` (ViT), the needed tap going on and off around the call if it was off; ``maps=`` fp32 [n, mh, mw]
+        brings the caller's own (a deep ensemble has no tap and must).  Deletion and insertion curves of ``steps`` steps are run
+        on those maps and on ``faithfulness.random_maps(n, (mh, mw), seed)``, each for the frame's own label.  -> the means of
+        ``faithfulness.summarize_curves`` - ``deletion_auc``, ``insertion_auc``, ``random_deletion_auc``,
+        ``random_insertion_auc``, ``deletion_gain`` = random - map, ``insertion_gain`` = map - random (both positive for a
+        faithful map), ``flip_fraction`` - plus ``n``, ``n_nonfinite`` (frames with a NaN curve, left out), ``steps``,
+        ``map_hw`` and under ``per_frame`` the four per-frame results.  Leaves the curve descriptor set.  On synthetic
+        checkpoints the sign of a gain means nothing."""
+        from .faithfulness import random_maps, summarize_curves
+        n = int(frames.shape[0])
+        if maps is None:
+            if int(self.cfg.n_members) > 1:
+                raise ValueError("faithfulness_report: a deep ensemble has no map tap; pass maps=")
+            vit = int(self.cfg.arch) in (_lib.ARCH_VIT_B16, _lib.ARCH_VIT_TINY)
+            tap, head = (self.set_attn_tap, self.classify_rollout) if vit else (self.set_map_tap, self.classify_cam)
+            was_on = (self._attn_tap_on if vit else self._map_tap_on)
+            if not was_on:
+                tap(True)
+            try:
+                parts = [_to_numpy(head(frames[b:e], first_index=b)["map"]) for b, e in self._batches(n)]
+            finally:
+                if not was_on:
+                    tap(False)
+            maps = np.concatenate(parts, axis=0)
+        maps = np.ascontiguousarray(_to_numpy(maps), dtype=np.float32)
+        mh, mw = int(maps.shape[1]), int(maps.shape[2])
+        rnd = random_maps(n, (mh, mw), seed)
+        self.set_curve(steps, fill)
+        runs = {}
+        for name, mp in (("map", maps), ("random", rnd)):
+            for mode in _lib.CURVE_MODES:
+                r = self.classify_curve(frames, mp, None, mode)
+                runs[f"{name}_{mode}"] = {k: _to_numpy(v) for k, v in r.items()}
+        rep = summarize_curves(runs["map_deletion"], runs["map_insertion"], runs["random_deletion"], runs["random_insertion"], mh * mw)
+        return dict(rep, steps=int(steps), map_hw=(mh, mw), per_frame=runs)
 
     # what the two localisation taps (the map tap with its CAM head, the attention tap with its rollout head) share
     def _tap_info(self, fn, names) -> dict:

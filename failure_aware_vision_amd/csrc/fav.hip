@@ -33,6 +33,7 @@
 #include "fav_mapbox.hpp"
 #include "fav_cam.hpp"
 #include "fav_rollout.hpp"
+#include "fav_curve.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -188,6 +189,13 @@ struct fav_handle {
     // rows of the call (at most max_batch), a part at its frame offset
     LocTap attn_tap;
     fav::AttnTapDims attn;
+    // Curve descriptor (fav_set_curve): the descriptor in force and ONE buffer the setter allocates for max_batch frames, with
+    // its parts: occ (the occluded frames of one step, sized for fp32), rank [max_batch][1024], prob and lab (the planes
+    // [steps + 1][max_batch]), lab0 and conf0 (the unoccluded pass's label and confidence); curve_on: one is set
+    struct CurveDev { fav_curve desc{}; void* buf = nullptr; void* occ = nullptr; int32_t* rank = nullptr; float* prob = nullptr;
+                      int32_t* lab = nullptr; int32_t* lab0 = nullptr; float* conf0 = nullptr; };
+    CurveDev curve;
+    bool curve_on = false;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -658,8 +666,15 @@ const char* check_sweep(const HeadSweep& sw, int C, int T, int kind) {
     return nullptr;
 }
 
+// the class-probability head (fav_curve.hpp): pbar of classes[i] (NULL: of the frame's label) to prob, the label to labels (may be NULL)
+struct HeadClassProb {
+    const int32_t* classes;
+    float* prob;
+    int32_t* labels;
+};
+
 // What the head writes: labels and conf out_stride elements apart (2: interleaved records), the optional failure flags and
-// scores, and at most one of rec (one fav_uncertainty per frame), sets and sweep.  The public entry points build it;
+// scores, and at most one of rec (one fav_uncertainty per frame), sets, sweep and cprob.  The public entry points build it;
 // classify_gate and classify_on_stream pass it through.
 struct HeadOut {
     int32_t* labels = nullptr;
@@ -670,10 +685,12 @@ struct HeadOut {
     fav_uncertainty* rec = nullptr;
     const HeadSets* sets = nullptr;
     const HeadSweep* sweep = nullptr;
+    const HeadClassProb* cprob = nullptr;
 };
 
 // rec (one fav_uncertainty per frame) or conf_kind FAV_CONF_MUTUAL_INFO: head_unc_kernel; sets: head_sets_kernel;
-// sweep: head_sweep_kernel (temperature, tau, labels .. score are then not used); otherwise head_kernel
+// sweep: head_sweep_kernel (temperature, tau, labels .. score are then not used); cprob: head_class_prob_kernel (kind, tau,
+// labels .. score are not used); otherwise head_kernel
 const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C, int ld, float temperature, int kind,
                         float tau, const HeadOut& out, hipStream_t s) {
     const HeadSets* const sets = out.sets;
@@ -737,6 +754,17 @@ const char* launch_head(fav_handle* h, const float* logits, int T, int n, int C,
         Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + (sets->true_labels ? 8.0 : 0.0) * n +
                                        (sets->rec ? 160.0 : 0.0) * n + (out.fail ? 1.0 : 0.0) * n + (out.score ? 4.0 : 0.0) * n);
         FAV_LAUNCH_HEAD(head_sets_kernel, 0, inv_lnK, p, sets->true_labels, sets->true_scores, (int*)sets->rec, out.fail, out.score);
+    } else if (out.cprob) {
+        if (T < 1 || T > 4096) return "head: the class-probability head takes 1 <= T <= 4096 samples";
+        if (!out.cprob->prob || (((uintptr_t)out.cprob->prob | (uintptr_t)out.cprob->classes | (uintptr_t)out.cprob->labels) & 3))
+            return "head: prob must be non-NULL; prob, classes and labels 4-byte aligned";
+        Prof pr(h, s, FAV_K_HEAD, 0.0, 4.0 * (double)T * n * C + 12.0 * n);
+        if (C <= 256)
+            hipLaunchKernelGGL((head_class_prob_kernel<1>), dim3(n), dim3(256), 0, s, logits, T, n, C, ld, inv_temp, out.cprob->classes,
+                               out.cprob->prob, out.cprob->labels);
+        else
+            hipLaunchKernelGGL((head_class_prob_kernel<4>), dim3(n), dim3(256), 0, s, logits, T, n, C, ld, inv_temp, out.cprob->classes,
+                               out.cprob->prob, out.cprob->labels);
     } else if (out.rec || kind == FAV_CONF_MUTUAL_INFO) {
         if (T < 1 || T > 4096) return "head: the uncertainty head takes 1 <= T <= 4096 samples";
         // bytes: the logits, the second pass's p_t[label] reloads, the outputs
@@ -1098,7 +1126,7 @@ void free_all(fav_handle* h) {
     for (void* q : {(void*)h->ood.mu, (void*)h->ood.Pt, (void*)h->ood.Mt, (void*)h->ood.cls}) if (q) (void)hipFree(q);
     for (void* q : {h->knn.bank, h->knn.ws, (void*)h->knn.cls}) if (q) (void)hipFree(q);
     if (h->drift.ws) (void)hipFree(h->drift.ws);
-    for (void* q : {h->map_tap.buf, h->attn_tap.buf}) if (q) (void)hipFree(q);
+    for (void* q : {h->map_tap.buf, h->attn_tap.buf, h->curve.buf}) if (q) (void)hipFree(q);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
@@ -1214,6 +1242,42 @@ void launch_views_of(const U* in, U* out, int n, int H, int W, const fav_view* v
 void launch_views(const void* in, void* out, int n, int H, int W, int layout, const fav_view* views, int n_views, hipStream_t s) {
     if (layout == FAV_LAYOUT_NHWC_U8) launch_views_of((const uint8_t*)in, (uint8_t*)out, n, H, W, views, n_views, s);
     else launch_views_of((const uint32_t*)in, (uint32_t*)out, n, H, W, views, n_views, s);
+}
+
+// The launches behind the curve ops and fav_classify_curve (fav_curve.hpp).  The arguments have been checked.
+void launch_rank_cells(const float* map, int n, int cells, int32_t* rank, hipStream_t s) {
+    hipLaunchKernelGGL(rank_cells_kernel, dim3((unsigned)n), dim3(256), 0, s, map, cells, rank);
+}
+template <class U>
+void launch_occlude_of(const U* in, U* out, const int32_t* rank, int n, int H, int W, const OccludeArg& oa, hipStream_t s) {
+    const int G = 1 + (W + 3) / 4;
+    const int parts = (int)(((long long)H * G + 255) / 256);
+    const long long blocks = (long long)n * parts, max_grid = (1ll << 24) - 1;
+    const size_t units = (size_t)n * H * W * 3;
+    const U* lo = (const U*)(((uintptr_t)in + 3) & ~(uintptr_t)3);
+    const U* hi = (const U*)((uintptr_t)(in + units) & ~(uintptr_t)3);
+    hipLaunchKernelGGL((occlude_kernel<U>), dim3((unsigned)std::min(blocks, max_grid)), dim3(256), 0, s, in, out, rank, n, H, W, oa,
+                       parts, fastdiv_make((uint32_t)G), blocks, lo, hi);
+}
+void launch_occlude(const void* in, void* out, const int32_t* rank, int n, int H, int W, int layout, int mh, int mw, int mode, int S,
+                    int s0, int s1, const uint32_t* fill, hipStream_t s) {
+    OccludeArg oa;
+    memset(&oa, 0, sizeof oa);
+    for (int c = 0; c < 3; ++c) oa.fill[c] = layout == FAV_LAYOUT_NHWC_U8 ? (fill[c] & 255u) : fill[c];
+    oa.mode = mode; oa.S = S; oa.s0 = s0; oa.s1 = s1; oa.mh = mh; oa.mw = mw; oa.cells = mh * mw;
+    oa.wide = H > (1 << 23) || W > (1 << 23);
+    oa.div_h = fastdiv_make((uint32_t)H); oa.div_w = fastdiv_make((uint32_t)W);
+    if (layout == FAV_LAYOUT_NHWC_U8) launch_occlude_of((const uint8_t*)in, (uint8_t*)out, rank, n, H, W, oa, s);
+    else launch_occlude_of((const uint32_t*)in, (uint32_t*)out, rank, n, H, W, oa, s);
+}
+// num_classes = 0: not known, only a negative class is out of range
+void launch_curve(const float* prob, const int32_t* labels, const int32_t* classes, int n, int S, int cells, int mode, int num_classes,
+                  float* curve, fav_curve_record* rec, hipStream_t s) {
+    CurveParams cp;
+    cp.prob = prob; cp.labels = labels; cp.classes = classes; cp.curve = curve; cp.rec = (int32_t*)rec;
+    cp.n = n; cp.S = S; cp.cells = cells; cp.mode = mode; cp.num_classes = num_classes;
+    cp.half_step = (float)(0.5 / S);
+    hipLaunchKernelGGL(curve_kernel, dim3((unsigned)((n + CV_CURVE_THREADS - 1) / CV_CURVE_THREADS)), dim3(CV_CURVE_THREADS), 0, s, cp);
 }
 
 }  // namespace
@@ -1714,6 +1778,11 @@ fav_status fav_set_views(fav_handle* h, const fav_view* views, int32_t n_views) 
         if (fav_check_views(views, n_views, h->cfg.in_h, h->cfg.in_w, why, sizeof why) != FAV_OK) {
             h->err = fmt("fav_set_views: %s", why);
             return FAV_ERR_INVALID_ARG;
+        }
+        if (h->curve_on) {
+            h->err = "fav_set_views: a curve descriptor is set; an occluded frame's views are not what the map was made for (clear it "
+                     "first: fav_set_curve)";
+            return FAV_ERR_UNSUPPORTED;
         }
         if (!h->vit && h->plan.has_mc) {
             h->err = "fav_set_views: this handle draws MC-Dropout masks, which are keyed by batch row; views are not supported on it";
@@ -2486,6 +2555,125 @@ fav_status fav_classify_rollout(fav_handle* h, const void* images, int32_t n, in
                              score, stream, [&](hipStream_t s) { return rollout_on_tap(h, first_layer, map, rec, s); });
 }
 
+// ---- deletion / insertion curves (fav_curve.hpp) --------------------------------
+fav_status fav_check_curve(const fav_curve* desc, int32_t H, int32_t W, int32_t layout, char* err, size_t err_cap) {
+    static_assert(sizeof(fav_curve) == 32, "fav_curve is 8 dwords");
+    return check_reply(curve_desc_error(desc, H, W, layout), err, err_cap);
+}
+
+fav_status fav_set_curve(fav_handle* h, const fav_curve* desc) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!desc) {
+        if (!h->curve_on) return FAV_OK;
+        HIP_TRY(h, hipSetDevice(h->cfg.device));
+        if (fav_status st = wait_enqueued(h)) return st;
+        h->curve_on = false;
+        void* buf = h->curve.buf;
+        h->curve = fav_handle::CurveDev{};
+        if (buf) HIP_TRY(h, hipFree(buf));
+        return FAV_OK;
+    }
+    std::string why = curve_desc_error(desc, h->cfg.in_h, h->cfg.in_w, FAV_LAYOUT_NHWC_U8);
+    if (why.empty()) why = curve_desc_error(desc, h->cfg.in_h, h->cfg.in_w, FAV_LAYOUT_NHWC_F32);
+    if (!why.empty()) { h->err = fmt("fav_set_curve: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (h->n_views > 0) {
+        h->err = "fav_set_curve: views are set; an occluded frame's views are not what the map was made for (turn them off first: "
+                 "fav_set_views)";
+        return FAV_ERR_UNSUPPORTED;
+    }
+    // one buffer, every part on a 256-byte boundary
+    const size_t B = (size_t)h->cfg.max_batch, planes = (size_t)desc->steps + 1;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t occ_b = pad(B * h->cfg.in_h * h->cfg.in_w * 3 * 4), rank_b = pad(B * CV_MAX_CELLS * 4), plane_b = pad(planes * B * 4),
+                 first_b = pad(B * 4);
+    const size_t bytes = occ_b + rank_b + 2 * plane_b + 2 * first_b;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    fav_handle::CurveDev nw;
+    nw.desc = *desc;
+    if (hipMalloc(&nw.buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->err = fmt("fav_set_curve: cannot allocate the %zu bytes a curve of max_batch=%d frames and %d steps takes", bytes,
+                     (int)h->cfg.max_batch, desc->steps);
+        return FAV_ERR_HIP;
+    }
+    char* q = (char*)nw.buf;
+    nw.occ = q; q += occ_b;
+    nw.rank = (int32_t*)q; q += rank_b;
+    nw.prob = (float*)q; q += plane_b;
+    nw.lab = (int32_t*)q; q += plane_b;
+    nw.lab0 = (int32_t*)q; q += first_b;
+    nw.conf0 = (float*)q;
+    if (h->curve_on) {      // replacing: what is enqueued still uses the old buffer
+        if (fav_status st = wait_enqueued(h)) { (void)hipFree(nw.buf); return st; }
+        if (h->curve.buf) (void)hipFree(h->curve.buf);
+    }
+    h->curve = nw;
+    h->curve_on = true;
+    return FAV_OK;
+}
+
+fav_status fav_classify_curve(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, const float* map,
+                              int32_t mh, int32_t mw, const int32_t* classes, int32_t mode, int32_t* labels, float* conf, float* curve,
+                              fav_curve_record* rec, void* stream) {
+    static_assert(sizeof(fav_curve_record) == 32, "fav_curve_record is 8 dwords");
+    const char* fn = "fav_classify_curve";
+    route_clear();
+    if (!h) return FAV_ERR_INVALID_ARG;
+    auto refuse = [&](const std::string& why) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; };
+    if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", fn); return FAV_ERR_NO_WEIGHTS; }
+    if (!h->curve_on) return refuse("no curve descriptor set (fav_set_curve)");
+    if (!images || !map || !curve || !rec || (((uintptr_t)map | (uintptr_t)curve | (uintptr_t)classes | (uintptr_t)labels | (uintptr_t)conf) & 3) ||
+        ((uintptr_t)rec & 7))
+        return refuse(kBadRecords);
+    if (n < 1 || n > h->cfg.max_batch) return refuse(fmt("n=%d outside [1, max_batch=%d]", n, h->cfg.max_batch));
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return refuse("unknown layout");
+    if (layout == FAV_LAYOUT_NHWC_F32 && ((uintptr_t)images & 3)) return refuse("fp32 frames must be 4-byte aligned");
+    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) return refuse("first_image_index out of range");
+    std::string why = curve_mode_error(mode);
+    if (why.empty()) why = curve_map_error(mh, mw);
+    if (!why.empty()) return refuse(why);
+    if (h->n_views > 0) { h->err = fmt("%s: views are set", fn); return FAV_ERR_UNSUPPORTED; }   // fav_set_views refuses them; kept as a guard
+    const fav_handle::CurveDev& cv = h->curve;
+    const int S = cv.desc.steps, cells = mh * mw, H = h->cfg.in_h, W = h->cfg.in_w;
+    const uint32_t* fill = layout == FAV_LAYOUT_NHWC_U8 ? cv.desc.fill_u8 : cv.desc.fill_f32_bits;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_last_use(h, s)) return st;
+    launch_rank_cells(map, n, cells, cv.rank, s);
+    // the unoccluded pass writes the caller's labels and confidences, or the handle's own copies
+    int32_t* const lab0 = labels ? labels : cv.lab0;
+    const int32_t* const cls = classes ? classes : lab0;
+    fav_status st = FAV_OK;
+    for (int k = 0; k <= S && st == FAV_OK; ++k) {
+        const int step = mode == FAV_CURVE_DELETION ? k : S - k;         // the unoccluded step first, then by increasing occlusion
+        launch_occlude(images, cv.occ, cv.rank, n, H, W, layout, mh, mw, mode, S, step, step + 1, fill, s);
+        const Frames f{cv.occ, layout, n, first_index};
+        const HeadClassProb cp{cls, cv.prob + (size_t)step * n, cv.lab + (size_t)step * n};
+        HeadOut out;
+        if (k == 0) {
+            out.labels = lab0; out.conf = conf ? conf : cv.conf0;
+            st = classify_on_stream(h, f, out, s);
+            if (st != FAV_OK) break;
+            HeadOut second;
+            second.cprob = &cp;
+            if (const char* e = launch_head(h, h->logits, h->last_T, n, h->cfg.num_classes, h->plan.cpad, h->cfg.temperature,
+                                            h->cfg.conf_kind, h->cfg.tau, second, s)) {
+                h->err = fmt("%s: %s", fn, e);
+                st = FAV_ERR_INVALID_ARG;
+            }
+        } else {
+            out.cprob = &cp;
+            st = classify_on_stream(h, f, out, s);
+        }
+    }
+    if (st == FAV_OK) launch_curve(cv.prob, cv.lab, cls, n, S, cells, mode, h->cfg.num_classes, curve, rec, s);
+    route_clear();            // the report speaks of fav_op_* launches only
+    mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
+    if (st != FAV_OK) return st;
+    HIP_TRY(h, hipGetLastError());
+    return FAV_OK;
+}
+
 fav_status fav_set_profiling(fav_handle* h, int32_t enable) {
     if (!h) return FAV_ERR_INVALID_ARG;
     h->profiling = enable != 0;
@@ -3012,6 +3200,71 @@ fav_status fav_op_attn_rollout(const float* a, int32_t L, int32_t n, int32_t gh,
     if (((uintptr_t)a | (uintptr_t)map) & 3) return op_rejected(fn, "a_dev and map_dev must be 4-byte aligned");
     if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
     launch_rollout(a, (long long)n * (gh * gw + 1) * ld, L, n, gh, gw, ld, first_layer, map, rec, (hipStream_t)stream);
+    return op_done(nullptr);
+}
+
+fav_status fav_op_rank_cells(const float* map, int32_t n, int32_t cells, int32_t* rank, void* stream) {
+    const char* fn = "fav_op_rank_cells";
+    route_clear();
+    if (!map || !rank) return op_rejected(fn, "null pointer");
+    if (n < 1) return op_rejected(fn, "n must be at least 1");
+    if (cells < 1 || cells > CV_MAX_CELLS) return op_rejected(fn, fmt("cells=%d outside [1, %d]", cells, CV_MAX_CELLS).c_str());
+    if (((uintptr_t)map | (uintptr_t)rank) & 3) return op_rejected(fn, "map_dev and rank_dev must be 4-byte aligned");
+    launch_rank_cells(map, n, cells, rank, (hipStream_t)stream);
+    return op_done(nullptr);
+}
+
+fav_status fav_op_occlude(const void* frames, void* out, int32_t n, int32_t H, int32_t W, int32_t layout, const int32_t* rank,
+                          int32_t mh, int32_t mw, int32_t mode, int32_t S, int32_t s0, int32_t s1, const uint32_t* fill, void* stream) {
+    const char* fn = "fav_op_occlude";
+    route_clear();
+    if (!frames || !out || !rank || !fill) return op_rejected(fn, "null pointer");
+    if (n < 1) return op_rejected(fn, "n must be at least 1");
+    std::string why = curve_frame_error(H, W, layout);
+    if (why.empty()) why = curve_steps_error(S);
+    if (why.empty()) why = curve_map_error(mh, mw);
+    if (why.empty()) why = curve_mode_error(mode);
+    if (why.empty() && (s0 < 0 || s0 >= s1 || s1 > S + 1)) why = fmt("steps [%d, %d) outside 0 <= s0 < s1 <= S + 1 = %d", s0, s1, S + 1);
+    if (why.empty()) why = curve_fill_error(fill, layout);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    const size_t esz = layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4;
+    if (((uintptr_t)frames | (uintptr_t)out) % esz != 0) return op_rejected(fn, "fp32 frames and out must be 4-byte aligned");
+    if ((uintptr_t)rank & 3) return op_rejected(fn, "rank_dev must be 4-byte aligned");
+    if ((long long)n * (s1 - s0) > 0x7FFFFFFFll) return op_rejected(fn, "n * (s1 - s0) above 2^31 - 1");
+    const long long frame_bytes = (long long)H * W * 3 * (long long)esz;
+    const uintptr_t in_lo = (uintptr_t)frames, in_hi = in_lo + (uintptr_t)frame_bytes * (uintptr_t)n;
+    const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + (uintptr_t)frame_bytes * (uintptr_t)n * (uintptr_t)(s1 - s0);
+    if (in_lo < out_hi && out_lo < in_hi) return op_rejected(fn, "out overlaps frames");
+    launch_occlude(frames, out, rank, n, H, W, layout, mh, mw, mode, S, s0, s1, fill, (hipStream_t)stream);
+    return op_done(nullptr);
+}
+
+fav_status fav_op_head_class_prob(const float* logits, int32_t T, int32_t n, int32_t C, int32_t ld, float temperature,
+                                  const int32_t* classes, float* prob, int32_t* labels, void* stream) {
+    const char* fn = "fav_op_head_class_prob";
+    route_clear();
+    if (!logits || !prob) return op_rejected(fn, "null pointer");
+    if (T < 1 || T > 4096 || n < 1 || !(temperature > 0.f)) return op_rejected(fn, "needs 1 <= T <= 4096, n >= 1 and temperature > 0");
+    const HeadClassProb cp{classes, prob, labels};
+    HeadOut out;
+    out.cprob = &cp;
+    return op_done(fn, launch_head(nullptr, logits, T, n, C, ld, temperature, 0, 0.f, out, (hipStream_t)stream));
+}
+
+fav_status fav_op_curve(const float* prob, const int32_t* labels, const int32_t* classes, int32_t n, int32_t S, int32_t cells,
+                        int32_t mode, float* curve, fav_curve_record* rec, void* stream) {
+    const char* fn = "fav_op_curve";
+    route_clear();
+    if (!prob || !labels || !classes || !curve || !rec) return op_rejected(fn, "null pointer");
+    if (n < 1) return op_rejected(fn, "n must be at least 1");
+    std::string why = curve_steps_error(S);
+    if (why.empty() && (cells < 1 || cells > CV_MAX_CELLS)) why = fmt("cells=%d outside [1, %d]", cells, CV_MAX_CELLS);
+    if (why.empty()) why = curve_mode_error(mode);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    if (((uintptr_t)prob | (uintptr_t)labels | (uintptr_t)classes | (uintptr_t)curve) & 3)
+        return op_rejected(fn, "prob_dev, labels_dev, classes_dev and curve_dev must be 4-byte aligned");
+    if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
+    launch_curve(prob, labels, classes, n, S, cells, mode, 0, curve, rec, (hipStream_t)stream);
     return op_done(nullptr);
 }
 

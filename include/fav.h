@@ -602,6 +602,70 @@ fav_status fav_classify_rollout(fav_handle* h, const void* images_dev, int32_t n
                                 int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev, int32_t first_layer,
                                 float* map_dev, fav_rollout_record* rec_dev, void* hip_stream);
 
+/* ---- Deletion / insertion curves (Petsiuk et al. 2018, RISE).  The two heads above say WHERE a
+ * decision comes from; this one says whether such a map means anything for the checkpoint in use.  The cells of a map are
+ * ranked, most salient first; the frames are classified again with the k_s most salient cells filled (deletion) or with only
+ * those cells shown on a filled frame (insertion), for s = 0 .. S, and the probability of one class is integrated over the
+ * steps.  A faithful map makes deletion fall fast (low AUC) and insertion rise fast (high AUC), both against a random ranking.
+ * No labels, no boxes, no backward pass; any arch, any source of samples, any map - CAM, rollout or the caller's own.  What the
+ * tests of this library verify is the algebra and its bits on synthetic checkpoints, where the SIGN of a gain carries no
+ * meaning; whether a map is faithful is a property of trained weights.
+ *
+ * One frame's curve summary, 32 bytes, 8-byte aligned.  With p[s] = prob[s][i] the class probability of frame i at step s and
+ * lab[s] = labels[s][i] the label of that pass, everything fp32, every operation rounded on its own, in this order:
+ *   1. curve[i][s] = p[s]
+ *   2. auc         acc = +0; for s = 0 .. S-1 in order acc = acc + (p[s] + p[s+1]); auc = acc * (float)(0.5 / S), the
+ *                  constant rounded once from double
+ *   3. p_first = p[0], p_last = p[S]; p_min: best = +inf, for s ascending: if (p[s] < best) best = p[s] - a NaN never wins
+ *   4. flip_step   FAV_CURVE_DELETION: the first s with lab[s] != class_id; FAV_CURVE_INSERTION: the first s with
+ *                  lab[s] == class_id; -1 when there is none.  flip_cells = flip_step * cells / S in integer division (the
+ *                  cells occluded, or shown, at that step), or -1
+ *   5. reserved = 0
+ *   6. a class outside the range: class_id = -1, the four floats NaN, flip_step = flip_cells = -1; the curve row is still
+ *      what the class-probability head wrote, which is NaN
+ * Non-finite probabilities have no rule of their own: the chains carry them. */
+typedef enum fav_curve_mode { FAV_CURVE_DELETION = 0, FAV_CURVE_INSERTION = 1 } fav_curve_mode;
+typedef struct fav_curve_record { int32_t class_id; float auc, p_first; int32_t flip_step; float p_last, p_min;
+                                  int32_t flip_cells, reserved; } fav_curve_record;
+/* The descriptor of a handle's curves: S = steps in [1, 256]; the fill of an occluded pixel, a byte a channel for uint8 frames
+ * (each <= 255) and the bits of an fp32 a channel for fp32 frames (any word). */
+typedef struct fav_curve { uint32_t struct_size; int32_t steps; uint32_t fill_u8[3]; uint32_t fill_f32_bits[3]; } fav_curve;   /* 32 bytes */
+/* Host only, no device: the descriptor's ranges for H x W frames of `layout`, the one place they live; fav_set_curve calls it
+ * first, for both layouts.  Refused (FAV_ERR_INVALID_ARG, a message in err, which may be NULL): a NULL descriptor, a wrong
+ * struct_size, steps outside [1, 256], H or W below 1, an unknown layout, H * W above (2^31 - 1) / 12, and under
+ * FAV_LAYOUT_NHWC_U8 a fill_u8 above 255. */
+fav_status fav_check_curve(const fav_curve* desc, int32_t H, int32_t W, int32_t layout, char* err, size_t err_cap);
+/* The handle's curve descriptor (copied; NULL: none, the default).  The setter validates it and allocates everything a later
+ * fav_classify_curve needs for max_batch frames, in one buffer: the occluded frames of ONE step sized for the fp32 layout, the
+ * ranks [max_batch][1024], the probability and label planes [steps + 1][max_batch] and the first pass's labels and confidences.
+ * It may synchronise; a refusal for lack of memory carries the size.  Replacing or clearing waits on the host for the work
+ * enqueued on the handle and frees the old buffer.  FAV_ERR_UNSUPPORTED while views are set, and fav_set_views is refused
+ * (FAV_ERR_UNSUPPORTED) while a descriptor is set: an occluded frame's views are not what the map was made for.  A rejected call
+ * leaves the handle as it was.  With no descriptor set a fav_classify* call enqueues exactly what it did before; with one set, too. */
+fav_status fav_set_curve(fav_handle* h, const fav_curve* desc);
+/* The curve of n frames under one map each: map_dev fp32 [n][mh*mw] (4-byte aligned; 1 <= mh*mw <= 1024, mh, mw <= 256),
+ * classes_dev int32 [n] or NULL: the class whose probability is followed - NULL: the label of the unoccluded pass, read on the
+ * device, so nothing synchronises.  Outputs: curve_dev fp32 [n][steps + 1] (4-byte aligned), rec_dev [n] (8-byte aligned),
+ * labels_dev / conf_dev (either may be NULL): label and confidence of the unoccluded pass, bit-identical to fav_classify_ex on
+ * the same frames.  Never allocates or synchronises.  Enqueued on hip_stream, in this order:
+ *   1. fav_op_rank_cells on the maps
+ *   2. for every step: fav_op_occlude with s1 - s0 = 1 into the handle's buffer, the unchanged forward pass of fav_classify_ex
+ *      on it, and fav_op_head_class_prob into the step's plane (the unoccluded step also runs the handle's own head for
+ *      labels_dev / conf_dev).  The unoccluded step runs first - step 0 for deletion, step S for insertion - and the others
+ *      follow by increasing occlusion (deletion 1 .. S, insertion S-1 .. 0)
+ *   3. fav_op_curve
+ * Every pass gets the SAME first_image_index.  MC-Dropout masks are keyed by the global frame index, so all steps of a frame
+ * see the same masks (common random numbers): the curve then moves with the occlusion only, not with the draw.  Ensembles and
+ * ViTs need nothing special: the class-probability head is a function of [T][n][ld] logits.  Afterwards fav_get_logits returns
+ * the LAST pass, which is the fully occluded one, and every tap that is on holds that pass.  A class >= num_classes is outside
+ * the range like a negative one.  The launches of steps 1 and 3 and the occlusions are booked in no kernel class.
+ * FAV_ERR_INVALID_ARG: no descriptor set, n outside [1, max_batch], an unknown layout or mode, a map out of range, a NULL or
+ * misaligned map, curve or record buffer, misaligned fp32 frames. */
+fav_status fav_classify_curve(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
+                              const float* map_dev, int32_t mh, int32_t mw, const int32_t* classes_dev, int32_t mode,
+                              int32_t* labels_dev, float* conf_dev, float* curve_dev, fav_curve_record* rec_dev,
+                              void* hip_stream);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -970,6 +1034,50 @@ fav_status fav_op_attn_mean(const void* qkv_bf16, float* a_dev, int32_t n, int32
  * gh * gw + 1 <= 256; ld >= T, a multiple of 4.  Refusals as fav_op_attn_mean. */
 fav_status fav_op_attn_rollout(const float* a_dev, int32_t L, int32_t n, int32_t gh, int32_t gw, int32_t ld, int32_t first_layer,
                                float* map_dev, fav_rollout_record* rec_dev, void* hip_stream);
+
+/* ---- The four operations behind fav_classify_curve, on device arrays.  Each: one launch, no allocation, no workspace, no
+ * synchronisation, vector stores only.  A refused call (FAV_ERR_INVALID_ARG) launches nothing and leaves a message that names
+ * the function in fav_last_error(NULL).
+ *
+ * The ranking: map_dev fp32 [n][cells] -> rank_dev int32 [n][cells] (both 4-byte aligned), n >= 1, 1 <= cells <= 1024.
+ * rank[i][c] = the number of cells of frame i that come before c in the order "more salient first".  Cell a comes before b when
+ *   - a is not NaN and b is NaN, or
+ *   - both are not NaN and M[a] > M[b], or
+ *   - neither value is greater - equal values, +0 against -0, both NaN - and a < b.
+ * So every NaN ranks behind -inf, ties go to the lower index, and the ranks of a frame are a permutation of 0 .. cells-1.  One
+ * block a frame, the comparisons run from LDS. */
+fav_status fav_op_rank_cells(const float* map_dev, int32_t n, int32_t cells, int32_t* rank_dev, void* hip_stream);
+/* The occlusion: frames [n][H][W][3] of `layout` -> out [s1 - s0][n][H][W][3] of the same element type, the steps s0 .. s1-1
+ * of S, 0 <= s0 < s1 <= S + 1.  With cells = mh * mw:
+ *   1. the cell of pixel (y, x) is (y * mh / H) * mw + (x * mw / W), integer division (a map finer than the frame is legal:
+ *      some cells then hold no pixel)
+ *   2. k_s = s * cells / S, integer division, for s = 0 .. S: k_0 = 0, k_S = cells
+ *   3. FAV_CURVE_DELETION: a pixel of step s is `fill` when rank[i][cell] < k_s, else the source pixel;
+ *      FAV_CURVE_INSERTION: the source pixel when rank[i][cell] < k_s, else `fill`
+ * Every copied element is copied bit for bit (an fp32 NaN keeps its payload, as in fav_op_views).  fill: three words read before
+ * the call returns - under uint8 each <= 255 and its low byte is stored, under fp32 the word is the fp32's bits.  rank_dev int32
+ * [n][cells] is NOT validated on the device: any value below k_s occludes, so a caller may bring a ranking that is no permutation.
+ * Ranges: n, H, W >= 1; 1 <= S <= 256; 1 <= mh * mw <= 1024 with mh, mw <= 256; H * W at most (2^31 - 1) / 12;
+ * n * (s1 - s0) at most 2^31 - 1; frames and out need the element type's alignment only (any byte for uint8, 4 for fp32),
+ * rank_dev 4; out must not overlap frames.  The source pixels are read once, whatever s1 - s0 is. */
+fav_status fav_op_occlude(const void* frames_dev, void* out_dev, int32_t n, int32_t H, int32_t W, int32_t layout,
+                          const int32_t* rank_dev, int32_t mh, int32_t mw, int32_t mode, int32_t S, int32_t s0, int32_t s1,
+                          const uint32_t* fill, void* hip_stream);
+/* The class-probability head: logits fp32 [T][n][ld] -> prob_dev fp32 [n] and labels_dev int32 [n] (may be NULL).  pbar is
+ * computed by the heads' shared core exactly as fav_classify_ex computes it; prob[i] = pbar[classes_dev[i]], labels[i] is
+ * fav_classify_ex's label.  classes_dev int32 [n] may be NULL: the frame's own label - prob is then the mean_prob of
+ * fav_uncertainty, bit for bit.  A class outside [0, num_classes) gives prob = NaN, the label is still written.  A non-finite
+ * frame (the rule above fav_classify) gives prob = NaN and label 0.  T <= 4096, num_classes <= 1024, ld >= num_classes and a
+ * multiple of 4, temperature > 0; only the first num_classes values of a row are read. */
+fav_status fav_op_head_class_prob(const float* logits, int32_t T, int32_t n, int32_t num_classes, int32_t ld, float temperature,
+                                  const int32_t* classes_dev, float* prob_dev, int32_t* labels_dev, void* hip_stream);
+/* The curve head defined beside fav_curve_record: prob_dev fp32 [S + 1][n], labels_dev int32 [S + 1][n], classes_dev int32 [n]
+ * -> curve_dev fp32 [n][S + 1] (all 4-byte aligned) and rec_dev [n] (8-byte aligned).  n >= 1, 1 <= S <= 256,
+ * 1 <= cells <= 1024, mode a fav_curve_mode value.  A thread a frame.  This entry point is not told the number of classes: the
+ * class outside the range is, for it, a negative one (the class-probability head has written NaN for any other, and the chains
+ * carry it); fav_classify_curve passes the handle's num_classes along. */
+fav_status fav_op_curve(const float* prob_dev, const int32_t* labels_dev, const int32_t* classes_dev, int32_t n, int32_t S,
+                        int32_t cells, int32_t mode, float* curve_dev, fav_curve_record* rec_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
