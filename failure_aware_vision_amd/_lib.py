@@ -176,6 +176,19 @@ class FavCurveRecord(C.Structure):
                 ("p_last", C.c_float), ("p_min", C.c_float), ("flip_cells", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FavRise(C.Structure):
+    """fav_rise: the masks of a RISE map - their number, the grid, the keep threshold in 256ths, the seed - and the fill of a
+    masked-out pixel in either layout (48 bytes)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_masks", C.c_int32), ("grid", C.c_int32), ("keep", C.c_int32), ("seed", C.c_uint64),
+                ("fill_u8", C.c_uint32 * 3), ("fill_f32_bits", C.c_uint32 * 3)]
+
+
+class FavRiseRecord(C.Structure):
+    """fav_rise_record: one 32-byte summary per frame (rise.unpack_rise_records reads it as int32[..., 8])."""
+    _fields_ = [("class_id", C.c_int32), ("p_full", C.c_float), ("peak", C.c_float), ("peak_cell", C.c_int32),
+                ("floor", C.c_float), ("p_mean", C.c_float), ("n_above", C.c_int32), ("box", C.c_int32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -274,6 +287,14 @@ _SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_op_curve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                C.c_void_p, C.c_void_p]),
+    "fav_check_rise": (C.c_int, [C.POINTER(FavRise), C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    "fav_set_rise": (C.c_int, [C.c_void_p, C.POINTER(FavRise)]),
+    "fav_classify_rise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_rise_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(FavRise), C.c_int64,
+                                   C.c_int32, C.c_int32, C.c_void_p]),
+    "fav_op_rise_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FavRise), C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),

@@ -755,6 +755,76 @@ class Backend:
         rep = summarize_curves(runs["map_deletion"], runs["map_insertion"], runs["random_deletion"], runs["random_insertion"], mh * mw)
         return dict(rep, steps=int(steps), map_hw=(mh, mw), per_frame=runs)
 
+    # -- RISE saliency (rise.py; include/fav.h fav_set_rise, fav_classify_rise) --------------------------------------------------
+    def set_rise(self, n_masks: int | None = 256, grid: int = 7, keep: float = 0.5, seed: int = 0, fill=None):
+        """Prepare the handle for ``classify_rise`` (fav_set_rise): ``n_masks`` random masks (1 .. 8192) a frame, each a
+        (grid+1) x (grid+1) grid of cells (``grid`` 1 .. 15, at most the frame's shorter side) that are ON with probability
+        ``keep`` - stored as round(256 keep), 1 .. 255 -, shifted at random and upsampled bilinearly; ``seed`` keys the draws.  A
+        masked-out pixel becomes ``fill`` as in ``set_curve``.  Everything a later call needs is allocated here, for max_batch
+        frames.  ``n_masks`` None: clear.  Refused while views are set, and views are refused while this is; independent of
+        ``set_curve``."""
+        from .rise import keep_threshold
+        if n_masks is None:
+            _lib.check(self.lib.fav_set_rise(self._h, None), self._h)
+            return
+        d = _lib.FavRise()
+        d.struct_size = C.sizeof(_lib.FavRise)
+        d.n_masks, d.grid, d.keep, d.seed = int(n_masks), int(grid), keep_threshold(keep), int(seed) & 0xFFFFFFFFFFFFFFFF
+        if fill is None:
+            u8, f32 = (128, 128, 128), (0.5, 0.5, 0.5)
+        else:
+            f32 = tuple(float(v) for v in (fill if np.ndim(fill) else (fill,) * 3))
+            if len(f32) != 3:
+                raise ValueError("fill is a number or a 3-tuple")
+            u8 = tuple(int(round(255.0 * v)) for v in f32)
+        for c in range(3):
+            d.fill_u8[c] = u8[c] & 0xFFFFFFFF
+            d.fill_f32_bits[c] = int(np.float32(f32[c]).view(np.uint32))
+        _lib.check(self.lib.fav_set_rise(self._h, C.byref(d)), self._h)
+
+    def classify_rise(self, frames, classes=None, map_hw=(14, 14), heatmap: bool = False, first_index: int = 0) -> dict:
+        """The RISE saliency map of every frame (fav_classify_rise): ``classes`` int [n], or None: each frame's label on the
+        unmasked frame, read on the device; ``map_hw`` the cells of the map, at most 1024 and no finer than the frame.  ->
+        ``map`` fp32 [n, mh, mw] (the class probability averaged over the masks, weighted by how much of the cell each mask
+        showed), the record fields of ``rise.unpack_rise_records``, each [n], and ``label``, ``confidence`` of the unmasked pass.
+        ``heatmap``: also ``heatmap`` uint8 [n, H, W], the overlay fav_op_cam_heatmap draws from the map and its record.  Costs
+        n_masks + 1 forward passes a frame; every pass of a frame draws the same MC-Dropout masks.  Works on every arch, a deep
+        ensemble included: ``faithfulness_report(frames, maps=classify_rise(frames)["map"])`` scores the map.  Frames beyond
+        ``frames_per_call`` go in further calls with ``first_index`` advanced.  torch CUDA frames in -> CUDA tensors out,
+        asynchronous on the current stream; numpy in -> numpy out.  Needs ``set_rise``."""
+        from .rise import RISE_RECORD_DWORDS, unpack_rise_records
+        torch = self._torch
+        img, host, n, layout, stream = self._classify_args(frames)
+        dev = img.device
+        mh, mw = (int(v) for v in map_hw)
+        if mh < 1 or mw < 1:
+            raise ValueError(f"map_hw must be two positive sizes, got {map_hw!r}")
+        cls = None
+        if classes is not None:
+            cls = torch.as_tensor(np.asarray(classes) if not hasattr(classes, "is_cuda") else classes).to(device=dev, dtype=torch.int32)
+            cls = cls.contiguous()
+            if tuple(cls.shape) != (n,):
+                raise ValueError(f"classes must be [n] for the n={n} frames, got {tuple(cls.shape)}")
+        m = torch.empty((n, mh, mw), dtype=torch.float32, device=dev)
+        rec = torch.empty((n, RISE_RECORD_DWORDS), dtype=torch.int32, device=dev)
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        conf = torch.empty(n, dtype=torch.float32, device=dev)
+        for b, e in (self._batches(n) if n else ()):
+            _lib.check(self.lib.fav_classify_rise(
+                self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b, cls[b:e].data_ptr() if cls is not None else None,
+                mh, mw, labels[b:e].data_ptr(), conf[b:e].data_ptr(), m[b:e].data_ptr(), rec[b:e].data_ptr(), stream), self._h)
+        out = dict(map=m, label=labels, confidence=conf)
+        if heatmap:
+            H, W = int(self.cfg.in_h), int(self.cfg.in_w)
+            heat = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+            if n:
+                _lib.check(self.lib.fav_op_cam_heatmap(m.data_ptr(), rec.data_ptr(), n, mh, mw, H, W, heat.data_ptr(), stream))
+            out["heatmap"] = heat
+        if host:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+            rec = rec.cpu().numpy()
+        return dict(unpack_rise_records(rec), **out)
+
     # what the two localisation taps (the map tap with its CAM head, the attention tap with its rollout head) share
     def _tap_info(self, fn, names) -> dict:
         """fav_map_tap_info / fav_attn_tap_info (``fn``) -> ``bytes`` of the buffer and the int32 sizes under ``names``."""

@@ -34,6 +34,7 @@
 #include "fav_cam.hpp"
 #include "fav_rollout.hpp"
 #include "fav_curve.hpp"
+#include "fav_rise.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -196,6 +197,13 @@ struct fav_handle {
                       int32_t* lab = nullptr; int32_t* lab0 = nullptr; float* conf0 = nullptr; };
     CurveDev curve;
     bool curve_on = false;
+    // RISE descriptor (fav_set_rise): the descriptor in force and ONE buffer the setter allocates for max_batch frames, with its
+    // parts: masked (the masked frames of one pass, sized for fp32), prob (the planes [n_masks + 1][max_batch]), lab0 and conf0
+    // (the unmasked pass's label and confidence); rise_on: one is set
+    struct RiseDev { fav_rise desc{}; void* buf = nullptr; void* masked = nullptr; float* prob = nullptr; int32_t* lab0 = nullptr;
+                     float* conf0 = nullptr; };
+    RiseDev rise;
+    bool rise_on = false;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
     void *v_patches = nullptr, *v_emb = nullptr, *v_x = nullptr, *v_y = nullptr, *v_qkv = nullptr, *v_hid = nullptr, *v_cls = nullptr;
@@ -1126,7 +1134,7 @@ void free_all(fav_handle* h) {
     for (void* q : {(void*)h->ood.mu, (void*)h->ood.Pt, (void*)h->ood.Mt, (void*)h->ood.cls}) if (q) (void)hipFree(q);
     for (void* q : {h->knn.bank, h->knn.ws, (void*)h->knn.cls}) if (q) (void)hipFree(q);
     if (h->drift.ws) (void)hipFree(h->drift.ws);
-    for (void* q : {h->map_tap.buf, h->attn_tap.buf, h->curve.buf}) if (q) (void)hipFree(q);
+    for (void* q : {h->map_tap.buf, h->attn_tap.buf, h->curve.buf, h->rise.buf}) if (q) (void)hipFree(q);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
@@ -1278,6 +1286,37 @@ void launch_curve(const float* prob, const int32_t* labels, const int32_t* class
     cp.n = n; cp.S = S; cp.cells = cells; cp.mode = mode; cp.num_classes = num_classes;
     cp.half_step = (float)(0.5 / S);
     hipLaunchKernelGGL(curve_kernel, dim3((unsigned)((n + CV_CURVE_THREADS - 1) / CV_CURVE_THREADS)), dim3(CV_CURVE_THREADS), 0, s, cp);
+}
+
+// The launches behind the RISE ops and fav_classify_rise (fav_rise.hpp).  The arguments have been checked.
+template <class U>
+void launch_rise_mask_of(const U* in, U* out, int n, int H, int W, const RiseArg& ra, const uint32_t* fill, int m0, int m1, hipStream_t s) {
+    const int G = 1 + (W + 3) / 4;
+    const int parts = (int)(((long long)H * G + 255) / 256);
+    const long long blocks = (long long)n * parts, max_grid = (1ll << 24) - 1;
+    const size_t units = (size_t)n * H * W * 3;
+    const U* lo = (const U*)(((uintptr_t)in + 3) & ~(uintptr_t)3);
+    const U* hi = (const U*)((uintptr_t)(in + units) & ~(uintptr_t)3);
+    hipLaunchKernelGGL((rise_mask_kernel<U>), dim3((unsigned)std::min(blocks, max_grid)), dim3(256), 0, s, in, out, n, H, W, ra, fill[0],
+                       fill[1], fill[2], m0, m1, parts, fastdiv_make((uint32_t)G), blocks, lo, hi);
+}
+void launch_rise_mask(const void* in, void* out, int n, int H, int W, int layout, const fav_rise& d, long long first_index, int m0, int m1,
+                      hipStream_t s) {
+    const RiseArg ra = rise_arg(d, first_index, H, W);
+    uint32_t fill[3];
+    for (int c = 0; c < 3; ++c) fill[c] = layout == FAV_LAYOUT_NHWC_U8 ? (d.fill_u8[c] & 255u) : d.fill_f32_bits[c];
+    if (layout == FAV_LAYOUT_NHWC_U8) launch_rise_mask_of((const uint8_t*)in, (uint8_t*)out, n, H, W, ra, fill, m0, m1, s);
+    else launch_rise_mask_of((const uint32_t*)in, (uint32_t*)out, n, H, W, ra, fill, m0, m1, s);
+}
+// num_classes = 0: not known, only a negative class is out of range
+void launch_rise_accumulate(const float* prob, const int32_t* classes, int n, const fav_rise& d, long long first_index, int H, int W, int mh,
+                            int mw, int num_classes, float* map, fav_rise_record* rec, hipStream_t s) {
+    RiseAccParams p;
+    p.prob = prob; p.classes = classes; p.map = map; p.rec = (int32_t*)rec;
+    p.ra = rise_arg(d, first_index, H, W);
+    p.n = n; p.N = d.n_masks; p.H = H; p.W = W; p.mh = mh; p.mw = mw; p.num_classes = num_classes;
+    p.inv_n = (float)(1.0 / d.n_masks);
+    hipLaunchKernelGGL(rise_accumulate_kernel, dim3((unsigned)n), dim3(RISE_ACC_THREADS), 0, s, p);
 }
 
 }  // namespace
@@ -1782,6 +1821,11 @@ fav_status fav_set_views(fav_handle* h, const fav_view* views, int32_t n_views) 
         if (h->curve_on) {
             h->err = "fav_set_views: a curve descriptor is set; an occluded frame's views are not what the map was made for (clear it "
                      "first: fav_set_curve)";
+            return FAV_ERR_UNSUPPORTED;
+        }
+        if (h->rise_on) {
+            h->err = "fav_set_views: a RISE descriptor is set; a masked frame's views are not what the map is made for (clear it "
+                     "first: fav_set_rise)";
             return FAV_ERR_UNSUPPORTED;
         }
         if (!h->vit && h->plan.has_mc) {
@@ -2674,6 +2718,118 @@ fav_status fav_classify_curve(fav_handle* h, const void* images, int32_t n, int3
     return FAV_OK;
 }
 
+// ---- RISE saliency (fav_rise.hpp) ------------------------------------------------
+fav_status fav_check_rise(const fav_rise* desc, int32_t H, int32_t W, int32_t layout, char* err, size_t err_cap) {
+    static_assert(sizeof(fav_rise) == 48 && offsetof(fav_rise, seed) == 16 && offsetof(fav_rise, fill_u8) == 24, "fav_rise is 12 dwords");
+    return check_reply(rise_desc_error(desc, H, W, layout), err, err_cap);
+}
+
+fav_status fav_set_rise(fav_handle* h, const fav_rise* desc) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!desc) {
+        if (!h->rise_on) return FAV_OK;
+        HIP_TRY(h, hipSetDevice(h->cfg.device));
+        if (fav_status st = wait_enqueued(h)) return st;
+        h->rise_on = false;
+        void* buf = h->rise.buf;
+        h->rise = fav_handle::RiseDev{};
+        if (buf) HIP_TRY(h, hipFree(buf));
+        return FAV_OK;
+    }
+    std::string why = rise_desc_error(desc, h->cfg.in_h, h->cfg.in_w, FAV_LAYOUT_NHWC_U8);
+    if (why.empty()) why = rise_desc_error(desc, h->cfg.in_h, h->cfg.in_w, FAV_LAYOUT_NHWC_F32);
+    if (!why.empty()) { h->err = fmt("fav_set_rise: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (h->n_views > 0) {
+        h->err = "fav_set_rise: views are set; a masked frame's views are not what the map is made for (turn them off first: "
+                 "fav_set_views)";
+        return FAV_ERR_UNSUPPORTED;
+    }
+    // one buffer, every part on a 256-byte boundary
+    const size_t B = (size_t)h->cfg.max_batch, planes = (size_t)desc->n_masks + 1;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t masked_b = pad(B * h->cfg.in_h * h->cfg.in_w * 3 * 4), plane_b = pad(planes * B * 4), first_b = pad(B * 4);
+    const size_t bytes = masked_b + plane_b + 2 * first_b;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    fav_handle::RiseDev nw;
+    nw.desc = *desc;
+    if (hipMalloc(&nw.buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->err = fmt("fav_set_rise: cannot allocate the %zu bytes RISE of max_batch=%d frames and %d masks takes", bytes,
+                     (int)h->cfg.max_batch, desc->n_masks);
+        return FAV_ERR_HIP;
+    }
+    char* q = (char*)nw.buf;
+    nw.masked = q; q += masked_b;
+    nw.prob = (float*)q; q += plane_b;
+    nw.lab0 = (int32_t*)q; q += first_b;
+    nw.conf0 = (float*)q;
+    if (h->rise_on) {       // replacing: what is enqueued still uses the old buffer
+        if (fav_status st = wait_enqueued(h)) { (void)hipFree(nw.buf); return st; }
+        if (h->rise.buf) (void)hipFree(h->rise.buf);
+    }
+    h->rise = nw;
+    h->rise_on = true;
+    return FAV_OK;
+}
+
+fav_status fav_classify_rise(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, const int32_t* classes,
+                             int32_t mh, int32_t mw, int32_t* labels, float* conf, float* map, fav_rise_record* rec, void* stream) {
+    static_assert(sizeof(fav_rise_record) == 32, "fav_rise_record is 8 dwords");
+    static_assert(offsetof(fav_rise_record, peak) == offsetof(fav_cam_record, peak) && offsetof(fav_rise_record, floor) == offsetof(fav_cam_record, floor),
+                  "fav_op_cam_heatmap reads peak and floor of either record");
+    const char* fn = "fav_classify_rise";
+    route_clear();
+    if (!h) return FAV_ERR_INVALID_ARG;
+    auto refuse = [&](const std::string& why) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; };
+    if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", fn); return FAV_ERR_NO_WEIGHTS; }
+    if (!h->rise_on) return refuse("no RISE descriptor set (fav_set_rise)");
+    if (!images || !map || !rec || (((uintptr_t)map | (uintptr_t)classes | (uintptr_t)labels | (uintptr_t)conf) & 3) || ((uintptr_t)rec & 7))
+        return refuse(kBadRecords);
+    if (n < 1 || n > h->cfg.max_batch) return refuse(fmt("n=%d outside [1, max_batch=%d]", n, h->cfg.max_batch));
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return refuse("unknown layout");
+    if (layout == FAV_LAYOUT_NHWC_F32 && ((uintptr_t)images & 3)) return refuse("fp32 frames must be 4-byte aligned");
+    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) return refuse("first_image_index out of range");
+    const int H = h->cfg.in_h, W = h->cfg.in_w;
+    const std::string why = rise_map_error(mh, mw, H, W);
+    if (!why.empty()) return refuse(why);
+    if (h->n_views > 0) { h->err = fmt("%s: views are set", fn); return FAV_ERR_UNSUPPORTED; }   // fav_set_views refuses them; kept as a guard
+    const fav_handle::RiseDev& rv = h->rise;
+    const int N = rv.desc.n_masks;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_last_use(h, s)) return st;
+    // the unmasked pass writes the caller's labels and confidences, or the handle's own copies
+    int32_t* const lab0 = labels ? labels : rv.lab0;
+    const int32_t* const cls = classes ? classes : lab0;
+    fav_status st = FAV_OK;
+    for (int k = 0; k <= N && st == FAV_OK; ++k) {
+        const HeadClassProb cp{cls, rv.prob + (size_t)k * n, nullptr};
+        HeadOut out;
+        if (k == 0) {
+            out.labels = lab0; out.conf = conf ? conf : rv.conf0;
+            st = classify_on_stream(h, Frames{images, layout, n, first_index}, out, s);
+            if (st != FAV_OK) break;
+            HeadOut second;
+            second.cprob = &cp;
+            if (const char* e = launch_head(h, h->logits, h->last_T, n, h->cfg.num_classes, h->plan.cpad, h->cfg.temperature,
+                                            h->cfg.conf_kind, h->cfg.tau, second, s)) {
+                h->err = fmt("%s: %s", fn, e);
+                st = FAV_ERR_INVALID_ARG;
+            }
+        } else {
+            launch_rise_mask(images, rv.masked, n, H, W, layout, rv.desc, first_index, k - 1, k, s);
+            out.cprob = &cp;
+            st = classify_on_stream(h, Frames{rv.masked, layout, n, first_index}, out, s);
+        }
+    }
+    if (st == FAV_OK) launch_rise_accumulate(rv.prob, cls, n, rv.desc, first_index, H, W, mh, mw, h->cfg.num_classes, map, rec, s);
+    route_clear();            // the report speaks of fav_op_* launches only
+    mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
+    if (st != FAV_OK) return st;
+    HIP_TRY(h, hipGetLastError());
+    return FAV_OK;
+}
+
 fav_status fav_set_profiling(fav_handle* h, int32_t enable) {
     if (!h) return FAV_ERR_INVALID_ARG;
     h->profiling = enable != 0;
@@ -3265,6 +3421,45 @@ fav_status fav_op_curve(const float* prob, const int32_t* labels, const int32_t*
         return op_rejected(fn, "prob_dev, labels_dev, classes_dev and curve_dev must be 4-byte aligned");
     if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
     launch_curve(prob, labels, classes, n, S, cells, mode, 0, curve, rec, (hipStream_t)stream);
+    return op_done(nullptr);
+}
+
+fav_status fav_op_rise_mask(const void* frames, void* out, int32_t n, int32_t H, int32_t W, int32_t layout, const fav_rise* desc,
+                            int64_t first_index, int32_t m0, int32_t m1, void* stream) {
+    const char* fn = "fav_op_rise_mask";
+    route_clear();
+    if (!frames || !out) return op_rejected(fn, "null pointer");
+    if (n < 1) return op_rejected(fn, "n must be at least 1");
+    std::string why = rise_desc_error(desc, H, W, layout);
+    if (why.empty() && (m0 < 0 || m0 >= m1 || m1 > desc->n_masks))
+        why = fmt("masks [%d, %d) outside 0 <= m0 < m1 <= n_masks = %d", m0, m1, desc->n_masks);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    const size_t esz = layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4;
+    if (((uintptr_t)frames | (uintptr_t)out) % esz != 0) return op_rejected(fn, "fp32 frames and out must be 4-byte aligned");
+    if ((long long)n * (m1 - m0) > 0x7FFFFFFFll) return op_rejected(fn, "n * (m1 - m0) above 2^31 - 1");
+    const long long frame_bytes = (long long)H * W * 3 * (long long)esz;
+    const uintptr_t in_lo = (uintptr_t)frames, in_hi = in_lo + (uintptr_t)frame_bytes * (uintptr_t)n;
+    const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + (uintptr_t)frame_bytes * (uintptr_t)n * (uintptr_t)(m1 - m0);
+    if (in_lo < out_hi && out_lo < in_hi) return op_rejected(fn, "out overlaps frames");
+    launch_rise_mask(frames, out, n, H, W, layout, *desc, first_index, m0, m1, (hipStream_t)stream);
+    return op_done(nullptr);
+}
+
+fav_status fav_op_rise_accumulate(const float* prob, const int32_t* classes, int32_t n, const fav_rise* desc, int64_t first_index,
+                                  int32_t H, int32_t W, int32_t mh, int32_t mw, int32_t num_classes, float* map, fav_rise_record* rec,
+                                  void* stream) {
+    const char* fn = "fav_op_rise_accumulate";
+    route_clear();
+    if (!prob || !classes || !map || !rec) return op_rejected(fn, "null pointer");
+    if (n < 1) return op_rejected(fn, "n must be at least 1");
+    std::string why = rise_desc_error(desc, H, W, FAV_LAYOUT_NHWC_F32);       // the fill is not read: no byte range to hold it to
+    if (why.empty()) why = rise_map_error(mh, mw, H, W);
+    if (why.empty() && num_classes < 0) why = fmt("num_classes=%d is negative", num_classes);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    if (((uintptr_t)prob | (uintptr_t)classes | (uintptr_t)map) & 3)
+        return op_rejected(fn, "prob_dev, classes_dev and map_dev must be 4-byte aligned");
+    if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
+    launch_rise_accumulate(prob, classes, n, *desc, first_index, H, W, mh, mw, num_classes, map, rec, (hipStream_t)stream);
     return op_done(nullptr);
 }
 

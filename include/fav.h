@@ -666,6 +666,84 @@ fav_status fav_classify_curve(fav_handle* h, const void* images_dev, int32_t n, 
                               int32_t* labels_dev, float* conf_dev, float* curve_dev, fav_curve_record* rec_dev,
                               void* hip_stream);
 
+/* ---- RISE saliency (Petsiuk et al. 2018).  The classifier as a black box: the frames are
+ * classified under N random smooth masks, every mask is weighted by the probability the class got under it, and the weighted
+ * masks are summed.  No tap, no backward pass, no special checkpoint: the map is a function of the input alone, it exists for
+ * every arch - a deep ensemble included, which has neither a map tap nor an attention tap - and for any class, and it is a
+ * second, independent map to hold against CAM or rollout under the curves above.  What the tests of this library verify is the
+ * algebra and its bits on synthetic checkpoints; where a map peaks is a property of trained weights.
+ *
+ * The descriptor: n_masks N in [1, 8192]; grid g in [1, 15]; keep in [1, 255] (a grid cell is ON with probability keep / 256);
+ * seed; the fill of a masked-out pixel as in fav_curve.  Valid for frames H x W with g <= min(H, W).
+ *
+ * The mask is a pure integer function.  Let ch = ceil(H / g), cw = ceil(W / g), F = the low 32 bits of first_image_index + i for
+ * frame i of a call, m the mask index, philox4x32_10(counter, key) the generator of the MC-Dropout masks with key = (seed's low
+ * word, seed's high word), and byte b (0 .. 15) of a draw (x, y, z, w) = bits 8 (b % 4) .. 8 (b % 4) + 7 of word b / 4 - x's low
+ * byte first, the order of the dropout draws:
+ *   1. grid bits: the grid has (g+1) x (g+1) cells, cell j = gy * (g+1) + gx; cell j is ON (b[gy][gx] = 1) iff byte j % 16 of
+ *      philox4x32_10((j / 16, F, m, 0x715E), key) is < keep
+ *   2. shift: (x, y, ., .) = philox4x32_10((16, F, m, 0x715E), key); dy = mulhi32(x, ch) in [0, ch-1], dx = mulhi32(y, cw) in
+ *      [0, cw-1] (mulhi32: the high word of the 64-bit product)
+ *   3. bilinear upsampling with half-pixel centres, in integers.  For pixel row y: P = y + dy, num = max(2P + 1 - ch, 0),
+ *      y0 = num / (2ch), fy = num % (2ch); if y0 >= g then y0 = g and fy = 0; y1 = min(y0 + 1, g).  Columns alike with cw, dx.
+ *      top = (2cw - fx) b[y0][x0] + fx b[y0][x1], bot the same on row y1, num2 = (2ch - fy) top + fy bot in [0, 4 ch cw],
+ *      mq = (256 num2 + 2 ch cw) / (4 ch cw) in integer division, in [0, 256]
+ * The contract is the mathematical integer.  The kernels compute it in 32 bits, which holds it exactly while
+ * 1026 ch cw < 2^31; fav_check_rise refuses the frames beyond (ch cw above 2093057 - at g = 1 a frame of about 1446 x 1446). */
+typedef struct fav_rise { uint32_t struct_size; int32_t n_masks, grid, keep; uint64_t seed; uint32_t fill_u8[3];
+                          uint32_t fill_f32_bits[3]; } fav_rise;   /* 48 bytes */
+/* One frame's RISE summary, 32 bytes, 8-byte aligned.  peak (byte 8) and floor (byte 16) stand where fav_cam_record has them,
+ * so fav_op_cam_heatmap accepts an array of these records unchanged.  With p[k] = prob[k][i] (plane 0 the unmasked pass, plane
+ * 1 + m mask m), cls = classes[i], and for cell c = cy * mw + cx the sample pixel (yc, xc): lo = ceil(cy * H / mh),
+ * hi = ceil((cy + 1) * H / mh) - 1, yc = (lo + hi) / 2 in integer division, xc alike - the middle of the pixels fav_op_occlude
+ * assigns to the cell - and wq[m][c] = mq of mask m at (yc, xc); everything fp32, every operation rounded on its own:
+ *   1. acc[c] = +0, cov[c] = 0; for m = 0 .. N-1 in that order: acc[c] = acc[c] + p[1 + m] * ((float)wq[m][c] * 2^-8) and
+ *      cov[c] += wq[m][c] (an integer, at most 2^21)
+ *   2. M[c] = cov[c] > 0 ? acc[c] / ((float)cov[c] * 2^-8) : +0 - the mean of the class probability over the masks, weighted by
+ *      how much of the cell each showed.  Dividing by the coverage a cell got, not by N keep / 256, is the usual correction
+ *   3. p_full = p[0]; p_mean = (+0 plus p[1 + m] in mask order) * (float)(1.0 / N), the constant rounded once from double
+ *   4. peak, peak_cell, floor, n_above and box: steps 5 and 6 of fav_rollout_record over the mh x mw map (the midpoint threshold)
+ *   5. a class outside the range: class_id = -1, the four floats NaN, peak_cell = -1, n_above = 0, box = -1; the map row is
+ *      still what the chains give
+ * Non-finite probabilities have no rule of their own: the chains carry them. */
+typedef struct fav_rise_record { int32_t class_id; float p_full, peak; int32_t peak_cell; float floor, p_mean;
+                                 int32_t n_above, box; } fav_rise_record;
+/* Host only, no device: the descriptor's ranges for H x W frames of `layout`, the one place they live; fav_set_rise calls it
+ * first, for both layouts.  Refused (FAV_ERR_INVALID_ARG, a message in err, which may be NULL): a NULL descriptor, a wrong
+ * struct_size, n_masks outside [1, 8192], grid outside [1, 15] or above min(H, W), keep outside [1, 255], H or W below 1, an
+ * unknown layout, H * W above (2^31 - 1) / 12, 1026 ceil(H / grid) ceil(W / grid) at 2^31 or above, and under
+ * FAV_LAYOUT_NHWC_U8 a fill_u8 above 255. */
+fav_status fav_check_rise(const fav_rise* desc, int32_t H, int32_t W, int32_t layout, char* err, size_t err_cap);
+/* The handle's RISE descriptor (copied; NULL: none, the default).  The setter validates it and allocates everything a later
+ * fav_classify_rise needs for max_batch frames, in one buffer: the masked frames of ONE pass sized for the fp32 layout, the
+ * probability planes [n_masks + 1][max_batch] and the first pass's labels and confidences.  It may synchronise; a refusal for
+ * lack of memory carries the size.  Replacing or clearing waits on the host for the work enqueued on the handle and frees the
+ * old buffer.  FAV_ERR_UNSUPPORTED while views are set, and fav_set_views is refused (FAV_ERR_UNSUPPORTED) while a descriptor
+ * is set: a masked frame's views are not what the map is made for.  Independent of the curve descriptor: both may be set.  A
+ * rejected call leaves the handle as it was.  With no descriptor set a fav_classify* call enqueues exactly what it did before;
+ * with one set, too. */
+fav_status fav_set_rise(fav_handle* h, const fav_rise* desc);
+/* The RISE map of n frames: classes_dev int32 [n] or NULL: the class whose probability weights the masks - NULL: the label of
+ * the unmasked pass, read on the device, so nothing synchronises.  The map has mh x mw cells with mh <= in_h, mw <= in_w,
+ * mh, mw <= 256 and mh * mw <= 1024.  Outputs: map_dev fp32 [n][mh*mw] (4-byte aligned), rec_dev [n] (8-byte aligned),
+ * labels_dev / conf_dev (either may be NULL): label and confidence of the unmasked pass, bit-identical to fav_classify_ex on
+ * the same frames.  Never allocates or synchronises.  Costs n_masks + 1 forward passes of the n frames.  Enqueued on hip_stream:
+ *   1. the unchanged forward pass of fav_classify_ex on the frames, the handle's own head for labels_dev / conf_dev and
+ *      fav_op_head_class_prob into plane 0
+ *   2. for m = 0 .. n_masks-1: fav_op_rise_mask with m1 - m0 = 1 into the handle's buffer, the unchanged forward pass on it and
+ *      fav_op_head_class_prob into plane 1 + m
+ *   3. fav_op_rise_accumulate, told the handle's num_classes
+ * Every pass gets the SAME first_image_index.  MC-Dropout masks are keyed by the global frame index, so all passes of a frame
+ * see the same dropout masks (common random numbers): the probability then moves with the RISE mask only.  Several masks of one
+ * frame in one batch would break exactly that, so a pass holds one mask of every frame.  Afterwards fav_get_logits returns the
+ * LAST masked pass, and every tap that is on holds that pass.  A class >= num_classes is outside the range like a negative one.
+ * The mask launches and the head's are booked in no kernel class.
+ * FAV_ERR_INVALID_ARG: no descriptor set, n outside [1, max_batch], first_image_index < 0 or first_image_index + n > 2^32 - 1,
+ * an unknown layout, a map out of range, a NULL or misaligned map or record buffer, misaligned fp32 frames or classes. */
+fav_status fav_classify_rise(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
+                             const int32_t* classes_dev, int32_t mh, int32_t mw, int32_t* labels_dev, float* conf_dev,
+                             float* map_dev, fav_rise_record* rec_dev, void* hip_stream);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -1078,6 +1156,32 @@ fav_status fav_op_head_class_prob(const float* logits, int32_t T, int32_t n, int
  * carry it); fav_classify_curve passes the handle's num_classes along. */
 fav_status fav_op_curve(const float* prob_dev, const int32_t* labels_dev, const int32_t* classes_dev, int32_t n, int32_t S,
                         int32_t cells, int32_t mode, float* curve_dev, fav_curve_record* rec_dev, void* hip_stream);
+
+/* ---- The two operations behind fav_classify_rise (beside fav_op_head_class_prob above), on device arrays.  Each: one launch,
+ * no allocation, no workspace, no synchronisation, vector stores only.  A refused call (FAV_ERR_INVALID_ARG) launches nothing
+ * and leaves a message that names the function in fav_last_error(NULL).  desc is a host pointer read before the call returns
+ * and checked by fav_check_rise for H x W frames; the mask function stands beside fav_rise.  first_image_index may be any
+ * value: only its low 32 bits count, and frame i's index wraps past 2^32 with them.
+ *
+ * The masks applied: frames [n][H][W][3] of `layout` -> out [m1 - m0][n][H][W][3] of the same element type, the masks
+ * m0 .. m1-1 of desc->n_masks, 0 <= m0 < m1 <= n_masks.  With mq the mask value of the pixel:
+ *   uint8: out = (p * mq + fill * (256 - mq) + 128) >> 8 a channel, so mq = 256 copies the pixel and mq = 0 stores the fill
+ *   fp32:  mq == 256 copies the source bits (a NaN keeps its payload), mq == 0 stores the fill's bits, otherwise
+ *          w = (float)mq * 2^-8 and out = f + w * (p - f), the three operations rounded on their own (no FMA contraction)
+ * Ranges and alignment as fav_op_occlude: n, H, W >= 1; H * W at most (2^31 - 1) / 12; n * (m1 - m0) at most 2^31 - 1; frames
+ * and out need the element type's alignment only (any byte for uint8, 4 for fp32); out must not overlap frames.  The source
+ * pixels are read once, whatever m1 - m0 is; the grid bits and the shift of a (frame, mask) pair are drawn once a block. */
+fav_status fav_op_rise_mask(const void* frames_dev, void* out_dev, int32_t n, int32_t H, int32_t W, int32_t layout,
+                            const fav_rise* desc, int64_t first_image_index, int32_t m0, int32_t m1, void* hip_stream);
+/* The accumulate head defined beside fav_rise_record: prob_dev fp32 [N + 1][n] with N = desc->n_masks, classes_dev int32 [n]
+ * -> map_dev fp32 [n][mh*mw] (all 4-byte aligned) and rec_dev [n] (8-byte aligned).  n >= 1; 1 <= mh <= H, 1 <= mw <= W,
+ * mh, mw <= 256, mh * mw <= 1024; H and W as fav_check_rise takes them under either layout (the fill is not read).  No frame is
+ * read: a block a frame derives the mask values again at the cells' sample pixels.  num_classes: a class >= num_classes is
+ * outside the range like a negative one; 0: not known, only a negative class then is (the class-probability head has written
+ * NaN for any other, and the chains carry it). */
+fav_status fav_op_rise_accumulate(const float* prob_dev, const int32_t* classes_dev, int32_t n, const fav_rise* desc,
+                                  int64_t first_image_index, int32_t H, int32_t W, int32_t mh, int32_t mw, int32_t num_classes,
+                                  float* map_dev, fav_rise_record* rec_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
