@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FAV_LIB_PATH") or os.path.join(_HERE, "lib", "libfav_hip.so")   # FAV_LIB_PATH: A/B of two builds
 
 FAV_OK = 0
+FAV_ERR_INVALID_ARG = 1
 STATUS_NAMES = {0: "FAV_OK", 1: "FAV_ERR_INVALID_ARG", 2: "FAV_ERR_BAD_BLOB", 3: "FAV_ERR_NO_WEIGHTS",
                 4: "FAV_ERR_HIP", 5: "FAV_ERR_NO_DEVICE", 6: "FAV_ERR_UNSUPPORTED"}
 LAYOUT_NHWC_U8, LAYOUT_NHWC_F32 = 0, 1
@@ -161,6 +162,19 @@ class FavRolloutRecord(C.Structure):
                 ("floor", C.c_float), ("patch_sum", C.c_float), ("n_above", C.c_int32), ("box", C.c_int32)]
 
 
+class FavPatchBank(C.Structure):
+    """fav_patch_bank: a bank of L2-normalised bf16 patch-feature rows, host pointers (patch.PatchBank.to_c fills it)."""
+    _fields_ = [("struct_size", C.c_uint32), ("D", C.c_int32), ("N", C.c_int32), ("chunk_rows", C.c_int32),
+                ("rows", C.POINTER(C.c_uint16)), ("threshold", C.c_float)]
+
+
+class FavPatchRecord(C.Structure):
+    """fav_patch_record: one 32-byte summary per frame (patch.unpack_patch_records reads it as int32[..., 8]); peak and floor
+    stand where FavCamRecord has them."""
+    _fields_ = [("n_degenerate", C.c_int32), ("mean_dist", C.c_float), ("peak", C.c_float), ("peak_cell", C.c_int32),
+                ("floor", C.c_float), ("peak_row", C.c_int32), ("n_above", C.c_int32), ("box", C.c_int32)]
+
+
 CURVE_DELETION, CURVE_INSERTION = 0, 1
 CURVE_MODES = ("deletion", "insertion")
 
@@ -295,6 +309,15 @@ _SIGNATURES = {
                                    C.c_int32, C.c_int32, C.c_void_p]),
     "fav_op_rise_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FavRise), C.c_int64, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_check_patch_bank": (C.c_int, [C.POINTER(FavPatchBank), C.c_int32, C.c_char_p, C.c_size_t]),
+    "fav_set_patch_bank": (C.c_int, [C.c_void_p, C.POINTER(FavPatchBank)]),
+    "fav_patch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_classify_patch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_patch_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "fav_patch_chunk_rows": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "fav_op_patch_score": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                     C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),

@@ -108,6 +108,7 @@ class Backend:
         self._T_head = cfg.n_samples if self.mc else max(1, cfg.n_members)
         self._tap, self._ood, self._knn = False, None, None   # the caller's own feature tap; the ood.OODModel, the ood.KNNBank in force
         self._drift = None                                    # the ood.DriftReference in force
+        self._patch = None                                    # the patch.PatchBank in force
         self._map_hw = None                                   # (Hf, Wf) of the map tap, known from the first set_map_tap(True) on
         self._attn_grid = None                                # (gh, gw) of the attention tap, known from the first set_attn_tap(True) on
         self._map_tap_on = self._attn_tap_on = False          # the two localisation taps as this object last set them
@@ -998,6 +999,124 @@ class Backend:
         from .ood import separation_report
         return separation_report(self._head_distances(self.classify_knn, "kth_dist", id_frames),
                                  self._head_distances(self.classify_knn, "kth_dist", ood_frames), self.knn_bank.threshold)
+
+    # -- patch-level anomaly maps (patch.py PatchBank; include/fav.h fav_set_patch_bank) -------------------------------------
+    @property
+    def patch_bank(self):
+        """The ``patch.PatchBank`` in force, None when off."""
+        return self._patch
+
+    def _patch_grid(self) -> tuple:
+        """(Hf, Wf) of the map a patch bank is cut from, from the planner (refused on a ViT arch and on a deep ensemble)."""
+        if self._map_hw is None:
+            info = self.map_tap_info()
+            self._map_hw = (info["hf"], info["wf"])
+        return self._map_hw
+
+    def _with_map_tap(self, run):
+        """``run()`` with the map tap on; a tap that only this call needs goes off again."""
+        was_on = self._map_tap_on
+        if not was_on:
+            self.set_map_tap(True)
+        try:
+            return run()
+        finally:
+            if not was_on:
+                self.set_map_tap(False)
+
+    def fit_patch_bank(self, frames, **kw):
+        """Build a ``patch.PatchBank`` from in-distribution frames: batches of frames_per_call frames run through the
+        classifier with the map tap on, every cell of every map goes through ``patch.cell_rows`` and all of them to
+        ``patch.bank_from_rows`` (``max_rows``, ``seed``, ``threshold``, ``chunk_rows``).  The subsample is random; a greedy
+        coreset is out of scope.  The handle is left as it was, the map tap included: see ``set_patch_bank``."""
+        from .patch import bank_from_rows, cell_rows
+        grid = self._patch_grid()
+
+        def run():
+            parts = []
+            for b, e in self._batches(int(frames.shape[0])):
+                self.classify_detect(frames[b:e], b)
+                parts.append(cell_rows(self.maps())[:2])
+            return parts
+        parts = self._with_map_tap(run)
+        return bank_from_rows(np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]), grid=grid, **kw)
+
+    def set_patch_bank(self, bank):
+        """Adopt a ``patch.PatchBank`` (fav_set_patch_bank: copied to the device, the workspace allocated for max_batch frames;
+        the map tap is not touched), or None: off.  Refused on a ViT arch and on a deep ensemble, for a bank whose D is not
+        the map's channel count, and for a bank cut from another grid than this configuration's map."""
+        if bank is None:
+            _lib.check(self.lib.fav_set_patch_bank(self._h, None), self._h)
+        else:
+            if bank.grid is not None:
+                try:
+                    grid = tuple(self._patch_grid())
+                except _lib.FavError:
+                    grid = bank.grid               # no map here: the setter refuses the configuration in its own words
+                if grid != tuple(bank.grid):
+                    raise ValueError(f"the bank was cut from a {bank.grid} map, this configuration's is {grid}")
+            c = bank.to_c()
+            _lib.check(self.lib.fav_set_patch_bank(self._h, C.byref(c)), self._h)
+        self._patch = bank
+
+    def classify_patch(self, images, heatmap: bool = False, first_index: int = 0) -> dict:
+        """frames -> ``label``, ``conf``, ``fail``, ``score`` as ``classify_detect`` gives them, plus the anomaly map of each
+        frame (fav_classify_patch): ``dist`` fp32 [n, Hf, Wf], the squared distance of every cell's normalised feature to its
+        nearest bank row (NaN for a cell without a direction), ``nn_row`` int32 [n, Hf, Wf], that row (-1 there), and the record
+        fields of ``patch.unpack_patch_records``, each [n]: ``n_degenerate``, ``mean_dist``, ``peak`` (the frame's score),
+        ``peak_cell``, ``floor``, ``peak_row``, ``n_above`` (cells at the bank's threshold or above), ``box`` and its ``x0``,
+        ``y0``, ``x1``, ``y1``, ``anomalous``.  ``heatmap``: also ``heatmap`` uint8 [n, H, W], ``dist`` resized to the frame and
+        normalised from its floor to its peak (fav_op_cam_heatmap).  The map tap goes on for the call if it is off, and off
+        again.  torch CUDA frames in -> CUDA tensors out, asynchronous on the current stream; numpy in -> numpy out,
+        synchronous.  Needs a bank; refused while views are set."""
+        from .patch import PATCH_RECORD_DWORDS, unpack_patch_records
+        torch = self._torch
+        if self._patch is None:
+            raise _lib.FavError(_lib.FAV_ERR_INVALID_ARG, "classify_patch: no patch bank set (set_patch_bank)")
+        hw = self._patch_grid()
+
+        def run():
+            img, host, n, layout, stream = self._classify_args(images)
+            labels, conf, fail, score = self._detect_buffers(n, img.device)
+            dist = torch.empty((n, *hw), dtype=torch.float32, device=img.device)
+            row = torch.empty((n, *hw), dtype=torch.int32, device=img.device)
+            rec = torch.empty((n, PATCH_RECORD_DWORDS), dtype=torch.int32, device=img.device)
+            _lib.check(self.lib.fav_classify_patch(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(), conf.data_ptr(),
+                                                   fail.data_ptr(), score.data_ptr(), dist.data_ptr(), row.data_ptr(), rec.data_ptr(),
+                                                   stream), self._h)
+            out = dict(label=labels, conf=conf, fail=fail, score=score, dist=dist, nn_row=row)
+            if heatmap:
+                H, W = int(self.cfg.in_h), int(self.cfg.in_w)
+                heat = torch.empty((n, H, W), dtype=torch.uint8, device=img.device)
+                _lib.check(self.lib.fav_op_cam_heatmap(dist.data_ptr(), rec.data_ptr(), n, *hw, H, W, heat.data_ptr(), stream))
+                out["heatmap"] = heat
+            if host:
+                out = {k: v.cpu().numpy() for k, v in out.items()}
+                rec = rec.cpu().numpy()
+            return dict(unpack_patch_records(rec), **out)
+        return self._with_map_tap(run)
+
+    def calibrate_patch(self, frames, tpr: float = 0.95) -> float:
+        """Set the bank's threshold so that at least ``tpr`` of these in-distribution frames have no cell above it - the
+        ceil(tpr * n)-th smallest ``peak``, raised by one float32 step, since a cell counts at equality - and return it."""
+        if self.patch_bank is None:
+            raise ValueError("calibrate_patch needs a bank: set_patch_bank first")
+        from .ood import threshold_for_tpr
+        peaks = self._patch_peaks(frames)
+        thr = float(np.nextafter(np.float32(threshold_for_tpr(peaks, tpr)), np.float32(np.inf)))
+        self.set_patch_bank(self.patch_bank.with_threshold(thr))
+        return thr
+
+    def patch_report(self, id_frames, ood_frames) -> dict:
+        """How well ``peak`` separates ``ood_frames`` from ``id_frames``: the keys of ``ood_report``."""
+        if self.patch_bank is None:
+            raise ValueError("patch_report needs a bank: set_patch_bank first")
+        from .ood import separation_report
+        return separation_report(self._patch_peaks(id_frames), self._patch_peaks(ood_frames), self.patch_bank.threshold)
+
+    def _patch_peaks(self, frames) -> np.ndarray:
+        """``classify_patch`` over batches of frames_per_call frames -> every frame's ``peak``, the map tap staying on throughout."""
+        return self._with_map_tap(lambda: self._head_distances(lambda f, b: self.classify_patch(f, first_index=b), "peak", frames))
 
     # -- window-level drift detection (ood.py DriftReference; include/fav.h fav_set_drift) -------------------------------
     @property

@@ -35,6 +35,7 @@
 #include "fav_rollout.hpp"
 #include "fav_curve.hpp"
 #include "fav_rise.hpp"
+#include "fav_patch.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -171,6 +172,12 @@ struct fav_handle {
     struct KnnDev { void *bank = nullptr, *ws = nullptr; int32_t* cls = nullptr; int D = 0, N = 0, k = 0; float threshold = 0.f; };
     KnnDev knn;
     bool knn_on = false;
+    // patch bank (fav_set_patch_bank): the device copy, padded with zero rows to Npad, and the head's workspace for max_batch *
+    // Hf * Wf cells (fav_patch.hpp patch_workspace, its zero bias written once by the setter); Hf, Wf: the planner's map, which
+    // the map tap holds when it is on.  patch_on: one is set.  It reads the map tap and never turns it on or off
+    struct PatchDev { void *bank = nullptr, *ws = nullptr; int D = 0, N = 0, chunk_rows = 0, Hf = 0, Wf = 0; float threshold = 0.f; };
+    PatchDev patch;
+    bool patch_on = false;
     // drift reference (fav_set_drift): the workspace for max_batch frames (fav_drift.hpp drift_workspace, cached_ref), its
     // pool holding the reference and U the reference's block of distances, both written once by the setter; drift_on: one is set
     struct DriftDev { void* ws = nullptr; int D = 0, R = 0, n_perm = 0; uint64_t seed = 0; float alpha = 0.f; };
@@ -1134,6 +1141,7 @@ void free_all(fav_handle* h) {
     for (void* q : {(void*)h->ood.mu, (void*)h->ood.Pt, (void*)h->ood.Mt, (void*)h->ood.cls}) if (q) (void)hipFree(q);
     for (void* q : {h->knn.bank, h->knn.ws, (void*)h->knn.cls}) if (q) (void)hipFree(q);
     if (h->drift.ws) (void)hipFree(h->drift.ws);
+    for (void* q : {h->patch.bank, h->patch.ws}) if (q) (void)hipFree(q);
     for (void* q : {h->map_tap.buf, h->attn_tap.buf, h->curve.buf, h->rise.buf}) if (q) (void)hipFree(q);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
@@ -2224,16 +2232,31 @@ fav_status fav_classify_ood(fav_handle* h, const void* images, int32_t n, int32_
 
 // ---- nearest-neighbour OOD scoring (fav_knn.hpp) ----------------------------
 namespace {
-// What the head needs of a workspace before its first launch: the zero bias, and the rows of the bank behind its last whole
-// 64 as a zero-padded tile.  A padded bank (the handle's copy) needs the bias only, once.
-fav_status knn_prepare(const KnnWs& w, void* ws, const void* bank, int D, int N, bool padded_bank, hipStream_t s) {
-    if (hipMemsetAsync((char*)ws + w.bias, 0, (size_t)w.Npad * 4, s) != hipSuccess) return FAV_ERR_HIP;
+// What the k-NN head and the patch head need of a workspace before their first launch: the zero bias of bias_floats values, and
+// the rows of the bank behind its last whole 64 as a zero-padded tile.  A padded bank (the handle's copy) needs the bias only, once.
+fav_status bank_prepare(void* zero_bias, int bias_floats, void* tile, const void* bank, int D, int N, bool padded_bank, hipStream_t s) {
+    if (hipMemsetAsync(zero_bias, 0, (size_t)bias_floats * 4, s) != hipSuccess) return FAV_ERR_HIP;
     const int rest = N % 64;
     if (rest == 0 || padded_bank) return FAV_OK;
     const size_t row = (size_t)D * 2;
-    if (hipMemsetAsync((char*)ws + w.tile + rest * row, 0, (size_t)(64 - rest) * row, s) != hipSuccess) return FAV_ERR_HIP;
-    if (hipMemcpyAsync((char*)ws + w.tile, (const char*)bank + (size_t)(N - rest) * row, rest * row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FAV_ERR_HIP;
+    if (hipMemsetAsync((char*)tile + rest * row, 0, (size_t)(64 - rest) * row, s) != hipSuccess) return FAV_ERR_HIP;
+    if (hipMemcpyAsync(tile, (const char*)bank + (size_t)(N - rest) * row, rest * row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FAV_ERR_HIP;
     return FAV_OK;
+}
+fav_status knn_prepare(const KnnWs& w, void* ws, const void* bank, int D, int N, bool padded_bank, hipStream_t s) {
+    return bank_prepare((char*)ws + w.bias, w.Npad, (char*)ws + w.tile, bank, D, N, padded_bank, s);
+}
+
+// The similarity GEMM of the k-NN head and the patch head: q [n][D] bf16 against `cols` rows of a bank (a multiple of 64) as a
+// 1x1 convolution over n one-pixel frames, fp32 output into y (row pitch ldy), a zero bias - the production accumulator
+const char* sim_gemm(const void* q, int n, int D, const void* rows, const float* zero_bias, float* y, int cols, int ldy, hipStream_t s) {
+    fav_conv_desc d;
+    memset(&d, 0, sizeof d);
+    d.x = q; d.w = rows; d.bias = zero_bias; d.y = y;
+    d.n_frames = n; d.H = 1; d.W = 1; d.Cin = D; d.Cout = cols;
+    d.kh = 1; d.kw = 1; d.stride = 1; d.pad = 0; d.relu = 0; d.out_f32 = 1; d.math_mode = FAV_MATH_BF16;
+    d.drop.site = -1;
+    return launch_conv(nullptr, d, cols, ldy, false, Group{}, s);
 }
 
 // The head on a prepared workspace: the query kernel, the GEMM (one launch; two when an unpadded bank ends in a part tile),
@@ -2245,14 +2268,8 @@ const char* launch_knn(const void* feat, int S, int n, int D, const void* bank, 
     qp.S = S; qp.n = n; qp.D = D; qp.inv_S = (float)(1.0 / S);
     hipLaunchKernelGGL(knn_query_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, s, qp);
     float* const sim = (float*)((char*)ws + w.sim);
-    auto gemm = [&](const void* rows, int col0, int cols) -> const char* {
-        fav_conv_desc d;
-        memset(&d, 0, sizeof d);
-        d.x = qp.q; d.w = rows; d.bias = (const float*)((char*)ws + w.bias) + col0; d.y = sim + col0;
-        d.n_frames = n; d.H = 1; d.W = 1; d.Cin = D; d.Cout = cols;
-        d.kh = 1; d.kw = 1; d.stride = 1; d.pad = 0; d.relu = 0; d.out_f32 = 1; d.math_mode = FAV_MATH_BF16;
-        d.drop.site = -1;
-        return launch_conv(nullptr, d, cols, w.Npad, false, Group{}, s);
+    auto gemm = [&](const void* rows, int col0, int cols) {
+        return sim_gemm(qp.q, n, D, rows, (const float*)((char*)ws + w.bias) + col0, sim + col0, cols, w.Npad, s);
     };
     const int whole = padded_bank ? w.Npad : (N & ~63);
     if (whole > 0)
@@ -2597,6 +2614,136 @@ fav_status fav_classify_rollout(fav_handle* h, const void* images, int32_t n, in
     return classify_map_head(h, "fav_classify_rollout", kAttnWords, &fav_handle::attn_tap, bad_rollout_buffers(map, rec),
                              [&] { return rollout_handle_dims_error(h, first_layer); }, images, n, layout, first_index, labels, conf, fail,
                              score, stream, [&](hipStream_t s) { return rollout_on_tap(h, first_layer, map, rec, s); });
+}
+
+// ---- patch-level anomaly maps (fav_patch.hpp) -----------------------------------
+namespace {
+// bank_prepare on the head's workspace: the zero bias serves every chunk
+fav_status patch_prepare(const PatchWs& w, void* ws, const void* bank, int D, int N, bool padded_bank, hipStream_t s) {
+    return bank_prepare((char*)ws + w.bias, w.chunk, (char*)ws + w.tile, bank, D, N, padded_bank, s);
+}
+
+// The head on a prepared workspace: the query kernel, a cell a block; per column chunk of the bank the GEMM into the slab (two
+// launches where an unpadded bank's part tile falls into the chunk) and the fold of the slab; the score kernel, a frame a
+// block.  Stream order makes reusing the slab safe.  The arguments have been checked (patch_map_error, knn_dims_error, the
+// pointers).  Returns the conv launcher's refusal, if any.
+const char* launch_patch(const void* maps, int S, int n, int Hf, int Wf, int C, const void* bank, int N, float threshold, const PatchWs& w,
+                         void* ws, bool padded_bank, float* dist, int32_t* row, fav_patch_record* rec, hipStream_t s) {
+    const int HW = Hf * Wf, M = n * HW;
+    KnnQueryParams qp;
+    qp.feat = (const uint16_t*)maps; qp.q = (uint16_t*)((char*)ws + w.q); qp.flags = (int32_t*)((char*)ws + w.flags);
+    qp.S = S; qp.n = M; qp.D = C; qp.inv_S = (float)(1.0 / S);
+    hipLaunchKernelGGL(knn_query_kernel, dim3((unsigned)M), dim3(KNN_THREADS), 0, s, qp);
+    float* const slab = (float*)((char*)ws + w.slab);
+    const float* const zero_bias = (const float*)((char*)ws + w.bias);
+    const int whole = padded_bank ? w.Npad : (N & ~63);        // the rows the GEMM reads in place
+    PatchFoldParams fp;
+    fp.sim = slab; fp.flags = qp.flags; fp.best = (uint2*)((char*)ws + w.best); fp.M = M; fp.ld = w.chunk;
+    for (int c0 = 0; c0 < w.Npad; c0 += w.chunk) {
+        const int cols = std::min(w.chunk, w.Npad - c0), in_place = std::max(0, std::min(cols, whole - c0));
+        if (in_place > 0)
+            if (const char* e = sim_gemm(qp.q, M, C, (const char*)bank + (size_t)c0 * C * 2, zero_bias, slab, in_place, w.chunk, s)) return e;
+        if (in_place < cols)
+            if (const char* e = sim_gemm(qp.q, M, C, (const char*)ws + w.tile, zero_bias, slab + in_place, 64, w.chunk, s)) return e;
+        fp.cols = std::min(cols, N - c0); fp.row0 = c0; fp.first = c0 == 0 ? 1 : 0;
+        hipLaunchKernelGGL(patch_fold_kernel, dim3((unsigned)((M + PATCH_FOLD_ROWS - 1) / PATCH_FOLD_ROWS)), dim3(PATCH_FOLD_THREADS), 0, s, fp);
+    }
+    PatchScoreParams sp;
+    sp.best = fp.best; sp.flags = qp.flags; sp.dist = dist; sp.row = row; sp.rec = (int32_t*)rec;
+    sp.HW = HW; sp.Wf = Wf; sp.threshold = threshold; sp.inv_HW = (float)(1.0 / HW);
+    hipLaunchKernelGGL(patch_score_kernel, dim3((unsigned)n), dim3(PATCH_SCORE_THREADS), 0, s, sp);
+    return nullptr;
+}
+
+void free_patch(fav_handle::PatchDev* o) {
+    for (void* q : {o->bank, o->ws}) if (q) (void)hipFree(q);
+    *o = fav_handle::PatchDev{};
+}
+bool bad_patch_buffers(const void* dist, const void* row, const void* rec) {
+    return !dist || !rec || ((uintptr_t)dist & 3) || ((uintptr_t)row & 3) || ((uintptr_t)rec & 7);
+}
+// what the head's two entry points refuse once the tap is known to be on, and its launch on the maps the tap holds
+extern "C++" std::string patch_handle_error(const fav_handle* h) {
+    return h->patch_on ? std::string() : std::string("no patch bank set (fav_set_patch_bank)");
+}
+const char* patch_on_tap(const fav_handle* h, float* dist, int32_t* row, fav_patch_record* rec, hipStream_t s) {
+    const fav_handle::PatchDev& o = h->patch;
+    const PatchWs w = patch_workspace((long long)h->cfg.max_batch * o.Hf * o.Wf, o.D, o.N, o.chunk_rows, true);
+    return launch_patch(h->map_tap.buf, h->map_tap.S, h->map_tap.n, o.Hf, o.Wf, o.D, o.bank, o.N, o.threshold, w, o.ws, true, dist, row, rec, s);
+}
+}  // namespace
+
+fav_status fav_check_patch_bank(const fav_patch_bank* b, int32_t D_expected, char* err, size_t err_cap) {
+    static_assert(sizeof(fav_patch_record) == 32, "fav_patch_record is 8 dwords");
+    static_assert(offsetof(fav_patch_record, peak) == offsetof(fav_cam_record, peak) && offsetof(fav_patch_record, floor) == offsetof(fav_cam_record, floor),
+                  "fav_op_cam_heatmap reads peak and floor of either record");
+    return check_reply(patch_bank_error(b, D_expected), err, err_cap);
+}
+
+size_t fav_patch_workspace_bytes(int32_t cells_total, int32_t D, int32_t N, int32_t chunk_rows) {
+    if (cells_total < 1 || !knn_dims_error(D, N, 1).empty() || !patch_chunk_error(chunk_rows).empty()) return 0;
+    return patch_workspace(cells_total, D, N, chunk_rows, false).bytes;
+}
+
+int32_t fav_patch_chunk_rows(int32_t cells_total, int32_t N, int32_t chunk_rows) {
+    if (cells_total < 1 || N < 1 || N > KNN_MAX_N || !patch_chunk_error(chunk_rows).empty()) return 0;
+    return patch_chunk(cells_total, N, chunk_rows);
+}
+
+fav_status fav_set_patch_bank(fav_handle* h, const fav_patch_bank* b) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    if (!b) {
+        if (!h->patch_on) return FAV_OK;
+        if (fav_status st = wait_enqueued(h)) return st;
+        free_patch(&h->patch);
+        h->patch_on = false;
+        return FAV_OK;
+    }
+    if (const char* why = map_tap_unsupported(h->cfg.arch, h->n_members, h->cfg.math_mode)) {
+        h->err = fmt("fav_set_patch_bank: %s", why);
+        return FAV_ERR_UNSUPPORTED;
+    }
+    const MapTapDims d = map_tap_dims(h->plan, h->cfg.max_batch);
+    std::string why = patch_bank_error(b, d.C);
+    if (why.empty()) why = patch_map_error(h->cfg.max_batch, d.Hf, d.Wf);
+    if (!why.empty()) { h->err = fmt("fav_set_patch_bank: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
+    const long long cells = (long long)h->cfg.max_batch * d.Hf * d.Wf;
+    const PatchWs w = patch_workspace(cells, b->D, b->N, b->chunk_rows, true);
+    if (w.bytes > PATCH_MAX_WS_BYTES) {
+        h->err = fmt("fav_set_patch_bank: the workspace of max_batch=%d frames of %d x %d cells against N=%d rows in chunks of %d is %zu bytes, "
+                     "above the limit of %zu", (int)h->cfg.max_batch, d.Hf, d.Wf, b->N, w.chunk, w.bytes, PATCH_MAX_WS_BYTES);
+        return FAV_ERR_INVALID_ARG;
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    // the new copy first: a failure leaves the handle as it was
+    fav_handle::PatchDev nw;
+    nw.D = b->D; nw.N = b->N; nw.chunk_rows = b->chunk_rows; nw.Hf = d.Hf; nw.Wf = d.Wf; nw.threshold = b->threshold;
+    const size_t row = (size_t)b->D * 2, bank_bytes = (size_t)b->N * row, pad_bytes = (size_t)(w.Npad - b->N) * row;
+    bool ok = hipMalloc(&nw.bank, (size_t)w.Npad * row) == hipSuccess && hipMalloc(&nw.ws, w.bytes) == hipSuccess &&
+              hipMemcpy(nw.bank, b->rows, bank_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+              (pad_bytes == 0 || hipMemset((char*)nw.bank + bank_bytes, 0, pad_bytes) == hipSuccess);
+    ok = ok && patch_prepare(w, nw.ws, nw.bank, b->D, b->N, true, nullptr) == FAV_OK && hipStreamSynchronize(nullptr) == hipSuccess;
+    fav_status st = FAV_OK;
+    if (!ok) { h->err = fmt("fav_set_patch_bank: cannot copy the bank to the device: %s", hipGetErrorString(hipGetLastError())); st = FAV_ERR_HIP; }
+    if (st == FAV_OK && h->patch_on) st = wait_enqueued(h);
+    if (st != FAV_OK) { free_patch(&nw); return st; }
+    if (h->patch_on) free_patch(&h->patch);
+    h->patch = nw;
+    h->patch_on = true;
+    return FAV_OK;
+}
+
+fav_status fav_patch(fav_handle* h, float* dist, int32_t* row, fav_patch_record* rec, void* stream) {
+    return map_head_on_last_call(h, "fav_patch", kMapWords, &fav_handle::map_tap, bad_patch_buffers(dist, row, rec),
+                                 [&] { return patch_handle_error(h); }, stream,
+                                 [&](hipStream_t s) { return patch_on_tap(h, dist, row, rec, s); });
+}
+
+fav_status fav_classify_patch(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
+                              float* conf, uint8_t* fail, float* score, float* dist, int32_t* row, fav_patch_record* rec, void* stream) {
+    return classify_map_head(h, "fav_classify_patch", kMapWords, &fav_handle::map_tap, bad_patch_buffers(dist, row, rec),
+                             [&] { return patch_handle_error(h); }, images, n, layout, first_index, labels, conf, fail, score, stream,
+                             [&](hipStream_t s) { return patch_on_tap(h, dist, row, rec, s); });
 }
 
 // ---- deletion / insertion curves (fav_curve.hpp) --------------------------------
@@ -3278,6 +3425,29 @@ fav_status fav_op_knn_score(const void* feat, int32_t S, int32_t n, int32_t D, c
     hipStream_t s = (hipStream_t)stream;
     if (knn_prepare(w, ws, bank, D, N, false, s) != FAV_OK) { g_create_error = fmt("%s: cannot prepare the workspace: %s", fn, hipGetErrorString(hipGetLastError())); return FAV_ERR_HIP; }
     return op_done(fn, launch_knn(feat, S, n, D, bank, N, k, class_id, threshold, w, ws, false, records, s));
+}
+
+fav_status fav_op_patch_score(const void* maps, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C, const void* bank, int32_t N,
+                              int32_t chunk_rows, float threshold, void* ws, size_t ws_bytes, float* dist, int32_t* row,
+                              fav_patch_record* rec, void* stream) {
+    const char* fn = "fav_op_patch_score";
+    route_clear();
+    if (!maps || !bank || !ws || !dist || !rec) return op_rejected(fn, "null pointer");
+    PatchWs w;
+    std::string dims = patch_map_error(n, Hf, Wf);
+    if (dims.empty()) dims = knn_dims_error(C, N, 1);
+    if (dims.empty()) dims = patch_chunk_error(chunk_rows);
+    const std::string why = score_gate(S, KNN_MAX_S, n, dims, threshold, rec, [&]() -> std::string {
+        w = patch_workspace((long long)n * Hf * Wf, C, N, chunk_rows, false);
+        if (ws_bytes < w.bytes) return fmt("ws_bytes=%zu is below fav_patch_workspace_bytes=%zu", ws_bytes, w.bytes);
+        if ((uintptr_t)ws & 255) return "ws_dev must be 256-byte aligned";
+        if (((uintptr_t)dist | (uintptr_t)row) & 3) return "dist_dev and row_dev must be 4-byte aligned";
+        return (uintptr_t)bank & 15 ? "bank_dev must be 16-byte aligned" : "";
+    });
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    hipStream_t s = (hipStream_t)stream;
+    if (patch_prepare(w, ws, bank, C, N, false, s) != FAV_OK) { g_create_error = fmt("%s: cannot prepare the workspace: %s", fn, hipGetErrorString(hipGetLastError())); return FAV_ERR_HIP; }
+    return op_done(fn, launch_patch(maps, S, n, Hf, Wf, C, bank, N, threshold, w, ws, false, dist, row, rec, s));
 }
 
 fav_status fav_op_drift_test(const void* feat, int32_t S, int32_t n, int32_t D, const void* ref, int32_t R, int32_t n_perm,

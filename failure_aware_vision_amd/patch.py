@@ -1,0 +1,159 @@
+"""Patch-level anomaly maps (include/fav.h fav_patch_bank, fav_patch_record; PatchCore, Roth et
+al. 2022): the host side of ``Backend.fit_patch_bank``, ``set_patch_bank`` and ``classify_patch`` - the bank of in-distribution
+patch features, how it is made from tapped feature maps, and the record unpacking.
+
+The feature-space heads (``ood.py``) see a frame through the average pool, which dilutes a local fault 49 to 1 on a 7 x 7 map;
+the localisation heads (``cam.py``, ``rollout.py``, ``rise.py``) explain the classifier's decision, not the frame's novelty.
+Here every cell of the last feature map is scored on its own: the squared distance of its normalised feature to the nearest
+row of a bank of in-distribution cells.  The map of those distances is an anomaly heat map and its peak a frame score.
+
+The bank is a seeded random subsample of the cells.  PatchCore's greedy coreset selection is out of scope: it is host work
+that changes which rows a bank holds, not what the device does with them."""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import math
+
+import numpy as np
+
+from . import _lib
+from .ood import _bf16_bits, _check, _subsample
+
+#: dwords of one fav_patch_record (include/fav.h)
+PATCH_RECORD_DWORDS = 8
+_FIELDS = ("n_degenerate", "mean_dist", "peak", "peak_cell", "floor", "peak_row", "n_above", "box")
+_FLOAT_DWORDS = (1, 2, 4)
+
+
+@dataclasses.dataclass(frozen=True)
+class PatchBank:
+    """``rows`` uint16[N, D]: L2-normalised in-distribution patch features as bf16 bit patterns; ``threshold``: a cell counts
+    as above when dist >= threshold (+inf: never); ``chunk_rows``: the bank rows one slab of similarities covers, 0 for the
+    library's rule (nothing in a result depends on it); ``grid``: the (hf, wf) map the rows were cut from, or None;
+    ``n_dropped``: the zero and non-finite cells ``build_patch_bank`` left out."""
+    rows: np.ndarray
+    threshold: float = math.inf
+    chunk_rows: int = 0
+    grid: tuple | None = None
+    n_dropped: int = 0
+
+    def __post_init__(self):
+        if np.asarray(self.rows).dtype != np.uint16:
+            raise ValueError("rows are bf16 bit patterns: uint16 (build_patch_bank makes them from feature maps)")
+        object.__setattr__(self, "rows", np.ascontiguousarray(self.rows, np.uint16))
+        object.__setattr__(self, "threshold", float(self.threshold))
+        object.__setattr__(self, "chunk_rows", int(self.chunk_rows))
+        object.__setattr__(self, "n_dropped", int(self.n_dropped))
+        if self.grid is not None:
+            object.__setattr__(self, "grid", (int(self.grid[0]), int(self.grid[1])))
+        if self.rows.ndim != 2:
+            raise ValueError("rows is a matrix [N, D]")
+
+    @property
+    def N(self) -> int:
+        return int(self.rows.shape[0])
+
+    @property
+    def D(self) -> int:
+        return int(self.rows.shape[1])
+
+    def with_threshold(self, threshold: float) -> "PatchBank":
+        return dataclasses.replace(self, threshold=float(threshold))
+
+    def save(self, path):
+        extra = {} if self.grid is None else {"grid": np.asarray(self.grid, np.int32)}
+        np.savez(path, rows=self.rows, threshold=np.float32(self.threshold), chunk_rows=np.int32(self.chunk_rows),
+                 n_dropped=np.int64(self.n_dropped), **extra)
+
+    @classmethod
+    def load(cls, path) -> "PatchBank":
+        with np.load(path) as z:
+            grid = tuple(int(v) for v in z["grid"]) if "grid" in z.files else None
+            return cls(z["rows"], float(z["threshold"]), int(z["chunk_rows"]), grid, int(z["n_dropped"]))
+
+    def to_c(self) -> _lib.FavPatchBank:
+        """The fav_patch_bank that points into this bank's rows (which it keeps alive)."""
+        b = _lib.FavPatchBank()
+        b.struct_size = C.sizeof(_lib.FavPatchBank)
+        b.D, b.N, b.chunk_rows = self.D, self.N, self.chunk_rows
+        b.rows = self.rows.ctypes.data_as(C.POINTER(C.c_uint16))
+        b.threshold = self.threshold
+        b._keep = self
+        return b
+
+    def check(self, D_expected: int = -1):
+        """fav_check_patch_bank (host only); raises ValueError with the library's message."""
+        _check("fav_check_patch_bank", self.to_c(), D_expected)
+
+
+def _maps_f64(maps) -> np.ndarray:
+    """bf16 maps as a torch tensor, as uint16 bit patterns or as numpy floats -> float64, same shape."""
+    if hasattr(maps, "detach"):
+        import torch
+        return maps.detach().to(device="cpu", dtype=torch.float64).numpy()
+    a = np.asarray(maps)
+    if a.dtype == np.uint16:
+        return (a.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+    return a.astype(np.float64)
+
+
+def cell_rows(maps):
+    """maps [S, n, HW, C] or [S, n, Hf, Wf, C] -> (rows uint16 [n * HW, C], ok bool [n * HW], grid or None): the mean over the
+    samples of every cell, divided by its Euclidean norm in float64, rounded to bf16 (nearest even).  ``ok`` is False for a
+    cell that has no direction - a zero cell, a non-finite value - whose row is all zero."""
+    x = _maps_f64(maps)
+    if x.ndim not in (4, 5) or x.shape[0] < 1:
+        raise ValueError(f"maps must be [S, n, HW, C] or [S, n, Hf, Wf, C], got shape {x.shape}")
+    grid = (int(x.shape[2]), int(x.shape[3])) if x.ndim == 5 else None
+    with np.errstate(all="ignore"):
+        f = x.mean(axis=0).reshape(-1, x.shape[-1])
+        norm = np.sqrt((f * f).sum(axis=1))
+        ok = np.isfinite(f).all(axis=1) & (norm > 0) & np.isfinite(norm)
+        unit = np.where(ok[:, None], f / np.where(ok, norm, 1.0)[:, None], 0.0)
+    return _bf16_bits(unit.astype(np.float32)), ok, grid
+
+
+def bank_from_rows(rows, ok, max_rows: int | None = None, seed: int = 0, grid=None, threshold: float = math.inf,
+                   chunk_rows: int = 0) -> PatchBank:
+    """What ``cell_rows`` made, of one batch or of several concatenated -> the bank: the cells without a direction dropped
+    and counted, then ``max_rows`` of the rest kept, drawn as ``ood.build_knn_bank`` draws them (without replacement by
+    ``np.random.default_rng(seed)``, in their original order)."""
+    rows, ok = np.asarray(rows, np.uint16), np.asarray(ok, bool)
+    if rows.ndim != 2 or ok.shape != (rows.shape[0],):
+        raise ValueError(f"shapes do not fit: rows {rows.shape}, ok {ok.shape}")
+    kept = rows[ok]
+    if kept.shape[0] < 1:
+        raise ValueError("no cell has a direction: every one is zero or non-finite")
+    kept, _ = _subsample(kept, max_rows, seed)
+    return PatchBank(kept, threshold, chunk_rows, grid, int((~ok).sum()))
+
+
+def build_patch_bank(maps, max_rows: int | None = None, seed: int = 0, **kw) -> PatchBank:
+    """bf16 feature maps [S, n, HW, C] (or [S, n, Hf, Wf, C], as ``Backend.maps()`` gives them) of in-distribution frames ->
+    the bank: ``bank_from_rows`` of ``cell_rows``.  ``bank.n_dropped`` counts the zero and non-finite cells left out.  The
+    subsample is random; a greedy coreset is out of scope."""
+    rows, ok, grid = cell_rows(maps)
+    kw.setdefault("grid", grid)
+    return bank_from_rows(rows, ok, max_rows, seed, **kw)
+
+
+def unpack_patch_records(records) -> dict:
+    """int32[..., 8] fav_patch_record records (torch tensor or numpy) -> ``n_degenerate`` int32, ``mean_dist``, ``peak`` fp32,
+    ``peak_cell`` int32, ``floor`` fp32, ``peak_row``, ``n_above``, ``box`` int32 (packed; -1: none), each [...] and a view of the
+    record buffer, plus the box unpacked to ``x0``, ``y0``, ``x1``, ``y1`` (inclusive map cells; all -1 when the box is -1) and
+    ``anomalous`` = (n_above > 0) | (n_degenerate > 0): a cell at or above the threshold, or one that could not be scored."""
+    if records.ndim < 1 or int(records.shape[-1]) != PATCH_RECORD_DWORDS:
+        raise ValueError(f"expected int32[..., {PATCH_RECORD_DWORDS}] records, got shape {tuple(records.shape)}")
+    if isinstance(records, np.ndarray):
+        f32, where = np.float32, np.where
+    else:
+        import torch
+        f32, where = torch.float32, torch.where
+    out = {name: records[..., j].view(f32) if j in _FLOAT_DWORDS else records[..., j] for j, name in enumerate(_FIELDS)}
+    box = out["box"]
+    none = box == -1
+    for name, shift in (("x0", 0), ("y0", 8), ("x1", 16), ("y1", 24)):
+        out[name] = where(none, box, (box >> shift) & 0xFF)
+    out["anomalous"] = (out["n_above"] > 0) | (out["n_degenerate"] > 0)
+    return out

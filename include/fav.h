@@ -744,6 +744,63 @@ fav_status fav_classify_rise(fav_handle* h, const void* images_dev, int32_t n, i
                              const int32_t* classes_dev, int32_t mh, int32_t mw, int32_t* labels_dev, float* conf_dev,
                              float* map_dev, fav_rise_record* rec_dev, void* hip_stream);
 
+/* ---- Patch-level anomaly maps (PatchCore, Roth et al. 2022).  The feature-space heads above say
+ * WHETHER a frame is unlike the training data, the localisation heads WHERE the classifier's decision comes from; this one says
+ * WHERE a frame is unlike the training data.  A BANK holds N L2-normalised in-distribution PATCH features - cells of the last
+ * feature map - as bf16 rows; every cell of a frame's map gets the squared Euclidean distance of its normalised feature to its
+ * nearest bank row.  That is an anomaly heat map, and its peak is a frame score that the average pool does not dilute.  ResNet
+ * arches only (the map tap's).  All pointers are HOST pointers.
+ * Ranges (fav_check_patch_bank; FAV_ERR_INVALID_ARG and a message that names the field): struct_size == sizeof(fav_patch_bank);
+ * D and N as in fav_knn_bank, D also the map's channel count C when set on a handle; chunk_rows 0 (the default rule below) or a
+ * multiple of 64 in [64, 262144]; no row value NaN or inf; threshold not NaN.  The rows are meant to be unit vectors; this is
+ * not checked. */
+typedef struct fav_patch_bank {
+    uint32_t struct_size; int32_t D, N, chunk_rows;
+    const uint16_t* rows;   /* [N][D] bf16 bit patterns, meant to be unit vectors (host) */
+    float threshold;        /* a cell is above when dist >= threshold; +inf: never */
+} fav_patch_bank;
+/* One frame's summary, 32 bytes, 8-byte aligned.  peak (byte 8) and floor (byte 16) stand where fav_cam_record has them, so
+ * fav_op_cam_heatmap draws the dist map from this record.  Row r = i * HW + c is frame i, cell c; the maps are x[S][n][HW][C]:
+ *   1. q[r], DEGENERATE   steps 1 to 3 and 7 of fav_knn_record with feat = x read as [S][n * HW][C]: a cell is a frame there
+ *   2. sim[r][b]          b < N: step 4 of fav_knn_record, unchanged: the production GEMM accumulator plus +0.0f
+ *   3. nn_sim[r]          the largest sim[r][b]; nn_row[r] the LOWEST b that holds it; dist[r] = fmaxf(2.0f - 2.0f * nn_sim[r],
+ *                         +0.0f).  A degenerate cell gets dist = NaN (0x7FC00000) and nn_row = -1, and touches no other cell
+ *   4. the record of frame i over dist[i][0 .. HW):
+ *        n_degenerate     the count of degenerate cells
+ *        mean_dist        +0 plus dist[hw] in index order, times (float)(1.0 / HW); a NaN carries through
+ *        peak, peak_cell, floor   step 4 of fav_cam_record: strict > from -inf, strict < from +inf, the lowest cell on a tie,
+ *                         a NaN never wins (all cells degenerate: peak -inf, floor +inf, peak_cell -1)
+ *        peak_row         nn_row[peak_cell], -1 when peak_cell is -1
+ *        n_above, box     the cells with dist >= threshold (a NaN cell is not one) and the inclusive extent of them, packed as
+ *                         in fav_cam_record over the Hf x Wf grid; -1 when n_above == 0
+ *   5. nothing in a record or a map depends on chunk_rows: the maximum of (sim, -row) is associative and commutative, so the
+ *      columns of the bank may be folded in any grouping. */
+typedef struct fav_patch_record { int32_t n_degenerate; float mean_dist, peak; int32_t peak_cell; float floor;
+                                  int32_t peak_row, n_above, box; } fav_patch_record;
+/* Host only, no device: the ranges above (D_expected < 0: any width in range), the one place they live; fav_set_patch_bank
+ * calls it first.  err (may be NULL) receives the message. */
+fav_status fav_check_patch_bank(const fav_patch_bank* bank, int32_t D_expected, char* err, size_t err_cap);
+/* The handle's patch bank (NULL: none), as fav_set_knn in every respect that is not the tap: copied to the device (padded with
+ * zero rows to a multiple of 64), D checked against the map's channel count, the whole workspace allocated here for max_batch *
+ * Hf * Wf cells (Hf, Wf, C from the planner, as fav_map_tap_info reports them) - fav_classify_patch never allocates or
+ * synchronises - and a workspace above 1 GiB refused with the numbers in the message.  The map tap is NOT touched: it stays
+ * the caller's, as for fav_cam.  Independent of the feature-space heads: a k-NN bank and a patch bank may be set together.
+ * Replacing or clearing a bank waits on the host for the work enqueued on the handle and frees the old copy.
+ * FAV_ERR_UNSUPPORTED on a ViT arch and on a deep-ensemble handle, as fav_set_map_tap.  A rejected call leaves the handle as it
+ * was. */
+fav_status fav_set_patch_bank(fav_handle* h, const fav_patch_bank* bank);
+/* The head on the maps of the LAST fav_classify* call: dist_dev fp32 [n][Hf*Wf] (4-byte aligned), row_dev int32 [n][Hf*Wf]
+ * (4-byte aligned) or NULL, rec_dev [n] (8-byte aligned), n the frames of that call.  No second forward pass, no allocation,
+ * no synchronisation.  FAV_ERR_INVALID_ARG with the tap off, before the first tapped call, without a bank and for a NULL or
+ * misaligned buffer.  FAV_ERR_UNSUPPORTED while views are set or when the last call ran under views, as fav_cam. */
+fav_status fav_patch(fav_handle* h, float* dist_dev, int32_t* row_dev, fav_patch_record* rec_dev, void* hip_stream);
+/* fav_classify_ex unchanged, then fav_patch on the same stream.  Needs the map tap on and a bank (FAV_ERR_INVALID_ARG
+ * otherwise); FAV_ERR_UNSUPPORTED while views are set.  Never allocates or synchronises.  fail_dev / score_dev may be NULL.
+ * The head's launches are booked in no kernel class. */
+fav_status fav_classify_patch(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
+                              int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev, float* dist_dev,
+                              int32_t* row_dev, fav_patch_record* rec_dev, void* hip_stream);
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -1182,6 +1239,26 @@ fav_status fav_op_rise_mask(const void* frames_dev, void* out_dev, int32_t n, in
 fav_status fav_op_rise_accumulate(const float* prob_dev, const int32_t* classes_dev, int32_t n, const fav_rise* desc,
                                   int64_t first_image_index, int32_t H, int32_t W, int32_t mh, int32_t mw, int32_t num_classes,
                                   float* map_dev, fav_rise_record* rec_dev, void* hip_stream);
+
+/* ---- The patch head defined beside fav_patch_record, on device arrays: maps_bf16 [S][n][Hf*Wf][C] bf16, bank_dev [N][C] bf16
+ * (16-byte aligned; exactly N rows - the caller never pads), ws_dev a workspace of at least fav_patch_workspace_bytes(n * Hf *
+ * Wf, C, N, chunk_rows) bytes on a 256-byte boundary, dist_dev fp32 [n][Hf*Wf] and row_dev int32 [n][Hf*Wf] or NULL (4-byte
+ * aligned), rec_dev [n] (8-byte aligned).  The k-NN head's query kernel on a grid of n * Hf * Wf blocks; then, one column chunk
+ * of the bank at a time, the similarity GEMM through the convolution launcher into one slab sim[n * Hf * Wf][chunk] (1x1, fp32
+ * output, zero bias; fav_op_last_route names its tile; an unpadded bank's last part tile goes through a zero-padded 64-row tile
+ * in the workspace) and the fold of that slab into a running (similarity, row) a cell - stream order makes reusing the slab
+ * safe; then the score kernel, a block a frame.  The chunk: chunk_rows when given, else the largest multiple of 128 whose slab
+ * fits 256 MiB, at least 128; either way at most N padded to 64 (fav_patch_chunk_rows).  No allocation, no synchronisation;
+ * vector stores only.  Padding columns and degenerate cells' rows of the slab are never read by the fold.
+ * A refused call (FAV_ERR_INVALID_ARG: a NULL pointer other than row_dev, S outside [1, 4096], n < 1, Hf*Wf outside [1, 1024] or
+ * a side above 256, n*Hf*Wf above 2^31 - 1, C or N outside the ranges of fav_patch_bank, a bad chunk_rows, a NaN threshold, a
+ * workspace too small or misaligned, a misaligned bank_dev, dist_dev, row_dev or rec_dev) launches nothing and leaves a message
+ * that names the function in fav_last_error(NULL). */
+size_t fav_patch_workspace_bytes(int32_t cells_total, int32_t D, int32_t N, int32_t chunk_rows);   /* host only; 0 for sizes out of range */
+int32_t fav_patch_chunk_rows(int32_t cells_total, int32_t N, int32_t chunk_rows);   /* host only: the slab's columns; 0 out of range */
+fav_status fav_op_patch_score(const void* maps_bf16, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C,
+                              const void* bank_dev, int32_t N, int32_t chunk_rows, float threshold, void* ws_dev,
+                              size_t ws_bytes, float* dist_dev, int32_t* row_dev, fav_patch_record* rec_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
