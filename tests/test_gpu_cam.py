@@ -235,13 +235,20 @@ def bits_of(t):
 
 
 E2E = {
-    "r18_single": dict(arch="resnet18_cifar", hw=32, n=5, kw=dict(), pooled=False, S=1, chunks=dict(chunk_a=2, chunk_b=3)),
-    "r18_mc_all_blocks": dict(arch="resnet18_cifar", hw=32, n=5, kw=dict(n_samples=3, dropout_policy="all_blocks", dropout_p=0.1, seed=4),
+    "r18_single": dict(arch="resnet18_cifar", hw=(32, 32), n=5, kw=dict(), pooled=False, S=1, chunks=dict(chunk_a=2, chunk_b=3)),
+    "r18_mc_all_blocks": dict(arch="resnet18_cifar", hw=(32, 32), n=5, kw=dict(n_samples=3, dropout_policy="all_blocks", dropout_p=0.1, seed=4),
                               pooled=False, S=3, chunks=dict(chunk_a=4, chunk_b=7)),
-    "r18_mc_pooled_only": dict(arch="resnet18_cifar", hw=32, n=5, kw=dict(n_samples=3, dropout_policy="last_layer", dropout_p=0.1, seed=4),
+    "r18_mc_pooled_only": dict(arch="resnet18_cifar", hw=(32, 32), n=5, kw=dict(n_samples=3, dropout_policy="last_layer", dropout_p=0.1, seed=4),
                                pooled=True, S=1, chunks=dict(chunk_a=2, chunk_b=2)),
-    "r50_64": dict(arch="resnet50", hw=64, n=3, kw=dict(), pooled=False, S=1, chunks=dict(chunk_a=1, chunk_b=2)),
+    "r50_64": dict(arch="resnet50", hw=(64, 64), n=3, kw=dict(), pooled=False, S=1, chunks=dict(chunk_a=1, chunk_b=2)),
+    # odd frame sizes: a 2 x 2 map (33 -> 17 -> 9 -> 5 -> 3 -> 2, 47 -> 24 -> 12 -> 6 -> 3 -> 2) upsampled to 33 x 47, and a 4 x 6 one
+    "r50_33x47": dict(arch="resnet50", hw=(33, 47), n=3, kw=dict(), pooled=False, S=1, chunks=dict(chunk_a=1, chunk_b=2)),
+    "r18_31x45": dict(arch="resnet18_cifar", hw=(31, 45), n=5, kw=dict(n_samples=3, dropout_policy="all_blocks", dropout_p=0.1, seed=4),
+                      pooled=False, S=3, chunks=dict(chunk_a=4, chunk_b=7)),
 }
+# (Hf, Wf) of the map: fav_map_tap_info's, which tests/test_odd_frames_host.py holds to the oracle's shapes at every size
+E2E_MAPS = {"r18_single": (4, 4), "r18_mc_all_blocks": (4, 4), "r18_mc_pooled_only": (4, 4), "r50_64": (2, 2), "r50_33x47": (2, 2),
+            "r18_31x45": (4, 6)}
 
 
 @pytest.mark.parametrize("case", list(E2E))
@@ -249,13 +256,14 @@ def test_end_to_end(case, r18_blob, r50_blob):
     c = E2E[case]
     blob = (r18_blob if c["arch"] == "resnet18_cifar" else r50_blob)[0]
     n, hw = c["n"], c["hw"]
-    frames = torch.from_numpy(synth.synthetic_frames_u8(n, hw, hw, seed=11)).cuda()
+    frames = torch.from_numpy(synth.synthetic_frames_u8(n, hw[0], hw[1], seed=11)).cuda()
     wb, bias = fc_of(blob)
     NCLS, D = wb.shape
-    be = Backend(c["arch"], blob, max_batch=8, in_hw=(hw, hw), **c["kw"])
+    be = Backend(c["arch"], blob, max_batch=8, in_hw=hw, **c["kw"])
     try:
         info = be.map_tap_info()
-        Hf = Wf = hw // 8 if c["arch"] == "resnet18_cifar" else hw // 32
+        Hf, Wf = info["hf"], info["wf"]
+        assert (Hf, Wf) == E2E_MAPS[case]
         assert info == dict(bytes=c["S"] * 8 * Hf * Wf * D * 2, samples=c["S"], hf=Hf, wf=Wf, c=D)
         # 1. the tap changes no result
         off = [t.cpu().numpy() for t in be.classify_detect(frames)] + [bits_of(be.logits())]
@@ -285,7 +293,7 @@ def test_end_to_end(case, r18_blob, r50_blob):
         for key, v in want.items():
             assert R.same_bits(out[key].cpu().numpy(), np.ascontiguousarray(v)), key
         assert np.array_equal(out["class_id"].cpu().numpy(), labels)
-        assert np.array_equal(out["heatmap"].cpu().numpy(), R.heatmap(Mr[:, 0], rr[:, 0], Hf, Wf, hw, hw))
+        assert np.array_equal(out["heatmap"].cpu().numpy(), R.heatmap(Mr[:, 0], rr[:, 0], Hf, Wf, hw[0], hw[1]))
         # 4. cam(top-5) after classify_uncertainty: no second pass, any classes
         unc = be.classify_uncertainty(frames)
         top5 = unc["top_label"]
@@ -312,7 +320,7 @@ def test_end_to_end(case, r18_blob, r50_blob):
                     bound = 2.0 ** -8 * (np.abs(w64[cc])[None, :] * x64[:, i].mean(axis=1)).sum(axis=1).mean()
                     assert abs(lm[i, k] - mean_logit) <= bound, (i, k, lm[i, k], mean_logit, bound)
         # 6. chunking: several chunks a phase leave the same maps
-        chunked = Backend(c["arch"], blob, max_batch=8, in_hw=(hw, hw), **c["kw"], **c["chunks"])
+        chunked = Backend(c["arch"], blob, max_batch=8, in_hw=hw, **c["kw"], **c["chunks"])
         try:
             chunked.set_map_tap(True)
             lab2, _ = chunked.classify(frames)

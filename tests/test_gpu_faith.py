@@ -389,7 +389,7 @@ def handle(request):
 def compose(be, frames_dev, maps_dev, classes, mode, first, fill):
     """fav_classify_curve restated with the public ops through the C ABI -> (curve, records, label, confidence), numpy."""
     lib, h, s = be.lib, be._h, stream()
-    n, size = int(frames_dev.shape[0]), int(frames_dev.shape[1])
+    n, fh, fw = (int(v) for v in frames_dev.shape[:3])
     mh, mw = int(maps_dev.shape[1]), int(maps_dev.shape[2])
     layout = U8 if frames_dev.dtype == torch.uint8 else F32
     S, Cc, cells = STEPS, int(be.cfg.num_classes), mh * mw
@@ -405,7 +405,7 @@ def compose(be, frames_dev, maps_dev, classes, mode, first, fill):
     cls = dev(np.asarray(classes, np.int32)) if classes is not None else lab0
     for k in range(S + 1):
         step = k if mode == R.DELETION else S - k
-        _lib.check(lib.fav_op_occlude(frames_dev.data_ptr(), occ.data_ptr(), n, size, size, layout, rank.data_ptr(), mh, mw, mode, S, step,
+        _lib.check(lib.fav_op_occlude(frames_dev.data_ptr(), occ.data_ptr(), n, fh, fw, layout, rank.data_ptr(), mh, mw, mode, S, step,
                                       step + 1, fill_words(fill), s))
         _lib.check(lib.fav_classify_ex(h, occ.data_ptr(), n, layout, first, (lab0 if k == 0 else scratch_l).data_ptr(),
                                        (conf0 if k == 0 else scratch_c).data_ptr(), None, None, s), h)
@@ -521,6 +521,61 @@ def test_chunked_calls_equal_one_call(handle):
     assert R.same_bits(got["curve"][:N], host(whole["curve"]))
     if kind != "resnet18_mc":                                                   # other global indices, other masks
         assert R.same_bits(got["curve"][N:2 * N], host(whole["curve"]))
+
+
+# ---- a frame size no cell grid divides -------------------------------------------------------------------------------------
+ODD_HW = (31, 45)
+
+
+@pytest.fixture(scope="module")
+def odd_handle():
+    """One ResNet-18 MC-Dropout handle at 31 x 45 (every stage odd: 31 x 45, 16 x 23, 8 x 12, 4 x 6) with a curve of STEPS steps."""
+    blob, _ = weights.make_synthetic("resnet18_cifar", seed=1)
+    be = Backend("resnet18_cifar", blob, in_hw=ODD_HW, max_batch=MAX_BATCH, temperature=1.3, n_samples=3, dropout_policy="all_blocks",
+                 dropout_p=0.1, seed=4)
+    be.set_curve(STEPS, fill=(0.25, 0.5, 1.0))
+    yield be, synth.synthetic_frames_u8(N, *ODD_HW, seed=21)
+    be.close()
+
+
+@pytest.mark.parametrize("dtype", ("u8", "f32"))
+@pytest.mark.parametrize("mhw", ((4, 4), (2, 3)), ids=ids)
+def test_classify_curve_at_an_odd_frame_size(odd_handle, lib, mhw, dtype):
+    """31 x 45 under 4 x 4 and 2 x 3 cells: neither grid divides the frame (a cell is 7.75 x 11.25 or 15.5 x 15 pixels).  The
+    handle's curve is the composition of the ops, the unoccluded pass is the plain call, and the occluded pixels are
+    faith_ref's cells of the frame, not of a square."""
+    be, frames = odd_handle
+    maps = R.tricky_maps(N, mhw[0] * mhw[1], seed=5)[::-1].reshape(N, *mhw).copy()
+    maps[2] = faithfulness.random_maps(1, mhw, 9)[0]
+    fd = dev(frames) if dtype == "u8" else dev(frames.astype(np.float32) / np.float32(255.0))
+    fill = U8_FILL if dtype == "u8" else F32_FILL
+    md = dev(maps)
+    plain_lab, plain_conf = (host(v) for v in be.classify_detect(fd, first_index=FIRST)[:2])
+    mean_prob = host(be.classify_uncertainty(fd, first_index=FIRST)["mean_prob"])
+    res = {}
+    for mode_name, mode in (("deletion", R.DELETION), ("insertion", R.INSERTION)):
+        got = be.classify_curve(fd, md, None, mode_name, first_index=FIRST)
+        curve, rec, lab0, conf0, rank = compose(be, fd, md, None, mode, FIRST, fill)
+        assert R.same_bits(host(got["curve"]), curve) and R.same_records(records_of(got), rec), mode_name
+        assert np.array_equal(host(got["label"]), plain_lab) and R.same_bits(host(got["confidence"]), plain_conf)
+        assert np.array_equal(lab0, plain_lab) and R.same_bits(conf0, plain_conf)
+        assert np.array_equal(rank, R.rank_cells(maps.reshape(N, -1)))
+        assert not np.isnan(curve).any()
+        res[mode_name] = {k: host(v) for k, v in got.items()}
+        # the pixels the op fills at this frame size: whole steps, against the reference's mask of an H x W frame
+        src = host(fd)
+        occ = run_occlude(lib, src, rank, mhw[0], mhw[1], mode, STEPS, 0, STEPS + 1, fill)
+        assert bits_equal(occ, R.occlude(src, rank, mhw[0], mhw[1], mode, STEPS, 0, STEPS + 1, fill))
+        for s in range(STEPS + 1):
+            m = R.occluded_mask(rank, ODD_HW[0], ODD_HW[1], mhw[0], mhw[1], STEPS, s)
+            filled = m if mode == R.DELETION else ~m
+            assert bits_equal(occ[s][~filled], src[~filled])
+    assert R.same_bits(res["deletion"]["p_first"], mean_prob) and R.same_bits(res["insertion"]["p_last"], mean_prob)
+    assert R.same_bits(res["deletion"]["p_last"], res["insertion"]["p_first"])
+    # chunked over the frames: other first_index, the same masks for the same global frame
+    a = be.classify_curve(fd[:2], md[:2], None, "deletion", first_index=FIRST)
+    b = be.classify_curve(fd[2:], md[2:], None, "deletion", first_index=FIRST + 2)
+    assert R.same_bits(np.concatenate([host(a["curve"]), host(b["curve"])]), res["deletion"]["curve"])
 
 
 def test_handle_refusals():

@@ -282,21 +282,28 @@ def maps_are_tapped(be):
 
 
 MC = dict(n_samples=3, dropout_policy="all_blocks", dropout_p=0.1, seed=4)
-E2E = {"r18_single": dict(arch="resnet18_cifar", hw=32, n=5, kw=dict(), S=1, map=(4, 4, 512)),
-       "r18_mc": dict(arch="resnet18_cifar", hw=32, n=5, kw=MC, S=3, map=(4, 4, 512)),
-       "r50_single": dict(arch="resnet50", hw=64, n=2, kw=dict(), S=1, map=(2, 2, 2048)),
-       "r50_mc": dict(arch="resnet50", hw=64, n=2, kw=MC, S=3, map=(2, 2, 2048))}
+E2E = {"r18_single": dict(arch="resnet18_cifar", hw=(32, 32), n=5, kw=dict(), S=1, map=(4, 4, 512)),
+       "r18_mc": dict(arch="resnet18_cifar", hw=(32, 32), n=5, kw=MC, S=3, map=(4, 4, 512)),
+       "r50_single": dict(arch="resnet50", hw=(64, 64), n=2, kw=dict(), S=1, map=(2, 2, 2048)),
+       "r50_mc": dict(arch="resnet50", hw=(64, 64), n=2, kw=MC, S=3, map=(2, 2, 2048)),
+       # odd frame sizes: the 2 x 2 map of a 33 x 47 frame, the 4 x 6 map of a 31 x 45 one, their heat maps upsampled to the frame
+       "r50_33x47": dict(arch="resnet50", hw=(33, 47), n=2, kw=MC, S=3, map=(2, 2, 2048)),
+       "r18_31x45": dict(arch="resnet18_cifar", hw=(31, 45), n=5, kw=dict(), S=1, map=(4, 6, 512))}
 
 
 @pytest.mark.parametrize("case", list(E2E))
 def test_end_to_end(lib, case, r18_blob, r50_blob):
     c = E2E[case]
     blob = (r18_blob if c["arch"] == "resnet18_cifar" else r50_blob)[0]
-    n, hw, (Hf, Wf, Cc) = c["n"], c["hw"], c["map"]
-    frames = dev(synth.synthetic_frames_u8(n, hw, hw, seed=11))
-    fit = dev(synth.synthetic_frames_u8(11, hw, hw, seed=12))                        # two batches of max_batch = 8
-    be = Backend(c["arch"], blob, max_batch=8, in_hw=(hw, hw), **c["kw"])
+    n, hw = c["n"], c["hw"]
+    frames = dev(synth.synthetic_frames_u8(n, hw[0], hw[1], seed=11))
+    fit = dev(synth.synthetic_frames_u8(11, hw[0], hw[1], seed=12))                  # two batches of max_batch = 8
+    be = Backend(c["arch"], blob, max_batch=8, in_hw=hw, **c["kw"])
     try:
+        # the map's geometry: fav_map_tap_info's (tests/test_odd_frames_host.py holds it to the oracle's shapes at every size)
+        info = be.map_tap_info()
+        Hf, Wf, Cc = info["hf"], info["wf"], info["c"]
+        assert (Hf, Wf, Cc) == c["map"] and info["samples"] == c["S"] and info["bytes"] == c["S"] * 8 * Hf * Wf * Cc * 2
         plain = [t.cpu().numpy() for t in be.classify_detect(frames)]
         bank = be.fit_patch_bank(fit, max_rows=100, seed=3)
         assert (bank.N, bank.D, bank.grid) == (min(100, 11 * Hf * Wf - bank.n_dropped), Cc, (Hf, Wf))
@@ -322,7 +329,7 @@ def test_end_to_end(lib, case, r18_blob, r50_blob):
         dist, row, rec = R.score(xb, bank.rows, Wf, bank.threshold)
         assert got["dist"].shape == (n, Hf, Wf) and got["nn_row"].shape == (n, Hf, Wf)
         assert same((got["dist"].reshape(n, -1), got["nn_row"].reshape(n, -1), records_of(got)), (dist, row, rec))
-        assert np.array_equal(got["heatmap"], cam_ref.heatmap(dist, rec, Hf, Wf, hw, hw))
+        assert np.array_equal(got["heatmap"], cam_ref.heatmap(dist, rec, Hf, Wf, hw[0], hw[1]))
         assert (np.nan_to_num(dist) > 0).any()
         # fav_patch on the maps of the last call: the same bytes, no second pass; and the op on those maps
         d2 = torch.empty((n, Hf * Wf), dtype=torch.float32, device="cuda")

@@ -395,7 +395,7 @@ def call_rise(be, frames_dev, classes, first, mhw=MAP):
 def compose(be, frames_dev, classes, first, mhw=MAP):
     """fav_classify_rise restated with the public ops through the C ABI -> (map, records, label, confidence), numpy."""
     lib, h, s = be.lib, be._h, stream()
-    n, size = int(frames_dev.shape[0]), int(frames_dev.shape[1])
+    n, fh, fw = (int(v) for v in frames_dev.shape[:3])
     layout = U8 if frames_dev.dtype == torch.uint8 else F32
     Cc = int(be.cfg.num_classes)
     ld = (Cc + 3) // 4 * 4
@@ -409,7 +409,7 @@ def compose(be, frames_dev, classes, first, mhw=MAP):
     for k in range(D.n_masks + 1):
         src = frames_dev
         if k > 0:
-            _lib.check(lib.fav_op_rise_mask(frames_dev.data_ptr(), masked.data_ptr(), n, size, size, layout, C.byref(cd), first, k - 1, k, s))
+            _lib.check(lib.fav_op_rise_mask(frames_dev.data_ptr(), masked.data_ptr(), n, fh, fw, layout, C.byref(cd), first, k - 1, k, s))
             src = masked
         _lib.check(lib.fav_classify_ex(h, src.data_ptr(), n, layout, first, (lab0 if k == 0 else scratch_l).data_ptr(),
                                        (conf0 if k == 0 else scratch_c).data_ptr(), None, None, s), h)
@@ -420,7 +420,7 @@ def compose(be, frames_dev, classes, first, mhw=MAP):
                                               prob[k].data_ptr(), None, s))
     mp = torch.empty((n, mhw[0] * mhw[1]), dtype=torch.float32, device="cuda")
     rec = torch.empty((n, 8), dtype=torch.int32, device="cuda")
-    _lib.check(lib.fav_op_rise_accumulate(prob.data_ptr(), cls.data_ptr(), n, C.byref(cd), first, size, size, mhw[0], mhw[1], Cc, mp.data_ptr(),
+    _lib.check(lib.fav_op_rise_accumulate(prob.data_ptr(), cls.data_ptr(), n, C.byref(cd), first, fh, fw, mhw[0], mhw[1], Cc, mp.data_ptr(),
                                           rec.data_ptr(), s))
     torch.cuda.synchronize()
     return mp.cpu().numpy(), rec.cpu().numpy(), lab0.cpu().numpy(), conf0.cpu().numpy(), prob.cpu().numpy()
@@ -468,6 +468,45 @@ def test_classify_rise_takes_fp32_frames_and_classes_outside_the_range(handle):
     bad = [-1, R.NAN_BITS, R.NAN_BITS, -1, R.NAN_BITS, R.NAN_BITS, 0, -1]
     assert rec[1].tolist() == bad and rec[2].tolist() == bad and np.isnan(mp[1:3]).all(), kind
     assert rec[0, 0] == 0 and rec[3, 0] == Cc - 1 and not np.isnan(mp[[0, 3]]).any()
+
+
+# ---- a frame size neither the grid nor the map divides -------------------------------------------------------------------
+ODD_HW = (31, 45)
+
+
+@pytest.fixture(scope="module")
+def odd_handle():
+    """One ResNet-18 MC-Dropout handle at 31 x 45 with the end-to-end descriptor: grid 3, so a mask cell is ceil(31 / 3) = 11 by
+    ceil(45 / 3) = 15 pixels and the 4 x 4 grid of shifted cells overhangs the frame on both axes."""
+    be, _ = make_backend("resnet18_mc", in_hw=ODD_HW, temperature=1.3)
+    assert R.cell_sizes(*ODD_HW, D.grid) == (11, 15)
+    set_e2e(be)
+    yield be, synth.synthetic_frames_u8(3, *ODD_HW, seed=21)
+    be.close()
+
+
+@pytest.mark.parametrize("dtype", ("u8", "f32"))
+@pytest.mark.parametrize("mhw", ((4, 4), (2, 3)), ids=ids)
+def test_classify_rise_at_an_odd_frame_size(odd_handle, lib, mhw, dtype):
+    be, frames = odd_handle
+    n = frames.shape[0]
+    fd = dev(frames) if dtype == "u8" else dev(frames.astype(np.float32) / np.float32(255.0))
+    Cc = int(be.cfg.num_classes)
+    plain_lab, plain_conf = (host(v) for v in be.classify_detect(fd, first_index=FIRST)[:2])
+    # the masked frames of this size are the reference's, not those of a square
+    got = run_mask(lib, host(fd), D, FIRST, 0, D.n_masks)
+    want, mq = R.rise_mask(host(fd), D, FIRST, 0, D.n_masks)
+    assert masked_equal(got, want, mq)
+    for classes in (None, (np.arange(n, dtype=np.int32) * 3 + 1) % Cc):
+        mp, rec, lab, conf = call_rise(be, fd, classes, FIRST, mhw)
+        wmp, wrec, wlab, wconf, prob = compose(be, fd, classes, FIRST, mhw)
+        assert same_map_bits(mp, wmp) and R.same_records(rec, wrec), (rec, wrec)
+        assert np.array_equal(lab, plain_lab) and np.array_equal(conf.view(np.uint32), plain_conf.view(np.uint32))
+        assert np.array_equal(wlab, plain_lab) and np.array_equal(wconf.view(np.uint32), plain_conf.view(np.uint32))
+        assert np.array_equal(rec[:, 0], plain_lab if classes is None else classes)
+        ref_map, ref_rec, _ = R.accumulate(prob, rec[:, 0], D, FIRST, ODD_HW[0], ODD_HW[1], mhw[0], mhw[1], Cc)
+        assert same_map_bits(mp, ref_map) and R.same_records(rec, ref_rec)
+        assert not np.isnan(mp).any() and mp.any()
 
 
 def test_handle_refusals():

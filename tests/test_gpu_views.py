@@ -323,6 +323,46 @@ def test_handle_logits_and_heads(lib, handle):
     be.set_views(None)
 
 
+# ---- views at odd frame sizes, against the oracle -----------------------------------------------------------------------
+ODD_VIEWS = {
+    # 31 x 45: every stage of ResNet-18 is odd along one axis at least (31 x 45, 16 x 23, 8 x 12, 4 x 6), and no view may swap
+    # the axes.  The mirror images, then one shift under each border rule - beyond the frame's edge on both axes
+    (31, 45): [views.View(), views.View(flip_x=True), views.View(flip_y=True), views.View(dy=3, dx=-5, border="reflect101"),
+               views.View(dy=-2, dx=4, border="replicate"), views.View(dy=5, dx=7, border="zero")],
+    # 33 x 33: one pixel more than the transposed kernel's 32-pixel tile
+    (33, 33): [views.View(), views.View(transpose=True), views.View(flip_x=True, transpose=True, dy=1, border="replicate")],
+}
+
+
+@pytest.mark.parametrize("hw", list(ODD_VIEWS), ids=ids)
+def test_views_at_an_odd_frame_size_against_the_oracle(hw):
+    """The handle's logits under views are the oracle's (the bit-exact model of the production mode) on views_ref's expanded
+    frames: sample a of frame i is view a of frame i - which pins the view kernel's H x W indexing and the forward pass at
+    this size in one comparison."""
+    from oracle import fav_oracle as O
+    vs = ODD_VIEWS[hw]
+    blob, _ = weights.make_synthetic("resnet18_cifar", seed=1)
+    frames = synth.synthetic_frames_u8(N, hw[0], hw[1], seed=21)
+    expanded = R.apply_views(frames, vs)                                            # [A, N, H, W, 3]
+    assert all(not np.array_equal(expanded[0], expanded[a]) for a in range(1, len(vs)))
+    want = O.classify(O.parse_blob(blob), expanded.reshape(len(vs) * N, hw[0], hw[1], 3), O.ClassifyConfig(exact="mfma"),
+                      return_logits=True)[2]
+    want = want.reshape(len(vs), N, -1)
+    be = Backend("resnet18_cifar", blob, in_hw=hw, max_batch=MAX_BATCH, views=vs)
+    try:
+        assert be.T == len(vs)
+        for dev in (torch.from_numpy(frames).cuda(), torch.from_numpy(frames.astype(np.float32) / np.float32(255.0)).cuda()):
+            if dev.dtype == torch.float32:                                          # fp32 frames: the oracle on the same pixels
+                want = O.classify(O.parse_blob(blob), R.apply_views(dev.cpu().numpy(), vs).reshape(len(vs) * N, hw[0], hw[1], 3),
+                                  O.ClassifyConfig(exact="mfma"), return_logits=True)[2].reshape(len(vs), N, -1)
+            be.classify(dev)
+            got = be.logits().cpu().numpy()
+            assert got.shape == want.shape and np.array_equal(got.view(np.int32), want.view(np.int32)), str(dev.dtype)
+            assert not np.array_equal(got[0], got[1])
+    finally:
+        be.close()
+
+
 def test_handle_host_frames_and_f32(handle):
     be, frames, _ = handle
     be.set_views(VIEWS)

@@ -439,7 +439,8 @@ def test_fused_schedule_computes_the_layer_by_layer_dataflow(lib):
                  weights.site_mask_for(arch, "layer4+fc"), 0b101000, 1 << 3, (1 << nb) | 1]
         for mask in masks:
             for regroup in (-1, 0, 1, 3, 7, 8, nb):
-                for hw in ((224, 224), (64, 64), (240, 320), (1024, 2048)):
+                for hw in ((224, 224), (64, 64), (240, 320), (1024, 2048), (8, 8), (9, 11), (33, 47), (47, 33), (63, 65), (225, 223),
+                           (8, 225)):
                     kw = dict(in_h=hw[0], in_w=hw[1], site_mask=mask, n_samples=3 if mask else 1, dropout_p=0.1 if mask else 0.0,
                               regroup_block=regroup)
                     fused, plain = _plan(lib, arch, 0, **kw), _plan(lib, arch, 1, **kw)
