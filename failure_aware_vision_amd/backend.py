@@ -665,16 +665,7 @@ class Backend:
         d = _lib.FavCurve()
         d.struct_size = C.sizeof(_lib.FavCurve)
         d.steps = int(steps)
-        if fill is None:
-            u8, f32 = (128, 128, 128), (0.5, 0.5, 0.5)
-        else:
-            f32 = tuple(float(v) for v in (fill if np.ndim(fill) else (fill,) * 3))
-            if len(f32) != 3:
-                raise ValueError("fill is a number or a 3-tuple")
-            u8 = tuple(int(round(255.0 * v)) for v in f32)
-        for c in range(3):
-            d.fill_u8[c] = u8[c] & 0xFFFFFFFF
-            d.fill_f32_bits[c] = int(np.float32(f32[c]).view(np.uint32))
+        d.fill_u8[:], d.fill_f32_bits[:] = self._fill_words(fill)
         _lib.check(self.lib.fav_set_curve(self._h, C.byref(d)), self._h)
         self._curve_steps = int(steps)
 
@@ -687,36 +678,20 @@ class Backend:
         Frames beyond ``frames_per_call`` go in further calls with ``first_index`` advanced.  torch CUDA frames in -> CUDA tensors
         out, asynchronous on the current stream; numpy in -> numpy out.  Needs ``set_curve``."""
         from .faithfulness import CURVE_RECORD_DWORDS, unpack_curve_records
-        torch = self._torch
         if mode not in _lib.CURVE_MODES:
             raise ValueError(f"mode must be one of {_lib.CURVE_MODES}, got {mode!r}")
-        img, host, n, layout, stream = self._classify_args(frames)
-        dev = img.device
-        m = torch.as_tensor(maps).to(device=dev, dtype=torch.float32).contiguous()
+        args = self._classify_args(frames)
+        n = args[2]
+        m = self._torch.as_tensor(maps).to(device=args[0].device, dtype=self._torch.float32).contiguous()
         if m.ndim != 3 or int(m.shape[0]) != n:
             raise ValueError(f"maps must be [n, mh, mw] for the n={n} frames, got {tuple(m.shape)}")
         mh, mw = int(m.shape[1]), int(m.shape[2])
-        cls = None
-        if classes is not None:
-            cls = torch.as_tensor(np.asarray(classes) if not hasattr(classes, "is_cuda") else classes).to(device=dev, dtype=torch.int32)
-            cls = cls.contiguous()
-            if tuple(cls.shape) != (n,):
-                raise ValueError(f"classes must be [n] for the n={n} frames, got {tuple(cls.shape)}")
         S = self._curve_steps if self._curve_steps is not None else 0     # never set: fav_classify_curve refuses before it writes
-        curve = torch.empty((n, S + 1), dtype=torch.float32, device=dev)
-        rec = torch.empty((n, CURVE_RECORD_DWORDS), dtype=torch.int32, device=dev)
-        labels = torch.empty(n, dtype=torch.int32, device=dev)
-        conf = torch.empty(n, dtype=torch.float32, device=dev)
-        for b, e in (self._batches(n) if n else ()):
-            _lib.check(self.lib.fav_classify_curve(
-                self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b, m[b:e].data_ptr(), mh, mw,
-                cls[b:e].data_ptr() if cls is not None else None, _lib.CURVE_MODES.index(mode), labels[b:e].data_ptr(),
-                conf[b:e].data_ptr(), curve[b:e].data_ptr(), rec[b:e].data_ptr(), stream), self._h)
-        out = dict(curve=curve, label=labels, confidence=conf)
-        if host:
-            out = {k: v.cpu().numpy() for k, v in out.items()}
-            rec = rec.cpu().numpy()
-        return dict(unpack_curve_records(rec), **out)
+        return self._classify_perturb_head(
+            lambda b, e, img, k, layout, first, cls, labels, conf, curve, rec, stream: self.lib.fav_classify_curve(
+                self._h, img, k, layout, first, m[b:e].data_ptr(), mh, mw, cls, _lib.CURVE_MODES.index(mode), labels, conf, curve, rec,
+                stream),
+            args, classes, "curve", (S + 1,), CURVE_RECORD_DWORDS, unpack_curve_records, False, first_index)
 
     def faithfulness_report(self, frames, steps: int = 16, seed: int = 0, fill=None, maps=None) -> dict:
         """Is this checkpoint's saliency map faithful on these frames?  The maps come from ``classify_cam`` (ResNet) or
@@ -771,16 +746,7 @@ class Backend:
         d = _lib.FavRise()
         d.struct_size = C.sizeof(_lib.FavRise)
         d.n_masks, d.grid, d.keep, d.seed = int(n_masks), int(grid), keep_threshold(keep), int(seed) & 0xFFFFFFFFFFFFFFFF
-        if fill is None:
-            u8, f32 = (128, 128, 128), (0.5, 0.5, 0.5)
-        else:
-            f32 = tuple(float(v) for v in (fill if np.ndim(fill) else (fill,) * 3))
-            if len(f32) != 3:
-                raise ValueError("fill is a number or a 3-tuple")
-            u8 = tuple(int(round(255.0 * v)) for v in f32)
-        for c in range(3):
-            d.fill_u8[c] = u8[c] & 0xFFFFFFFF
-            d.fill_f32_bits[c] = int(np.float32(f32[c]).view(np.uint32))
+        d.fill_u8[:], d.fill_f32_bits[:] = self._fill_words(fill)
         _lib.check(self.lib.fav_set_rise(self._h, C.byref(d)), self._h)
 
     def classify_rise(self, frames, classes=None, map_hw=(14, 14), heatmap: bool = False, first_index: int = 0) -> dict:
@@ -794,37 +760,67 @@ class Backend:
         ``frames_per_call`` go in further calls with ``first_index`` advanced.  torch CUDA frames in -> CUDA tensors out,
         asynchronous on the current stream; numpy in -> numpy out.  Needs ``set_rise``."""
         from .rise import RISE_RECORD_DWORDS, unpack_rise_records
-        torch = self._torch
-        img, host, n, layout, stream = self._classify_args(frames)
-        dev = img.device
+        args = self._classify_args(frames)
         mh, mw = (int(v) for v in map_hw)
         if mh < 1 or mw < 1:
             raise ValueError(f"map_hw must be two positive sizes, got {map_hw!r}")
+        return self._classify_perturb_head(
+            lambda b, e, img, k, layout, first, cls, labels, conf, m, rec, stream: self.lib.fav_classify_rise(
+                self._h, img, k, layout, first, cls, mh, mw, labels, conf, m, rec, stream),
+            args, classes, "map", (mh, mw), RISE_RECORD_DWORDS, unpack_rise_records, heatmap, first_index)
+
+    # what the two perturbation heads (the curves, RISE) share
+    @staticmethod
+    def _fill_words(fill) -> tuple:
+        """``fill`` - a number in [0, 1], a 3-tuple of them, or None: mid grey - -> (fill_u8, fill_f32_bits), the three words
+        each of a fav_curve or fav_rise descriptor."""
+        if fill is None:
+            u8, f32 = (128, 128, 128), (0.5, 0.5, 0.5)
+        else:
+            f32 = tuple(float(v) for v in (fill if np.ndim(fill) else (fill,) * 3))
+            if len(f32) != 3:
+                raise ValueError("fill is a number or a 3-tuple")
+            u8 = tuple(int(round(255.0 * v)) for v in f32)
+        return [v & 0xFFFFFFFF for v in u8], [int(np.float32(v).view(np.uint32)) for v in f32]
+
+    def _classify_perturb_head(self, call, args, classes, key: str, shape: tuple, record_dwords: int, unpack, heatmap: bool,
+                               first_index: int) -> dict:
+        """fav_classify_curve / fav_classify_rise behind ``call(b, e, frames, e - b, layout, first_index + b, classes, labels,
+        conf, out, records, stream)``, once for every ``frames_per_call`` frames [b, e) of ``args``, the frames'
+        ``_classify_args``; ``classes`` int [n] or None.  -> ``unpack`` of the head's int32[n, record_dwords] records plus
+        ``label``, ``confidence`` and under ``key`` the head's fp32 [n, *shape] output, with ``heatmap`` its overlay too; numpy
+        frames in -> numpy out.  The counterpart of ``_classify_map_head``."""
+        torch = self._torch
+        img, host, n, layout, stream = args
+        dev = img.device
         cls = None
         if classes is not None:
             cls = torch.as_tensor(np.asarray(classes) if not hasattr(classes, "is_cuda") else classes).to(device=dev, dtype=torch.int32)
             cls = cls.contiguous()
             if tuple(cls.shape) != (n,):
                 raise ValueError(f"classes must be [n] for the n={n} frames, got {tuple(cls.shape)}")
-        m = torch.empty((n, mh, mw), dtype=torch.float32, device=dev)
-        rec = torch.empty((n, RISE_RECORD_DWORDS), dtype=torch.int32, device=dev)
+        res = torch.empty((n, *shape), dtype=torch.float32, device=dev)
+        rec = torch.empty((n, record_dwords), dtype=torch.int32, device=dev)
         labels = torch.empty(n, dtype=torch.int32, device=dev)
         conf = torch.empty(n, dtype=torch.float32, device=dev)
         for b, e in (self._batches(n) if n else ()):
-            _lib.check(self.lib.fav_classify_rise(
-                self._h, img[b:e].data_ptr(), e - b, layout, int(first_index) + b, cls[b:e].data_ptr() if cls is not None else None,
-                mh, mw, labels[b:e].data_ptr(), conf[b:e].data_ptr(), m[b:e].data_ptr(), rec[b:e].data_ptr(), stream), self._h)
-        out = dict(map=m, label=labels, confidence=conf)
-        if heatmap:
-            H, W = int(self.cfg.in_h), int(self.cfg.in_w)
-            heat = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+            _lib.check(call(b, e, img[b:e].data_ptr(), e - b, layout, int(first_index) + b, cls[b:e].data_ptr() if cls is not None else None,
+                            labels[b:e].data_ptr(), conf[b:e].data_ptr(), res[b:e].data_ptr(), rec[b:e].data_ptr(), stream), self._h)
+        return self._map_result(unpack, rec, {key: res, "label": labels, "confidence": conf}, host, shape if heatmap else None, stream)
+
+    def _map_result(self, unpack, rec, out: dict, host: bool, heatmap_hw, stream) -> dict:
+        """What a head with records hands back: ``unpack(rec)`` plus ``out``, with ``heatmap_hw`` = (mh, mw) also ``heatmap``
+        uint8 [n, H, W], the overlay fav_op_cam_heatmap draws from ``out['map']`` and the records; all numpy when ``host``."""
+        if heatmap_hw is not None:
+            n, H, W = int(rec.shape[0]), int(self.cfg.in_h), int(self.cfg.in_w)
+            out["heatmap"] = self._torch.empty((n, H, W), dtype=self._torch.uint8, device=rec.device)
             if n:
-                _lib.check(self.lib.fav_op_cam_heatmap(m.data_ptr(), rec.data_ptr(), n, mh, mw, H, W, heat.data_ptr(), stream))
-            out["heatmap"] = heat
+                _lib.check(self.lib.fav_op_cam_heatmap(out["map"].data_ptr(), rec.data_ptr(), n, *heatmap_hw, H, W,
+                                                       out["heatmap"].data_ptr(), stream))
         if host:
             out = {k: v.cpu().numpy() for k, v in out.items()}
             rec = rec.cpu().numpy()
-        return dict(unpack_rise_records(rec), **out)
+        return dict(unpack(rec), **out)
 
     # what the two localisation taps (the map tap with its CAM head, the attention tap with its rollout head) share
     def _tap_info(self, fn, names) -> dict:
@@ -849,16 +845,8 @@ class Backend:
         rec = torch.empty((n, record_dwords), dtype=torch.int32, device=img.device)
         _lib.check(fn(self._h, img.data_ptr(), n, layout, int(first_index), labels.data_ptr(), conf.data_ptr(), fail.data_ptr(),
                       score.data_ptr(), *head_args, m.data_ptr(), rec.data_ptr(), stream), self._h)
-        out = dict(label=labels, conf=conf, fail=fail, score=score, map=m)
-        if heatmap:
-            H, W = int(self.cfg.in_h), int(self.cfg.in_w)
-            heat = torch.empty((n, H, W), dtype=torch.uint8, device=img.device)
-            _lib.check(self.lib.fav_op_cam_heatmap(m.data_ptr(), rec.data_ptr(), n, *map_hw, H, W, heat.data_ptr(), stream))
-            out["heatmap"] = heat
-        if host:
-            out = {k: v.cpu().numpy() for k, v in out.items()}
-            rec = rec.cpu().numpy()
-        return dict(unpack(rec), **out)
+        return self._map_result(unpack, rec, dict(label=labels, conf=conf, fail=fail, score=score, map=m), host,
+                                map_hw if heatmap else None, stream)
 
     # what the two feature heads (the Mahalanobis model, the k-NN bank) share
     @staticmethod

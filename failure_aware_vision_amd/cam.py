@@ -15,23 +15,27 @@ CAM_RECORD_DWORDS = 8
 CAM_MAX_CLASSES = 8
 
 
-def _unpack_map_records(records, names) -> dict:
-    """The layout fav_cam_record and fav_rollout_record share, under the eight field ``names`` of one of them: dwords 1, 2, 4
-    and 5 are fp32, the others int32, the last the packed box (-1: none), which also comes unpacked to ``x0`` .. ``y1``."""
+def _unpack_fields(records, names) -> tuple:
+    """int32[..., len(names)] records (torch tensor or numpy) -> (the fields under ``names``, each [...] and a view of the record
+    buffer - dwords 1, 2, 4 and 5 as fp32, the others int32, the layout every localisation and curve record has -, the module
+    the records are of: numpy or torch)."""
     if records.ndim < 1 or int(records.shape[-1]) != len(names):
         raise ValueError(f"expected int32[..., {len(names)}] records, got shape {tuple(records.shape)}")
     if isinstance(records, np.ndarray):
-        f32 = np.float32
-        where = np.where
+        xp = np
     else:
-        import torch
-        f32 = torch.float32
-        where = torch.where
-    out = {name: records[..., j].view(f32) if j in (1, 2, 4, 5) else records[..., j] for j, name in enumerate(names)}
+        import torch as xp
+    return {name: records[..., j].view(xp.float32) if j in (1, 2, 4, 5) else records[..., j] for j, name in enumerate(names)}, xp
+
+
+def _unpack_map_records(records, names) -> dict:
+    """The layout fav_cam_record and fav_rollout_record share, under the eight field ``names`` of one of them: the last is the
+    packed box (-1: none), which also comes unpacked to ``x0`` .. ``y1``."""
+    out, xp = _unpack_fields(records, names)
     box = out[names[7]]
     none = box == -1
     for name, shift in (("x0", 0), ("y0", 8), ("x1", 16), ("y1", 24)):
-        out[name] = where(none, box, (box >> shift) & 0xFF)
+        out[name] = xp.where(none, box, (box >> shift) & 0xFF)
     return out
 
 

@@ -197,19 +197,18 @@ struct fav_handle {
     // rows of the call (at most max_batch), a part at its frame offset
     LocTap attn_tap;
     fav::AttnTapDims attn;
-    // Curve descriptor (fav_set_curve): the descriptor in force and ONE buffer the setter allocates for max_batch frames, with
-    // its parts: occ (the occluded frames of one step, sized for fp32), rank [max_batch][1024], prob and lab (the planes
-    // [steps + 1][max_batch]), lab0 and conf0 (the unoccluded pass's label and confidence); curve_on: one is set
-    struct CurveDev { fav_curve desc{}; void* buf = nullptr; void* occ = nullptr; int32_t* rank = nullptr; float* prob = nullptr;
-                      int32_t* lab = nullptr; int32_t* lab0 = nullptr; float* conf0 = nullptr; };
-    CurveDev curve;
+    // The two perturbation heads (fav_set_curve, fav_set_rise) share one record: ONE buffer the setter allocates for max_batch
+    // frames, with its parts - frames (the occluded or masked frames of one pass, sized for fp32), prob (the planes
+    // [passes][max_batch]; passes = steps + 1 or n_masks + 1), lab0 and conf0 (the unperturbed pass's label and confidence),
+    // and the curve head's own rank [max_batch][1024] and lab (planes like prob), both null for RISE.  Each stands beside
+    // the descriptor in force and its flag (one is set).  The steps on it: perturb_clear .. classify_perturb_head below.
+    struct PerturbDev { void* buf = nullptr; void* frames = nullptr; float* prob = nullptr; int32_t* lab0 = nullptr; float* conf0 = nullptr;
+                        int32_t* rank = nullptr; int32_t* lab = nullptr; int passes = 0; };
+    fav_curve curve_desc{};
+    PerturbDev curve;
     bool curve_on = false;
-    // RISE descriptor (fav_set_rise): the descriptor in force and ONE buffer the setter allocates for max_batch frames, with its
-    // parts: masked (the masked frames of one pass, sized for fp32), prob (the planes [n_masks + 1][max_batch]), lab0 and conf0
-    // (the unmasked pass's label and confidence); rise_on: one is set
-    struct RiseDev { fav_rise desc{}; void* buf = nullptr; void* masked = nullptr; float* prob = nullptr; int32_t* lab0 = nullptr;
-                     float* conf0 = nullptr; };
-    RiseDev rise;
+    fav_rise rise_desc{};
+    PerturbDev rise;
     bool rise_on = false;
     // ViT path (arch 2, 3): layers in blob order (kh == 0: a pair of fp32 vectors kept in w_m / b_m), fixed buffers
     bool vit = false;
@@ -1225,6 +1224,25 @@ fav_status run_vit(fav_handle* h, const void* images_all, int layout, int f0, in
     return FAV_OK;
 }
 
+// The launch geometry of the kernels that work a frame in row groups (views_straight_kernel, occlude_kernel,
+// rise_mask_kernel): G groups a row, `parts` blocks of 256 of them a frame, `blocks` over the `pairs` (frame, variant) pairs one
+// launch covers, the grid they are spread over, and [lo, hi): the 4-byte aligned part of the n input frames
+template <class U>
+struct RowGroups { int parts; FastDiv div_g; long long blocks; dim3 grid; const U *lo, *hi; };
+template <class U>
+RowGroups<U> row_groups(const U* in, int n, int H, int W, long long pairs) {
+    const int G = 1 + (W + 3) / 4;
+    const int parts = (int)(((long long)H * G + 255) / 256);
+    const long long blocks = pairs * parts, max_grid = (1ll << 24) - 1;
+    const size_t units = (size_t)n * H * W * 3;
+    return {parts, fastdiv_make((uint32_t)G), blocks, dim3((unsigned)std::min(blocks, max_grid)),
+            (const U*)(((uintptr_t)in + 3) & ~(uintptr_t)3), (const U*)((uintptr_t)(in + units) & ~(uintptr_t)3)};
+}
+// a fill colour as the kernels take it: a uint8 frame's words hold one byte each
+void fill_words(const uint32_t* fill, int layout, uint32_t out[3]) {
+    for (int c = 0; c < 3; ++c) out[c] = layout == FAV_LAYOUT_NHWC_U8 ? (fill[c] & 255u) : fill[c];
+}
+
 // The two launches behind fav_op_views and a handle's views (fav_views.hpp): the views without transpose, those with.  The
 // arguments have been checked (fav_check_views, the sizes, the alignment).
 template <class U>
@@ -1239,14 +1257,9 @@ void launch_views_of(const U* in, U* out, int n, int H, int W, const fav_view* v
             if (views[a].transpose == tr) va.idx[va.count++] = (uint8_t)a;
         if (!va.count) continue;
         if (!tr) {
-            const int G = 1 + (W + 3) / 4;
-            const int parts = (int)(((long long)H * G + 255) / 256);
-            const long long blocks = (long long)va.count * n * parts;
-            const size_t units = (size_t)n * H * W * 3;
-            const U* lo = (const U*)(((uintptr_t)in + 3) & ~(uintptr_t)3);
-            const U* hi = (const U*)((uintptr_t)(in + units) & ~(uintptr_t)3);
-            hipLaunchKernelGGL((views_straight_kernel<U>), dim3((unsigned)std::min(blocks, max_grid)), dim3(256), 0, s, in, out, n, H,
-                               W, va, parts, fastdiv_make((uint32_t)G), blocks, lo, hi);
+            const RowGroups<U> g = row_groups(in, n, H, W, (long long)va.count * n);
+            hipLaunchKernelGGL((views_straight_kernel<U>), g.grid, dim3(256), 0, s, in, out, n, H, W, va, g.parts, g.div_g, g.blocks,
+                               g.lo, g.hi);
         } else {
             const int t1 = (H + VW_TILE - 1) / VW_TILE;
             const long long tiles = (long long)va.count * n * t1 * t1;
@@ -1266,20 +1279,14 @@ void launch_rank_cells(const float* map, int n, int cells, int32_t* rank, hipStr
 }
 template <class U>
 void launch_occlude_of(const U* in, U* out, const int32_t* rank, int n, int H, int W, const OccludeArg& oa, hipStream_t s) {
-    const int G = 1 + (W + 3) / 4;
-    const int parts = (int)(((long long)H * G + 255) / 256);
-    const long long blocks = (long long)n * parts, max_grid = (1ll << 24) - 1;
-    const size_t units = (size_t)n * H * W * 3;
-    const U* lo = (const U*)(((uintptr_t)in + 3) & ~(uintptr_t)3);
-    const U* hi = (const U*)((uintptr_t)(in + units) & ~(uintptr_t)3);
-    hipLaunchKernelGGL((occlude_kernel<U>), dim3((unsigned)std::min(blocks, max_grid)), dim3(256), 0, s, in, out, rank, n, H, W, oa,
-                       parts, fastdiv_make((uint32_t)G), blocks, lo, hi);
+    const RowGroups<U> g = row_groups(in, n, H, W, n);
+    hipLaunchKernelGGL((occlude_kernel<U>), g.grid, dim3(256), 0, s, in, out, rank, n, H, W, oa, g.parts, g.div_g, g.blocks, g.lo, g.hi);
 }
 void launch_occlude(const void* in, void* out, const int32_t* rank, int n, int H, int W, int layout, int mh, int mw, int mode, int S,
                     int s0, int s1, const uint32_t* fill, hipStream_t s) {
     OccludeArg oa;
     memset(&oa, 0, sizeof oa);
-    for (int c = 0; c < 3; ++c) oa.fill[c] = layout == FAV_LAYOUT_NHWC_U8 ? (fill[c] & 255u) : fill[c];
+    fill_words(fill, layout, oa.fill);
     oa.mode = mode; oa.S = S; oa.s0 = s0; oa.s1 = s1; oa.mh = mh; oa.mw = mw; oa.cells = mh * mw;
     oa.wide = H > (1 << 23) || W > (1 << 23);
     oa.div_h = fastdiv_make((uint32_t)H); oa.div_w = fastdiv_make((uint32_t)W);
@@ -1299,20 +1306,15 @@ void launch_curve(const float* prob, const int32_t* labels, const int32_t* class
 // The launches behind the RISE ops and fav_classify_rise (fav_rise.hpp).  The arguments have been checked.
 template <class U>
 void launch_rise_mask_of(const U* in, U* out, int n, int H, int W, const RiseArg& ra, const uint32_t* fill, int m0, int m1, hipStream_t s) {
-    const int G = 1 + (W + 3) / 4;
-    const int parts = (int)(((long long)H * G + 255) / 256);
-    const long long blocks = (long long)n * parts, max_grid = (1ll << 24) - 1;
-    const size_t units = (size_t)n * H * W * 3;
-    const U* lo = (const U*)(((uintptr_t)in + 3) & ~(uintptr_t)3);
-    const U* hi = (const U*)((uintptr_t)(in + units) & ~(uintptr_t)3);
-    hipLaunchKernelGGL((rise_mask_kernel<U>), dim3((unsigned)std::min(blocks, max_grid)), dim3(256), 0, s, in, out, n, H, W, ra, fill[0],
-                       fill[1], fill[2], m0, m1, parts, fastdiv_make((uint32_t)G), blocks, lo, hi);
+    const RowGroups<U> g = row_groups(in, n, H, W, n);
+    hipLaunchKernelGGL((rise_mask_kernel<U>), g.grid, dim3(256), 0, s, in, out, n, H, W, ra, fill[0], fill[1], fill[2], m0, m1, g.parts,
+                       g.div_g, g.blocks, g.lo, g.hi);
 }
 void launch_rise_mask(const void* in, void* out, int n, int H, int W, int layout, const fav_rise& d, long long first_index, int m0, int m1,
                       hipStream_t s) {
     const RiseArg ra = rise_arg(d, first_index, H, W);
     uint32_t fill[3];
-    for (int c = 0; c < 3; ++c) fill[c] = layout == FAV_LAYOUT_NHWC_U8 ? (d.fill_u8[c] & 255u) : d.fill_f32_bits[c];
+    fill_words(layout == FAV_LAYOUT_NHWC_U8 ? d.fill_u8 : d.fill_f32_bits, layout, fill);
     if (layout == FAV_LAYOUT_NHWC_U8) launch_rise_mask_of((const uint8_t*)in, (uint8_t*)out, n, H, W, ra, fill, m0, m1, s);
     else launch_rise_mask_of((const uint32_t*)in, (uint32_t*)out, n, H, W, ra, fill, m0, m1, s);
 }
@@ -1721,6 +1723,9 @@ fav_status classify_gate(const char* who, fav_handle* h, const char* bad, const 
     return st;
 }
 const char* const kBadRecords = "null or misaligned buffer";
+// why views and a perturbation head exclude each other, as fav_set_views and the head's setter both say it
+const char* const kCurveViews = "an occluded frame's views are not what the map was made for";
+const char* const kRiseViews = "a masked frame's views are not what the map is made for";
 const char* bad_sets_args(const void* images, const HeadSets& hs) {
     if (const char* e = check_conformal(hs.cp)) return e;
     return !images || (!hs.rec && !hs.true_scores) || (hs.true_scores && !hs.true_labels) || ((uintptr_t)hs.rec & 7) ? kBadRecords : nullptr;
@@ -1826,14 +1831,11 @@ fav_status fav_set_views(fav_handle* h, const fav_view* views, int32_t n_views) 
             h->err = fmt("fav_set_views: %s", why);
             return FAV_ERR_INVALID_ARG;
         }
-        if (h->curve_on) {
-            h->err = "fav_set_views: a curve descriptor is set; an occluded frame's views are not what the map was made for (clear it "
-                     "first: fav_set_curve)";
-            return FAV_ERR_UNSUPPORTED;
-        }
-        if (h->rise_on) {
-            h->err = "fav_set_views: a RISE descriptor is set; a masked frame's views are not what the map is made for (clear it "
-                     "first: fav_set_rise)";
+        const struct { bool on; const char *what, *why, *setter; } perturb[] = {{h->curve_on, "a curve", kCurveViews, "fav_set_curve"},
+                                                                                {h->rise_on, "a RISE", kRiseViews, "fav_set_rise"}};
+        for (const auto& p : perturb) {
+            if (!p.on) continue;
+            h->err = fmt("fav_set_views: %s descriptor is set; %s (clear it first: %s)", p.what, p.why, p.setter);
             return FAV_ERR_UNSUPPORTED;
         }
         if (!h->vit && h->plan.has_mc) {
@@ -2152,6 +2154,121 @@ fav_status classify_map_head(fav_handle* h, const char* fn, const TapWords& w, f
     if (fav_status st = map_head_gate(h, fn, w, h->*tap, bad_buffers, dims_error)) return st;
     if (fav_status st = fav_classify_ex(h, images, n, layout, first_index, labels, conf, fail, score, stream)) return st;
     return map_head_on_stream(h, fn, launch, (hipStream_t)stream);
+}
+
+// ---- the steps the two perturbation heads share (fav_set_curve / fav_set_rise and their fav_classify_*): each perturbs the
+// frames, classifies every perturbed copy and reduces one class's probability over the copies
+// a setter's NULL argument: the head goes with its buffer, once what is enqueued has run
+fav_status perturb_clear(fav_handle* h, fav_handle::PerturbDev& cur, bool& on) {
+    if (!on) return FAV_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_enqueued(h)) return st;
+    on = false;
+    void* buf = cur.buf;
+    cur = fav_handle::PerturbDev{};
+    if (buf) HIP_TRY(h, hipFree(buf));
+    return FAV_OK;
+}
+// ... and a descriptor: `check(layout)` is the descriptor's complaint, asked under both layouts; `views_why` the head's
+// sentence when views are set; then `plan(fresh, what)` names the parts of the buffer - bytes each, where its address goes -
+// and says in `what` whose they are, for the reply when ONE allocation with every part on a 256-byte boundary fails.  A
+// buffer being replaced is freed once what is enqueued, which still uses it, has run.  Any failure leaves the handle as it was.
+struct PerturbPart { size_t bytes; void** at; };
+template <class Check, class Plan>
+fav_status perturb_commit(fav_handle* h, const char* fn, fav_handle::PerturbDev& cur, bool& on, Check check, const char* views_why, Plan plan) {
+    std::string why = check(FAV_LAYOUT_NHWC_U8);
+    if (why.empty()) why = check(FAV_LAYOUT_NHWC_F32);
+    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (h->n_views > 0) { h->err = fmt("%s: views are set; %s (turn them off first: fav_set_views)", fn, views_why); return FAV_ERR_UNSUPPORTED; }
+    fav_handle::PerturbDev fresh;
+    std::string what;
+    const std::vector<PerturbPart> parts = plan(fresh, what);
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t bytes = 0;
+    for (const PerturbPart& p : parts) bytes += pad(p.bytes);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (hipMalloc(&fresh.buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->err = fmt("%s: cannot allocate the %zu bytes %s takes", fn, bytes, what.c_str());
+        return FAV_ERR_HIP;
+    }
+    char* q = (char*)fresh.buf;
+    for (const PerturbPart& p : parts) { *p.at = q; q += pad(p.bytes); }
+    if (on) {
+        if (fav_status st = wait_enqueued(h)) { (void)hipFree(fresh.buf); return st; }
+        if (cur.buf) (void)hipFree(cur.buf);
+    }
+    cur = fresh;
+    on = true;
+    return FAV_OK;
+}
+// the parts both heads have: the perturbed frames of one pass, `passes` probability planes, the unperturbed pass's label and
+// confidence, for the handle's max_batch frames; d.passes is set here
+std::vector<PerturbPart> perturb_parts(const fav_handle* h, fav_handle::PerturbDev& d, int passes) {
+    const size_t B = (size_t)h->cfg.max_batch;
+    d.passes = passes;
+    return {{B * h->cfg.in_h * h->cfg.in_w * 3 * 4, &d.frames}, {(size_t)passes * B * 4, (void**)&d.prob}, {B * 4, (void**)&d.lab0},
+            {B * 4, (void**)&d.conf0}};
+}
+// One pass of a perturbation head: the frames to classify, and the planes the class probability and (curve) the label go to
+struct PerturbPass { const void* frames; float* prob; int32_t* lab; };
+// fav_classify_curve, fav_classify_rise: the argument gate - `missing` names what is not set when `on` is off, `own()` is
+// the head's complaint about its map and mode - then, behind the previous user of the handle's buffers, the passes.
+// `pass(k, s)` enqueues the perturbation of pass k and says what to classify and where to; pass 0, the unperturbed one, also
+// writes the caller's labels / conf or the handle's own copies, and a second head launch on its logits fills its plane.
+// `reduce(classes, s)` enqueues the head's reduction over the planes; classes: the caller's, or pass 0's labels.
+template <class Own, class Pass, class Reduce>
+fav_status classify_perturb_head(fav_handle* h, const char* fn, bool fav_handle::*on, const char* missing,
+                                 fav_handle::PerturbDev fav_handle::*dev, bool bad_buffers, const void* images, int32_t n, int32_t layout,
+                                 int64_t first_index, const int32_t* classes, int32_t* labels, float* conf, void* stream, Own own, Pass pass,
+                                 Reduce reduce) {
+    route_clear();
+    if (!h) return FAV_ERR_INVALID_ARG;
+    auto refuse = [&](const std::string& why) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; };
+    if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", fn); return FAV_ERR_NO_WEIGHTS; }
+    if (!(h->*on)) return refuse(missing);
+    if (bad_buffers) return refuse(kBadRecords);
+    if (n < 1 || n > h->cfg.max_batch) return refuse(fmt("n=%d outside [1, max_batch=%d]", n, h->cfg.max_batch));
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return refuse("unknown layout");
+    if (layout == FAV_LAYOUT_NHWC_F32 && ((uintptr_t)images & 3)) return refuse("fp32 frames must be 4-byte aligned");
+    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) return refuse("first_image_index out of range");
+    const std::string why = own();
+    if (!why.empty()) return refuse(why);
+    if (h->n_views > 0) { h->err = fmt("%s: views are set", fn); return FAV_ERR_UNSUPPORTED; }   // fav_set_views refuses them; kept as a guard
+    const fav_handle::PerturbDev& d = h->*dev;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (fav_status st = wait_last_use(h, s)) return st;
+    int32_t* const lab0 = labels ? labels : d.lab0;
+    const int32_t* const cls = classes ? classes : lab0;
+    fav_status st = FAV_OK;
+    for (int k = 0; k < d.passes && st == FAV_OK; ++k) {
+        const PerturbPass p = pass(k, s);
+        const Frames f{p.frames, layout, n, first_index};
+        const HeadClassProb cp{cls, p.prob, p.lab};
+        HeadOut out;
+        if (k > 0) {
+            out.cprob = &cp;
+            st = classify_on_stream(h, f, out, s);
+            continue;
+        }
+        out.labels = lab0; out.conf = conf ? conf : d.conf0;
+        st = classify_on_stream(h, f, out, s);
+        if (st != FAV_OK) break;
+        HeadOut second;
+        second.cprob = &cp;
+        if (const char* e = launch_head(h, h->logits, h->last_T, n, h->cfg.num_classes, h->plan.cpad, h->cfg.temperature, h->cfg.conf_kind,
+                                        h->cfg.tau, second, s)) {
+            h->err = fmt("%s: %s", fn, e);
+            st = FAV_ERR_INVALID_ARG;
+        }
+    }
+    if (st == FAV_OK) reduce(cls, s);
+    route_clear();            // the report speaks of fav_op_* launches only
+    mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
+    if (st != FAV_OK) return st;
+    HIP_TRY(h, hipGetLastError());
+    return FAV_OK;
 }
 }  // extern "C++"
 }  // namespace
@@ -2754,115 +2871,43 @@ fav_status fav_check_curve(const fav_curve* desc, int32_t H, int32_t W, int32_t 
 
 fav_status fav_set_curve(fav_handle* h, const fav_curve* desc) {
     if (!h) return FAV_ERR_INVALID_ARG;
-    if (!desc) {
-        if (!h->curve_on) return FAV_OK;
-        HIP_TRY(h, hipSetDevice(h->cfg.device));
-        if (fav_status st = wait_enqueued(h)) return st;
-        h->curve_on = false;
-        void* buf = h->curve.buf;
-        h->curve = fav_handle::CurveDev{};
-        if (buf) HIP_TRY(h, hipFree(buf));
-        return FAV_OK;
-    }
-    std::string why = curve_desc_error(desc, h->cfg.in_h, h->cfg.in_w, FAV_LAYOUT_NHWC_U8);
-    if (why.empty()) why = curve_desc_error(desc, h->cfg.in_h, h->cfg.in_w, FAV_LAYOUT_NHWC_F32);
-    if (!why.empty()) { h->err = fmt("fav_set_curve: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
-    if (h->n_views > 0) {
-        h->err = "fav_set_curve: views are set; an occluded frame's views are not what the map was made for (turn them off first: "
-                 "fav_set_views)";
-        return FAV_ERR_UNSUPPORTED;
-    }
-    // one buffer, every part on a 256-byte boundary
-    const size_t B = (size_t)h->cfg.max_batch, planes = (size_t)desc->steps + 1;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t occ_b = pad(B * h->cfg.in_h * h->cfg.in_w * 3 * 4), rank_b = pad(B * CV_MAX_CELLS * 4), plane_b = pad(planes * B * 4),
-                 first_b = pad(B * 4);
-    const size_t bytes = occ_b + rank_b + 2 * plane_b + 2 * first_b;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    fav_handle::CurveDev nw;
-    nw.desc = *desc;
-    if (hipMalloc(&nw.buf, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->err = fmt("fav_set_curve: cannot allocate the %zu bytes a curve of max_batch=%d frames and %d steps takes", bytes,
-                     (int)h->cfg.max_batch, desc->steps);
-        return FAV_ERR_HIP;
-    }
-    char* q = (char*)nw.buf;
-    nw.occ = q; q += occ_b;
-    nw.rank = (int32_t*)q; q += rank_b;
-    nw.prob = (float*)q; q += plane_b;
-    nw.lab = (int32_t*)q; q += plane_b;
-    nw.lab0 = (int32_t*)q; q += first_b;
-    nw.conf0 = (float*)q;
-    if (h->curve_on) {      // replacing: what is enqueued still uses the old buffer
-        if (fav_status st = wait_enqueued(h)) { (void)hipFree(nw.buf); return st; }
-        if (h->curve.buf) (void)hipFree(h->curve.buf);
-    }
-    h->curve = nw;
-    h->curve_on = true;
-    return FAV_OK;
+    if (!desc) return perturb_clear(h, h->curve, h->curve_on);
+    const fav_status st = perturb_commit(
+        h, "fav_set_curve", h->curve, h->curve_on, [&](int layout) { return curve_desc_error(desc, h->cfg.in_h, h->cfg.in_w, layout); },
+        kCurveViews, [&](fav_handle::PerturbDev& d, std::string& what) {
+            what = fmt("a curve of max_batch=%d frames and %d steps", (int)h->cfg.max_batch, desc->steps);
+            std::vector<PerturbPart> parts = perturb_parts(h, d, desc->steps + 1);
+            parts.push_back({(size_t)h->cfg.max_batch * CV_MAX_CELLS * 4, (void**)&d.rank});
+            parts.push_back({parts[1].bytes, (void**)&d.lab});
+            return parts;
+        });
+    if (st == FAV_OK) h->curve_desc = *desc;
+    return st;
 }
 
 fav_status fav_classify_curve(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, const float* map,
                               int32_t mh, int32_t mw, const int32_t* classes, int32_t mode, int32_t* labels, float* conf, float* curve,
                               fav_curve_record* rec, void* stream) {
     static_assert(sizeof(fav_curve_record) == 32, "fav_curve_record is 8 dwords");
-    const char* fn = "fav_classify_curve";
-    route_clear();
-    if (!h) return FAV_ERR_INVALID_ARG;
-    auto refuse = [&](const std::string& why) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; };
-    if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", fn); return FAV_ERR_NO_WEIGHTS; }
-    if (!h->curve_on) return refuse("no curve descriptor set (fav_set_curve)");
-    if (!images || !map || !curve || !rec || (((uintptr_t)map | (uintptr_t)curve | (uintptr_t)classes | (uintptr_t)labels | (uintptr_t)conf) & 3) ||
-        ((uintptr_t)rec & 7))
-        return refuse(kBadRecords);
-    if (n < 1 || n > h->cfg.max_batch) return refuse(fmt("n=%d outside [1, max_batch=%d]", n, h->cfg.max_batch));
-    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return refuse("unknown layout");
-    if (layout == FAV_LAYOUT_NHWC_F32 && ((uintptr_t)images & 3)) return refuse("fp32 frames must be 4-byte aligned");
-    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) return refuse("first_image_index out of range");
-    std::string why = curve_mode_error(mode);
-    if (why.empty()) why = curve_map_error(mh, mw);
-    if (!why.empty()) return refuse(why);
-    if (h->n_views > 0) { h->err = fmt("%s: views are set", fn); return FAV_ERR_UNSUPPORTED; }   // fav_set_views refuses them; kept as a guard
-    const fav_handle::CurveDev& cv = h->curve;
-    const int S = cv.desc.steps, cells = mh * mw, H = h->cfg.in_h, W = h->cfg.in_w;
-    const uint32_t* fill = layout == FAV_LAYOUT_NHWC_U8 ? cv.desc.fill_u8 : cv.desc.fill_f32_bits;
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (fav_status st = wait_last_use(h, s)) return st;
-    launch_rank_cells(map, n, cells, cv.rank, s);
-    // the unoccluded pass writes the caller's labels and confidences, or the handle's own copies
-    int32_t* const lab0 = labels ? labels : cv.lab0;
-    const int32_t* const cls = classes ? classes : lab0;
-    fav_status st = FAV_OK;
-    for (int k = 0; k <= S && st == FAV_OK; ++k) {
+    const bool bad = !images || !map || !curve || !rec ||
+                     (((uintptr_t)map | (uintptr_t)curve | (uintptr_t)classes | (uintptr_t)labels | (uintptr_t)conf) & 3) || ((uintptr_t)rec & 7);
+    // every pass, the unoccluded one too, is classified from the occlusion buffer; its plane is its step
+    auto pass = [&](int k, hipStream_t s) {
+        const fav_handle::PerturbDev& cv = h->curve;
+        const int S = h->curve_desc.steps, H = h->cfg.in_h, W = h->cfg.in_w;
         const int step = mode == FAV_CURVE_DELETION ? k : S - k;         // the unoccluded step first, then by increasing occlusion
-        launch_occlude(images, cv.occ, cv.rank, n, H, W, layout, mh, mw, mode, S, step, step + 1, fill, s);
-        const Frames f{cv.occ, layout, n, first_index};
-        const HeadClassProb cp{cls, cv.prob + (size_t)step * n, cv.lab + (size_t)step * n};
-        HeadOut out;
-        if (k == 0) {
-            out.labels = lab0; out.conf = conf ? conf : cv.conf0;
-            st = classify_on_stream(h, f, out, s);
-            if (st != FAV_OK) break;
-            HeadOut second;
-            second.cprob = &cp;
-            if (const char* e = launch_head(h, h->logits, h->last_T, n, h->cfg.num_classes, h->plan.cpad, h->cfg.temperature,
-                                            h->cfg.conf_kind, h->cfg.tau, second, s)) {
-                h->err = fmt("%s: %s", fn, e);
-                st = FAV_ERR_INVALID_ARG;
-            }
-        } else {
-            out.cprob = &cp;
-            st = classify_on_stream(h, f, out, s);
-        }
-    }
-    if (st == FAV_OK) launch_curve(cv.prob, cv.lab, cls, n, S, cells, mode, h->cfg.num_classes, curve, rec, s);
-    route_clear();            // the report speaks of fav_op_* launches only
-    mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
-    if (st != FAV_OK) return st;
-    HIP_TRY(h, hipGetLastError());
-    return FAV_OK;
+        if (k == 0) launch_rank_cells(map, n, mh * mw, cv.rank, s);
+        launch_occlude(images, cv.frames, cv.rank, n, H, W, layout, mh, mw, mode, S, step, step + 1,
+                       layout == FAV_LAYOUT_NHWC_U8 ? h->curve_desc.fill_u8 : h->curve_desc.fill_f32_bits, s);
+        return PerturbPass{cv.frames, cv.prob + (size_t)step * n, cv.lab + (size_t)step * n};
+    };
+    return classify_perturb_head(
+        h, "fav_classify_curve", &fav_handle::curve_on, "no curve descriptor set (fav_set_curve)", &fav_handle::curve, bad, images, n, layout,
+        first_index, classes, labels, conf, stream,
+        [&] { const std::string why = curve_mode_error(mode); return why.empty() ? curve_map_error(mh, mw) : why; }, pass,
+        [&](const int32_t* cls, hipStream_t s) {
+            launch_curve(h->curve.prob, h->curve.lab, cls, n, h->curve_desc.steps, mh * mw, mode, h->cfg.num_classes, curve, rec, s);
+        });
 }
 
 // ---- RISE saliency (fav_rise.hpp) ------------------------------------------------
@@ -2873,50 +2918,15 @@ fav_status fav_check_rise(const fav_rise* desc, int32_t H, int32_t W, int32_t la
 
 fav_status fav_set_rise(fav_handle* h, const fav_rise* desc) {
     if (!h) return FAV_ERR_INVALID_ARG;
-    if (!desc) {
-        if (!h->rise_on) return FAV_OK;
-        HIP_TRY(h, hipSetDevice(h->cfg.device));
-        if (fav_status st = wait_enqueued(h)) return st;
-        h->rise_on = false;
-        void* buf = h->rise.buf;
-        h->rise = fav_handle::RiseDev{};
-        if (buf) HIP_TRY(h, hipFree(buf));
-        return FAV_OK;
-    }
-    std::string why = rise_desc_error(desc, h->cfg.in_h, h->cfg.in_w, FAV_LAYOUT_NHWC_U8);
-    if (why.empty()) why = rise_desc_error(desc, h->cfg.in_h, h->cfg.in_w, FAV_LAYOUT_NHWC_F32);
-    if (!why.empty()) { h->err = fmt("fav_set_rise: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
-    if (h->n_views > 0) {
-        h->err = "fav_set_rise: views are set; a masked frame's views are not what the map is made for (turn them off first: "
-                 "fav_set_views)";
-        return FAV_ERR_UNSUPPORTED;
-    }
-    // one buffer, every part on a 256-byte boundary
-    const size_t B = (size_t)h->cfg.max_batch, planes = (size_t)desc->n_masks + 1;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t masked_b = pad(B * h->cfg.in_h * h->cfg.in_w * 3 * 4), plane_b = pad(planes * B * 4), first_b = pad(B * 4);
-    const size_t bytes = masked_b + plane_b + 2 * first_b;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    fav_handle::RiseDev nw;
-    nw.desc = *desc;
-    if (hipMalloc(&nw.buf, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->err = fmt("fav_set_rise: cannot allocate the %zu bytes RISE of max_batch=%d frames and %d masks takes", bytes,
-                     (int)h->cfg.max_batch, desc->n_masks);
-        return FAV_ERR_HIP;
-    }
-    char* q = (char*)nw.buf;
-    nw.masked = q; q += masked_b;
-    nw.prob = (float*)q; q += plane_b;
-    nw.lab0 = (int32_t*)q; q += first_b;
-    nw.conf0 = (float*)q;
-    if (h->rise_on) {       // replacing: what is enqueued still uses the old buffer
-        if (fav_status st = wait_enqueued(h)) { (void)hipFree(nw.buf); return st; }
-        if (h->rise.buf) (void)hipFree(h->rise.buf);
-    }
-    h->rise = nw;
-    h->rise_on = true;
-    return FAV_OK;
+    if (!desc) return perturb_clear(h, h->rise, h->rise_on);
+    const fav_status st = perturb_commit(
+        h, "fav_set_rise", h->rise, h->rise_on, [&](int layout) { return rise_desc_error(desc, h->cfg.in_h, h->cfg.in_w, layout); },
+        kRiseViews, [&](fav_handle::PerturbDev& d, std::string& what) {
+            what = fmt("RISE of max_batch=%d frames and %d masks", (int)h->cfg.max_batch, desc->n_masks);
+            return perturb_parts(h, d, desc->n_masks + 1);
+        });
+    if (st == FAV_OK) h->rise_desc = *desc;
+    return st;
 }
 
 fav_status fav_classify_rise(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, const int32_t* classes,
@@ -2924,57 +2934,22 @@ fav_status fav_classify_rise(fav_handle* h, const void* images, int32_t n, int32
     static_assert(sizeof(fav_rise_record) == 32, "fav_rise_record is 8 dwords");
     static_assert(offsetof(fav_rise_record, peak) == offsetof(fav_cam_record, peak) && offsetof(fav_rise_record, floor) == offsetof(fav_cam_record, floor),
                   "fav_op_cam_heatmap reads peak and floor of either record");
-    const char* fn = "fav_classify_rise";
-    route_clear();
-    if (!h) return FAV_ERR_INVALID_ARG;
-    auto refuse = [&](const std::string& why) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; };
-    if (!h->weights_loaded) { h->err = fmt("%s: no weights loaded", fn); return FAV_ERR_NO_WEIGHTS; }
-    if (!h->rise_on) return refuse("no RISE descriptor set (fav_set_rise)");
-    if (!images || !map || !rec || (((uintptr_t)map | (uintptr_t)classes | (uintptr_t)labels | (uintptr_t)conf) & 3) || ((uintptr_t)rec & 7))
-        return refuse(kBadRecords);
-    if (n < 1 || n > h->cfg.max_batch) return refuse(fmt("n=%d outside [1, max_batch=%d]", n, h->cfg.max_batch));
-    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return refuse("unknown layout");
-    if (layout == FAV_LAYOUT_NHWC_F32 && ((uintptr_t)images & 3)) return refuse("fp32 frames must be 4-byte aligned");
-    if (first_index < 0 || first_index + n > 0xFFFFFFFFll) return refuse("first_image_index out of range");
-    const int H = h->cfg.in_h, W = h->cfg.in_w;
-    const std::string why = rise_map_error(mh, mw, H, W);
-    if (!why.empty()) return refuse(why);
-    if (h->n_views > 0) { h->err = fmt("%s: views are set", fn); return FAV_ERR_UNSUPPORTED; }   // fav_set_views refuses them; kept as a guard
-    const fav_handle::RiseDev& rv = h->rise;
-    const int N = rv.desc.n_masks;
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (fav_status st = wait_last_use(h, s)) return st;
-    // the unmasked pass writes the caller's labels and confidences, or the handle's own copies
-    int32_t* const lab0 = labels ? labels : rv.lab0;
-    const int32_t* const cls = classes ? classes : lab0;
-    fav_status st = FAV_OK;
-    for (int k = 0; k <= N && st == FAV_OK; ++k) {
-        const HeadClassProb cp{cls, rv.prob + (size_t)k * n, nullptr};
-        HeadOut out;
-        if (k == 0) {
-            out.labels = lab0; out.conf = conf ? conf : rv.conf0;
-            st = classify_on_stream(h, Frames{images, layout, n, first_index}, out, s);
-            if (st != FAV_OK) break;
-            HeadOut second;
-            second.cprob = &cp;
-            if (const char* e = launch_head(h, h->logits, h->last_T, n, h->cfg.num_classes, h->plan.cpad, h->cfg.temperature,
-                                            h->cfg.conf_kind, h->cfg.tau, second, s)) {
-                h->err = fmt("%s: %s", fn, e);
-                st = FAV_ERR_INVALID_ARG;
-            }
-        } else {
-            launch_rise_mask(images, rv.masked, n, H, W, layout, rv.desc, first_index, k - 1, k, s);
-            out.cprob = &cp;
-            st = classify_on_stream(h, Frames{rv.masked, layout, n, first_index}, out, s);
-        }
-    }
-    if (st == FAV_OK) launch_rise_accumulate(rv.prob, cls, n, rv.desc, first_index, H, W, mh, mw, h->cfg.num_classes, map, rec, s);
-    route_clear();            // the report speaks of fav_op_* launches only
-    mark_last_use(h, s);      // also after a failure: whatever was queued before it still uses the buffers
-    if (st != FAV_OK) return st;
-    HIP_TRY(h, hipGetLastError());
-    return FAV_OK;
+    const bool bad = !images || !map || !rec || (((uintptr_t)map | (uintptr_t)classes | (uintptr_t)labels | (uintptr_t)conf) & 3) ||
+                     ((uintptr_t)rec & 7);
+    // the unmasked pass is classified from the caller's frames; pass k > 0 is mask k - 1 and fills plane k
+    auto pass = [&](int k, hipStream_t s) {
+        const fav_handle::PerturbDev& rv = h->rise;
+        if (k == 0) return PerturbPass{images, rv.prob, nullptr};
+        launch_rise_mask(images, rv.frames, n, h->cfg.in_h, h->cfg.in_w, layout, h->rise_desc, first_index, k - 1, k, s);
+        return PerturbPass{rv.frames, rv.prob + (size_t)k * n, nullptr};
+    };
+    return classify_perturb_head(
+        h, "fav_classify_rise", &fav_handle::rise_on, "no RISE descriptor set (fav_set_rise)", &fav_handle::rise, bad, images, n, layout,
+        first_index, classes, labels, conf, stream, [&] { return rise_map_error(mh, mw, h->cfg.in_h, h->cfg.in_w); }, pass,
+        [&](const int32_t* cls, hipStream_t s) {
+            launch_rise_accumulate(h->rise.prob, cls, n, h->rise_desc, first_index, h->cfg.in_h, h->cfg.in_w, mh, mw, h->cfg.num_classes, map,
+                                   rec, s);
+        });
 }
 
 fav_status fav_set_profiling(fav_handle* h, int32_t enable) {
@@ -3263,6 +3238,20 @@ static fav_status op_rejected(const char* fn, const char* why) {
     g_create_error = fmt("%s: %s", fn, why);
     return FAV_ERR_INVALID_ARG;
 }
+// What an op that streams n frames in and n * count frames out (fav_op_views, fav_op_occlude, fav_op_rise_mask) refuses once
+// its own parameters are in range: frames of another alignment than their elements', `own` (the op's complaint that stands in
+// between; NULL: none), n * count (`span` in the message) beyond 31 bits, out overlapping frames.  "": nothing.
+static std::string stream_out_error(const void* frames, const void* out, int n, int H, int W, int layout, int count, const char* span,
+                                    const char* own) {
+    const size_t esz = layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4;
+    if (((uintptr_t)frames | (uintptr_t)out) % esz != 0) return "fp32 frames and out must be 4-byte aligned";
+    if (own) return own;
+    if ((long long)n * count > 0x7FFFFFFFll) return fmt("n * %s above 2^31 - 1", span);
+    const long long frame_bytes = (long long)H * W * 3 * (long long)esz;
+    const uintptr_t in_lo = (uintptr_t)frames, in_hi = in_lo + (uintptr_t)frame_bytes * (uintptr_t)n;
+    const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + (uintptr_t)frame_bytes * (uintptr_t)n * (uintptr_t)count;
+    return in_lo < out_hi && out_lo < in_hi ? "out overlaps frames" : "";
+}
 
 // The gate in front of a scoring head's launch: what fav_op_ood_score and fav_op_knn_score refuse alike, in the order both
 // report it, or "".  dims: the head's *_dims_error; own(): the checks only that head has, which stand in front of the records'.
@@ -3381,17 +3370,12 @@ fav_status fav_op_views(const void* frames, void* out, int32_t n, int32_t H, int
     if (!frames || !out) return op_rejected(fn, "null pointer");
     if (n < 1 || H < 1 || W < 1) return op_rejected(fn, "n, H and W must be at least 1");
     if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return op_rejected(fn, "unknown layout");
-    const std::string why = views_error(views, n_views, H, W);
-    if (!why.empty()) return op_rejected(fn, why.c_str());
-    const size_t esz = layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4;
-    if (((uintptr_t)frames | (uintptr_t)out) % esz != 0) return op_rejected(fn, "fp32 frames and out must be 4-byte aligned");
+    std::string why = views_error(views, n_views, H, W);
     // the kernels hold a frame's work items in 32 bits: H * (1 + ceil(W / 4)) <= H * W / 4 + 2 H stays below 2^31
-    if ((long long)H * W > 0x7FFFFFFFll / 12) return op_rejected(fn, "H * W above (2^31 - 1) / 12 pixels");
-    const long long frame_bytes = (long long)H * W * 3 * (long long)esz;
-    if ((long long)n * n_views > 0x7FFFFFFFll) return op_rejected(fn, "n * n_views above 2^31 - 1");
-    const uintptr_t in_lo = (uintptr_t)frames, in_hi = in_lo + (uintptr_t)frame_bytes * (uintptr_t)n;
-    const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + (uintptr_t)frame_bytes * (uintptr_t)n * (uintptr_t)n_views;
-    if (in_lo < out_hi && out_lo < in_hi) return op_rejected(fn, "out overlaps frames");
+    if (why.empty())
+        why = stream_out_error(frames, out, n, H, W, layout, n_views, "n_views",
+                               (long long)H * W > 0x7FFFFFFFll / 12 ? "H * W above (2^31 - 1) / 12 pixels" : nullptr);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
     launch_views(frames, out, n, H, W, layout, views, n_views, (hipStream_t)stream);
     return op_done(nullptr);
 }
@@ -3552,15 +3536,10 @@ fav_status fav_op_occlude(const void* frames, void* out, int32_t n, int32_t H, i
     if (why.empty()) why = curve_mode_error(mode);
     if (why.empty() && (s0 < 0 || s0 >= s1 || s1 > S + 1)) why = fmt("steps [%d, %d) outside 0 <= s0 < s1 <= S + 1 = %d", s0, s1, S + 1);
     if (why.empty()) why = curve_fill_error(fill, layout);
+    if (why.empty())
+        why = stream_out_error(frames, out, n, H, W, layout, s1 - s0, "(s1 - s0)",
+                               (uintptr_t)rank & 3 ? "rank_dev must be 4-byte aligned" : nullptr);
     if (!why.empty()) return op_rejected(fn, why.c_str());
-    const size_t esz = layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4;
-    if (((uintptr_t)frames | (uintptr_t)out) % esz != 0) return op_rejected(fn, "fp32 frames and out must be 4-byte aligned");
-    if ((uintptr_t)rank & 3) return op_rejected(fn, "rank_dev must be 4-byte aligned");
-    if ((long long)n * (s1 - s0) > 0x7FFFFFFFll) return op_rejected(fn, "n * (s1 - s0) above 2^31 - 1");
-    const long long frame_bytes = (long long)H * W * 3 * (long long)esz;
-    const uintptr_t in_lo = (uintptr_t)frames, in_hi = in_lo + (uintptr_t)frame_bytes * (uintptr_t)n;
-    const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + (uintptr_t)frame_bytes * (uintptr_t)n * (uintptr_t)(s1 - s0);
-    if (in_lo < out_hi && out_lo < in_hi) return op_rejected(fn, "out overlaps frames");
     launch_occlude(frames, out, rank, n, H, W, layout, mh, mw, mode, S, s0, s1, fill, (hipStream_t)stream);
     return op_done(nullptr);
 }
@@ -3603,14 +3582,8 @@ fav_status fav_op_rise_mask(const void* frames, void* out, int32_t n, int32_t H,
     std::string why = rise_desc_error(desc, H, W, layout);
     if (why.empty() && (m0 < 0 || m0 >= m1 || m1 > desc->n_masks))
         why = fmt("masks [%d, %d) outside 0 <= m0 < m1 <= n_masks = %d", m0, m1, desc->n_masks);
+    if (why.empty()) why = stream_out_error(frames, out, n, H, W, layout, m1 - m0, "(m1 - m0)", nullptr);
     if (!why.empty()) return op_rejected(fn, why.c_str());
-    const size_t esz = layout == FAV_LAYOUT_NHWC_U8 ? 1 : 4;
-    if (((uintptr_t)frames | (uintptr_t)out) % esz != 0) return op_rejected(fn, "fp32 frames and out must be 4-byte aligned");
-    if ((long long)n * (m1 - m0) > 0x7FFFFFFFll) return op_rejected(fn, "n * (m1 - m0) above 2^31 - 1");
-    const long long frame_bytes = (long long)H * W * 3 * (long long)esz;
-    const uintptr_t in_lo = (uintptr_t)frames, in_hi = in_lo + (uintptr_t)frame_bytes * (uintptr_t)n;
-    const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + (uintptr_t)frame_bytes * (uintptr_t)n * (uintptr_t)(m1 - m0);
-    if (in_lo < out_hi && out_lo < in_hi) return op_rejected(fn, "out overlaps frames");
     launch_rise_mask(frames, out, n, H, W, layout, *desc, first_index, m0, m1, (hipStream_t)stream);
     return op_done(nullptr);
 }

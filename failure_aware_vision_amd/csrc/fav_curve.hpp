@@ -8,7 +8,8 @@
 //   head_class_prob_kernel  the heads' shared core (fav_kernels.hpp), then pbar of a named class
 //   curve_kernel            a thread a frame: the fixed-order chains over the steps, a record of eight dwords
 // Included by fav.hip after fav_views.hpp (ViewPx, vgroup_load / vgroup_store), fav_corrupt_c.hpp (px_group), fav_route.hpp
-// (fmt) and fav_mapbox.hpp (map_record_store).
+// (fmt) and fav_mapbox.hpp (map_record_store), and in front of fav_rise.hpp, whose head shares the host steps in fav.hip
+// (perturb_clear .. classify_perturb_head, row_groups, fill_words, stream_out_error) and map_record_no_class below.
 #pragma once
 
 namespace fav {
@@ -206,6 +207,13 @@ __global__ __launch_bounds__(256) void head_class_prob_kernel(const float* __res
     }
 }
 
+// a class outside the range has no curve and no map (curve_kernel, rise_accumulate_kernel): its record is class -1 with NaN in
+// the four fp32 fields and cell -1, then the head's own two last dwords
+__device__ __forceinline__ void map_record_no_class(int32_t* rec, int d6, int d7) {
+    const int nan = 0x7fc00000;
+    map_record_store(rec, -1, nan, nan, -1, nan, nan, d6, d7);
+}
+
 // ---- the curve: a thread a frame, every chain in step order.  prob / labels are [S + 1][n] planes, curve is [n][S + 1].
 struct CurveParams {
     const float* prob;
@@ -237,8 +245,7 @@ __global__ __launch_bounds__(CV_CURVE_THREADS) void curve_kernel(const CurvePara
     const float auc = acc * cp.half_step;
     int32_t* const rec = cp.rec + (size_t)i * 8;
     if (cls < 0 || (cp.num_classes > 0 && cls >= cp.num_classes)) {
-        const int nan = 0x7fc00000;
-        map_record_store(rec, -1, nan, nan, -1, nan, nan, -1, 0);
+        map_record_no_class(rec, -1, 0);
         return;
     }
     map_record_store(rec, cls, __float_as_int(auc), __float_as_int(first), flip, __float_as_int(prev), __float_as_int(pmin),

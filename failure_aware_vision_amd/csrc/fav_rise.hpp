@@ -10,7 +10,8 @@
 //   rise_accumulate_kernel  a block a frame, a thread up to four cells: the mask values are derived again at each cell's sample
 //                           pixel from draws staged in LDS (no frame is read), the chains run in mask order, one lane scans
 //                           the map for the record
-// Included by fav.hip after fav_curve.hpp (curve_frame_error, curve_map_error, curve_fill_error, vpx_fill), fav_views.hpp,
+// Included by fav.hip after fav_curve.hpp (curve_frame_error, curve_map_error, curve_fill_error, vpx_fill, map_record_no_class;
+// the curve head is this head's twin on the host: perturb_clear .. classify_perturb_head in fav.hip), fav_views.hpp,
 // fav_corrupt_c.hpp (px_group), fav_mapbox.hpp (map_box_scan, map_record_store) and fav_kernels.hpp (philox4x32_10, FastDiv).
 #pragma once
 
@@ -314,8 +315,7 @@ __global__ __launch_bounds__(RISE_ACC_THREADS) void rise_accumulate_kernel(const
     int32_t* const rec = p.rec + 8 * (size_t)i;
     const int cls = p.classes[i];
     if (cls < 0 || (p.num_classes > 0 && cls >= p.num_classes)) {
-        const int nan = 0x7fc00000;
-        map_record_store(rec, -1, nan, nan, -1, nan, nan, 0, -1);
+        map_record_no_class(rec, 0, -1);
         return;
     }
     float peak = -INFINITY, flo = INFINITY;

@@ -11,6 +11,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .cam import _unpack_fields
+
 #: dwords of one fav_curve_record
 CURVE_RECORD_DWORDS = 8
 #: the most cells of a map, steps of a curve
@@ -18,21 +20,15 @@ CURVE_MAX_CELLS = 1024
 CURVE_MAX_STEPS = 256
 
 _FIELDS = ("class_id", "auc", "p_first", "flip_step", "p_last", "p_min", "flip_cells", "reserved")
-_FLOATS = (1, 2, 4, 5)
 
 
 def unpack_curve_records(records) -> dict:
     """int32[..., 8] fav_curve_record records (torch tensor or numpy) -> ``class_id`` int32, ``auc``, ``p_first`` fp32,
     ``flip_step`` int32 (-1: the label never flipped), ``p_last``, ``p_min`` fp32, ``flip_cells`` int32, each [...] and a view
     of the record buffer."""
-    if records.ndim < 1 or int(records.shape[-1]) != CURVE_RECORD_DWORDS:
-        raise ValueError(f"expected int32[..., {CURVE_RECORD_DWORDS}] records, got shape {tuple(records.shape)}")
-    if isinstance(records, np.ndarray):
-        f32 = np.float32
-    else:
-        import torch
-        f32 = torch.float32
-    return {name: records[..., j].view(f32) if j in _FLOATS else records[..., j] for j, name in enumerate(_FIELDS[:7])}
+    out, _ = _unpack_fields(records, _FIELDS)
+    del out["reserved"]
+    return out
 
 
 def random_maps(n: int, map_hw, seed: int = 0) -> np.ndarray:

@@ -166,3 +166,107 @@ def test_summarize_curves_leaves_nan_frames_out():
     assert rep["deletion_auc"] == pytest.approx(0.3) and rep["insertion_auc"] == pytest.approx(0.7)
     assert rep["deletion_gain"] == pytest.approx(0.2) and rep["insertion_gain"] == pytest.approx(0.3)
     assert rep["flip_fraction"] == pytest.approx(0.3)
+
+
+# ---- refusal texts, word for word.  fav_check_curve and every refusal of fav_op_occlude and fav_op_views come before any
+# launch, so none needs a device and an address only has to look like one.  FB: the bytes of an 8 x 8 uint8 frame.  The last
+# cases of each op hold the order of its refusals: the frames' alignment, the op's own complaint, n * count, the overlap.
+FRAMES, OUT, RANK, FB = 0x10000, 0x100000, 0x200000, 8 * 8 * 3
+CHECK_CURVE_TEXTS = (
+    (dict(steps=0), "steps=0 outside [1, 256]"),
+    (dict(steps=257), "steps=257 outside [1, 256]"),
+    (dict(steps=-1), "steps=-1 outside [1, 256]"),
+    (dict(struct_size=28), "struct_size is not sizeof(fav_curve)"),
+    (dict(struct_size=0), "struct_size is not sizeof(fav_curve)"),
+    (dict(fill_u8=(256, 0, 0)), "fill[0]=256 is above 255, the largest uint8"),
+    (dict(fill_u8=(0, 0, 1000)), "fill[2]=1000 is above 255, the largest uint8"),
+    (None, "desc is NULL"),
+)
+CHECK_CURVE_FRAME_TEXTS = (
+    (dict(H=0), "frame size 0x32: H and W must be at least 1"),
+    (dict(W=0), "frame size 32x0: H and W must be at least 1"),
+    (dict(layout=2), "unknown layout"),
+    (dict(H=20000, W=20000), "H * W above (2^31 - 1) / 12 pixels"),
+)
+OCCLUDE_TEXTS = (
+    (dict(frames=None), "fav_op_occlude: null pointer"),
+    (dict(out=None), "fav_op_occlude: null pointer"),
+    (dict(rank=None), "fav_op_occlude: null pointer"),
+    (dict(fill=None), "fav_op_occlude: null pointer"),
+    (dict(s0=3, s1=3), "fav_op_occlude: steps [3, 3) outside 0 <= s0 < s1 <= S + 1 = 17"),
+    (dict(s0=4, s1=3), "fav_op_occlude: steps [4, 3) outside 0 <= s0 < s1 <= S + 1 = 17"),
+    (dict(s0=-1, s1=3), "fav_op_occlude: steps [-1, 3) outside 0 <= s0 < s1 <= S + 1 = 17"),
+    (dict(s1=18), "fav_op_occlude: steps [0, 18) outside 0 <= s0 < s1 <= S + 1 = 17"),
+    (dict(S=0, s1=1), "fav_op_occlude: steps=0 outside [1, 256]"),
+    (dict(S=257), "fav_op_occlude: steps=257 outside [1, 256]"),
+    (dict(fill=(1, 256, 3)), "fav_op_occlude: fill[1]=256 is above 255, the largest uint8"),
+    (dict(n=0), "fav_op_occlude: n must be at least 1"),
+    (dict(H=0), "fav_op_occlude: frame size 0x8: H and W must be at least 1"),
+    (dict(layout=2), "fav_op_occlude: unknown layout"),
+    (dict(mode=2), "fav_op_occlude: mode=2 is not a fav_curve_mode value"),
+    (dict(mh=0), "fav_op_occlude: map 0x2: needs 1 <= mh, mw <= 256 and mh * mw <= 1024 cells"),
+    (dict(mh=25, mw=41), "fav_op_occlude: map 25x41: needs 1 <= mh, mw <= 256 and mh * mw <= 1024 cells"),
+    (dict(mh=257, mw=1), "fav_op_occlude: map 257x1: needs 1 <= mh, mw <= 256 and mh * mw <= 1024 cells"),
+    (dict(frames=FRAMES + 2, layout=F32, s1=1), "fav_op_occlude: fp32 frames and out must be 4-byte aligned"),
+    (dict(out=OUT + 1, layout=F32, s1=1), "fav_op_occlude: fp32 frames and out must be 4-byte aligned"),
+    (dict(rank=RANK + 2), "fav_op_occlude: rank_dev must be 4-byte aligned"),
+    (dict(n=2 ** 31 - 1, s1=2), "fav_op_occlude: n * (s1 - s0) above 2^31 - 1"),
+    (dict(out=FRAMES, s1=1), "fav_op_occlude: out overlaps frames"),
+    (dict(out=FRAMES + 2 * FB - 1, s1=1), "fav_op_occlude: out overlaps frames"),
+    (dict(frames=OUT + 5 * FB), "fav_op_occlude: out overlaps frames"),
+    (dict(frames=OUT + 2 * 2 * FB - 1, s1=2), "fav_op_occlude: out overlaps frames"),
+    (dict(frames=OUT + 2, out=OUT + 1, layout=F32, rank=RANK + 2, n=2 ** 31 - 1),
+     "fav_op_occlude: fp32 frames and out must be 4-byte aligned"),
+    (dict(out=FRAMES, rank=RANK + 2, n=2 ** 31 - 1), "fav_op_occlude: rank_dev must be 4-byte aligned"),
+    (dict(out=FRAMES, n=2 ** 31 - 1), "fav_op_occlude: n * (s1 - s0) above 2^31 - 1"),
+)
+VIEWS_TEXTS = (
+    (dict(n_views=65), "fav_op_views: n_views=65 outside [1, FAV_MAX_VIEWS=64]"),
+    (dict(n_views=0), "fav_op_views: n_views=0 outside [1, FAV_MAX_VIEWS=64]"),
+    (dict(frames=None), "fav_op_views: null pointer"),
+    (dict(out=None), "fav_op_views: null pointer"),
+    (dict(view=None), "fav_op_views: views is NULL"),
+    (dict(n=0), "fav_op_views: n, H and W must be at least 1"),
+    (dict(H=0), "fav_op_views: n, H and W must be at least 1"),
+    (dict(layout=2), "fav_op_views: unknown layout"),
+    (dict(W=4, view=(0, 0, 1, 0, 0, 0)), "fav_op_views: view 0: transpose needs H == W, the frames are 8x4"),
+    (dict(view=(0, 0, 0, 0, 0, 3)), "fav_op_views: view 0: border=3 is not a fav_border value"),
+    (dict(frames=FRAMES + 2, layout=F32), "fav_op_views: fp32 frames and out must be 4-byte aligned"),
+    (dict(out=OUT + 1, layout=F32), "fav_op_views: fp32 frames and out must be 4-byte aligned"),
+    (dict(H=20000, W=20000), "fav_op_views: H * W above (2^31 - 1) / 12 pixels"),
+    (dict(n=2 ** 31 - 1, n_views=2), "fav_op_views: n * n_views above 2^31 - 1"),
+    (dict(out=FRAMES), "fav_op_views: out overlaps frames"),
+    (dict(out=FRAMES + 2 * FB - 1), "fav_op_views: out overlaps frames"),
+    (dict(frames=OUT + 3 * FB, n_views=5), "fav_op_views: out overlaps frames"),
+    (dict(frames=OUT + 2 * 2 * FB - 1, n_views=2), "fav_op_views: out overlaps frames"),
+    (dict(frames=OUT + 2, layout=F32, H=20000, W=20000, n=2 ** 31 - 1, n_views=2),
+     "fav_op_views: fp32 frames and out must be 4-byte aligned"),
+    (dict(out=FRAMES, H=20000, W=20000, n=2 ** 31 - 1, n_views=2), "fav_op_views: H * W above (2^31 - 1) / 12 pixels"),
+    (dict(out=FRAMES, n=2 ** 31 - 1, n_views=2), "fav_op_views: n * n_views above 2^31 - 1"),
+)
+
+
+def op_text(fn, args):
+    assert fn(*args, None) == 1, args
+    return _lib.load().fav_last_error(None).decode()
+
+
+def test_check_curve_refusal_texts():
+    for kw, text in CHECK_CURVE_TEXTS:
+        assert check(None if kw is None else desc(**kw)) == (1, text), kw
+    for kw, text in CHECK_CURVE_FRAME_TEXTS:
+        assert check(desc(), **kw) == (1, text), kw
+
+
+def test_op_occlude_refusal_texts():
+    def args(frames=FRAMES, out=OUT, n=2, H=8, W=8, layout=U8, rank=RANK, mh=2, mw=2, mode=0, S=16, s0=0, s1=17, fill=(1, 2, 3)):
+        return (frames, out, n, H, W, layout, rank, mh, mw, mode, S, s0, s1, None if fill is None else (C.c_uint32 * 3)(*fill))
+    for kw, text in OCCLUDE_TEXTS:
+        assert op_text(_lib.load().fav_op_occlude, args(**kw)) == text, kw
+
+
+def test_op_views_refusal_texts():
+    def args(frames=FRAMES, out=OUT, n=2, H=8, W=8, layout=U8, view=(0, 0, 0, 0, 0, 0), n_views=1):
+        return (frames, out, n, H, W, layout, None if view is None else (_lib.FavView * 65)(*[_lib.FavView(*view)] * 65), n_views)
+    for kw, text in VIEWS_TEXTS:
+        assert op_text(_lib.load().fav_op_views, args(**kw)) == text, kw

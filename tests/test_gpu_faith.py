@@ -14,11 +14,10 @@ pytestmark = pytest.mark.gpu
 import torch  # noqa: E402
 import faith_ref as R  # noqa: E402
 import heads_ref as H  # noqa: E402
+from perturb_gpu import PAT, Out, dev, frames_of, host, last_error, stream  # noqa: E402
 from failure_aware_vision_amd import Backend, _lib, faithfulness, synth, views, weights  # noqa: E402
 from failure_aware_vision_amd.backend import unpack_uncertainty  # noqa: E402
 
-GUARD = 64
-PAT = 0xA5
 U8, F32 = _lib.LAYOUT_NHWC_U8, _lib.LAYOUT_NHWC_F32
 ids = lambda s: "x".join(map(str, s)) if isinstance(s, tuple) else str(s)  # noqa: E731
 
@@ -27,35 +26,6 @@ ids = lambda s: "x".join(map(str, s)) if isinstance(s, tuple) else str(s)  # noq
 def lib():
     assert torch.cuda.is_available(), "GPU tests need a MI355X"
     return _lib.load()
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-class Out:
-    """nbytes of device output, `off` bytes into a 16-byte aligned buffer, with GUARD bytes of PAT on either side."""
-    def __init__(self, nbytes, off=0):
-        self.nbytes, self.lo = nbytes, GUARD + off
-        self.t = torch.full((GUARD + 16 + nbytes + GUARD,), PAT, dtype=torch.uint8, device="cuda")
-        assert self.t.data_ptr() % 16 == 0
-        self.ptr = self.t.data_ptr() + self.lo
-
-    def get(self, dtype, shape):
-        host = self.t.cpu().numpy()
-        assert (host[:self.lo] == PAT).all() and (host[self.lo + self.nbytes:] == PAT).all(), "a guard byte was written"
-        return host[self.lo:self.lo + self.nbytes].copy().view(dtype).reshape(shape)
-
-    def untouched(self):
-        return bool((self.t == PAT).all())
-
-
-def last_error(lib):
-    return lib.fav_last_error(None).decode()
 
 
 def fill_words(fill):
@@ -91,14 +61,6 @@ def test_op_rank_cells_refusals_launch_nothing(lib):
 
 
 # ---- fav_op_occlude ------------------------------------------------------------------------------------------------------
-def frames_of(n, H_, W, dtype, seed=0):
-    """uint8: random bytes.  float32: random BIT PATTERNS (NaNs of both kinds, infinities and subnormals among them)."""
-    rng = np.random.default_rng(1000 * H_ + W + seed)
-    if dtype == np.uint8:
-        return rng.integers(0, 256, (n, H_, W, 3), dtype=np.uint8)
-    return rng.integers(0, 2 ** 32, (n, H_, W, 3), dtype=np.uint32).view(np.float32)
-
-
 def fill_for(dtype):
     return (17, 255, 0) if dtype == np.uint8 else (0x7FC12345, 0x80000000, 0x3F000000)     # fp32: a NaN payload, -0, 0.5
 
@@ -427,10 +389,6 @@ def records_of(r):
     return np.stack([c.view(np.int32) for c in cols] + [np.zeros_like(cols[0], dtype=np.int32)], axis=1)
 
 
-def host(v):
-    return v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
-
-
 U8_FILL = (64, 128, 255)                                  # round(255 * (0.25, 0.5, 1.0))
 F32_FILL = tuple(int(np.float32(v).view(np.uint32)) for v in (0.25, 0.5, 1.0))
 
@@ -598,16 +556,21 @@ def test_handle_refusals():
         big = dev(synth.synthetic_frames_u8(MAX_BATCH + 1, size, size, seed=3))
         bigmap = dev(np.zeros((MAX_BATCH + 1, 1025), np.float32))
 
-        def call(n=N, layout=U8, mh=mhw[0], mw=mhw[1], mode=0, frames_=big, maps_=bigmap, curve_=curve.data_ptr(), rec_=rec.data_ptr()):
-            st = be.lib.fav_classify_curve(be._h, frames_.data_ptr() if frames_ is not None else None, n, layout, 0,
-                                           maps_.data_ptr() if maps_ is not None else None, mh, mw, None, mode, None, None, curve_, rec_, s)
+        def call(n=N, layout=U8, first=0, mh=mhw[0], mw=mhw[1], mode=0, frames_=big.data_ptr(), maps_=bigmap.data_ptr(), classes=None,
+                 curve_=curve.data_ptr(), rec_=rec.data_ptr()):
+            st = be.lib.fav_classify_curve(be._h, frames_, n, layout, first, maps_, mh, mw, classes, mode, None, None, curve_, rec_, s)
             torch.cuda.synchronize()
             return st, be.lib.fav_last_error(be._h).decode()
         for why, kw, text in (("n above max_batch", dict(n=MAX_BATCH + 1), "n=9 outside [1, max_batch=8]"), ("n 0", dict(n=0), "n=0"),
                               ("1025 cells", dict(mh=25, mw=41), "map 25x41"), ("a side of 257", dict(mh=257, mw=1), "map 257x1"),
-                              ("mode", dict(mode=2), "mode=2"), ("layout", dict(layout=3), "layout"), ("null frames", dict(frames_=None), "null"),
-                              ("null maps", dict(maps_=None), "null"), ("null curve", dict(curve_=None), "null"), ("null rec", dict(rec_=None), "null"),
-                              ("curve + 2", dict(curve_=curve.data_ptr() + 2), "misaligned"), ("rec + 4", dict(rec_=rec.data_ptr() + 4), "misaligned")):
+                              ("map 0", dict(mw=0), "map 4x0"), ("mode", dict(mode=2), "mode=2"), ("layout", dict(layout=3), "layout"),
+                              ("first", dict(first=-1), "first_image_index"), ("first + n", dict(first=2 ** 32 - 3), "first_image_index"),
+                              ("null frames", dict(frames_=None), "null"), ("null maps", dict(maps_=None), "null"),
+                              ("null curve", dict(curve_=None), "null"), ("null rec", dict(rec_=None), "null"),
+                              ("maps + 2", dict(maps_=bigmap.data_ptr() + 2), "misaligned"),
+                              ("curve + 2", dict(curve_=curve.data_ptr() + 2), "misaligned"), ("rec + 4", dict(rec_=rec.data_ptr() + 4), "misaligned"),
+                              ("classes + 2", dict(classes=rec.data_ptr() + 2), "misaligned"),
+                              ("f32 frames + 2", dict(layout=F32, frames_=big.data_ptr() + 2), "aligned")):
             st, msg = call(**kw)
             assert st == 1 and "fav_classify_curve" in msg and text in msg, (why, msg)
             assert bool((curve == 7.0).all()) and bool((rec == 7).all()), why

@@ -12,10 +12,9 @@ pytestmark = pytest.mark.gpu
 
 import torch  # noqa: E402
 import rise_ref as R  # noqa: E402
-from failure_aware_vision_amd import Backend, _lib, synth, views, weights  # noqa: E402
+from perturb_gpu import PAT, Out, dev, frames_of, host, last_error, stream  # noqa: E402
+from failure_aware_vision_amd import Backend, _lib, faithfulness, synth, views, weights  # noqa: E402
 
-GUARD = 64
-PAT = 0xA5
 U8, F32 = _lib.LAYOUT_NHWC_U8, _lib.LAYOUT_NHWC_F32
 ids = lambda s: "x".join(map(str, s)) if isinstance(s, tuple) else str(s)  # noqa: E731
 
@@ -26,39 +25,6 @@ def lib():
     return _lib.load()
 
 
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(v):
-    return v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
-
-
-class Out:
-    """nbytes of device output, `off` bytes into a 16-byte aligned buffer, with GUARD bytes of PAT on either side."""
-    def __init__(self, nbytes, off=0):
-        self.nbytes, self.lo = nbytes, GUARD + off
-        self.t = torch.full((GUARD + 16 + nbytes + GUARD,), PAT, dtype=torch.uint8, device="cuda")
-        assert self.t.data_ptr() % 16 == 0
-        self.ptr = self.t.data_ptr() + self.lo
-
-    def get(self, dtype, shape):
-        host_ = self.t.cpu().numpy()
-        assert (host_[:self.lo] == PAT).all() and (host_[self.lo + self.nbytes:] == PAT).all(), "a guard byte was written"
-        return host_[self.lo:self.lo + self.nbytes].copy().view(dtype).reshape(shape)
-
-    def untouched(self):
-        return bool((self.t == PAT).all())
-
-
-def last_error(lib):
-    return lib.fav_last_error(None).decode()
-
-
 def c_desc(d, struct_size=None):
     c = _lib.FavRise()
     c.struct_size = C.sizeof(_lib.FavRise) if struct_size is None else struct_size
@@ -66,14 +32,6 @@ def c_desc(d, struct_size=None):
     for k in range(3):
         c.fill_u8[k], c.fill_f32_bits[k] = d.fill_u8[k], d.fill_f32_bits[k]
     return c
-
-
-def frames_of(n, H_, W, dtype, seed=0):
-    """uint8: random bytes.  float32: random BIT PATTERNS (NaNs of both kinds, infinities and subnormals among them)."""
-    rng = np.random.default_rng(1000 * H_ + W + seed)
-    if dtype == np.uint8:
-        return rng.integers(0, 256, (n, H_, W, 3), dtype=np.uint8)
-    return rng.integers(0, 2 ** 32, (n, H_, W, 3), dtype=np.uint32).view(np.float32)
 
 
 def desc_of(dtype, **kw):
@@ -597,6 +555,43 @@ def test_a_rise_descriptor_changes_no_classify_call():
             assert before[5] == other[5] and before[6] == other[6]
     finally:
         be.close()
+
+
+@pytest.mark.parametrize("dtype", ("u8", "f32"))
+def test_the_curve_and_rise_heads_share_a_handle_without_cross_talk(dtype):
+    """The two heads share a record type and a driver: with both descriptors in force every output of either is, bit for bit,
+    what a handle holding that descriptor alone gives, in any order of the calls and after the other descriptor is cleared."""
+    n, backends = 3, [make_backend("resnet18")[0] for _ in range(3)]
+    both, curve_only, rise_only = backends
+    try:
+        u8 = synth.synthetic_frames_u8(n, 32, 32, seed=3)
+        frames = dev(u8) if dtype == "u8" else dev(u8.astype(np.float32) / np.float32(255.0))
+        maps = dev(faithfulness.random_maps(n, (4, 4), 0))
+
+        def bits(r):
+            return {k: (v.shape, v.dtype.str, np.ascontiguousarray(v).tobytes()) for k, v in ((k, host(v)) for k, v in r.items())}
+
+        def curve(be):
+            return [bits(be.classify_curve(frames, maps, None, mode, first_index=FIRST)) for mode in _lib.CURVE_MODES]
+
+        def rise(be):
+            return bits(be.classify_rise(frames, map_hw=(4, 4), heatmap=True, first_index=FIRST))
+        for be in (both, curve_only):
+            be.set_curve(4)
+        for be in (both, rise_only):
+            be.set_rise(5, grid=2)
+        want_curve, want_rise = curve(curve_only), rise(rise_only)
+        assert curve(both) == want_curve
+        assert rise(both) == want_rise
+        assert curve(both) == want_curve
+        both.set_rise(None)
+        assert curve(both) == want_curve
+        both.set_rise(5, grid=2)
+        both.set_curve(None)
+        assert rise(both) == want_rise
+    finally:
+        for be in backends:
+            be.close()
 
 
 def records_of(r):

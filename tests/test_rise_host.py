@@ -208,3 +208,80 @@ def test_the_end_to_end_inputs_cover_every_cell():
         for first in (R.E2E_FIRST, 0):
             _, _, cov = R.accumulate(prob, np.zeros(R.E2E_MAX_BATCH, np.int32), d, first, size, size, mh, mw)
             assert cov.shape == (R.E2E_MAX_BATCH, mh * mw) and (cov > 0).all(), (size, first, cov.min())
+
+
+# ---- refusal texts, word for word.  fav_check_rise and every refusal of fav_op_rise_mask come before any launch, so none
+# needs a device and an address only has to look like one.  FB: the bytes of an 8 x 8 uint8 frame.  The last cases of the op hold
+# the order of its refusals: the frames' alignment, n * (m1 - m0), the overlap.
+FRAMES, OUT, FB = 0x10000, 0x100000, 8 * 8 * 3
+CHECK_RISE_TEXTS = (
+    (None, "desc is NULL"),
+    (dict(struct_size=44), "struct_size is not sizeof(fav_rise)"),
+    (dict(struct_size=0), "struct_size is not sizeof(fav_rise)"),
+    (dict(n_masks=0), "n_masks=0 outside [1, 8192]"),
+    (dict(n_masks=8193), "n_masks=8193 outside [1, 8192]"),
+    (dict(n_masks=-1), "n_masks=-1 outside [1, 8192]"),
+    (dict(grid=0), "grid=0 outside [1, 15]"),
+    (dict(grid=16), "grid=16 outside [1, 15]"),
+    (dict(keep=0), "keep=0 outside [1, 255]"),
+    (dict(keep=256), "keep=256 outside [1, 255]"),
+    (dict(fill_u8=(256, 0, 0)), "fill[0]=256 is above 255, the largest uint8"),
+    (dict(fill_u8=(0, 0, 1000)), "fill[2]=1000 is above 255, the largest uint8"),
+)
+CHECK_RISE_FRAME_TEXTS = (
+    (dict(H=6, W=32), "grid=7 above min(H, W)=6"),
+    (dict(H=32, W=3), "grid=7 above min(H, W)=3"),
+    (dict(H=0), "frame size 0x32: H and W must be at least 1"),
+    (dict(W=0), "frame size 32x0: H and W must be at least 1"),
+    (dict(W=-3), "frame size 32x-3: H and W must be at least 1"),
+    (dict(layout=2), "unknown layout"),
+    (dict(H=20000, W=20000), "H * W above (2^31 - 1) / 12 pixels"),
+)
+MASK_TEXTS = (
+    (dict(frames=None), "fav_op_rise_mask: null pointer"),
+    (dict(out=None), "fav_op_rise_mask: null pointer"),
+    (dict(d=None), "fav_op_rise_mask: desc is NULL"),
+    (dict(d=dict(struct_size=40)), "fav_op_rise_mask: struct_size is not sizeof(fav_rise)"),
+    (dict(m0=3, m1=3), "fav_op_rise_mask: masks [3, 3) outside 0 <= m0 < m1 <= n_masks = 5"),
+    (dict(m0=4, m1=3), "fav_op_rise_mask: masks [4, 3) outside 0 <= m0 < m1 <= n_masks = 5"),
+    (dict(m0=-1, m1=3), "fav_op_rise_mask: masks [-1, 3) outside 0 <= m0 < m1 <= n_masks = 5"),
+    (dict(m1=6), "fav_op_rise_mask: masks [0, 6) outside 0 <= m0 < m1 <= n_masks = 5"),
+    (dict(d=dict(n_masks=0)), "fav_op_rise_mask: n_masks=0 outside [1, 8192]"),
+    (dict(d=dict(n_masks=8193)), "fav_op_rise_mask: n_masks=8193 outside [1, 8192]"),
+    (dict(d=dict(grid=0)), "fav_op_rise_mask: grid=0 outside [1, 15]"),
+    (dict(d=dict(grid=16)), "fav_op_rise_mask: grid=16 outside [1, 15]"),
+    (dict(d=dict(grid=9)), "fav_op_rise_mask: grid=9 above min(H, W)=8"),
+    (dict(d=dict(keep=0)), "fav_op_rise_mask: keep=0 outside [1, 255]"),
+    (dict(d=dict(keep=256)), "fav_op_rise_mask: keep=256 outside [1, 255]"),
+    (dict(d=dict(fill_u8=(1, 256, 3))), "fav_op_rise_mask: fill[1]=256 is above 255, the largest uint8"),
+    (dict(n=0), "fav_op_rise_mask: n must be at least 1"),
+    (dict(H=0), "fav_op_rise_mask: frame size 0x8: H and W must be at least 1"),
+    (dict(layout=2), "fav_op_rise_mask: unknown layout"),
+    (dict(frames=FRAMES + 2, layout=F32, m1=1), "fav_op_rise_mask: fp32 frames and out must be 4-byte aligned"),
+    (dict(out=OUT + 1, layout=F32, m1=1), "fav_op_rise_mask: fp32 frames and out must be 4-byte aligned"),
+    (dict(n=2 ** 31 - 1, m1=2), "fav_op_rise_mask: n * (m1 - m0) above 2^31 - 1"),
+    (dict(out=FRAMES, m1=1), "fav_op_rise_mask: out overlaps frames"),
+    (dict(out=FRAMES + 2 * FB - 1, m1=1), "fav_op_rise_mask: out overlaps frames"),
+    (dict(frames=OUT + 3 * FB), "fav_op_rise_mask: out overlaps frames"),
+    (dict(frames=OUT + 2 * 2 * FB - 1, m1=2), "fav_op_rise_mask: out overlaps frames"),
+    (dict(frames=OUT + 2, layout=F32, n=2 ** 31 - 1), "fav_op_rise_mask: fp32 frames and out must be 4-byte aligned"),
+    (dict(out=FRAMES, n=2 ** 31 - 1), "fav_op_rise_mask: n * (m1 - m0) above 2^31 - 1"),
+)
+
+
+def test_check_rise_refusal_texts():
+    for kw, text in CHECK_RISE_TEXTS:
+        assert check(None if kw is None else desc(**kw)) == (1, text), kw
+    for kw, text in CHECK_RISE_FRAME_TEXTS:
+        assert check(desc(), **kw) == (1, text), kw
+
+
+def test_op_rise_mask_refusal_texts():
+    lib = _lib.load()
+
+    def args(frames=FRAMES, out=OUT, n=2, H=8, W=8, layout=U8, d=dict(), first=0, m0=0, m1=5):      # d: what differs from a good descriptor
+        return (frames, out, n, H, W, layout, None if d is None else C.byref(desc(**dict(dict(n_masks=5, grid=3, fill_u8=(1, 2, 3)), **d))),
+                first, m0, m1, None)
+    for kw, text in MASK_TEXTS:
+        assert lib.fav_op_rise_mask(*args(**kw)) == 1, kw
+        assert lib.fav_last_error(None).decode() == text, kw
