@@ -129,10 +129,31 @@ def lib():
     return _lib.load()
 
 
+def out_hw(c):
+    return (c.H + 2 * c.pad - c.kh) // c.stride + 1, (c.W + 2 * c.pad - c.kw) // c.stride + 1
+
+
+def case_seed(c):
+    return sum(ord(ch) * (i + 1) for i, ch in enumerate(c.name))
+
+
+def host_operands(c):
+    """[x, w, bias, residual] of a case drawn on the host: fp32 arrays of bf16 values (bias: any fp32); no device needed."""
+    assert not c.device
+    ho, wo = out_hw(c)
+    k = c.kh * c.kw * c.cin
+    rng = np.random.default_rng(case_seed(c))
+    x = O.bf16_round((rng.standard_normal((c.n, c.H, c.W, c.cin)) * np.exp2(rng.integers(-2, 3, (c.n, c.H, c.W, c.cin)))).astype(np.float32))
+    w = O.bf16_round((rng.standard_normal((c.cout, c.kh, c.kw, c.cin)) * np.sqrt(2.0 / k)).astype(np.float32))
+    b = (rng.standard_normal(c.cout) * 0.2).astype(np.float32)
+    r = O.bf16_round(rng.standard_normal((c.n, ho, wo, c.cout)).astype(np.float32)) if c.res else None
+    return [x, w, b, r]
+
+
 def operands(c):
     """x, w, bias, residual as fp32 arrays of bf16 values (bias: any fp32), and their device tensors."""
-    ho, wo = (c.H + 2 * c.pad - c.kh) // c.stride + 1, (c.W + 2 * c.pad - c.kw) // c.stride + 1
-    seed = sum(ord(ch) * (i + 1) for i, ch in enumerate(c.name))
+    ho, wo = out_hw(c)
+    seed = case_seed(c)
     k = c.kh * c.kw * c.cin
     if c.device:
         g = torch.Generator(device="cuda").manual_seed(seed)
@@ -142,12 +163,7 @@ def operands(c):
         rd = torch.randn((c.n, ho, wo, c.cout), device="cuda", generator=g).to(torch.bfloat16) if c.res else None
         host = [t.float().cpu().numpy() if t is not None else None for t in (xd, wd, bd, rd)]
     else:
-        rng = np.random.default_rng(seed)
-        x = O.bf16_round((rng.standard_normal((c.n, c.H, c.W, c.cin)) * np.exp2(rng.integers(-2, 3, (c.n, c.H, c.W, c.cin)))).astype(np.float32))
-        w = O.bf16_round((rng.standard_normal((c.cout, c.kh, c.kw, c.cin)) * np.sqrt(2.0 / k)).astype(np.float32))
-        b = (rng.standard_normal(c.cout) * 0.2).astype(np.float32)
-        r = O.bf16_round(rng.standard_normal((c.n, ho, wo, c.cout)).astype(np.float32)) if c.res else None
-        host = [x, w, b, r]
+        host = x, w, b, r = host_operands(c)
         xd, wd, bd = (torch.from_numpy(x).cuda().to(torch.bfloat16), torch.from_numpy(w).cuda().to(torch.bfloat16),
                       torch.from_numpy(b).cuda())
         rd = torch.from_numpy(r).cuda().to(torch.bfloat16) if c.res else None

@@ -76,9 +76,11 @@ CASES = [
 ROUTE_OF = {c[:6]: c[6] for c in CASES}
 
 
-@pytest.mark.parametrize("cmid,nred,has3x3,H,W,n", [c[:6] for c in CASES])
-@pytest.mark.parametrize("with_drop", [False, True])
-def test_tail_bitwise_vs_separate_launches_and_oracle(lib, cmid, nred, has3x3, H, W, n, with_drop):
+TAIL_DROP = dict(site=5, thr=26, seed=0x1234567ABC, v0=3, first=40)      # the dropout arm: virtual frames 3 .. 3 + n of n + 1 frames
+
+
+def tail_operands(cmid, nred, has3x3, H, W, n):
+    """x, wb, bb, wc, bc, res, wa, ba of a case, drawn on the host (wb, bb None without the 3x3; wa, ba None without a reduce)."""
     rng = np.random.default_rng(cmid * 31 + nred * 7 + H * W + n + int(has3x3))
     cout = 4 * cmid
     x = O.bf16_round(np.maximum(rng.standard_normal((n, H, W, cmid)) * np.exp2(rng.integers(-2, 3, (n, H, W, cmid))), -0.2).astype(np.float32))
@@ -89,8 +91,29 @@ def test_tail_bitwise_vs_separate_launches_and_oracle(lib, cmid, nred, has3x3, H
     res = O.bf16_round(np.maximum(rng.standard_normal((n, H, W, cout)), 0).astype(np.float32))
     wa = O.bf16_round((rng.standard_normal((nred, 1, 1, cout)) * np.sqrt(2.0 / cout)).astype(np.float32)) if nred else None
     ba = (rng.standard_normal(nred) * 0.2).astype(np.float32) if nred else None
-    thr = 26
-    dd = drop_desc(site=5, thr=thr, scale=float(O.dropout_scale(thr)), seed=0x1234567ABC, v0=3, n_img=n + 1, first=40) if with_drop else None
+    return x, wb, bb, wc, bc, res, wa, ba
+
+
+def tail_drop_desc(n):
+    t = TAIL_DROP
+    return drop_desc(site=t["site"], thr=t["thr"], scale=float(O.dropout_scale(t["thr"])), seed=t["seed"], v0=t["v0"], n_img=n + 1, first=t["first"])
+
+
+def tail_keep(n, elems):
+    """The keep masks [n, elems] of TAIL_DROP: virtual frame v = v0 + i is sample v // n_img of frame v % n_img + first."""
+    t = TAIL_DROP
+    v = t["v0"] + np.arange(n)
+    return np.stack([O.dropout_keep(t["seed"], int(tt), t["site"], np.array([ii]), elems, t["thr"])[0]
+                     for tt, ii in zip(v // (n + 1), v % (n + 1) + t["first"])])
+
+
+@pytest.mark.parametrize("cmid,nred,has3x3,H,W,n", [c[:6] for c in CASES])
+@pytest.mark.parametrize("with_drop", [False, True])
+def test_tail_bitwise_vs_separate_launches_and_oracle(lib, cmid, nred, has3x3, H, W, n, with_drop):
+    x, wb, bb, wc, bc, res, wa, ba = tail_operands(cmid, nred, has3x3, H, W, n)
+    cout = 4 * cmid
+    thr = TAIL_DROP["thr"]
+    dd = tail_drop_desc(n) if with_drop else None
     # (a) the separate launches
     t2 = run_conv(lib, x, wb, bb, None, 1, 1, relu=1) if has3x3 else x
     y_ref = run_conv(lib, t2, wc, bc, res, 1, 0, relu=1, drop=dd)
@@ -102,12 +125,7 @@ def test_tail_bitwise_vs_separate_launches_and_oracle(lib, cmid, nred, has3x3, H
         assert np.array_equal(t1n, t1n_ref), f"t1': {np.mean(t1n != t1n_ref):.5f} of elements differ"
     # (b) the oracle (MFMA model), small cases only
     if n * H * W <= 8000:
-        keep = None
-        if with_drop:
-            # virtual frame v = v0 + i: sample t = v // n_img, frame (v % n_img) + first
-            v = 3 + np.arange(n)
-            t, img = v // (n + 1), v % (n + 1) + 40
-            keep = np.stack([O.dropout_keep(0x1234567ABC, int(tt), 5, np.array([ii]), H * W * cout, thr)[0] for tt, ii in zip(t, img)])
+        keep = tail_keep(n, H * W * cout) if with_drop else None
         o2 = O.epilogue(O.conv_acc_exact(x, wb, 3, 3, 1, 1, mode="mfma"), bb) if has3x3 else x
         oy = O.epilogue(O.conv_acc_exact(o2, wc, 1, 1, 1, 0, mode="mfma"), bc, res=res, relu=True, keep=keep, scale=O.dropout_scale(thr))
         assert np.array_equal(y, oy), f"Y vs oracle: {np.mean(y != oy):.5f} differ"
