@@ -947,9 +947,11 @@ class Backend:
     def fit_knn(self, frames, labels=None, **kw):
         """Build an ``ood.KNNBank`` from in-distribution frames: batches of frames_per_call frames run through the classifier
         with the tap on, the mean over the samples of each frame's features goes to ``ood.build_knn_bank`` (``k``,
-        ``max_rows``, ``seed``).  The handle is left as it was: see ``set_knn``."""
+        ``max_rows``, ``seed``, ``select``: ``"coreset"`` picks the ``max_rows`` rows by greedy k-centre selection on this
+        Backend's device).  The handle is left as it was: see ``set_knn``."""
         from .ood import build_knn_bank
         lab = None if labels is None else self._frame_labels(labels, frames)
+        kw.setdefault("device", self.device)
         return build_knn_bank(self._tapped_mean_features(frames), lab, **kw)
 
     def set_knn(self, bank):
@@ -1015,10 +1017,13 @@ class Backend:
     def fit_patch_bank(self, frames, **kw):
         """Build a ``patch.PatchBank`` from in-distribution frames: batches of frames_per_call frames run through the
         classifier with the map tap on, every cell of every map goes through ``patch.cell_rows`` and all of them to
-        ``patch.bank_from_rows`` (``max_rows``, ``seed``, ``threshold``, ``chunk_rows``).  The subsample is random; a greedy
-        coreset is out of scope.  The handle is left as it was, the map tap included: see ``set_patch_bank``."""
+        ``patch.bank_from_rows`` (``max_rows``, ``seed``, ``threshold``, ``chunk_rows``, ``select``).  The subsample is random
+        by default; ``select="coreset"`` picks the ``max_rows`` cells by greedy k-centre selection on this Backend's device
+        (``coreset.select_coreset``) and ``bank.selection.radius`` is the coverage curve.  The handle is left as it was, the
+        map tap included: see ``set_patch_bank``."""
         from .patch import bank_from_rows, cell_rows
         grid = self._patch_grid()
+        kw.setdefault("device", self.device)
 
         def run():
             parts = []

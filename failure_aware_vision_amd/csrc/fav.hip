@@ -36,6 +36,7 @@
 #include "fav_curve.hpp"
 #include "fav_rise.hpp"
 #include "fav_patch.hpp"
+#include "fav_coreset.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -3432,6 +3433,31 @@ fav_status fav_op_patch_score(const void* maps, int32_t S, int32_t n, int32_t Hf
     hipStream_t s = (hipStream_t)stream;
     if (patch_prepare(w, ws, bank, C, N, false, s) != FAV_OK) { g_create_error = fmt("%s: cannot prepare the workspace: %s", fn, hipGetErrorString(hipGetLastError())); return FAV_ERR_HIP; }
     return op_done(fn, launch_patch(maps, S, n, Hf, Wf, C, bank, N, threshold, w, ws, false, dist, row, rec, s));
+}
+
+// ---- greedy coreset selection (fav_coreset.hpp) ----------------------------------
+fav_status fav_check_coreset(int32_t N, int32_t D, int32_t M, int32_t start_row, char* err, size_t err_cap) {
+    return check_reply(coreset_error(N, D, M, start_row), err, err_cap);
+}
+
+size_t fav_coreset_workspace_bytes(int32_t N, int32_t D, int32_t M) {
+    if (!coreset_error(N, D, M, 0).empty()) return 0;
+    return coreset_workspace(N).bytes;
+}
+
+fav_status fav_op_coreset_select(const void* rows, int32_t N, int32_t D, int32_t M, int32_t start_row, void* ws, size_t ws_bytes,
+                                 int32_t* order, float* radius, void* stream) {
+    const char* fn = "fav_op_coreset_select";
+    route_clear();
+    if (!rows || !ws || !order || !radius) return op_rejected(fn, "null pointer");
+    const std::string dims = coreset_error(N, D, M, start_row);
+    if (!dims.empty()) return op_rejected(fn, dims.c_str());
+    const size_t need = coreset_workspace(N).bytes;
+    if (ws_bytes < need) return op_rejected(fn, fmt("ws_bytes=%zu is below fav_coreset_workspace_bytes=%zu", ws_bytes, need).c_str());
+    if ((uintptr_t)ws & 255) return op_rejected(fn, "ws_dev must be 256-byte aligned");
+    if (((uintptr_t)rows | (uintptr_t)order | (uintptr_t)radius) & 15) return op_rejected(fn, "rows_bf16_dev, order_dev and radius_dev must be 16-byte aligned");
+    launch_coreset(rows, N, D, M, start_row, ws, order, radius, (hipStream_t)stream);
+    return op_done(nullptr);
 }
 
 fav_status fav_op_drift_test(const void* feat, int32_t S, int32_t n, int32_t D, const void* ref, int32_t R, int32_t n_perm,

@@ -210,11 +210,13 @@ def _bf16_bits(x: np.ndarray) -> np.ndarray:
 @dataclasses.dataclass(frozen=True)
 class KNNBank:
     """``rows`` uint16[N, D]: L2-normalised in-distribution features as bf16 bit patterns, ``class_id`` int32[N] or None, ``k``:
-    which neighbour's distance is the score, ``threshold``: a frame is flagged when not (kth_dist <= threshold)."""
+    which neighbour's distance is the score, ``threshold``: a frame is flagged when not (kth_dist <= threshold), ``selection``:
+    the ``coreset.CoresetSelection`` that chose the rows (``select="coreset"``), else None; it is not saved."""
     rows: np.ndarray
     class_id: np.ndarray | None = None
     k: int = 10
     threshold: float = math.inf
+    selection: object | None = None
 
     def __post_init__(self):
         if np.asarray(self.rows).dtype != np.uint16:
@@ -239,6 +241,14 @@ class KNNBank:
 
     def with_threshold(self, threshold: float) -> "KNNBank":
         return dataclasses.replace(self, threshold=float(threshold))
+
+    def take(self, indices) -> "KNNBank":
+        """The bank of the rows ``indices`` (in that order) and their ``class_id``; ``k`` and ``threshold`` are kept, ``k`` is
+        checked against the new N."""
+        idx = _take_indices(indices, self.N)
+        if not 1 <= self.k <= idx.shape[0]:
+            raise ValueError(f"k must be in [1, N={idx.shape[0]}], got {self.k}")
+        return KNNBank(self.rows[idx], None if self.class_id is None else self.class_id[idx], self.k, self.threshold)
 
     def save(self, path):
         extra = {} if self.class_id is None else {"class_id": self.class_id}
@@ -266,11 +276,18 @@ class KNNBank:
         _check("fav_check_knn_bank", self.to_c(), D_expected)
 
 
-def build_knn_bank(features, labels=None, k: int = 10, max_rows: int | None = None, seed: int = 0) -> KNNBank:
+def build_knn_bank(features, labels=None, k: int = 10, max_rows: int | None = None, seed: int = 0, select: str = "random",
+                   device=None) -> KNNBank:
     """features [N, D] (one row per in-distribution frame: the mean over the samples of its features), labels int[N] or None
     -> the bank: every row divided by its Euclidean norm in float64, then rounded to bf16 (nearest even).  ``max_rows``: keep
-    that many rows, drawn without replacement by ``np.random.default_rng(seed)`` and kept in their original order.  Refuses a
-    non-finite value and a zero row."""
+    that many rows, in their original order.  ``select="random"``: drawn without replacement by
+    ``np.random.default_rng(seed)``.  ``select="coreset"``: every row is normalised and rounded first, then
+    ``coreset.select_coreset(rows, max_rows, seed)`` picks them on ``device`` - greedy k-centre selection, which covers the
+    feature space where a draw samples its density - and ``bank.selection`` keeps the picks and the coverage curve; with
+    ``max_rows`` None or at least N it keeps everything, as the draw does, and touches no device.  Refuses a non-finite value
+    and a zero row."""
+    from .coreset import check_select, select_coreset
+    check_select(select)
     F = np.asarray(features, np.float64)
     if F.ndim != 2 or F.shape[0] < 1:
         raise ValueError("features must be [N, D] with at least one row")
@@ -285,6 +302,10 @@ def build_knn_bank(features, labels=None, k: int = 10, max_rows: int | None = No
             raise ValueError("labels must be integers")
         if (y < 0).any():
             raise ValueError("labels must not be negative")
+    if select == "coreset" and _subsample_count(F.shape[0], max_rows) is not None:
+        full = KNNBank(_unit_rows_bf16(F), None if y is None else y.astype(np.int32), k=k)
+        selection = select_coreset(full.rows, int(max_rows), seed, device=device)
+        return dataclasses.replace(full.take(selection.indices), selection=selection)
     F, keep = _subsample(F, max_rows, seed)
     if keep is not None and y is not None:
         y = y[keep]
@@ -294,17 +315,34 @@ def build_knn_bank(features, labels=None, k: int = 10, max_rows: int | None = No
     return KNNBank(rows, None if y is None else y.astype(np.int32), k=k)
 
 
+def _subsample_count(N: int, max_rows):
+    """-> how many of N rows ``max_rows`` keeps, or None when it keeps them all; refuses a count below 1."""
+    if max_rows is None:
+        return None
+    if max_rows < 1:
+        raise ValueError(f"max_rows must be at least 1, got {max_rows}")
+    return None if max_rows >= N else int(max_rows)
+
+
 def _subsample(F: np.ndarray, max_rows, seed: int):
     """-> (the rows kept, their indices or None when all are): ``max_rows`` of them, drawn without replacement by
     ``np.random.default_rng(seed)`` and kept in their original order."""
-    if max_rows is None:
+    count = _subsample_count(F.shape[0], max_rows)
+    if count is None:
         return F, None
-    if max_rows < 1:
-        raise ValueError(f"max_rows must be at least 1, got {max_rows}")
-    if max_rows >= F.shape[0]:
-        return F, None
-    keep = np.sort(np.random.default_rng(seed).choice(F.shape[0], size=int(max_rows), replace=False))
+    keep = np.sort(np.random.default_rng(seed).choice(F.shape[0], size=count, replace=False))
     return F[keep], keep
+
+
+def _take_indices(indices, N: int) -> np.ndarray:
+    """``indices`` of a bank's ``take`` -> int64 [m], m >= 1, every one a row of the bank."""
+    idx = np.asarray(indices)
+    if idx.ndim != 1 or idx.shape[0] < 1 or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError("indices is a non-empty vector of integers")
+    idx = idx.astype(np.int64)
+    if (idx < 0).any() or (idx >= N).any():
+        raise ValueError(f"indices must be in [0, N={N})")
+    return idx
 
 
 def _unit_rows_bf16(F: np.ndarray) -> np.ndarray:

@@ -7,8 +7,9 @@ the localisation heads (``cam.py``, ``rollout.py``, ``rise.py``) explain the cla
 Here every cell of the last feature map is scored on its own: the squared distance of its normalised feature to the nearest
 row of a bank of in-distribution cells.  The map of those distances is an anomaly heat map and its peak a frame score.
 
-The bank is a seeded random subsample of the cells.  PatchCore's greedy coreset selection is out of scope: it is host work
-that changes which rows a bank holds, not what the device does with them."""
+The bank is a subsample of the cells: by default a seeded random draw, with ``select="coreset"`` PatchCore's greedy k-centre
+selection, run on the device (``coreset.py``; item 5n), which covers the feature space where a draw samples its density - a
+rare in-distribution texture keeps a row and stops being reported as an anomaly."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,7 +19,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .ood import _bf16_bits, _check, _subsample
+from .coreset import check_select, select_coreset
+from .ood import _bf16_bits, _check, _subsample, _subsample_count, _take_indices
 
 #: dwords of one fav_patch_record (include/fav.h)
 PATCH_RECORD_DWORDS = 8
@@ -31,12 +33,15 @@ class PatchBank:
     """``rows`` uint16[N, D]: L2-normalised in-distribution patch features as bf16 bit patterns; ``threshold``: a cell counts
     as above when dist >= threshold (+inf: never); ``chunk_rows``: the bank rows one slab of similarities covers, 0 for the
     library's rule (nothing in a result depends on it); ``grid``: the (hf, wf) map the rows were cut from, or None;
-    ``n_dropped``: the zero and non-finite cells ``build_patch_bank`` left out."""
+    ``n_dropped``: the zero and non-finite cells ``build_patch_bank`` left out; ``selection``: the
+    ``coreset.CoresetSelection`` that chose the rows (``select="coreset"``; its indices count the cells that were not dropped),
+    else None; it is not saved."""
     rows: np.ndarray
     threshold: float = math.inf
     chunk_rows: int = 0
     grid: tuple | None = None
     n_dropped: int = 0
+    selection: object | None = None
 
     def __post_init__(self):
         if np.asarray(self.rows).dtype != np.uint16:
@@ -60,6 +65,10 @@ class PatchBank:
 
     def with_threshold(self, threshold: float) -> "PatchBank":
         return dataclasses.replace(self, threshold=float(threshold))
+
+    def take(self, indices) -> "PatchBank":
+        """The bank of the rows ``indices`` (in that order); ``threshold``, ``chunk_rows``, ``grid`` and ``n_dropped`` are kept."""
+        return PatchBank(self.rows[_take_indices(indices, self.N)], self.threshold, self.chunk_rows, self.grid, self.n_dropped)
 
     def save(self, path):
         extra = {} if self.grid is None else {"grid": np.asarray(self.grid, np.int32)}
@@ -115,16 +124,23 @@ def cell_rows(maps):
 
 
 def bank_from_rows(rows, ok, max_rows: int | None = None, seed: int = 0, grid=None, threshold: float = math.inf,
-                   chunk_rows: int = 0) -> PatchBank:
+                   chunk_rows: int = 0, select: str = "random", device=None) -> PatchBank:
     """What ``cell_rows`` made, of one batch or of several concatenated -> the bank: the cells without a direction dropped
-    and counted, then ``max_rows`` of the rest kept, drawn as ``ood.build_knn_bank`` draws them (without replacement by
-    ``np.random.default_rng(seed)``, in their original order)."""
+    and counted, then ``max_rows`` of the rest kept in their original order, chosen as ``ood.build_knn_bank`` chooses them:
+    ``select="random"`` draws them without replacement by ``np.random.default_rng(seed)``; ``select="coreset"`` picks them by
+    ``coreset.select_coreset(rows, max_rows, seed)`` on ``device`` and keeps the picks and the coverage curve in
+    ``bank.selection`` (``max_rows`` None or at least the cells there are: everything is kept and no device touched)."""
+    check_select(select)
     rows, ok = np.asarray(rows, np.uint16), np.asarray(ok, bool)
     if rows.ndim != 2 or ok.shape != (rows.shape[0],):
         raise ValueError(f"shapes do not fit: rows {rows.shape}, ok {ok.shape}")
     kept = rows[ok]
     if kept.shape[0] < 1:
         raise ValueError("no cell has a direction: every one is zero or non-finite")
+    if select == "coreset" and _subsample_count(kept.shape[0], max_rows) is not None:
+        selection = select_coreset(kept, int(max_rows), seed, device=device)
+        full = PatchBank(kept, threshold, chunk_rows, grid, int((~ok).sum()))
+        return dataclasses.replace(full.take(selection.indices), selection=selection)
     kept, _ = _subsample(kept, max_rows, seed)
     return PatchBank(kept, threshold, chunk_rows, grid, int((~ok).sum()))
 
@@ -132,7 +148,7 @@ def bank_from_rows(rows, ok, max_rows: int | None = None, seed: int = 0, grid=No
 def build_patch_bank(maps, max_rows: int | None = None, seed: int = 0, **kw) -> PatchBank:
     """bf16 feature maps [S, n, HW, C] (or [S, n, Hf, Wf, C], as ``Backend.maps()`` gives them) of in-distribution frames ->
     the bank: ``bank_from_rows`` of ``cell_rows``.  ``bank.n_dropped`` counts the zero and non-finite cells left out.  The
-    subsample is random; a greedy coreset is out of scope."""
+    subsample is random by default; ``select="coreset"`` (and ``device``) makes it the greedy k-centre selection."""
     rows, ok, grid = cell_rows(maps)
     kw.setdefault("grid", grid)
     return bank_from_rows(rows, ok, max_rows, seed, **kw)

@@ -801,6 +801,35 @@ fav_status fav_classify_patch(fav_handle* h, const void* images_dev, int32_t n, 
                               int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev, float* dist_dev,
                               int32_t* row_dev, fav_patch_record* rec_dev, void* hip_stream);
 
+/* ---- Greedy coreset selection (the k-centre selection of PatchCore, Roth et al. 2022).  WHICH
+ * rows a patch bank or a k-NN bank holds: a uniform draw keeps rows in proportion to how often they occur, so the rare
+ * in-distribution modes get no row and are then reported as anomalous; farthest-point sampling covers the feature space
+ * instead.  An operator on device arrays (fav_op_coreset_select, below); no handle takes part.
+ * In: rows[N][D] bf16 bit patterns, finite, meant to be unit vectors; M in [1, N]; start_row in [0, N).
+ * Out: order[M] int32, the rows in the order picked; radius[M + 1] fp32.
+ *   order[0] = start_row;  radius[0] = +inf;  mind[r] = +inf for every r;  no row taken
+ *   for t = 1 .. M:
+ *     1. c = order[t-1];  c becomes taken
+ *     2. sim[r] = rows[r] . rows[c] in ONE order for every D: 64 chains, element j in chain (j / 8) % 64; a chain runs
+ *        acc = acc + a[j] * b[j] in fp32 over its elements in ascending j from +0 (a product of two bf16 is exact in fp32, so
+ *        a fused multiply-add gives the same bits); then six halving steps s[l] = s[l] + s[l + w] for l < w, w = 32, 16, 8, 4,
+ *        2, 1; sim = s[0].  What a wave computes whose lane l reads 16 bytes at element 8 l + 512 step and ends with an xor
+ *        butterfly.  A chain without elements (D < 512) stays +0
+ *     3. d[r] = fmaxf(2.0f - 2.0f * sim[r], +0.0f), the product and the difference rounded on their own, as step 3 of
+ *        fav_patch_record;  mind[r] = min(mind[r], d[r]) for EVERY r
+ *     4. (key, row) = the lexicographic maximum of (mind[r], -r) over the rows not taken: the farthest row, the LOWEST on a
+ *        tie; none when every row is taken (t = M = N only)
+ *     5. radius[t] = that mind, 0.0f when none;  if t < M: order[t] = that row
+ * radius[1 .. M-1] is the distance at which each centre was picked and never increases; radius[M] is the covering radius of
+ * the finished selection: no row of the pool is farther than that from its nearest selected row.  A selection of M rows is a
+ * prefix of every longer one from the same start_row, so one run gives the whole coverage curve.
+ * The op cannot see a non-finite row: for a pool that holds a NaN or an infinity its picks are unspecified (every index it
+ * writes is still a row of the pool, and it never faults); the callers refuse such rows before upload, with the check of
+ * fav_check_patch_bank.
+ * Ranges (fav_check_coreset, the one place they live; FAV_ERR_INVALID_ARG and a message that names the field): D a multiple of
+ * 64 in [64, 4096]; N in [1, 2^24] - the pool may be larger than a bank; M in [1, min(N, 262144)]; start_row in [0, N). */
+fav_status fav_check_coreset(int32_t N, int32_t D, int32_t M, int32_t start_row, char* err, size_t err_cap);   /* host only */
+
 /* Host-buffer convenience (frames and results in host memory; synchronous). */
 fav_status fav_classify_host(fav_handle* h, const void* images_host, int32_t n, int32_t layout,
                              int64_t first_image_index, int32_t* labels_host, float* conf_host,
@@ -1259,6 +1288,21 @@ int32_t fav_patch_chunk_rows(int32_t cells_total, int32_t N, int32_t chunk_rows)
 fav_status fav_op_patch_score(const void* maps_bf16, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C,
                               const void* bank_dev, int32_t N, int32_t chunk_rows, float threshold, void* ws_dev,
                               size_t ws_bytes, float* dist_dev, int32_t* row_dev, fav_patch_record* rec_dev, void* hip_stream);
+
+/* ---- The selection defined beside fav_check_coreset, on device arrays: rows_bf16_dev [N][D] bf16, order_dev int32 [M],
+ * radius_dev fp32 [M + 1] (all three 16-byte aligned), ws_dev a workspace of at least fav_coreset_workspace_bytes(N, D, M) bytes
+ * on a 256-byte boundary: mind as uint32 keys [N] and two buffers of per-block partial (key, row) pairs.  No handle.  One step
+ * kernel launched M + 1 times on hip_stream, plain launches whose stream order is the only synchronisation: launch t finds the
+ * centre from the partials of launch t - 1 (every block reduces them itself; block 0 stores radius[t] and order[t]), then
+ * streams the pool once - N * D * 2 bytes a step - a wave a row, and leaves its own partials; launch M is one block and only
+ * stores radius[M].  No allocation, no synchronisation, no atomics, no cooperative launch, no block waits for another; vector
+ * stores only.  Launch 0 writes mind without reading it and every partial is written before it is read: what an earlier call
+ * left in the workspace reaches no result.  The host enqueues M + 1 launches, which is what a fit-time operation costs.
+ * A refused call (FAV_ERR_INVALID_ARG: anything fav_check_coreset refuses, a NULL or misaligned pointer, a workspace too
+ * small) launches nothing, writes nothing and leaves a message that names the function in fav_last_error(NULL). */
+size_t fav_coreset_workspace_bytes(int32_t N, int32_t D, int32_t M);   /* host only; 0 for sizes out of range */
+fav_status fav_op_coreset_select(const void* rows_bf16_dev, int32_t N, int32_t D, int32_t M, int32_t start_row, void* ws_dev,
+                                 size_t ws_bytes, int32_t* order_dev, float* radius_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
