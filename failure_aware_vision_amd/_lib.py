@@ -168,6 +168,11 @@ class FavPatchBank(C.Structure):
                 ("rows", C.POINTER(C.c_uint16)), ("threshold", C.c_float)]
 
 
+class FavPatchSite(C.Structure):
+    """fav_patch_site: where a patch bank's rows come from - the residual stage 1 .. 4 and the neighbourhood radius 0 .. 2."""
+    _fields_ = [("struct_size", C.c_uint32), ("stage", C.c_int32), ("radius", C.c_int32)]
+
+
 class FavPatchRecord(C.Structure):
     """fav_patch_record: one 32-byte summary per frame (patch.unpack_patch_records reads it as int32[..., 8]); peak and floor
     stand where FavCamRecord has them."""
@@ -318,6 +323,18 @@ _SIGNATURES = {
     "fav_patch_chunk_rows": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     "fav_op_patch_score": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                      C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_patch_score_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "fav_op_patch_query": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "fav_check_patch_site": (C.c_int, [C.POINTER(FavPatchSite), C.c_char_p, C.c_size_t]),
+    "fav_set_patch_bank_at": (C.c_int, [C.c_void_p, C.POINTER(FavPatchBank), C.POINTER(FavPatchSite)]),
+    "fav_set_stage_tap": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t]),
+    "fav_get_stage_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
+    "fav_stage_tap_info": (C.c_int, [C.POINTER(FavConfig), C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
     "fav_check_coreset": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
     "fav_coreset_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "fav_op_coreset_select": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,

@@ -112,6 +112,7 @@ class Backend:
         self._map_hw = None                                   # (Hf, Wf) of the map tap, known from the first set_map_tap(True) on
         self._attn_grid = None                                # (gh, gw) of the attention tap, known from the first set_attn_tap(True) on
         self._map_tap_on = self._attn_tap_on = False          # the two localisation taps as this object last set them
+        self._stage_tap = 0                                   # the stage tap as this object last set it (0: off)
         self._curve_steps = None                              # the steps of the curve descriptor in force (set_curve)
         self._views = ()
         if views:
@@ -539,6 +540,30 @@ class Backend:
         out = torch.empty(shape, dtype=torch.bfloat16, device=f"cuda:{self.device}")
         stream = torch.cuda.current_stream(out.device).cuda_stream
         _lib.check(self.lib.fav_get_maps(self._h, out.data_ptr(), None, None, None, None, None, stream), self._h)
+        return out
+
+    # -- the stage tap (include/fav.h fav_set_stage_tap) ---------------------------------------------------
+    def stage_tap_info(self, stage: int) -> dict:
+        """What the stage tap of this configuration holds for residual stage 1 .. 4 (torchvision's layer1 .. layer4), from the
+        planner alone (fav_stage_tap_info; no device work): ``bytes``, ``samples``, ``hf``, ``wf``, ``c``."""
+        return self._tap_info(lambda cfg, *rest: self.lib.fav_stage_tap_info(cfg, int(stage), *rest), ("samples", "hf", "wf", "c"))
+
+    def set_stage_tap(self, stage: int, budget_bytes: int = 2 << 30):
+        """Keep the output of residual stage ``stage``'s last block (fav_set_stage_tap) from the next call on; ``stage_maps()``
+        reads it, and so does a patch bank at that stage.  0: off.  One stage at a time; another stage reallocates.  Refused on
+        a ViT arch, on a deep ensemble, above ``budget_bytes`` and for a stage whose map has more than 1024 cells."""
+        _lib.check(self.lib.fav_set_stage_tap(self._h, int(stage), int(budget_bytes)), self._h)
+        self._stage_tap = int(stage)
+
+    def stage_maps(self):
+        """bf16 [S, n, Hf, Wf, C] maps of the last classify call made with the stage tap on (torch CUDA tensor), indexed like
+        ``maps()``: the output of the tapped stage's last block."""
+        torch = self._torch
+        v = [C.c_int32() for _ in range(6)]
+        _lib.check(self.lib.fav_get_stage_maps(self._h, None, *(C.byref(x) for x in v), None), self._h)
+        out = torch.empty(tuple(x.value for x in v[1:]), dtype=torch.bfloat16, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        _lib.check(self.lib.fav_get_stage_maps(self._h, out.data_ptr(), None, None, None, None, None, None, stream), self._h)
         return out
 
     def cam(self, classes) -> dict:
@@ -1003,8 +1028,18 @@ class Backend:
             self._map_hw = (info["hf"], info["wf"])
         return self._map_hw
 
-    def _with_map_tap(self, run):
-        """``run()`` with the map tap on; a tap that only this call needs goes off again."""
+    def _with_map_tap(self, run, stage=None):
+        """``run()`` with the map tap on - with ``stage`` the stage tap at that stage; a tap that only this call needs goes
+        off again, and a stage tap that stood at another stage goes back to it."""
+        if stage is not None:
+            was = self._stage_tap
+            if was != stage:
+                self.set_stage_tap(stage)
+            try:
+                return run()
+            finally:
+                if was != stage:
+                    self.set_stage_tap(was)
         was_on = self._map_tap_on
         if not was_on:
             self.set_map_tap(True)
@@ -1014,24 +1049,37 @@ class Backend:
             if not was_on:
                 self.set_map_tap(False)
 
-    def fit_patch_bank(self, frames, **kw):
+    def _site_grid(self, stage) -> tuple:
+        """(Hf, Wf) of the map a bank at ``stage`` is cut from (None: the last map)."""
+        if stage is None:
+            return self._patch_grid()
+        info = self.stage_tap_info(stage)
+        return (info["hf"], info["wf"])
+
+    def fit_patch_bank(self, frames, stage=None, radius: int = 0, **kw):
         """Build a ``patch.PatchBank`` from in-distribution frames: batches of frames_per_call frames run through the
         classifier with the map tap on, every cell of every map goes through ``patch.cell_rows`` and all of them to
         ``patch.bank_from_rows`` (``max_rows``, ``seed``, ``threshold``, ``chunk_rows``, ``select``).  The subsample is random
         by default; ``select="coreset"`` picks the ``max_rows`` cells by greedy k-centre selection on this Backend's device
         (``coreset.select_coreset``) and ``bank.selection.radius`` is the coverage curve.  The handle is left as it was, the
-        map tap included: see ``set_patch_bank``."""
+        map tap included: see ``set_patch_bank``.  ``stage`` (1 .. 4; with ``radius`` 0 .. 2): the bank of a SITE - the cells
+        of that residual stage's map through the stage tap, each replaced by ``patch.aggregate_cells`` of its neighbourhood
+        before it is normalised; ``stage=None, radius=0`` is the plain bank of the last map."""
         from .patch import bank_from_rows, cell_rows
-        grid = self._patch_grid()
+        if stage is None and int(radius) != 0:
+            raise ValueError("a neighbourhood radius needs a stage (stage=4 is the last map)")
+        grid = self._site_grid(stage)
         kw.setdefault("device", self.device)
 
         def run():
             parts = []
             for b, e in self._batches(int(frames.shape[0])):
                 self.classify_detect(frames[b:e], b)
-                parts.append(cell_rows(self.maps())[:2])
+                parts.append(cell_rows(self.maps())[:2] if stage is None else cell_rows(self.stage_maps(), int(radius))[:2])
             return parts
-        parts = self._with_map_tap(run)
+        parts = self._with_map_tap(run, stage)
+        if stage is not None:
+            kw.update(stage=int(stage), radius=int(radius))
         return bank_from_rows(np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]), grid=grid, **kw)
 
     def set_patch_bank(self, bank):
@@ -1043,13 +1091,16 @@ class Backend:
         else:
             if bank.grid is not None:
                 try:
-                    grid = tuple(self._patch_grid())
+                    grid = tuple(self._site_grid(bank.stage))
                 except _lib.FavError:
                     grid = bank.grid               # no map here: the setter refuses the configuration in its own words
                 if grid != tuple(bank.grid):
                     raise ValueError(f"the bank was cut from a {bank.grid} map, this configuration's is {grid}")
-            c = bank.to_c()
-            _lib.check(self.lib.fav_set_patch_bank(self._h, C.byref(c)), self._h)
+            c, site = bank.to_c(), bank.site_to_c()
+            if site is None:
+                _lib.check(self.lib.fav_set_patch_bank(self._h, C.byref(c)), self._h)
+            else:
+                _lib.check(self.lib.fav_set_patch_bank_at(self._h, C.byref(c), C.byref(site)), self._h)
         self._patch = bank
 
     def classify_patch(self, images, heatmap: bool = False, first_index: int = 0) -> dict:
@@ -1066,7 +1117,7 @@ class Backend:
         torch = self._torch
         if self._patch is None:
             raise _lib.FavError(_lib.FAV_ERR_INVALID_ARG, "classify_patch: no patch bank set (set_patch_bank)")
-        hw = self._patch_grid()
+        hw = self._site_grid(self._patch.stage)
 
         def run():
             img, host, n, layout, stream = self._classify_args(images)
@@ -1087,7 +1138,7 @@ class Backend:
                 out = {k: v.cpu().numpy() for k, v in out.items()}
                 rec = rec.cpu().numpy()
             return dict(unpack_patch_records(rec), **out)
-        return self._with_map_tap(run)
+        return self._with_map_tap(run, self._patch.stage)
 
     def calibrate_patch(self, frames, tpr: float = 0.95) -> float:
         """Set the bank's threshold so that at least ``tpr`` of these in-distribution frames have no cell above it - the
@@ -1109,7 +1160,8 @@ class Backend:
 
     def _patch_peaks(self, frames) -> np.ndarray:
         """``classify_patch`` over batches of frames_per_call frames -> every frame's ``peak``, the map tap staying on throughout."""
-        return self._with_map_tap(lambda: self._head_distances(lambda f, b: self.classify_patch(f, first_index=b), "peak", frames))
+        return self._with_map_tap(lambda: self._head_distances(lambda f, b: self.classify_patch(f, first_index=b), "peak", frames),
+                                  self._patch.stage)
 
     # -- window-level drift detection (ood.py DriftReference; include/fav.h fav_set_drift) -------------------------------
     @property

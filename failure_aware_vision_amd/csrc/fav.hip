@@ -176,7 +176,9 @@ struct fav_handle {
     // patch bank (fav_set_patch_bank): the device copy, padded with zero rows to Npad, and the head's workspace for max_batch *
     // Hf * Wf cells (fav_patch.hpp patch_workspace, its zero bias written once by the setter); Hf, Wf: the planner's map, which
     // the map tap holds when it is on.  patch_on: one is set.  It reads the map tap and never turns it on or off
-    struct PatchDev { void *bank = nullptr, *ws = nullptr; int D = 0, N = 0, chunk_rows = 0, Hf = 0, Wf = 0; float threshold = 0.f; };
+    // stage, radius: the site (fav_set_patch_bank_at; stage 0: none - the map tap and the k-NN head's query kernel, radius -1)
+    struct PatchDev { void *bank = nullptr, *ws = nullptr; int D = 0, N = 0, chunk_rows = 0, Hf = 0, Wf = 0; float threshold = 0.f;
+                      int stage = 0, radius = -1; };
     PatchDev patch;
     bool patch_on = false;
     // drift reference (fav_set_drift): the workspace for max_batch frames (fav_drift.hpp drift_workspace, cached_ref), its
@@ -193,6 +195,11 @@ struct fav_handle {
     // [map.S][max_batch][Hf * Wf][C] at most (map: fav_cam.hpp map_tap_dims of the plan), indexed [sample][frame] like the logits
     LocTap map_tap;
     fav::MapTapDims map;
+    // Stage tap (fav_set_stage_tap): while on, every pass copies the frames op stage.op of the plan has written (stage 4: the
+    // frames the pool reads, as the map tap) into stage_tap.buf, laid out like the map tap's; stage_no: the stage in force (0: off)
+    LocTap stage_tap;
+    fav::MapTapDims stage;
+    int stage_no = 0;
     // Attention tap (fav_set_attn_tap; ViT only): while on, every encoder layer of every run_vit part launches attn_mean_kernel
     // (fav_rollout.hpp) in front of its attention launch; attn_tap.buf holds fp32 [attn.L][n][attn.T][attn.ld] for the n frame
     // rows of the call (at most max_batch), a part at its frame offset
@@ -1044,6 +1051,7 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
             fav_dropout_desc dd;
             dd.site = o.site; dd.threshold = thr; dd.scale = scale; dd.seed = c.seed;
             dd.v0 = p.suffix ? v0 : 0; dd.n_img = n; dd.first_image_index = f.first_index;
+            const bool stage_here = h->stage_tap.on && k == h->stage.op;
             switch (o.kind) {
                 case OP_STEM_IM2COL: {
                     const LayerShape& L = h->plan.layers[o.layer];
@@ -1099,6 +1107,12 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
                         HIP_TRY(h, hipMemcpyAsync((char*)h->map_tap.buf + (size_t)v0 * frame, buf(o.in, o), (size_t)cn * frame,
                                                   hipMemcpyDeviceToDevice, s));
                     }
+                    if (stage_here) {
+                        // the stage tap at stage 4: the same frames, to its own buffer
+                        const size_t frame = (size_t)o.H * o.W * o.C * 2;
+                        HIP_TRY(h, hipMemcpyAsync((char*)h->stage_tap.buf + (size_t)v0 * frame, buf(o.in, o), (size_t)cn * frame,
+                                                  hipMemcpyDeviceToDevice, s));
+                    }
                     if (const char* e = launch_avgpool(h, buf(o.in, o), buf(o.out, o), cn, o.H * o.W, o.C, &dd, G, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
                 case OP_ENTRY_DROPOUT:
@@ -1108,6 +1122,12 @@ fav_status run_chunks(fav_handle* h, size_t pi, const Frames& f, const Lane& lan
                     if (const char* e = launch_entry_reduce(h, pin_base, o.skip_y ? nullptr : buf(o.out, o), LW(o.layer_a), LB(o.layer_a), buf(o.out2, o), o.C, o.Co2,
                                                             o.H * o.W, cn, &dd, s)) { h->err = e; return FAV_ERR_INVALID_ARG; }
                     break;
+            }
+            if (stage_here && o.kind != OP_AVGPOOL) {
+                // the stage tap: the frames this op has written, to [virtual frame] of its buffer, behind the launch
+                const size_t frame = (size_t)o.out_elems * 2;
+                HIP_TRY(h, hipMemcpyAsync((char*)h->stage_tap.buf + (size_t)v0 * frame, buf(o.out, o), (size_t)cn * frame,
+                                          hipMemcpyDeviceToDevice, s));
             }
         }
     }
@@ -1142,7 +1162,7 @@ void free_all(fav_handle* h) {
     for (void* q : {h->knn.bank, h->knn.ws, (void*)h->knn.cls}) if (q) (void)hipFree(q);
     if (h->drift.ws) (void)hipFree(h->drift.ws);
     for (void* q : {h->patch.bank, h->patch.ws}) if (q) (void)hipFree(q);
-    for (void* q : {h->map_tap.buf, h->attn_tap.buf, h->curve.buf, h->rise.buf}) if (q) (void)hipFree(q);
+    for (void* q : {h->map_tap.buf, h->stage_tap.buf, h->attn_tap.buf, h->curve.buf, h->rise.buf}) if (q) (void)hipFree(q);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     for (void* q : {h->v_patches, h->v_emb, h->v_x, h->v_y, h->v_qkv, h->v_hid, h->v_cls}) if (q) (void)hipFree(q);
@@ -1677,6 +1697,7 @@ fav_status classify_on_stream(fav_handle* h, const Frames& f, const HeadOut& out
     h->last_n = n_head;
     if (h->tap) { h->feat_T = T_head; h->feat_n = n_head; }
     if (h->map_tap.on) { h->map_tap.S = h->map.S * views; h->map_tap.n = n_head; h->map_tap.views = h->n_views; }
+    if (h->stage_tap.on) { h->stage_tap.S = h->stage.S * views; h->stage_tap.n = n_head; h->stage_tap.views = h->n_views; }
     if (h->attn_tap.on) { h->attn_tap.n = f.n; h->attn_tap.views = h->n_views; }
     return FAV_OK;
 }
@@ -2040,6 +2061,7 @@ fav_status classify_feature_head(fav_handle* h, bool fav_handle::*on, const char
 //      fav_classify_cam, the attention tap with fav_rollout and fav_classify_rollout).  The nouns of a tap in its refusals:
 struct TapWords { const char *tap, *setter, *getter, *thing; };
 const TapWords kMapWords = {"map", "fav_set_map_tap", "fav_get_maps", "map"};
+const TapWords kStageWords = {"stage", "fav_set_stage_tap", "fav_get_stage_maps", "map"};
 const TapWords kAttnWords = {"attention", "fav_set_attn_tap", "fav_get_attention", "rollout"};
 // sizes for the caller: each pointer may be NULL
 using Sizes = std::initializer_list<std::pair<int32_t*, int>>;
@@ -2645,6 +2667,54 @@ fav_status fav_get_maps(fav_handle* h, void* out, int32_t* s_out, int32_t* n_out
                    (size_t)t.S * t.n * d.Hf * d.Wf * d.C * 2, stream);
 }
 
+// ---- the stage tap (fav_cam.hpp stage_tap_dims): the map tap's steps on the output of a residual stage's last block
+fav_status fav_stage_tap_info(const fav_config* cfg, int32_t stage, size_t* bytes, int32_t* s_map, int32_t* hf, int32_t* wf, int32_t* c,
+                              char* err, size_t err_cap) {
+    return tap_info("fav_stage_tap_info", cfg, map_tap_unsupported, true, err, err_cap, [&](std::string* why) -> fav_status {
+        if (stage < 1 || stage > 4) { *why = fmt("stage=%d outside [1, 4]", stage); return FAV_ERR_INVALID_ARG; }
+        Plan P;
+        if (fav_status st = plan_resnet(*cfg, 1, false, &P, why)) return st;
+        const MapTapDims d = stage_tap_dims(P, cfg->max_batch, stage);
+        if (bytes) *bytes = d.bytes;
+        put_sizes({{s_map, d.S}, {hf, d.Hf}, {wf, d.Wf}, {c, d.C}});
+        return FAV_OK;
+    });
+}
+
+fav_status fav_set_stage_tap(fav_handle* h, int32_t stage, size_t max_bytes) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    const char* fn = "fav_set_stage_tap";
+    if (stage == 0) {
+        h->stage_no = 0;
+        return tap_off(h, h->stage_tap);
+    }
+    if (stage < 0 || stage > 4) { h->err = fmt("%s: stage=%d outside [0, 4]", fn, stage); return FAV_ERR_INVALID_ARG; }
+    if (const char* why = map_tap_unsupported(h->cfg.arch, h->n_members, h->cfg.math_mode)) { h->err = fmt("%s: %s", fn, why); return FAV_ERR_UNSUPPORTED; }
+    const MapTapDims d = stage_tap_dims(h->plan, h->cfg.max_batch, stage);
+    const char* what = "stage maps of max_batch frames take";
+    std::string why = d.op < 0 ? fmt("the plan has no stage %d", stage) : patch_map_error(h->cfg.max_batch, d.Hf, d.Wf);
+    if (!why.empty()) why = fmt("stage %d: %s", stage, why.c_str());
+    if (why.empty()) why = tap_budget_error(what, d.bytes, max_bytes, CAM_DEFAULT_BUDGET);
+    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (h->stage_tap.on && h->stage_no != stage) {              // another stage: the buffer goes once what is enqueued has run
+        h->stage_no = 0;
+        if (fav_status st = tap_off(h, h->stage_tap)) return st;
+    }
+    if (fav_status st = tap_on(h, fn, h->stage_tap, h->stage, nullptr, what, max_bytes, CAM_DEFAULT_BUDGET, [&] { return d; })) return st;
+    h->stage_no = stage;
+    return FAV_OK;
+}
+
+fav_status fav_get_stage_maps(fav_handle* h, void* out, int32_t* stage_out, int32_t* s_out, int32_t* n_out, int32_t* hf_out,
+                              int32_t* wf_out, int32_t* c_out, void* stream) {
+    if (!h) return FAV_ERR_INVALID_ARG;
+    const fav_handle::LocTap& t = h->stage_tap;
+    const MapTapDims& d = h->stage;
+    return tap_get(h, "fav_get_stage_maps", kStageWords, t,
+                   {{stage_out, h->stage_no}, {s_out, t.S}, {n_out, t.n}, {hf_out, d.Hf}, {wf_out, d.Wf}, {c_out, d.C}}, out,
+                   (size_t)t.S * t.n * d.Hf * d.Wf * d.C * 2, stream);
+}
+
 fav_status fav_cam(fav_handle* h, const int32_t* classes, int32_t K, float* cam, fav_cam_record* rec, void* stream) {
     static_assert(sizeof(fav_cam_record) == 32, "fav_cam_record is 8 dwords");
     return map_head_on_last_call(h, "fav_cam", kMapWords, &fav_handle::map_tap, bad_cam_buffers(classes, cam, rec),
@@ -2744,14 +2814,25 @@ fav_status patch_prepare(const PatchWs& w, void* ws, const void* bank, int D, in
 // The head on a prepared workspace: the query kernel, a cell a block; per column chunk of the bank the GEMM into the slab (two
 // launches where an unpadded bank's part tile falls into the chunk) and the fold of the slab; the score kernel, a frame a
 // block.  Stream order makes reusing the slab safe.  The arguments have been checked (patch_map_error, knn_dims_error, the
-// pointers).  Returns the conv launcher's refusal, if any.
-const char* launch_patch(const void* maps, int S, int n, int Hf, int Wf, int C, const void* bank, int N, float threshold, const PatchWs& w,
-                         void* ws, bool padded_bank, float* dist, int32_t* row, fav_patch_record* rec, hipStream_t s) {
+// pointers).  radius < 0: the k-NN head's query kernel, as it stands; 0 .. 2: the caller asked for a site, the locally aware
+// query (patch_query_error has passed, maps is 16-byte aligned).  Returns the conv launcher's refusal, if any.
+void launch_patch_query(const void* maps, int S, int n, int Hf, int Wf, int C, int radius, void* q, int32_t* flags, hipStream_t s) {
+    PatchQueryParams p;
+    p.maps = (const uint16_t*)maps; p.q = (uint16_t*)q; p.flags = flags;
+    p.S = S; p.n = n; p.Hf = Hf; p.Wf = Wf; p.C = C; p.CS = patch_query_slice(Wf, C); p.inv_S = (float)(1.0 / S);
+    void (*const fn)(const PatchQueryParams) = radius == 0 ? patch_local_query_kernel<0, 4> : radius == 1 ? patch_local_query_kernel<1, 2>
+                                                                                                       : patch_local_query_kernel<2, 1>;
+    const size_t lds = (size_t)Wf * (p.CS + PQ_PAD) * 4;      // at most PQ_LDS_BYTES
+    hipLaunchKernelGGL(fn, dim3((unsigned)(n * Hf)), dim3(PQ_THREADS), lds, s, p);
+}
+const char* launch_patch(const void* maps, int S, int n, int Hf, int Wf, int C, int radius, const void* bank, int N, float threshold,
+                         const PatchWs& w, void* ws, bool padded_bank, float* dist, int32_t* row, fav_patch_record* rec, hipStream_t s) {
     const int HW = Hf * Wf, M = n * HW;
     KnnQueryParams qp;
     qp.feat = (const uint16_t*)maps; qp.q = (uint16_t*)((char*)ws + w.q); qp.flags = (int32_t*)((char*)ws + w.flags);
     qp.S = S; qp.n = M; qp.D = C; qp.inv_S = (float)(1.0 / S);
-    hipLaunchKernelGGL(knn_query_kernel, dim3((unsigned)M), dim3(KNN_THREADS), 0, s, qp);
+    if (radius < 0) hipLaunchKernelGGL(knn_query_kernel, dim3((unsigned)M), dim3(KNN_THREADS), 0, s, qp);
+    else launch_patch_query(maps, S, n, Hf, Wf, C, radius, qp.q, qp.flags, s);
     float* const slab = (float*)((char*)ws + w.slab);
     const float* const zero_bias = (const float*)((char*)ws + w.bias);
     const int whole = padded_bank ? w.Npad : (N & ~63);        // the rows the GEMM reads in place
@@ -2787,7 +2868,14 @@ extern "C++" std::string patch_handle_error(const fav_handle* h) {
 const char* patch_on_tap(const fav_handle* h, float* dist, int32_t* row, fav_patch_record* rec, hipStream_t s) {
     const fav_handle::PatchDev& o = h->patch;
     const PatchWs w = patch_workspace((long long)h->cfg.max_batch * o.Hf * o.Wf, o.D, o.N, o.chunk_rows, true);
-    return launch_patch(h->map_tap.buf, h->map_tap.S, h->map_tap.n, o.Hf, o.Wf, o.D, o.bank, o.N, o.threshold, w, o.ws, true, dist, row, rec, s);
+    const fav_handle::LocTap& t = o.stage > 0 ? h->stage_tap : h->map_tap;
+    return launch_patch(t.buf, t.S, t.n, o.Hf, o.Wf, o.D, o.radius, o.bank, o.N, o.threshold, w, o.ws, true, dist, row, rec, s);
+}
+// a bank at a site reads the stage tap, which must be at the bank's stage (empty: nothing to say - a plain bank, or no bank)
+extern "C++" std::string patch_stage_error(const fav_handle* h) {
+    const int tap = h->stage_tap.on ? h->stage_no : 0;
+    if (!h->patch_on || h->patch.stage == 0 || tap == h->patch.stage) return std::string();
+    return fmt("the bank is at stage %d, the stage tap at stage %d (0: off; fav_set_stage_tap)", h->patch.stage, tap);
 }
 }  // namespace
 
@@ -2808,7 +2896,9 @@ int32_t fav_patch_chunk_rows(int32_t cells_total, int32_t N, int32_t chunk_rows)
     return patch_chunk(cells_total, N, chunk_rows);
 }
 
-fav_status fav_set_patch_bank(fav_handle* h, const fav_patch_bank* b) {
+namespace {
+// fav_set_patch_bank (site NULL) and fav_set_patch_bank_at: `fn` is the name the messages carry
+fav_status set_patch_bank(fav_handle* h, const fav_patch_bank* b, const fav_patch_site* site, const char* fn) {
     if (!h) return FAV_ERR_INVALID_ARG;
     if (!b) {
         if (!h->patch_on) return FAV_OK;
@@ -2818,31 +2908,34 @@ fav_status fav_set_patch_bank(fav_handle* h, const fav_patch_bank* b) {
         return FAV_OK;
     }
     if (const char* why = map_tap_unsupported(h->cfg.arch, h->n_members, h->cfg.math_mode)) {
-        h->err = fmt("fav_set_patch_bank: %s", why);
+        h->err = fmt("%s: %s", fn, why);
         return FAV_ERR_UNSUPPORTED;
     }
-    const MapTapDims d = map_tap_dims(h->plan, h->cfg.max_batch);
-    std::string why = patch_bank_error(b, d.C);
+    std::string why = site ? patch_site_error(site) : std::string();
+    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
+    const MapTapDims d = site ? stage_tap_dims(h->plan, h->cfg.max_batch, site->stage) : map_tap_dims(h->plan, h->cfg.max_batch);
+    why = patch_bank_error(b, d.C);
     if (why.empty()) why = patch_map_error(h->cfg.max_batch, d.Hf, d.Wf);
-    if (!why.empty()) { h->err = fmt("fav_set_patch_bank: %s", why.c_str()); return FAV_ERR_INVALID_ARG; }
+    if (!why.empty()) { h->err = fmt("%s: %s", fn, why.c_str()); return FAV_ERR_INVALID_ARG; }
     const long long cells = (long long)h->cfg.max_batch * d.Hf * d.Wf;
     const PatchWs w = patch_workspace(cells, b->D, b->N, b->chunk_rows, true);
     if (w.bytes > PATCH_MAX_WS_BYTES) {
-        h->err = fmt("fav_set_patch_bank: the workspace of max_batch=%d frames of %d x %d cells against N=%d rows in chunks of %d is %zu bytes, "
-                     "above the limit of %zu", (int)h->cfg.max_batch, d.Hf, d.Wf, b->N, w.chunk, w.bytes, PATCH_MAX_WS_BYTES);
+        h->err = fmt("%s: the workspace of max_batch=%d frames of %d x %d cells against N=%d rows in chunks of %d is %zu bytes, "
+                     "above the limit of %zu", fn, (int)h->cfg.max_batch, d.Hf, d.Wf, b->N, w.chunk, w.bytes, PATCH_MAX_WS_BYTES);
         return FAV_ERR_INVALID_ARG;
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     // the new copy first: a failure leaves the handle as it was
     fav_handle::PatchDev nw;
     nw.D = b->D; nw.N = b->N; nw.chunk_rows = b->chunk_rows; nw.Hf = d.Hf; nw.Wf = d.Wf; nw.threshold = b->threshold;
+    if (site) { nw.stage = site->stage; nw.radius = site->radius; }
     const size_t row = (size_t)b->D * 2, bank_bytes = (size_t)b->N * row, pad_bytes = (size_t)(w.Npad - b->N) * row;
     bool ok = hipMalloc(&nw.bank, (size_t)w.Npad * row) == hipSuccess && hipMalloc(&nw.ws, w.bytes) == hipSuccess &&
               hipMemcpy(nw.bank, b->rows, bank_bytes, hipMemcpyHostToDevice) == hipSuccess &&
               (pad_bytes == 0 || hipMemset((char*)nw.bank + bank_bytes, 0, pad_bytes) == hipSuccess);
     ok = ok && patch_prepare(w, nw.ws, nw.bank, b->D, b->N, true, nullptr) == FAV_OK && hipStreamSynchronize(nullptr) == hipSuccess;
     fav_status st = FAV_OK;
-    if (!ok) { h->err = fmt("fav_set_patch_bank: cannot copy the bank to the device: %s", hipGetErrorString(hipGetLastError())); st = FAV_ERR_HIP; }
+    if (!ok) { h->err = fmt("%s: cannot copy the bank to the device: %s", fn, hipGetErrorString(hipGetLastError())); st = FAV_ERR_HIP; }
     if (st == FAV_OK && h->patch_on) st = wait_enqueued(h);
     if (st != FAV_OK) { free_patch(&nw); return st; }
     if (h->patch_on) free_patch(&h->patch);
@@ -2850,16 +2943,44 @@ fav_status fav_set_patch_bank(fav_handle* h, const fav_patch_bank* b) {
     h->patch_on = true;
     return FAV_OK;
 }
+// the tap the head reads, and its nouns; a stage mismatch is refused in front of the shared gate, naming both stages
+bool patch_at_site(const fav_handle* h) { return h && h->patch_on && h->patch.stage > 0; }
+fav_status patch_stage_gate(fav_handle* h, const char* fn) {
+    if (!h) return FAV_OK;
+    const std::string why = patch_stage_error(h);
+    if (why.empty()) return FAV_OK;
+    route_clear();
+    h->err = fmt("%s: %s", fn, why.c_str());
+    return FAV_ERR_INVALID_ARG;
+}
+}  // namespace
+
+fav_status fav_set_patch_bank(fav_handle* h, const fav_patch_bank* b) { return set_patch_bank(h, b, nullptr, "fav_set_patch_bank"); }
+
+fav_status fav_check_patch_site(const fav_patch_site* site, char* err, size_t err_cap) {
+    static_assert(sizeof(fav_patch_site) == 12, "fav_patch_site is 3 dwords");
+    return check_reply(patch_site_error(site), err, err_cap);
+}
+
+fav_status fav_set_patch_bank_at(fav_handle* h, const fav_patch_bank* b, const fav_patch_site* site) {
+    return set_patch_bank(h, b, site, site ? "fav_set_patch_bank_at" : "fav_set_patch_bank");
+}
 
 fav_status fav_patch(fav_handle* h, float* dist, int32_t* row, fav_patch_record* rec, void* stream) {
-    return map_head_on_last_call(h, "fav_patch", kMapWords, &fav_handle::map_tap, bad_patch_buffers(dist, row, rec),
+    if (fav_status st = patch_stage_gate(h, "fav_patch")) return st;
+    const bool at = patch_at_site(h);
+    return map_head_on_last_call(h, "fav_patch", at ? kStageWords : kMapWords, at ? &fav_handle::stage_tap : &fav_handle::map_tap,
+                                 bad_patch_buffers(dist, row, rec),
                                  [&] { return patch_handle_error(h); }, stream,
                                  [&](hipStream_t s) { return patch_on_tap(h, dist, row, rec, s); });
 }
 
 fav_status fav_classify_patch(fav_handle* h, const void* images, int32_t n, int32_t layout, int64_t first_index, int32_t* labels,
                               float* conf, uint8_t* fail, float* score, float* dist, int32_t* row, fav_patch_record* rec, void* stream) {
-    return classify_map_head(h, "fav_classify_patch", kMapWords, &fav_handle::map_tap, bad_patch_buffers(dist, row, rec),
+    if (fav_status st = patch_stage_gate(h, "fav_classify_patch")) return st;
+    const bool at = patch_at_site(h);
+    return classify_map_head(h, "fav_classify_patch", at ? kStageWords : kMapWords, at ? &fav_handle::stage_tap : &fav_handle::map_tap,
+                             bad_patch_buffers(dist, row, rec),
                              [&] { return patch_handle_error(h); }, images, n, layout, first_index, labels, conf, fail, score, stream,
                              [&](hipStream_t s) { return patch_on_tap(h, dist, row, rec, s); });
 }
@@ -3412,10 +3533,11 @@ fav_status fav_op_knn_score(const void* feat, int32_t S, int32_t n, int32_t D, c
     return op_done(fn, launch_knn(feat, S, n, D, bank, N, k, class_id, threshold, w, ws, false, records, s));
 }
 
-fav_status fav_op_patch_score(const void* maps, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C, const void* bank, int32_t N,
-                              int32_t chunk_rows, float threshold, void* ws, size_t ws_bytes, float* dist, int32_t* row,
-                              fav_patch_record* rec, void* stream) {
-    const char* fn = "fav_op_patch_score";
+namespace {
+// fav_op_patch_score (radius -1: the k-NN head's query kernel) and fav_op_patch_score_at (radius checked by the caller)
+fav_status op_patch_score(const char* fn, const void* maps, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C, const void* bank,
+                          int32_t N, int32_t chunk_rows, float threshold, int radius, void* ws, size_t ws_bytes, float* dist,
+                          int32_t* row, fav_patch_record* rec, void* stream) {
     route_clear();
     if (!maps || !bank || !ws || !dist || !rec) return op_rejected(fn, "null pointer");
     PatchWs w;
@@ -3432,7 +3554,37 @@ fav_status fav_op_patch_score(const void* maps, int32_t S, int32_t n, int32_t Hf
     if (!why.empty()) return op_rejected(fn, why.c_str());
     hipStream_t s = (hipStream_t)stream;
     if (patch_prepare(w, ws, bank, C, N, false, s) != FAV_OK) { g_create_error = fmt("%s: cannot prepare the workspace: %s", fn, hipGetErrorString(hipGetLastError())); return FAV_ERR_HIP; }
-    return op_done(fn, launch_patch(maps, S, n, Hf, Wf, C, bank, N, threshold, w, ws, false, dist, row, rec, s));
+    return op_done(fn, launch_patch(maps, S, n, Hf, Wf, C, radius, bank, N, threshold, w, ws, false, dist, row, rec, s));
+}
+}  // namespace
+
+fav_status fav_op_patch_score(const void* maps, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C, const void* bank, int32_t N,
+                              int32_t chunk_rows, float threshold, void* ws, size_t ws_bytes, float* dist, int32_t* row,
+                              fav_patch_record* rec, void* stream) {
+    return op_patch_score("fav_op_patch_score", maps, S, n, Hf, Wf, C, bank, N, chunk_rows, threshold, -1, ws, ws_bytes, dist, row, rec, stream);
+}
+
+fav_status fav_op_patch_score_at(const void* maps, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C, const void* bank, int32_t N,
+                                 int32_t chunk_rows, float threshold, int32_t radius, void* ws, size_t ws_bytes, float* dist,
+                                 int32_t* row, fav_patch_record* rec, void* stream) {
+    const char* fn = "fav_op_patch_score_at";
+    const std::string why = patch_radius_error(radius);
+    if (!why.empty()) { route_clear(); return op_rejected(fn, why.c_str()); }
+    if ((uintptr_t)maps & 15) { route_clear(); return op_rejected(fn, "maps_bf16 must be 16-byte aligned"); }
+    return op_patch_score(fn, maps, S, n, Hf, Wf, C, bank, N, chunk_rows, threshold, radius, ws, ws_bytes, dist, row, rec, stream);
+}
+
+fav_status fav_op_patch_query(const void* maps, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C, int32_t radius, void* q,
+                              int32_t* flags, void* stream) {
+    const char* fn = "fav_op_patch_query";
+    route_clear();
+    if (!maps || !q || !flags) return op_rejected(fn, "null pointer");
+    const std::string why = patch_query_error(S, n, Hf, Wf, C, radius);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    if (((uintptr_t)maps | (uintptr_t)q) & 15) return op_rejected(fn, "maps_bf16 and q_dev must be 16-byte aligned");
+    if ((uintptr_t)flags & 3) return op_rejected(fn, "flags_dev must be 4-byte aligned");
+    launch_patch_query(maps, S, n, Hf, Wf, C, radius, q, flags, (hipStream_t)stream);
+    return op_done(nullptr);
 }
 
 // ---- greedy coreset selection (fav_coreset.hpp) ----------------------------------

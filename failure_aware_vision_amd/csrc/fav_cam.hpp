@@ -62,6 +62,21 @@ inline MapTapDims map_tap_dims(const fav_plan::Plan& P, int max_batch) {
         }
     return d;
 }
+// ---- host: what the stage tap of a planned schedule holds for residual stage 1 .. 4: the output of the op the planner marked
+//      (Op::stage_out), copied behind its launch; S as above.  Stage 4 is the buffer the average pool reads, so its tap is the
+//      map tap's own copy, in front of the pool (op: the pool; the same bytes under every dropout policy).  op < 0: no such stage
+inline MapTapDims stage_tap_dims(const fav_plan::Plan& P, int max_batch, int stage) {
+    if (stage == 4) return map_tap_dims(P, max_batch);
+    MapTapDims d;
+    for (const fav_plan::Phase& p : P.phases)
+        for (int k = p.op_begin; k < p.op_end; ++k) {
+            const fav_plan::Op& o = P.ops[k];
+            if (stage < 1 || o.stage_out != stage) continue;
+            d.op = k; d.S = p.suffix ? P.T_eff : 1; d.Hf = o.Ho; d.Wf = o.Wo; d.C = o.Co;
+            d.bytes = (size_t)d.S * (size_t)max_batch * (size_t)o.Ho * o.Wo * o.Co * 2;
+        }
+    return d;
+}
 // the configurations the tap refuses, from the config alone (nullptr: none); the math mode makes no difference to it
 inline const char* map_tap_unsupported(int arch, int n_members, int /*math_mode*/) {
     if (arch == 2 || arch == 3) return "a ViT arch has no pooled convolutional map";

@@ -197,4 +197,202 @@ __global__ __launch_bounds__(PATCH_SCORE_THREADS) void patch_score_kernel(const 
     }
 }
 
+// ---- locally aware patch features (fav_op_patch_query; the contract beside fav_patch_site in fav.h) ------
+//   patch_local_query_kernel<R> : one block of 256 threads a FRAME ROW (blockIdx.x = i * Hf + y), radius R.  Per channel slice
+//                        of cs channels: a lane owns (cell x, eight channels) units and reads them with 16-byte loads - the
+//                        2R + 1 rows of a unit, UB units at once, so four to six loads are in flight a lane - adds the samples,
+//                        then the rows, and leaves v[x][j] in LDS (fp32, a row of the slice plus sixteen spare floats a cell,
+//                        which break the bank conflicts of the chains and later hold the chains' sums and 1 / |a|).  A thread a
+//                        (cell, chain) then runs the sixteen strided chains of the squared norm over a = the 2R + 1 neighbours
+//                        of v; the chains carry on over the slices in ascending j, so the bits do not depend on the slicing.
+//                        A thread a cell adds the sixteen sums up, writes the flag and 1 / |a|; the units recompute a (the same
+//                        additions, so the same bits), scale, round and store eight bf16 as one 16-byte vector store.  With
+//                        more than one slice the second sweep reads the rows again (from cache).  A map row is read by the
+//                        2R + 1 blocks around it, from HBM by the first.  No atomics, no block waits for another.
+constexpr int PQ_THREADS = 256, PQ_PAD = 16, PQ_MAX_RADIUS = 2;
+constexpr int PQ_LDS_BYTES = 65536;                              // what one block may take: no opt-in, two blocks a CU
+constexpr int PQ_MAX_CHAINS = PATCH_MAX_SIDE * 16 / PQ_THREADS;  // (cell, chain) pairs a thread may own
+
+// the channels of one slice for a map Wf wide: the most whose row of v (plus the spare floats) fits, a multiple of 16
+inline int patch_query_slice(int Wf, int C) { return std::min(C, (PQ_LDS_BYTES / 4 / Wf - PQ_PAD) & ~15); }
+
+// ---- host: the one place the op's ranges live (fav_op_patch_query, fav_op_patch_score_at, fav_check_patch_site's radius)
+inline std::string patch_radius_error(int radius) {
+    if (radius < 0 || radius > PQ_MAX_RADIUS) return fmt("radius=%d outside [0, %d]", radius, PQ_MAX_RADIUS);
+    return std::string();
+}
+inline std::string patch_query_error(int S, int n, int Hf, int Wf, int C, int radius) {
+    if (S < 1 || S > KNN_MAX_S) return fmt("S=%d outside [1, %d]", S, KNN_MAX_S);
+    const std::string map = patch_map_error(n, Hf, Wf);
+    if (!map.empty()) return map;
+    if (C < 64 || C > KNN_MAX_D || C % 64 != 0) return fmt("C=%d is not a multiple of 64 in [64, %d]", C, KNN_MAX_D);
+    return patch_radius_error(radius);
+}
+inline std::string patch_site_error(const fav_patch_site* s) {
+    if (!s) return "site is NULL";
+    if (s->struct_size != sizeof(fav_patch_site)) return fmt("struct_size=%u is not sizeof(fav_patch_site)=%zu", s->struct_size, sizeof(fav_patch_site));
+    if (s->stage < 1 || s->stage > 4) return fmt("stage=%d outside [1, 4]", s->stage);
+    return patch_radius_error(s->radius);
+}
+
+struct PatchQueryParams {
+    const uint16_t* maps;        // [S][n][Hf * Wf][C] bf16, 16-byte aligned
+    uint16_t* q;                 // [n * Hf * Wf][C] bf16, 16-byte aligned
+    int32_t* flags;              // [n * Hf * Wf]
+    int S, n, Hf, Wf, C, CS;     // CS: patch_query_slice(Wf, C)
+    float inv_S;
+};
+
+// a[0 .. 7] of cell x at column j of the slice: +0 plus the 2R + 1 neighbours of v in ascending dx, those outside skipped
+template <int R>
+__device__ __forceinline__ void pq_neighbours8(const float* v_s, int ld, int Wf, int x, int j, float* a) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = 0.f;
+#pragma unroll
+    for (int d = -R; d <= R; ++d) {
+        const int xx = x + d;
+        if (xx < 0 || xx >= Wf) continue;
+        const float4 lo = *(const float4*)(v_s + xx * ld + j), hi = *(const float4*)(v_s + xx * ld + j + 4);
+        const float f[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = __fadd_rn(a[e], f[e]);
+    }
+}
+
+// steps 1 and 2 for the slice [c0, c0 + cs) of frame i, row y: v[x][j] to LDS
+template <int R, int UB>
+__device__ __forceinline__ void pq_fill(const PatchQueryParams& p, float* v_s, int ld, int i, int y, int c0, int cs) {
+    constexpr int NR = 2 * R + 1;
+    const int upc = cs >> 3, units = p.Wf * upc;
+    const size_t frame = (size_t)p.Hf * p.Wf * p.C, sample = (size_t)p.n * frame;
+    const long long row = (long long)p.Wf * p.C;
+    for (int u0 = threadIdx.x; u0 < units; u0 += PQ_THREADS * UB) {
+        float acc[UB][NR][8];
+        const uint16_t* src[UB];
+        int at[UB];
+#pragma unroll
+        for (int k = 0; k < UB; ++k) {
+            const int u = u0 + k * PQ_THREADS, x = u / upc, j = (u - x * upc) * 8;
+            at[k] = u < units ? x * ld + j : -1;
+            src[k] = p.maps + (size_t)i * frame + ((size_t)y * p.Wf + (u < units ? x : 0)) * p.C + c0 + (u < units ? j : 0);
+#pragma unroll
+            for (int d = 0; d < NR; ++d)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[k][d][e] = 0.f;
+        }
+        for (int s = 0; s < p.S; ++s) {
+            uint4 w[UB][NR];
+#pragma unroll
+            for (int k = 0; k < UB; ++k)
+#pragma unroll
+                for (int d = 0; d < NR; ++d) {
+                    const int yy = y + d - R;
+                    w[k][d] = make_uint4(0u, 0u, 0u, 0u);
+                    if (at[k] >= 0 && yy >= 0 && yy < p.Hf) w[k][d] = *(const uint4*)(src[k] + ((long long)s * (long long)sample + (long long)(d - R) * row));
+                }
+#pragma unroll
+            for (int k = 0; k < UB; ++k)
+#pragma unroll
+                for (int d = 0; d < NR; ++d) {
+                    float f[8];
+                    cam_unpack8(w[k][d], f);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[k][d][e] = __fadd_rn(acc[k][d][e], f[e]);
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < UB; ++k) {
+            if (at[k] < 0) continue;
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = 0.f;
+#pragma unroll
+            for (int d = 0; d < NR; ++d) {
+                const int yy = y + d - R;
+                if (yy < 0 || yy >= p.Hf) continue;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = __fadd_rn(v[e], __fmul_rn(acc[k][d][e], p.inv_S));
+            }
+            *(float4*)(v_s + at[k]) = make_float4(v[0], v[1], v[2], v[3]);
+            *(float4*)(v_s + at[k] + 4) = make_float4(v[4], v[5], v[6], v[7]);
+        }
+    }
+}
+
+// step 4's last part for the slice [c0, c0 + cs): q = bf16(a * inv), a zero row for a degenerate cell (inv == 0)
+template <int R>
+__device__ __forceinline__ void pq_store(const PatchQueryParams& p, const float* v_s, int ld, int i, int y, int c0, int cs) {
+    const int upc = cs >> 3, units = p.Wf * upc;
+    for (int u = threadIdx.x; u < units; u += PQ_THREADS) {
+        const int x = u / upc, j = (u - x * upc) * 8;
+        const float inv = v_s[x * ld + p.CS];
+        float a[8];
+        pq_neighbours8<R>(v_s, ld, p.Wf, x, j, a);
+        uint32_t o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t lo = inv == 0.f ? 0u : (uint32_t)f32_to_bf16_bits(__fmul_rn(a[2 * e], inv));
+            const uint32_t hi = inv == 0.f ? 0u : (uint32_t)f32_to_bf16_bits(__fmul_rn(a[2 * e + 1], inv));
+            o[e] = (lo & 0xFFFFu) | (hi << 16);
+        }
+        *(uint4*)(p.q + (((size_t)i * p.Hf + y) * p.Wf + x) * p.C + c0 + j) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+template <int R, int UB>
+__global__ __launch_bounds__(PQ_THREADS) void patch_local_query_kernel(const PatchQueryParams p) {
+    extern __shared__ float4 pq_lds[];
+    float* const v_s = (float*)pq_lds;
+    const int tid = threadIdx.x, i = blockIdx.x / p.Hf, y = blockIdx.x - i * p.Hf;
+    const int ld = p.CS + PQ_PAD, chains = p.Wf * 16;
+    const bool one_slice = p.CS == p.C;
+    float part[PQ_MAX_CHAINS];
+#pragma unroll
+    for (int k = 0; k < PQ_MAX_CHAINS; ++k) part[k] = 0.f;
+    for (int c0 = 0; c0 < p.C; c0 += p.CS) {
+        const int cs = min(p.CS, p.C - c0);
+        if (c0 > 0) __syncthreads();                           // the chains of the slice before have read v
+        pq_fill<R, UB>(p, v_s, ld, i, y, c0, cs);
+        __syncthreads();
+        // the sixteen chains of a cell, chain l over j = l, l + 16, ..: they carry on from slice to slice
+#pragma unroll
+        for (int k = 0; k < PQ_MAX_CHAINS; ++k) {
+            const int ch = tid + k * PQ_THREADS, x = ch >> 4;
+            float acc = part[k];
+            for (int j = ch < chains ? (ch & 15) : cs; j < cs; j += 16) {
+                float a = 0.f;
+#pragma unroll
+                for (int d = -R; d <= R; ++d)
+                    if (x + d >= 0 && x + d < p.Wf) a = __fadd_rn(a, v_s[(x + d) * ld + j]);
+                acc = __fadd_rn(acc, __fmul_rn(a, a));
+            }
+            part[k] = acc;
+        }
+    }
+    // the spare floats of cell x take its sixteen sums (nobody reads them as v: a slice ends in front of them)
+#pragma unroll
+    for (int k = 0; k < PQ_MAX_CHAINS; ++k) {
+        const int ch = tid + k * PQ_THREADS;
+        if (ch < chains) v_s[(ch >> 4) * ld + p.CS + (ch & 15)] = part[k];
+    }
+    __syncthreads();
+    for (int x = tid; x < p.Wf; x += PQ_THREADS) {
+        float* const sp = v_s + x * ld + p.CS;
+        float ss = sp[0];
+        for (int l = 1; l < 16; ++l) ss = __fadd_rn(ss, sp[l]);
+        const bool ok = ss > 0.f && ss < INFINITY;
+        sp[0] = ok ? __fdiv_rn(1.0f, fav_sqrtf(ss)) : 0.f;      // as knn_query_kernel; never 0 for a cell that is ok
+        p.flags[((size_t)i * p.Hf + y) * p.Wf + x] = ok ? 0 : 1;
+    }
+    __syncthreads();
+    if (one_slice) { pq_store<R>(p, v_s, ld, i, y, 0, p.C); return; }
+    for (int c0 = 0; c0 < p.C; c0 += p.CS) {
+        const int cs = min(p.CS, p.C - c0);
+        if (c0 > 0) __syncthreads();
+        pq_fill<R, UB>(p, v_s, ld, i, y, c0, cs);
+        __syncthreads();
+        pq_store<R>(p, v_s, ld, i, y, c0, cs);
+    }
+}
+
 }  // namespace fav

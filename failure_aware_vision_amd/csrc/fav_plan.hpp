@@ -62,6 +62,7 @@ struct Op {
     int site = -1;                     // dropout site fused into this op
     int res_entry = 0;                 // OP_TAIL: the residual is the cached prefix output under the entry dropout (RESE)
     int skip_y = 0;                    // OP_ENTRY_REDUCE: the dropped copies are not stored (the next tail recomputes them)
+    int stage_out = 0;                 // 1 .. 4: `out` is the output of that residual stage's last block (the stage tap's); 0: not
     long long in_elems = 0, out_elems = 0;  // per frame
 };
 
@@ -278,14 +279,16 @@ struct ResNetWalk {
         H = A.imagenet_stem ? Hp : Ho; W = A.imagenet_stem ? Wp : Wo;
     }
 
-    // residual block b: `pl` planes, 3x3 stride `stride`; next_pl: the planes of the block behind it (0: none)
-    void block(int b, int pl, int stride, int next_pl) {
+    // residual block b: `pl` planes, 3x3 stride `stride`; next_pl: the planes of the block behind it (0: none); stage_end:
+    // the residual stage (1 .. 4) this block is the last of, else 0
+    void block(int b, int pl, int stride, int next_pl, int stage_end) {
         if (b == regroup) low_res_from_here();
         const int Hn = conv_out(H, 3, stride, 1), Wn = conv_out(W, 3, stride, 1), exp = A.bottleneck ? 4 : 1;
         const bool ds = stride != 1 || C != pl * exp;       // projection shortcut
         if (A.bottleneck) bottleneck(b, pl, stride, ds, next_pl, Hn, Wn);
         else basic(pl, stride, ds, Hn, Wn);
         P.ops.back().site = site_at(b);
+        P.ops.back().stage_out = stage_end;
         entry_reduce = -1;
         H = Hn; W = Wn; C = pl * exp;
     }
@@ -406,7 +409,7 @@ inline fav_status plan_resnet(const fav_config& c, int n_members, bool no_fuse, 
     for (int st = 0, b = 0; st < 4; ++st)
         for (int bi = 0; bi < A.depths[st]; ++bi, ++b) {
             const int next_pl = bi + 1 < A.depths[st] ? A.planes[st] : (st < 3 ? A.planes[st + 1] : 0);
-            w.block(b, A.planes[st], (bi == 0 && st > 0) ? 2 : 1, next_pl);
+            w.block(b, A.planes[st], (bi == 0 && st > 0) ? 2 : 1, next_pl, bi + 1 == A.depths[st] ? st + 1 : 0);
             if (b == P.first_site) w.entry(A.bottleneck ? next_pl : 0);
         }
     w.pool_fc();

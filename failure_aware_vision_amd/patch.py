@@ -35,13 +35,17 @@ class PatchBank:
     library's rule (nothing in a result depends on it); ``grid``: the (hf, wf) map the rows were cut from, or None;
     ``n_dropped``: the zero and non-finite cells ``build_patch_bank`` left out; ``selection``: the
     ``coreset.CoresetSelection`` that chose the rows (``select="coreset"``; its indices count the cells that were not dropped),
-    else None; it is not saved."""
+    else None; it is not saved; ``stage``, ``radius``: the site the rows were cut at (fav_patch_site) - the
+    residual stage 1 .. 4 whose map the stage tap holds, None: the last map, through the map tap - and the half width 0 .. 2
+    of the neighbourhood every cell was aggregated over (``aggregate_cells``).  Both are saved when they are not the defaults."""
     rows: np.ndarray
     threshold: float = math.inf
     chunk_rows: int = 0
     grid: tuple | None = None
     n_dropped: int = 0
     selection: object | None = None
+    stage: int | None = None
+    radius: int = 0
 
     def __post_init__(self):
         if np.asarray(self.rows).dtype != np.uint16:
@@ -54,6 +58,10 @@ class PatchBank:
             object.__setattr__(self, "grid", (int(self.grid[0]), int(self.grid[1])))
         if self.rows.ndim != 2:
             raise ValueError("rows is a matrix [N, D]")
+        object.__setattr__(self, "stage", None if self.stage is None else int(self.stage))
+        object.__setattr__(self, "radius", int(self.radius))
+        if self.stage is None and self.radius != 0:
+            raise ValueError("a neighbourhood radius needs a stage (stage=4 is the last map)")
 
     @property
     def N(self) -> int:
@@ -68,10 +76,13 @@ class PatchBank:
 
     def take(self, indices) -> "PatchBank":
         """The bank of the rows ``indices`` (in that order); ``threshold``, ``chunk_rows``, ``grid`` and ``n_dropped`` are kept."""
-        return PatchBank(self.rows[_take_indices(indices, self.N)], self.threshold, self.chunk_rows, self.grid, self.n_dropped)
+        return PatchBank(self.rows[_take_indices(indices, self.N)], self.threshold, self.chunk_rows, self.grid, self.n_dropped,
+                         stage=self.stage, radius=self.radius)
 
     def save(self, path):
         extra = {} if self.grid is None else {"grid": np.asarray(self.grid, np.int32)}
+        if self.stage is not None:                     # a plain bank's file keeps the keys it always had
+            extra.update(stage=np.int32(self.stage), radius=np.int32(self.radius))
         np.savez(path, rows=self.rows, threshold=np.float32(self.threshold), chunk_rows=np.int32(self.chunk_rows),
                  n_dropped=np.int64(self.n_dropped), **extra)
 
@@ -79,7 +90,18 @@ class PatchBank:
     def load(cls, path) -> "PatchBank":
         with np.load(path) as z:
             grid = tuple(int(v) for v in z["grid"]) if "grid" in z.files else None
-            return cls(z["rows"], float(z["threshold"]), int(z["chunk_rows"]), grid, int(z["n_dropped"]))
+            stage = int(z["stage"]) if "stage" in z.files else None
+            radius = int(z["radius"]) if "radius" in z.files else 0
+            return cls(z["rows"], float(z["threshold"]), int(z["chunk_rows"]), grid, int(z["n_dropped"]), stage=stage, radius=radius)
+
+    def site_to_c(self):
+        """The fav_patch_site of this bank, None for a plain bank (``stage`` None)."""
+        if self.stage is None:
+            return None
+        s = _lib.FavPatchSite()
+        s.struct_size = C.sizeof(_lib.FavPatchSite)
+        s.stage, s.radius = self.stage, self.radius
+        return s
 
     def to_c(self) -> _lib.FavPatchBank:
         """The fav_patch_bank that points into this bank's rows (which it keeps alive)."""
@@ -107,10 +129,44 @@ def _maps_f64(maps) -> np.ndarray:
     return a.astype(np.float64)
 
 
-def cell_rows(maps):
+def aggregate_cells(maps, radius: int) -> np.ndarray:
+    """maps [S, n, Hf, Wf, C] (bf16 torch tensor, uint16 bits or floats) -> float32 [n, Hf, Wf, C]: steps 1 to 3 of the
+    contract beside fav_patch_site in their order, one float32 rounding an operation - the mean over the samples (the sum in
+    sample order, times float32(1 / S)), the sum down the 2 radius + 1 rows around a cell, then along the 2 radius + 1 columns,
+    rows and columns outside the map skipped.  No division by the count: the normalisation that follows removes it."""
+    radius = int(radius)
+    if radius < 0 or radius > 2:
+        raise ValueError(f"radius={radius} outside [0, 2]")
+    x = _maps_f64(maps).astype(np.float32)
+    if x.ndim != 5 or x.shape[0] < 1:
+        raise ValueError(f"maps must be [S, n, Hf, Wf, C], got shape {x.shape}")
+    S, n, Hf, Wf, Cc = x.shape
+    with np.errstate(all="ignore"):
+        m = np.zeros(x.shape[1:], np.float32)
+        for s in range(S):
+            m = m + x[s]
+        m = m * np.float32(1.0 / S)
+        v = np.zeros_like(m)
+        for d in range(-radius, radius + 1):
+            lo, hi = max(0, -d), min(Hf, Hf - d)                 # the rows y with y + d inside the map
+            if lo < hi:
+                v[:, lo:hi] = v[:, lo:hi] + m[:, lo + d:hi + d]
+        a = np.zeros_like(m)
+        for d in range(-radius, radius + 1):
+            lo, hi = max(0, -d), min(Wf, Wf - d)
+            if lo < hi:
+                a[:, :, lo:hi] = a[:, :, lo:hi] + v[:, :, lo + d:hi + d]
+    assert a.dtype == np.float32
+    return a
+
+
+def cell_rows(maps, radius: int | None = None):
     """maps [S, n, HW, C] or [S, n, Hf, Wf, C] -> (rows uint16 [n * HW, C], ok bool [n * HW], grid or None): the mean over the
     samples of every cell, divided by its Euclidean norm in float64, rounded to bf16 (nearest even).  ``ok`` is False for a
-    cell that has no direction - a zero cell, a non-finite value - whose row is all zero."""
+    cell that has no direction - a zero cell, a non-finite value - whose row is all zero.  ``radius`` (not None; the maps with
+    both map axes): every cell is first replaced by ``aggregate_cells`` of its neighbourhood."""
+    if radius is not None:
+        maps = aggregate_cells(maps, radius)[None]
     x = _maps_f64(maps)
     if x.ndim not in (4, 5) or x.shape[0] < 1:
         raise ValueError(f"maps must be [S, n, HW, C] or [S, n, Hf, Wf, C], got shape {x.shape}")
@@ -124,7 +180,7 @@ def cell_rows(maps):
 
 
 def bank_from_rows(rows, ok, max_rows: int | None = None, seed: int = 0, grid=None, threshold: float = math.inf,
-                   chunk_rows: int = 0, select: str = "random", device=None) -> PatchBank:
+                   chunk_rows: int = 0, select: str = "random", device=None, stage=None, radius: int = 0) -> PatchBank:
     """What ``cell_rows`` made, of one batch or of several concatenated -> the bank: the cells without a direction dropped
     and counted, then ``max_rows`` of the rest kept in their original order, chosen as ``ood.build_knn_bank`` chooses them:
     ``select="random"`` draws them without replacement by ``np.random.default_rng(seed)``; ``select="coreset"`` picks them by
@@ -139,10 +195,10 @@ def bank_from_rows(rows, ok, max_rows: int | None = None, seed: int = 0, grid=No
         raise ValueError("no cell has a direction: every one is zero or non-finite")
     if select == "coreset" and _subsample_count(kept.shape[0], max_rows) is not None:
         selection = select_coreset(kept, int(max_rows), seed, device=device)
-        full = PatchBank(kept, threshold, chunk_rows, grid, int((~ok).sum()))
+        full = PatchBank(kept, threshold, chunk_rows, grid, int((~ok).sum()), stage=stage, radius=radius)
         return dataclasses.replace(full.take(selection.indices), selection=selection)
     kept, _ = _subsample(kept, max_rows, seed)
-    return PatchBank(kept, threshold, chunk_rows, grid, int((~ok).sum()))
+    return PatchBank(kept, threshold, chunk_rows, grid, int((~ok).sum()), stage=stage, radius=radius)
 
 
 def build_patch_bank(maps, max_rows: int | None = None, seed: int = 0, **kw) -> PatchBank:

@@ -493,6 +493,28 @@ fav_status fav_get_maps(fav_handle* h, void* out_dev, int32_t* s_out, int32_t* n
  * FAV_ERR_INVALID_ARG for a configuration the planner refuses; err (may be NULL) receives the message. */
 fav_status fav_map_tap_info(const fav_config* cfg, size_t* bytes, int32_t* s_map, int32_t* hf, int32_t* wf, int32_t* c,
                             char* err, size_t err_cap);
+/* The STAGE TAP: the map tap's sibling for a mid-level map.  stage is the residual stage 1 .. 4
+ * (torchvision's layer1 .. layer4) on both ResNet arches; the tap holds the output of that stage's LAST block - what the next
+ * stage reads, behind that block's dropout when the block's own launch draws it - as bf16 [S][n][Hf*Wf][C], indexed like the
+ * map tap: every pass copies cn frames device to device BEHIND the launch that writes the block's output, at the chunk's
+ * virtual-frame offset.  S = the MC-Dropout samples when that launch runs once a sample, 1 when it runs once a frame (times
+ * the views).  When the block is the FIRST dropout site, its mask falls on the cached tensor in the next launch: the tap then
+ * holds the output in front of it, S = 1, as the map tap does at the pooled-feature site.  Stage 4 is the buffer the average
+ * pool reads: its tap is the map tap's own copy, the same bytes under every policy.
+ * One stage at a time.  stage 0 turns the tap off and frees the buffer (never refused); another stage than the one in force
+ * waits for the work enqueued on the handle and reallocates.  The budget is fav_set_map_tap's (0: 2 GiB).  Refused:
+ * FAV_ERR_UNSUPPORTED a ViT arch and a deep-ensemble handle, as fav_set_map_tap; FAV_ERR_INVALID_ARG a stage outside [0, 4], a
+ * buffer above the budget, and a stage whose map the patch head cannot take (more than 1024 cells or a side above 256: stage 1
+ * of a 224 x 224 frame has 3136), the message carrying the numbers.  A refused call leaves the tap as it was.  With the tap
+ * off nothing is enqueued for it; the tap changes no result and is independent of the map tap and the feature tap. */
+fav_status fav_set_stage_tap(fav_handle* h, int32_t stage, size_t max_bytes);
+/* fav_get_maps for the stage tap; *stage_out the stage in force.  Every size pointer and out_dev may be NULL. */
+fav_status fav_get_stage_maps(fav_handle* h, void* out_dev, int32_t* stage_out, int32_t* s_out, int32_t* n_out, int32_t* hf_out,
+                              int32_t* wf_out, int32_t* c_out, void* hip_stream);
+/* Host only, no device: fav_map_tap_info for stage 1 .. 4 (FAV_ERR_INVALID_ARG outside).  It reports every stage's geometry,
+ * also one fav_set_stage_tap would refuse for its cell count. */
+fav_status fav_stage_tap_info(const fav_config* cfg, int32_t stage, size_t* bytes, int32_t* s_map, int32_t* hf, int32_t* wf,
+                              int32_t* c, char* err, size_t err_cap);
 
 /* One (frame, class) map's summary, 32 bytes, 8-byte aligned.  For frame i and class c = classes[i][k], with x the maps
  * [S][n][HW][C] and w the weight rows, everything fp32, every product and every sum rounded on its own (no FMA contraction,
@@ -800,6 +822,33 @@ fav_status fav_patch(fav_handle* h, float* dist_dev, int32_t* row_dev, fav_patch
 fav_status fav_classify_patch(fav_handle* h, const void* images_dev, int32_t n, int32_t layout, int64_t first_image_index,
                               int32_t* labels_dev, float* conf_dev, uint8_t* fail_dev, float* score_dev, float* dist_dev,
                               int32_t* row_dev, fav_patch_record* rec_dev, void* hip_stream);
+
+/* ---- Mid-level patch maps (the rest of PatchCore).  The last map of a 224 x 224 frame has 7 x 7
+ * cells of 32 x 32 pixels; PatchCore reads layer2 / layer3 instead (28 x 28 and 14 x 14 cells) and replaces every cell by the
+ * aggregate of its neighbourhood before it is normalised.  A SITE says where a bank's rows come from and where the head reads:
+ * stage, the residual stage 1 .. 4 whose output the STAGE TAP (above, beside the map tap) holds, and radius, the half width of
+ * the neighbourhood: 0 (the cell alone), 1 (3 x 3) or 2 (5 x 5).
+ * The locally aware query of a site replaces step 1 of fav_patch_record.  With x the maps [S][n][Hf*Wf][C], r = radius, for
+ * frame i, cell (y, x), channel j, everything fp32, every operation rounded on its own, no re-association:
+ *   1. m[y][x][j] = (+0 + x[0] + x[1] + .. + x[S-1]) * (float)(1.0 / S), s ascending: step 1 of fav_knn_record
+ *   2. v[y][x][j] = +0 + m[y-r][x][j] + .. + m[y+r][x][j], dy ascending; a row outside [0, Hf) is SKIPPED, not added as zero
+ *   3. a[y][x][j] = +0 + v[y][x-r][j] + .. + v[y][x+r][j], dx ascending; a column outside [0, Wf) is skipped.  No division by
+ *      the count: the normalisation removes any positive scale.  A neighbourhood never crosses a frame
+ *   4. steps 2, 3 and 7 of fav_knn_record on a: the sixteen strided chains of the squared norm (chain l over j = l, l + 16, ..),
+ *      their sum in index order, fav_sqrtf, the correctly rounded reciprocal, q = bf16(a * inv); a cell whose ss is 0 or not
+ *      finite is DEGENERATE: flag 1 and a zero row of q.  A zero cell with a non-zero neighbour is not degenerate at r >= 1
+ * At radius 0 this is the k-NN head's query bit for bit (+0 + m is m, and m is never -0).  Only the algebra and the bits are
+ * verified here, on synthetic checkpoints; whether mid-level maps localise better is a property of trained weights. */
+typedef struct fav_patch_site { uint32_t struct_size; int32_t stage, radius; } fav_patch_site;   /* 12 bytes */
+/* Host only, no device: struct_size == sizeof(fav_patch_site), stage in [1, 4], radius in [0, 2]; the message names the field. */
+fav_status fav_check_patch_site(const fav_patch_site* site, char* err, size_t err_cap);
+/* fav_set_patch_bank at a site.  site == NULL: fav_set_patch_bank itself, byte for byte (the map tap, the k-NN head's query
+ * kernel).  With a site: D is checked against the STAGE's channel count, Hf, Wf and the workspace come from the stage's map (as
+ * fav_stage_tap_info reports it; the 1 GiB limit and its message stay), fav_patch and fav_classify_patch then read the STAGE
+ * TAP - which must be on and at that stage, FAV_ERR_INVALID_ARG with a message naming both stages otherwise - run
+ * fav_op_patch_query with the site's radius and write dist / row as [n][Hf*Wf] of that stage.  Records, fold and score kernel
+ * are unchanged.  A site {4, 0} gives the records of the plain bank.  The taps are not touched. */
+fav_status fav_set_patch_bank_at(fav_handle* h, const fav_patch_bank* bank, const fav_patch_site* site);
 
 /* ---- Greedy coreset selection (the k-centre selection of PatchCore, Roth et al. 2022).  WHICH
  * rows a patch bank or a k-NN bank holds: a uniform draw keeps rows in proportion to how often they occur, so the rare
@@ -1288,6 +1337,23 @@ int32_t fav_patch_chunk_rows(int32_t cells_total, int32_t N, int32_t chunk_rows)
 fav_status fav_op_patch_score(const void* maps_bf16, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C,
                               const void* bank_dev, int32_t N, int32_t chunk_rows, float threshold, void* ws_dev,
                               size_t ws_bytes, float* dist_dev, int32_t* row_dev, fav_patch_record* rec_dev, void* hip_stream);
+/* fav_op_patch_score with one more argument, radius in [0, 2]: step 1 of fav_patch_record is then the locally aware query
+ * defined beside fav_patch_site - fav_op_patch_query into the workspace - in place of the k-NN head's query kernel; everything
+ * behind it is unchanged.  maps_bf16 must be 16-byte aligned here.  At radius 0 dist, row and rec are fav_op_patch_score's. */
+fav_status fav_op_patch_score_at(const void* maps_bf16, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C,
+                                 const void* bank_dev, int32_t N, int32_t chunk_rows, float threshold, int32_t radius,
+                                 void* ws_dev, size_t ws_bytes, float* dist_dev, int32_t* row_dev, fav_patch_record* rec_dev,
+                                 void* hip_stream);
+/* ---- The locally aware query defined beside fav_patch_site, on device arrays: maps_bf16 [S][n][Hf*Wf][C] bf16 and q_dev bf16
+ * [n*Hf*Wf][C] (both 16-byte aligned), flags_dev int32 [n*Hf*Wf].  One launch of patch_local_query_kernel, a block of 256
+ * threads a frame row: 16-byte loads, several in flight a lane; a map row is read by the 2 radius + 1 blocks around it, from
+ * HBM by the first of them; where a row of C channels does not fit 64 KB of LDS the block works through channel slices and the
+ * sixteen chains carry on from slice to slice.  Vector stores only, no atomics, no block waits for another, no allocation, no
+ * synchronisation.  A refused call (FAV_ERR_INVALID_ARG: a NULL pointer, a misaligned maps_bf16, q_dev or flags_dev, S outside
+ * [1, 4096], n < 1, Hf*Wf outside [1, 1024] or a side above 256, n*Hf*Wf above 2^31 - 1, C not a multiple of 64 in [64, 4096],
+ * radius outside [0, 2]) launches nothing and leaves a message that names the function in fav_last_error(NULL). */
+fav_status fav_op_patch_query(const void* maps_bf16, int32_t S, int32_t n, int32_t Hf, int32_t Wf, int32_t C,
+                              int32_t radius, void* q_dev, int32_t* flags_dev, void* hip_stream);
 
 /* ---- The selection defined beside fav_check_coreset, on device arrays: rows_bf16_dev [N][D] bf16, order_dev int32 [M],
  * radius_dev fp32 [M + 1] (all three 16-byte aligned), ws_dev a workspace of at least fav_coreset_workspace_bytes(N, D, M) bytes
