@@ -11,7 +11,8 @@ from .calibration import (Calibration, fit_temperature, reliability, risk_covera
                           unpack_cells)
 from .corrupt import CORRUPTIONS, SEVERITY, Corruptor  # noqa: F401
 from .distributed import classify_sharded, shard_range  # noqa: F401
-from . import cam, coreset, faithfulness, ood, patch, robustness, rollout, synth, views, weights  # noqa: F401
+from . import autoencoder, cam, coreset, faithfulness, ood, patch, robustness, rollout, synth, views, weights  # noqa: F401
+from .autoencoder import Autoencoder, blob_from_state_dict, make_synthetic_ae, torch_module, unpack_ae_records  # noqa: F401
 from .coreset import CoresetSelection, select_coreset  # noqa: F401
 from .patch import PatchBank, build_patch_bank, unpack_patch_records  # noqa: F401
 from .cam import box_to_pixels, evidence_share, unpack_cam_records  # noqa: F401

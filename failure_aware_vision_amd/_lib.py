@@ -208,6 +208,19 @@ class FavRiseRecord(C.Structure):
                 ("floor", C.c_float), ("p_mean", C.c_float), ("n_above", C.c_int32), ("box", C.c_int32)]
 
 
+class FavAeConfig(C.Structure):
+    """fav_ae_config: the autoencoder sensor's frame size, level count, batch and cell (24 bytes)."""
+    _fields_ = [("struct_size", C.c_uint32), ("in_h", C.c_int32), ("in_w", C.c_int32), ("levels", C.c_int32),
+                ("max_batch", C.c_int32), ("cell", C.c_int32)]
+
+
+class FavAeRecord(C.Structure):
+    """fav_ae_record: one 32-byte summary per frame (autoencoder.unpack_ae_records reads it as int32[..., 8]); peak and floor
+    stand where FavCamRecord has them."""
+    _fields_ = [("sse_lo", C.c_uint32), ("mse", C.c_float), ("peak", C.c_float), ("peak_cell", C.c_int32),
+                ("floor", C.c_float), ("sse_hi", C.c_uint32), ("n_above", C.c_int32), ("box", C.c_int32)]
+
+
 class FavProfile(C.Structure):
     _fields_ = [("ms", C.c_double * K_COUNT), ("flops", C.c_double * K_COUNT), ("bytes", C.c_double * K_COUNT),
                 ("launches", C.c_int64 * K_COUNT)]
@@ -339,6 +352,18 @@ _SIGNATURES = {
     "fav_coreset_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "fav_op_coreset_select": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "fav_check_ae_config": (C.c_int, [C.POINTER(FavAeConfig), C.c_char_p, C.c_size_t]),
+    "fav_ae_info": (C.c_int, [C.POINTER(FavAeConfig), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                              C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
+    "fav_ae_check_blob": (C.c_int, [C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "fav_ae_create": (C.c_int, [C.POINTER(FavAeConfig), C.POINTER(C.c_void_p)]),
+    "fav_ae_load_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "fav_ae_set_threshold": (C.c_int, [C.c_void_p, C.c_float]),
+    "fav_ae_destroy": (None, [C.c_void_p]),
+    "fav_ae_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fav_op_ae_decode_compare": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "fav_classify_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "fav_get_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),

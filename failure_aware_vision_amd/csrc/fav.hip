@@ -37,6 +37,7 @@
 #include "fav_rise.hpp"
 #include "fav_patch.hpp"
 #include "fav_coreset.hpp"
+#include "fav_ae.hpp"
 
 using namespace fav_plan;    // the schedule: Plan, Op, Phase, the planner and the rules it shares with the launchers
 using namespace fav_route;   // the selector: which kernel a launch takes, on what grid (Route)
@@ -3781,6 +3782,209 @@ fav_status fav_op_rise_accumulate(const float* prob, const int32_t* classes, int
         return op_rejected(fn, "prob_dev, classes_dev and map_dev must be 4-byte aligned");
     if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
     launch_rise_accumulate(prob, classes, n, *desc, first_index, H, W, mh, mw, num_classes, map, rec, (hipStream_t)stream);
+    return op_done(nullptr);
+}
+
+}  // extern "C"
+
+// ---- the autoencoder anomaly sensor (fav_ae.hpp): an object of its own beside fav_handle ---------------------------
+struct fav_ae {
+    fav_ae_config cfg;
+    AeGeom g;
+    int device = 0;
+    char* ws = nullptr;              // two rotating activation buffers of g.buf_bytes
+    char* slab = nullptr;            // the weights, at the blob's own (64-byte aligned) offsets
+    size_t slab_bytes = 0;
+    size_t w_off[2 * AE_MAX_LEVELS] = {}, b_off[2 * AE_MAX_LEVELS] = {};
+    bool loaded = false;
+    float threshold = INFINITY;
+};
+
+namespace {
+// the blob's size for a level count: the header, the table, every range 64-byte aligned, in table order
+size_t ae_blob_bytes(int levels) {
+    size_t at = (AE_BLOB_HEADER + 16 * (size_t)(2 * levels) + AE_BLOB_ALIGN - 1) / AE_BLOB_ALIGN * AE_BLOB_ALIGN;
+    for (int k = 0; k < 2 * levels; ++k) {
+        const AeLayerShape s = ae_layer_shape(levels, k);
+        at += (s.w_elems * 2 + AE_BLOB_ALIGN - 1) / AE_BLOB_ALIGN * AE_BLOB_ALIGN;
+        at += (s.b_elems * 4 + AE_BLOB_ALIGN - 1) / AE_BLOB_ALIGN * AE_BLOB_ALIGN;
+    }
+    return at;
+}
+fav_status ae_rejected(const char* fn, const std::string& why, fav_status st = FAV_ERR_INVALID_ARG) {
+    g_create_error = fmt("%s: %s", fn, why.c_str());
+    return st;
+}
+std::string ae_info_error(const fav_ae_config* cfg, AeGeom* g) {
+    const std::string why = ae_config_error(cfg);
+    if (!why.empty()) return why;
+    *g = ae_geometry(*cfg);
+    if (g->ws_bytes > AE_MAX_WORKSPACE)
+        return fmt("max_batch=%d frames of %d x %d at %d levels need a workspace of %zu bytes, above %zu", cfg->max_batch, cfg->in_h,
+                   cfg->in_w, cfg->levels, g->ws_bytes, AE_MAX_WORKSPACE);
+    return std::string();
+}
+}  // namespace
+
+extern "C" {
+
+fav_status fav_check_ae_config(const fav_ae_config* cfg, char* err, size_t err_cap) {
+    return check_reply(ae_config_error(cfg), err, err_cap);
+}
+
+fav_status fav_ae_info(const fav_ae_config* cfg, int32_t h[4], int32_t w[4], int32_t* gh, int32_t* gw, size_t* workspace_bytes,
+                       char* err, size_t err_cap) {
+    AeGeom g;
+    const std::string why = ae_info_error(cfg, &g);
+    if (why.empty()) {
+        for (int l = 0; l < 4; ++l) { if (h) h[l] = g.h[l]; if (w) w[l] = g.w[l]; }
+        if (gh) *gh = g.gh;
+        if (gw) *gw = g.gw;
+        if (workspace_bytes) *workspace_bytes = g.ws_bytes;
+    }
+    return check_reply(why, err, err_cap);
+}
+
+fav_status fav_ae_check_blob(const void* blob, size_t size, char* err, size_t err_cap) {
+    const std::string why = ae_blob_error(blob, size, nullptr);
+    if (err && err_cap) snprintf(err, err_cap, "%s", why.c_str());
+    return why.empty() ? FAV_OK : FAV_ERR_BAD_BLOB;
+}
+
+fav_status fav_ae_create(const fav_ae_config* cfg, fav_ae** out) {
+    const char* fn = "fav_ae_create";
+    if (out) *out = nullptr;
+    if (!cfg || !out) return ae_rejected(fn, "null argument");
+    AeGeom g;
+    const std::string why = ae_info_error(cfg, &g);
+    if (!why.empty()) return ae_rejected(fn, why);
+    int device = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) {
+        (void)hipGetLastError();
+        return ae_rejected(fn, "no usable HIP device; this path has no CPU fallback", FAV_ERR_NO_DEVICE);
+    }
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return ae_rejected(fn, fmt("device %d is '%s', kernels are built for gfx950 only", device, prop.gcnArchName), FAV_ERR_NO_DEVICE);
+    fav_ae* ae = new fav_ae();
+    ae->cfg = *cfg; ae->g = g; ae->device = device;
+    ae->slab_bytes = ae_blob_bytes(cfg->levels);
+    if (hipMalloc((void**)&ae->ws, g.ws_bytes) != hipSuccess || hipMalloc((void**)&ae->slab, ae->slab_bytes) != hipSuccess) {
+        const std::string e = fmt("cannot allocate %zu + %zu bytes: %s", g.ws_bytes, ae->slab_bytes, hipGetErrorString(hipGetLastError()));
+        if (ae->ws) (void)hipFree(ae->ws);
+        delete ae;
+        return ae_rejected(fn, e, FAV_ERR_HIP);
+    }
+    *out = ae;
+    return FAV_OK;
+}
+
+void fav_ae_destroy(fav_ae* ae) {
+    if (!ae) return;
+    (void)hipSetDevice(ae->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(ae->ws);
+    (void)hipFree(ae->slab);
+    delete ae;
+}
+
+fav_status fav_ae_load_weights(fav_ae* ae, const void* blob, size_t size) {
+    const char* fn = "fav_ae_load_weights";
+    if (!ae) return ae_rejected(fn, "null object");
+    int levels = 0;
+    const std::string why = ae_blob_error(blob, size, &levels);
+    if (!why.empty()) return ae_rejected(fn, why, FAV_ERR_BAD_BLOB);
+    if (levels != ae->cfg.levels)
+        return ae_rejected(fn, fmt("the blob has levels=%d, the object was created with levels=%d", levels, ae->cfg.levels), FAV_ERR_BAD_BLOB);
+    if (size > ae->slab_bytes) return ae_rejected(fn, fmt("the blob has %zu bytes, its layers need at most %zu", size, ae->slab_bytes), FAV_ERR_BAD_BLOB);
+    // the work enqueued on the object may still read the old weights
+    if (hipSetDevice(ae->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(ae->slab, blob, size, hipMemcpyHostToDevice) != hipSuccess) {
+        ae->loaded = false;
+        return ae_rejected(fn, fmt("cannot copy the weights: %s", hipGetErrorString(hipGetLastError())), FAV_ERR_HIP);
+    }
+    for (int k = 0; k < 2 * levels; ++k) {
+        uint64_t off[2];
+        memcpy(off, (const uint8_t*)blob + AE_BLOB_HEADER + 16 * (size_t)k, 16);
+        ae->w_off[k] = (size_t)off[0]; ae->b_off[k] = (size_t)off[1];
+    }
+    ae->loaded = true;
+    return FAV_OK;
+}
+
+fav_status fav_ae_set_threshold(fav_ae* ae, float threshold) {
+    if (!ae) return ae_rejected("fav_ae_set_threshold", "null object");
+    if (std::isnan(threshold)) return ae_rejected("fav_ae_set_threshold", "threshold is NaN");
+    ae->threshold = threshold;
+    return FAV_OK;
+}
+
+fav_status fav_ae_score(fav_ae* ae, const void* images, int32_t n, int32_t layout, float* err_map, fav_ae_record* rec, uint8_t* recon,
+                        void* stream) {
+    const char* fn = "fav_ae_score";
+    route_clear();
+    if (!ae) return ae_rejected(fn, "null object");
+    if (!ae->loaded) return ae_rejected(fn, "no weights loaded (fav_ae_load_weights)", FAV_ERR_NO_WEIGHTS);
+    if (!images || !err_map || !rec) return ae_rejected(fn, "null pointer");
+    if (n < 1 || n > ae->cfg.max_batch) return ae_rejected(fn, fmt("n=%d outside [1, max_batch=%d]", n, ae->cfg.max_batch));
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return ae_rejected(fn, "unknown layout");
+    if (layout == FAV_LAYOUT_NHWC_F32 && ((uintptr_t)images & 3)) return ae_rejected(fn, "fp32 frames must be 4-byte aligned");
+    if ((uintptr_t)err_map & 3) return ae_rejected(fn, "err_map_dev must be 4-byte aligned");
+    if ((uintptr_t)rec & 7) return ae_rejected(fn, "rec_dev must be 8-byte aligned");
+    const AeGeom& g = ae->g;
+    const int L = g.L, H = ae->cfg.in_h, W = ae->cfg.in_w;
+    const std::string dims = ae_decode_dims_error(n, g.h[L], g.w[L], L - 1, H, W, ae->cfg.cell, ae->threshold);
+    if (!dims.empty()) return ae_rejected(fn, dims);
+    hipStream_t s = (hipStream_t)stream;
+    char* buf[2] = {ae->ws, ae->ws + g.buf_bytes};
+    int cur = 0;
+    static const float kZero3[3] = {0.f, 0.f, 0.f}, kOne3[3] = {1.f, 1.f, 1.f};
+    auto refused = [&](const char* e) { return ae_rejected(fn, e); };
+    // enc_1: the im2col matrix, then [rows][64] x [64][64]
+    if (const char* e = launch_stem(nullptr, images, layout, n, H, W, 3, 3, 2, 1, 64, kZero3, kOne3, buf[cur], s)) return refused(e);
+    auto gemm = [&](int k, int frames, int h, int w, int cin, int cout, int ksize, int stride, int pad) -> const char* {
+        fav_conv_desc d;
+        memset(&d, 0, sizeof d);
+        d.x = buf[cur]; d.w = ae->slab + ae->w_off[k]; d.bias = (const float*)(ae->slab + ae->b_off[k]); d.res = nullptr; d.y = buf[cur ^ 1];
+        d.n_frames = frames; d.H = h; d.W = w; d.Cin = cin; d.Cout = cout; d.kh = d.kw = ksize; d.stride = stride; d.pad = pad;
+        d.relu = 1; d.out_f32 = 0; d.math_mode = FAV_MATH_BF16;
+        d.drop.site = -1;
+        const char* e = launch_conv(nullptr, d, cout, cout, false, Group{}, s);
+        cur ^= 1;
+        return e;
+    };
+    if (const char* e = gemm(0, n, g.h[1], g.w[1], 64, 64, 1, 1, 0)) return refused(e);
+    for (int l = 2; l <= L; ++l)
+        if (const char* e = gemm(l - 1, n, g.h[l - 1], g.w[l - 1], ae_width(l - 1), ae_width(l), 3, 2, 1)) return refused(e);
+    // dec_L .. dec_2: [rows][C_l] x [4 C_{l-1}][C_l], the output read as four times the rows
+    int rows_per_frame = g.h[L] * g.w[L];
+    for (int l = L; l >= 2; --l) {
+        if (const char* e = gemm(2 * L - l, n, rows_per_frame, 1, ae_width(l), 4 * ae_width(l - 1), 1, 1, 0)) return refused(e);
+        rows_per_frame *= 4;
+    }
+    const int k1 = 2 * L - 1;
+    launch_ae_decode_compare(buf[cur], n, g.h[L], g.w[L], L - 1, ae->slab + ae->w_off[k1], (const float*)(ae->slab + ae->b_off[k1]), images,
+                             layout, H, W, ae->cfg.cell, ae->threshold, nullptr, err_map, rec, recon, s);
+    route_clear();
+    if (hipGetLastError() != hipSuccess) return ae_rejected(fn, "kernel launch failed", FAV_ERR_HIP);
+    return FAV_OK;
+}
+
+fav_status fav_op_ae_decode_compare(const void* hidden, int32_t n, int32_t hL, int32_t wL, int32_t m, const void* wg, const float* bias,
+                                    const void* frames, int32_t layout, int32_t H, int32_t W, int32_t cell, float threshold,
+                                    uint32_t* cell_sse, float* err_map, fav_ae_record* rec, uint8_t* recon, void* stream) {
+    const char* fn = "fav_op_ae_decode_compare";
+    route_clear();
+    if (!hidden || !wg || !bias || !frames || !err_map || !rec) return op_rejected(fn, "null pointer");
+    if (layout != FAV_LAYOUT_NHWC_U8 && layout != FAV_LAYOUT_NHWC_F32) return op_rejected(fn, "unknown layout");
+    const std::string why = ae_decode_dims_error(n, hL, wL, m, H, W, cell, threshold);
+    if (!why.empty()) return op_rejected(fn, why.c_str());
+    if (((uintptr_t)hidden | (uintptr_t)wg) & 15) return op_rejected(fn, "hidden_bf16 and wg12_bf16 must be 16-byte aligned");
+    if (((uintptr_t)bias | (uintptr_t)err_map | (uintptr_t)cell_sse) & 3) return op_rejected(fn, "bias3, err_map_dev and cell_sse_dev must be 4-byte aligned");
+    if (layout == FAV_LAYOUT_NHWC_F32 && ((uintptr_t)frames & 3)) return op_rejected(fn, "fp32 frames must be 4-byte aligned");
+    if ((uintptr_t)rec & 7) return op_rejected(fn, "rec_dev must be 8-byte aligned");
+    launch_ae_decode_compare(hidden, n, hL, wL, m, wg, bias, frames, layout, H, W, cell, threshold, cell_sse, err_map, rec, recon,
+                             (hipStream_t)stream);
     return op_done(nullptr);
 }
 

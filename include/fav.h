@@ -1370,6 +1370,95 @@ size_t fav_coreset_workspace_bytes(int32_t N, int32_t D, int32_t M);   /* host o
 fav_status fav_op_coreset_select(const void* rows_bf16_dev, int32_t N, int32_t D, int32_t M, int32_t start_row, void* ws_dev,
                                  size_t ws_bytes, int32_t* order_dev, float* radius_dev, void* hip_stream);
 
+/* ---- The autoencoder anomaly sensor: the one learned model of the reference's design
+ * (docs/system_notes.md 6.1: "Conv2d -> ReLU -> ConvTranspose2d", trained on normal frames only, anomaly_score =
+ * MSE(recon, frame)).  It needs no classifier and has a handle of its own; nothing of fav_handle is involved.
+ *
+ * The model, levels L in {1, 2, 3}, widths C_l = 64 * 2^(l-1), pixels in [0, 1] (u8 / 255, fp32 sanitised as the stem does; no
+ * mean or std):
+ *   enc_1: Conv2d(3, 64, 3, stride 2, pad 1) + ReLU          enc_l: Conv2d(C_{l-1}, C_l, 3, stride 2, pad 1) + ReLU, l = 2 .. L
+ *   dec_l: ConvTranspose2d(C_l, C_{l-1}, 2, stride 2) + ReLU, l = L .. 2          dec_1: ConvTranspose2d(64, 3, 2, stride 2) + Sigmoid
+ *   recon = net(x)[..., :H, :W]
+ * Grids: h_0 = H, h_l = (h_{l-1} - 1) / 2 + 1, likewise w; the decoder's output is 2^L h_L x 2^L w_L >= H x W and is cropped.
+ * Every layer rounds its output to bf16 once, as every convolution of the library does.  enc_1 is fav_op_stem_im2col (3x3/2/1,
+ * kpad 64, mean 0, inv_std 1) and a 1x1 fav_op_conv2d 64 -> 64 whose weight is [64][64], k = (r 3 + s) 3 + c, zero above 26;
+ * enc_l is fav_op_conv2d.  A 2x2 / stride-2 transposed convolution has no overlapping windows, so dec_l, l >= 2, is a 1x1
+ * fav_op_conv2d C_l -> 4 C_{l-1} whose weight row (2a + b) C_{l-1} + co holds wt[:, co, a, b] and whose bias is tiled four
+ * times; its output [rows][4 C] read as [4 rows][C] feeds the next one as it is.
+ * Row order.  With m = L - 1 such steps, row r of the last hidden matrix [n h_L w_L 4^m][64] has r / 4^m = (i h_L + y_L) w_L +
+ * x_L and the base-4 digits d_1 .. d_m of r % 4^m, most significant first, d_j = 2 a_j + b_j; it is pixel (y, x) of the
+ * 2^m h_L x 2^m w_L level-1 grid, from (y_L, x_L) by y = 2 y + a_j, x = 2 x + b_j for j = 1 .. m.
+ *
+ * Decode and compare, operation by operation (tests/ae_ref.py restates it; equal bits):
+ *   1. acc[r][(2a + b) 3 + co], 12 columns: the production accumulator of a 1x1 convolution 64 -> 12 over the hidden rows,
+ *      v_mfma_f32_16x16x32_bf16, k ascending, two issues, the accumulator starting at +0
+ *   2. z = acc + bias[co], one fp32 addition
+ *   3. s = 1.0f / (1.0f + exp(-z)): the library's fixed exponential sequence (the ViT path's), one addition, a correctly
+ *      rounded division
+ *   4. q = (int)rintf(s * 255.0f), 0 .. 255 (a NaN z: the exponential answers 0, hence 255); it is output pixel
+ *      (2 y + a, 2 x + b), channel co; pixels outside H x W are dropped
+ *   5. the frame's pixel in the same units: a u8 pixel as it is; fp32: rintf(min(max(sanitise(px), 0), 1) * 255.0f)
+ *   6. e = q - p and e^2 in integers; every sum below is an integer sum, so its order is free
+ *   7. cell in {8, 16, 32}; gh = ceil(H / cell), gw = ceil(W / cell), gh * gw <= 1024, gh and gw <= 256.  cell_sse[i][c], uint32:
+ *      the sum over the cell's pixels inside the frame and their 3 channels;
+ *      err_map[i][c] = (float)((double)cell_sse / ((double)(3 * pixels_inside) * 65025.0))
+ *   8. the record: sse the 64-bit frame sum; mse = (float)((double)sse / ((double)(3 H W) * 65025.0)), the reference's
+ *      anomaly_score on [0, 1] pixels; peak, peak_cell, floor as step 4 of fav_cam_record over err_map; n_above and box as
+ *      in fav_cam_record over the cells with err_map >= threshold (-1 when there is none)
+ *   9. optionally recon_u8 [n][H][W][3]: the bytes q.
+ * The record is 32 bytes, 8-byte aligned; peak (byte 8) and floor (byte 16) stand where fav_cam_record has them, so
+ * fav_op_cam_heatmap draws err_map from it. */
+typedef struct fav_ae_record { uint32_t sse_lo; float mse, peak; int32_t peak_cell; float floor;
+                               uint32_t sse_hi; int32_t n_above, box; } fav_ae_record;
+typedef struct fav_ae_config {
+    uint32_t struct_size;   /* sizeof(fav_ae_config) */
+    int32_t in_h, in_w;     /* frame size, 1 .. 4096 each */
+    int32_t levels;         /* 1 .. 3 */
+    int32_t max_batch;      /* largest n passed to fav_ae_score, >= 1 */
+    int32_t cell;           /* 8, 16 or 32 */
+} fav_ae_config;
+typedef struct fav_ae fav_ae;
+/* Host only: the ranges above; each refusal (FAV_ERR_INVALID_ARG) names the field in err (may be NULL). */
+fav_status fav_check_ae_config(const fav_ae_config* cfg, char* err, size_t err_cap);
+/* Host only, the one place the geometry lives: h[l], w[l] for l = 0 .. levels (0 beyond), the cell grid and the bytes
+ * fav_ae_create allocates for max_batch frames (two rotating activation buffers; every pointer may be NULL).  A workspace
+ * above 1 GiB is refused with both numbers in the message. */
+fav_status fav_ae_info(const fav_ae_config* cfg, int32_t h[4], int32_t w[4], int32_t* gh, int32_t* gw, size_t* workspace_bytes,
+                       char* err, size_t err_cap);
+/* Host only: structural validation of a FAVA v1 blob.  Header of 64 bytes: magic "FAVA", version 1, levels, layers = 2 levels
+ * (uint32 each), the total size (uint64); then a (weight offset, bias offset) uint64 pair a layer, in the order enc_1 .. enc_L,
+ * dec_L .. dec_2, dec_1; then the data, every range 64-byte aligned: bf16 weights in the device layouts above (dec_1: [12][64]),
+ * fp32 biases (dec_l: the tiled 4 C_{l-1}; dec_1: 3).  FAV_ERR_BAD_BLOB for a truncated blob, a misaligned or out-of-range
+ * offset, a wrong level or layer count and any non-finite value; err (may be NULL) says which. */
+fav_status fav_ae_check_blob(const void* blob_host, size_t size, char* err, size_t err_cap);
+/* Lifecycle: create -> load_weights -> score xN -> destroy, on the calling thread's current HIP device.  create allocates the
+ * whole workspace and the weight slab; load_weights runs fav_ae_check_blob first and refuses (FAV_ERR_BAD_BLOB) a blob of
+ * another level count; threshold (the cell threshold of step 8) defaults to +inf, so no cell counts as above until it is set;
+ * a NaN is refused.  A rejected call leaves the object as it was; its message is in fav_last_error(NULL). */
+fav_status fav_ae_create(const fav_ae_config* cfg, fav_ae** out);
+fav_status fav_ae_load_weights(fav_ae* ae, const void* blob_host, size_t size);
+fav_status fav_ae_set_threshold(fav_ae* ae, float threshold);
+void fav_ae_destroy(fav_ae* ae);
+/* n frames (1 <= n <= max_batch) -> err_map_dev fp32 [n][gh*gw], rec_dev [n] (8-byte aligned), and recon_u8_dev [n][H][W][3]
+ * unless NULL.  L + 1 encoder launches, L - 1 decoder GEMMs and the two launches of fav_op_ae_decode_compare, all on
+ * hip_stream; never allocates or synchronises.  FAV_ERR_NO_WEIGHTS before load_weights; FAV_ERR_INVALID_ARG for n out of range,
+ * an unknown layout and a NULL or misaligned buffer (fp32 frames and err_map_dev 4 bytes, rec_dev 8), before anything is
+ * launched.  Calls on one object must not overlap: they share its workspace. */
+fav_status fav_ae_score(fav_ae* ae, const void* images_dev, int32_t n, int32_t layout, float* err_map_dev, fav_ae_record* rec_dev,
+                        uint8_t* recon_u8_dev, void* hip_stream);
+/* Steps 1 - 9 on caller buffers: hidden_bf16 [n h_L w_L 4^m][64] in the row order above and wg12_bf16 [12][64] (both 16-byte
+ * aligned), bias3 fp32 [3], frames [n][H][W][3] in `layout`.  Two launches: a block a cell of a frame (it leaves the cell's
+ * integer sum in err_map_dev), then a block a frame for the means and the record; cell_sse_dev (may be NULL) receives the
+ * integer sums.  No allocation, no workspace, no synchronisation, no atomics, vector stores only.  Ranges: n >= 1; m 0 .. 2;
+ * H, W, h_L, w_L 1 .. 4096 with 2^(m+1) h_L >= H and 2^(m+1) w_L >= W; n h_L w_L 4^m <= 2^31 - 1; the cell and grid ranges of
+ * step 7; threshold not NaN.  A refused call (FAV_ERR_INVALID_ARG: one of these, a NULL pointer other than cell_sse_dev and
+ * recon_u8_dev, an unknown layout, a misaligned buffer) launches nothing and leaves a message that names the function in
+ * fav_last_error(NULL). */
+fav_status fav_op_ae_decode_compare(const void* hidden_bf16, int32_t n, int32_t h_L, int32_t w_L, int32_t m, const void* wg12_bf16,
+                                    const float* bias3, const void* frames, int32_t layout, int32_t H, int32_t W, int32_t cell,
+                                    float threshold, uint32_t* cell_sse_dev, float* err_map_dev, fav_ae_record* rec_dev,
+                                    uint8_t* recon_u8_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
